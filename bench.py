@@ -69,6 +69,28 @@ def spawn_ranks(args):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     log("bench.py: starting", args.gpus, "ranks:", " ".join(cmd))
     return subprocess.run(cmd, env=env).returncode
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, outputs, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what every timed leg computed in its last timed step (the solution a caller receives), as
+    <outdir>/<name>.npy in float64, within `budget` bytes in all.  An array longer than its even share of the budget is
+    written as a fixed sample of that many entries (seed 0, in index order): the same arguments give the same entries, so
+    two builds of the project can be compared file for file."""
+    os.makedirs(outdir, exist_ok=True)
+    if not outputs:
+        return
+    cap = (budget - 4096 * len(outputs)) // (8 * len(outputs))    # (4 KB per file for the .npy header, generously)
+    for name, x in sorted(outputs.items()):
+        x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        if x.size > cap:
+            x = x[np.sort(np.random.default_rng(0).choice(x.size, cap, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), x)
+    log("bench.py: wrote", len(outputs), "last-step outputs to", outdir)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -92,11 +114,15 @@ def main():
     ap.add_argument("--full-json", default=None, help="where the full record goes (default gpurun_out/bench_full_n<N>.json); the stdout line is the compact one")
     ap.add_argument("--group-reps", type=int, default=3, help="warm solves of the in-library device group leg (--gpus N, N > 1)")
     ap.add_argument("--no-group-leg", action="store_true", help="leave out the one-process device group leg at N > 1")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what each timed leg computed in its last step to DIR/<name>.npy (float64, 64 MB at most)")
     ap.add_argument("--no-cold-process", action="store_true", help="leave out the cold analyses in a process of their own (bench_legs/cold.py): analyze_ms_cold is then the in-process number")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args))
     rank = int(os.environ.get("RANK", "0"))
@@ -273,6 +299,8 @@ def main():
         except OSError as e:
             log("bench.py: could not write", full_path, e)
             full_path = None
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, TIMED_OUTPUTS)
         print(compact_line(out, full_path), flush=True)
 
 

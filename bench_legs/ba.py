@@ -240,6 +240,7 @@ def run_ba(args, rank, world, local_rank, dist, schur_sparse=-1, mode="band", ex
             parity = float(np.abs(lam_full.to_scipy() @ x_full - lam_full.rhs).max() / np.abs(lam_full.rhs).max())
     if rank != 0:
         return None
+    keep_output(f"ba_{n_cams}x{n_points_total}_{mode}_x", x_full if world > 1 else x_local)
     ms = dt / steps * 1e3
     n_values_total, n_scalars_total = int(lam_full.values.shape[0]), int(lam_full.n_scalars)
     dc_ = int(lam_full.cumsum[1] - lam_full.cumsum[0])

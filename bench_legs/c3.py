@@ -298,6 +298,7 @@ def run_c3(args, rank, world, local_rank, dist):
         return None
     # parity guard on the last timed solution: ||Lambda x - eta||_inf / ||eta||_inf
     x = bufs[-1].cpu().numpy()
+    keep_output("c3_x", x)
     resid = float(np.abs(lam.to_scipy() @ x - lam.rhs).max() / np.abs(lam.rhs).max())
     ms_per_step = dt / args.steps * 1e3
     prof = solver.profile()          # timed region: one event pair, around the leaf kernel (option profile = 3)

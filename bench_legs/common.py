@@ -11,7 +11,7 @@ import time
 
 import numpy as np
 
-__all__ = ['ROOT', 'HBM_PEAK_GBS', 'F64_MFMA_PEAK_TFLOPS', 'F64_MFMA_SUSTAINED_TFLOPS', 'C3_REF', '_KEEP', 'host_cores', 'log', 'timed_cold_analysis', 'load_traffic', 'kernel_traffic', 'kernel_traffic_mean', 'kernel_traffic_sum', 'host_path_leg', 'dropin_leg', '_DevPtr', 'make_allreduce', 'dataclasses_replace_points', 'shared_system']
+__all__ = ['ROOT', 'HBM_PEAK_GBS', 'F64_MFMA_PEAK_TFLOPS', 'F64_MFMA_SUSTAINED_TFLOPS', 'C3_REF', '_KEEP', 'TIMED_OUTPUTS', 'keep_output', 'host_cores', 'log', 'timed_cold_analysis', 'load_traffic', 'kernel_traffic', 'kernel_traffic_mean', 'kernel_traffic_sum', 'host_path_leg', 'dropin_leg', '_DevPtr', 'make_allreduce', 'dataclasses_replace_points', 'shared_system']
 
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))   # the repository
@@ -30,6 +30,9 @@ F64_MFMA_SUSTAINED_TFLOPS = 47.8
 # factor flops = fl, solve flops = 4 lnz, factor bytes = 8 (nnz + lnz), solve bytes = 16 lnz + 32 n.
 C3_REF = {"n": 600_000, "nnz_triu": 7_271_928, "lnz": 8_360_436, "fl": 122_411_332.0}
 _KEEP = {}
+TIMED_OUTPUTS = {}   # name -> what a leg's timed loop computed in its last step (float64, host): bench.py --dump-outputs writes them
+def keep_output(name, x):
+    TIMED_OUTPUTS[name] = np.array(x, dtype=np.float64, copy=True)
 def host_cores():
     from oracle import oracle_lib as O
     return O.host_cores()

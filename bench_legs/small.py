@@ -47,6 +47,7 @@ def run_small_configs(args, local_rank):
         solver.sync()
         ms = (time.perf_counter() - t0) / reps * 1e3
         x = bufs[-1].cpu().numpy()
+        keep_output(f"{key}_x", x)
         st = solver.stats()
         rec = {"workload": f"{name}, n={lam.n_scalars}", "ms_per_solve": ms, "analyze_ms_cold": analyze_ms,
                "dense_top_dim": st["schur_dim"], "n_stages": st["n_stages"],

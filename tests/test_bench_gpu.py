@@ -49,6 +49,24 @@ def test_bench_line(workload):
         assert d["solve_residual_rel_inf"] < 1e-9
 
 
+@pytest.mark.parametrize("workload", ["c3", "ba"])
+def test_bench_dump_outputs_are_the_last_step_solutions(workload, tmp_path):
+    """--dump-outputs DIR: the solution the timed loop's last step left, as DIR/<name>.npy in float64 -- it solves the
+    benchmark's own system."""
+    import numpy as np
+    from slam_plus_plus_amd import synth
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--c3-solve-only", "--ba-solve-only",
+                        "--full-json", str(tmp_path / "full.json"), "--dump-outputs", str(tmp_path / "out")] + SMALL,
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert last_json(r.stdout, full=False)["steps"] == (3 if workload == "c3" else 2)     # --steps; the BA legs take --ba-steps
+    name, lam = (("c3_x", synth.pose_chain(n=3000)) if workload == "c3" else
+                 ("ba_60x4000_band_x", synth.ba(60, 4000, k=4, mode="band", seed=777)))
+    x = np.load(tmp_path / "out" / f"{name}.npy")
+    assert x.dtype == np.float64 and x.shape == (lam.n_scalars,)
+    assert np.abs(lam.to_scipy() @ x - lam.rhs).max() / np.abs(lam.rhs).max() < 1e-9
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))

@@ -54,3 +54,21 @@ def test_gpus_n_without_devices_fails_loudly():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"], capture_output=True, text=True, timeout=300, cwd=ROOT,
                        env=dict(env, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"))
     assert r.returncode != 0 and not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_dump_outputs_stays_in_budget_and_samples_the_same_entries(tmp_path):
+    """--dump-outputs: float64 .npy files, 64 MB at most in all; an array over its share is a fixed sample, the same every run."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(1)
+    outputs = {"small_x": rng.standard_normal(1000), "big_x": rng.standard_normal(9_000_000), "big2_x": rng.standard_normal(5_000_000)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outputs)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["big2_x.npy", "big_x.npy", "small_x.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_BUDGET_BYTES
+    assert np.array_equal(np.load(tmp_path / "a" / "small_x.npy"), outputs["small_x"])
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+        assert np.isin(a, outputs[f[:-4]]).all()
