@@ -50,6 +50,7 @@
 
 #include "slam/LinearSolverTags.h"
 #include "slam/BlockMatrix.h"
+#include "slam/IncrementalPolicy.h" // EBlockMatrixPart (the covariance parts)
 #include "slam/LinearSolver_Schur.h" // the primary template specialized at the end of this file, and its guided ordering helper
 #include "slampp_hip.h"
 
@@ -850,6 +851,153 @@ public:
 		Gather_Or_Reanalyze(r_lambda, [&]() { SymbolicDecomposition_Blocky(r_lambda); });
 		return Solve_Gathered(r_lambda, r_eta);
 	}
+
+	/**
+	 *	@brief calculates the requested parts of the covariance matrix (the inverse of lambda): the parts of the reference's
+	 *		CMarginals::Calculate_DenseMarginals_Recurrent_FBS(margs, R, ordering, n_part), which CNonlinearSolver_Lambda calls
+	 *		after ordering and factoring lambda once more (NonlinearSolver_Lambda.h:690-752), with the matrix parts of
+	 *		IncrementalPolicy.h:366-372
+	 *
+	 *	@param[out] r_marginals is filled with the union of the requested parts, upper triangle, in lambda's block order (the
+	 *		shape the reference's margs_ordered.Permute_UpperTriangular_To() leaves in CMarginals::r_SparseMatrix())
+	 *	@param[in] r_lambda is the system matrix (symmetric layout, upper triangle stored)
+	 *	@param[in] n_part is a combination of mpart_Diagonal (blocks (i, i)), mpart_LastBlock ((n-1, n-1)), mpart_LastColumn
+	 *		((i, n-1) for all i) or mpart_FullMatrix (every (i, j), i <= j: all block columns, in passes); mpart_Column does
+	 *		not say which column: with it set (other than as part of mpart_FullMatrix) this throws std::runtime_error
+	 *		(Marginal_Columns() names the columns)
+	 *	@param[in] b_structure_of_lambda adds every stored block of lambda -- where the reference takes R's pattern
+	 *		(Marginals.h:1696, b_structure_of_R), which depends on the ordering, lambda's is the same under every ordering and
+	 *		lies inside every factor's pattern
+	 *
+	 *	@return Returns true on success, false if lambda is not positive definite.
+	 *	@note This function throws std::bad_alloc and std::runtime_error.
+	 */
+	bool Marginals(CUberBlockMatrix &r_marginals, const CUberBlockMatrix &r_lambda, EBlockMatrixPart n_part,
+		bool b_structure_of_lambda = false) // throw(std::bad_alloc, std::runtime_error)
+	{
+		const size_t n = r_lambda.n_BlockColumn_Num();
+		const bool b_full = (n_part & mpart_FullMatrix) == mpart_FullMatrix;
+		const bool b_last_col = b_full || (n_part & mpart_LastColumn) != 0;
+		const bool b_last_block = b_last_col || (n_part & mpart_LastBlock) != 0;
+		const bool b_diag = b_full || (n_part & mpart_Diagonal) != 0;
+		if((n_part & mpart_Column) && !b_full)
+			throw std::runtime_error("CLinearSolver_HIP::Marginals: mpart_Column does not say which column (use Marginal_Columns)");
+		r_lambda.CopyLayoutTo(r_marginals); // (blocks are then allocated anywhere in lambda's layout, in any order)
+		if(!n)
+			return true;
+		std::vector<double> v;
+		// blocks of lambda's pattern (the diagonal is among them), then the block columns asked for
+		bool b_have_factor = false;
+		if(b_structure_of_lambda || (b_diag && !b_full)) {
+			Gather_Or_Reanalyze(r_lambda, [&]() { SymbolicDecomposition_Blocky(r_lambda); });
+			if(!m_order.empty())
+				throw std::runtime_error("CLinearSolver_HIP::Marginals: a reordered structure");
+			size_t n_values = 0;
+			for(size_t j = 0; j < n; ++ j) {
+				for(size_t k = 0, m = r_lambda.n_BlockColumn_Block_Num(j); k < m; ++ k)
+					n_values += r_lambda.n_BlockColumn_Column_Num(r_lambda.n_Block_Row(j, k)) * r_lambda.n_BlockColumn_Column_Num(j);
+			}
+			v.resize(n_values);
+			const int n_result = slampp_hip_marginals_pattern(m_p_solver, m_p_values, v.empty()? 0 : &v[0]);
+			if(n_result == SLAMPP_HIP_NOT_POSDEF)
+				return false;
+			Throw_On_Error(n_result);
+			b_have_factor = true;
+			size_t n_at = 0;
+			for(size_t j = 0; j < n; ++ j) {
+				const size_t dj = r_lambda.n_BlockColumn_Column_Num(j);
+				for(size_t k = 0, m = r_lambda.n_BlockColumn_Block_Num(j); k < m; ++ k) {
+					const size_t i = r_lambda.n_Block_Row(j, k), di = r_lambda.n_BlockColumn_Column_Num(i);
+					if(b_structure_of_lambda || i == j)
+						Put_Block(r_marginals, i, j, di, dj, &v[n_at]);
+					n_at += di * dj;
+				}
+			}
+		}
+		std::vector<int64_t> cols;
+		if(b_full) {
+			for(size_t j = 0; j < n; ++ j)
+				cols.push_back(int64_t(j));
+		} else if(b_last_block)
+			cols.push_back(int64_t(n - 1));
+		for(size_t c0 = 0; c0 < cols.size();) { // at most 48 scalar columns at a time (one pass of the library)
+			size_t c1 = c0, n_k = 0;
+			while(c1 < cols.size() && (c1 == c0 || n_k + r_lambda.n_BlockColumn_Column_Num(size_t(cols[c1])) <= 48))
+				n_k += r_lambda.n_BlockColumn_Column_Num(size_t(cols[c1 ++]));
+			Eigen::MatrixXd X;
+			if(!Columns(X, r_lambda, std::vector<int64_t>(cols.begin() + c0, cols.begin() + c1), b_have_factor))
+				return false;
+			b_have_factor = true;
+			size_t n_col = 0;
+			for(size_t q = c0; q < c1; ++ q) {
+				const size_t j = size_t(cols[q]), dj = r_lambda.n_BlockColumn_Column_Num(j);
+				for(size_t i = b_last_col? 0 : j; i <= j; ++ i) { // (mpart_LastBlock alone: the diagonal block only)
+					const size_t di = r_lambda.n_BlockColumn_Column_Num(i), b0 = r_lambda.n_BlockColumn_Base(i);
+					std::vector<double> blk(di * dj);
+					for(size_t c = 0; c < dj; ++ c)
+						for(size_t r = 0; r < di; ++ r)
+							blk[r + c * di] = X(b0 + r, n_col + c);
+					Put_Block(r_marginals, i, j, di, dj, &blk[0]);
+				}
+				n_col += dj;
+			}
+			c0 = c1;
+		}
+		return true;
+	}
+
+	/**
+	 *	@brief calculates whole block columns of the covariance matrix (the inverse of lambda), the reference's mpart_Column
+	 *		and mpart_LastColumn parts (IncrementalPolicy.h:366-372), by substitutions with the factor of lambda
+	 *
+	 *	@param[out] r_columns is filled with n_scalars x k values, k = the sum of the listed columns' widths, in the listed order
+	 *	@param[in] r_lambda is the system matrix (symmetric layout, upper triangle stored)
+	 *	@param[in] r_block_columns lists distinct block column indices
+	 *
+	 *	@return Returns true on success, false if lambda is not positive definite.
+	 *	@note This function throws std::bad_alloc and std::runtime_error.
+	 */
+	bool Marginal_Columns(Eigen::MatrixXd &r_columns, const CUberBlockMatrix &r_lambda,
+		const std::vector<size_t> &r_block_columns) // throw(std::bad_alloc, std::runtime_error)
+	{
+		return Columns(r_columns, r_lambda, std::vector<int64_t>(r_block_columns.begin(), r_block_columns.end()), false);
+	}
+
+protected:
+	/** @brief block columns of the inverse; b_reuse_factor: the factor the last call left in place (no new factorization) */
+	bool Columns(Eigen::MatrixXd &r_columns, const CUberBlockMatrix &r_lambda, const std::vector<int64_t> &r_cols,
+		bool b_reuse_factor) // throw(std::bad_alloc, std::runtime_error)
+	{
+		if(!b_reuse_factor) {
+			Gather_Or_Reanalyze(r_lambda, [&]() { SymbolicDecomposition_Blocky(r_lambda); });
+			if(!m_order.empty())
+				throw std::runtime_error("CLinearSolver_HIP::Marginal_Columns: a reordered structure");
+		}
+		size_t n_k = 0;
+		for(size_t i = 0; i < r_cols.size(); ++ i) {
+			if(r_cols[i] < 0 || size_t(r_cols[i]) >= r_lambda.n_BlockColumn_Num())
+				throw std::runtime_error("CLinearSolver_HIP::Marginal_Columns: block column index out of range");
+			n_k += r_lambda.n_BlockColumn_Column_Num(size_t(r_cols[i]));
+		}
+		r_columns.resize(r_lambda.n_Column_Num(), n_k); // (column-major, as the library writes it)
+		const int n_result = slampp_hip_marginal_columns(m_p_solver, b_reuse_factor? 0 : m_p_values, int(r_cols.size()),
+			r_cols.empty()? 0 : &r_cols[0], r_columns.data());
+		if(n_result == SLAMPP_HIP_NOT_POSDEF)
+			return false;
+		Throw_On_Error(n_result);
+		return true;
+	}
+
+	/** @brief writes a di x dj column-major block at (i, j) of r_m */
+	static void Put_Block(CUberBlockMatrix &r_m, size_t i, size_t j, size_t di, size_t dj, const double *p_src)
+	{
+		double *p_dest = r_m.p_GetBlock_Log(i, j, di, dj, true, false);
+		if(!p_dest)
+			throw std::runtime_error("CLinearSolver_HIP: cannot write the marginals");
+		std::copy(p_src, p_src + di * dj, p_dest);
+	}
+
+public:
 };
 
 /**

@@ -275,6 +275,37 @@ int slampp_hip_solve_marginal_poses_device_async(slampp_hip_solver *p_solver, co
 int slampp_hip_marginals(slampp_hip_solver *p_solver, const double *p_values, double *p_block_diag);
 int slampp_hip_marginals_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, double *p_block_diag_dev);
 
+/* Sparse mode: Lambda^-1 at every stored block of Lambda -- the reference's CMarginals::Calculate_DenseMarginals_Recurrent_FBS
+ * computes the inverse on the pattern of its factor R (include/slam/Marginals.h:1696, b_structure_of_R); R's pattern
+ * depends on the ordering, so ours and CHOLMOD's differ, while Lambda's pattern is the same for every ordering and lies
+ * inside every factor's pattern: that is the pattern returned here.  p_cov has the length and layout of p_values (same
+ * block order, each block d_r x d_c column-major), so a caller can wrap it in Lambda's block structure.  Numeric
+ * factorization and the sparse inverse subset as slampp_hip_marginals, then one gather of the upper blocks (block (r, c)
+ * is read as the stored block (max, min) of the permuted pair, transposed where the permutation flips the pair; pairs
+ * inside the dense top element-wise from its dense inverse).  Same inputs as slampp_hip_marginals; Schur mode, handles
+ * over several devices and block columns wider than 8: SLAMPP_HIP_ERR_UNSUPPORTED.  Leaves the factor in place
+ * (slampp_hip_solve_again, slampp_hip_marginal_columns with values = NULL). */
+int slampp_hip_marginals_pattern(slampp_hip_solver *p_solver, const double *p_values, double *p_cov);
+int slampp_hip_marginals_pattern_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, double *p_cov_dev);
+
+/* Sparse mode: whole block columns of Lambda^-1 -- the reference's mpart_Column / mpart_LastColumn parts
+ * (include/slam/IncrementalPolicy.h:366-372, computed by CMarginals::Calculate_DenseMarginals_Recurrent_FBS from
+ * NonlinearSolver_Lambda.h:690-752 after ordering and factoring Lambda once more, the last vertex kept last).
+ * p_bcols (host): n_cols distinct block column indices; p_out: n_scalars x k doubles, column-major, k = the sum of the
+ * listed columns' dimensions, in the listed order; rows in the caller's scalar order.  p_values = NULL: the factor in
+ * place from the last factor_solve, marginals, marginals_pattern or marginal_columns call is used (SLAMPP_HIP_ERR_INVALID
+ * without one, e.g. after a factorization that was not positive definite, or a batch); otherwise these values are
+ * factored first.  Multi-right-hand-side substitutions with that factor, in passes of at most 48 scalar columns (a
+ * device workspace of n_scalars x 48 doubles, allocated once): the forward one only over the listed columns' paths to
+ * the root of the elimination tree, the backward one over every column.  n_cols <= 0, an index out of range or listed
+ * twice: SLAMPP_HIP_ERR_INVALID; Schur mode, several devices, block columns wider than 8: SLAMPP_HIP_ERR_UNSUPPORTED.
+ * Returns SLAMPP_HIP_NOT_POSDEF as the solve does.  The host version brings the result back in groups of at most 48
+ * columns (the device holds n_scalars x 48 of it at a time). */
+int slampp_hip_marginal_columns(slampp_hip_solver *p_solver, const double *p_values, int n_cols, const int64_t *p_bcols,
+	double *p_out);
+int slampp_hip_marginal_columns_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, int n_cols,
+	const int64_t *p_bcols, double *p_out_dev);
+
 /* Schur mode only: block diagonal of the covariance matrix Lambda^-1 -- the reference's
  * CSchurComplement_Marginals::Schur_Marginals (include/slam/BAMarginals.h:579-806, called from
  * NonlinearSolver_Lambda_LM.h:1326 and NonlinearSolver_Lambda_DL.h:1640 with the Cholesky factor of the Schur

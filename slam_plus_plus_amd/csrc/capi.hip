@@ -8,6 +8,7 @@
 #include <pthread.h>
 #include "solver.h"
 #include "sparse_inverse.h"
+#include "covariance.h"
 
 #include <algorithm>
 #include <atomic>
@@ -994,6 +995,68 @@ int slampp_hip_solve_marginal_poses_device_async(slampp_hip_solver *p_solver, co
 	});
 }
 
+namespace {
+
+// what slampp_hip_marginals and slampp_hip_marginals_pattern share: the numeric factorization and the sparse inverse
+// subset Z on the factor's pattern (d_Z; the dense top's part in d_Zd).  Inside guarded(), behind the caller's checks.
+int enqueue_sparse_inverse(slampp_hip_solver *p_solver, const double *p_values_dev, const char *p_s_name)
+{
+	slampp_hip_solver &s = *p_solver;
+	const Plan &P = s.plan;
+	if(!s.b_sinv_tried) {
+		s.b_sinv_tried = true;
+		s.p_sinv = sparse_inverse_setup(P, s.stream, true);
+		if(s.p_sinv) {
+			std::vector<int64_t> zoff(size_t(P.n));
+			for(int32_t c = 0; c < P.n; ++ c) {
+				const int32_t j = P.pinv[c];
+				zoff[c] = (P.dense_dim && P.dense_pos[j] >= 0)? -int64_t(P.dense_pos[j]) - 1 : P.loff[P.lptr[j]];
+			}
+			s.d_diag_zoff.Upload(zoff, s.stream);
+			if(!P.uniform_dim) { // mixed block sizes: where every caller's column's block goes, and how big it is
+				std::vector<int32_t> dims(size_t(P.n));
+				std::vector<int64_t> out_off(size_t(P.n));
+				int64_t n_at = 0;
+				for(int32_t c = 0; c < P.n; ++ c) {
+					dims[c] = int32_t(s.cumsum[c + 1] - s.cumsum[c]);
+					out_off[c] = n_at;
+					n_at += int64_t(dims[c]) * dims[c];
+				}
+				s.d_diag_dim.Upload(dims, s.stream);
+				s.d_diag_out_off.Upload(out_off, s.stream);
+			}
+			s.d_Z.Alloc(size_t(P.loff.back()));
+			if(s.n_dense_dim) {
+				s.d_Zd.Alloc(size_t(s.n_dense_pad) * s.n_dense_pad);
+				s.d_Zd_work.Alloc(size_t(s.n_dense_pad) * s.n_dense_pad);
+			}
+			SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream)); // zoff lives on this stack frame
+		}
+	}
+	if(!s.p_sinv)
+		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, (std::string(p_s_name) + ": mixed block sizes are taken without a dense top only (set the option dense_top_nb to 0), block sizes above 8 not at all").c_str());
+	// the fused forward substitution reads a right-hand side, and with a dense top it rides through that factorization
+	// as a row of the matrix: zeros (a NaN there would spread through 0 x NaN in the tile products)
+	s.d_rhs.Alloc(size_t(s.n_scalars));
+	SLAMPP_HIP_CHECK(hipMemsetAsync(s.d_rhs.p(), 0, size_t(s.n_scalars) * sizeof(double), s.stream));
+	// (with a dense top the whole factor + solve runs: the top is factored on the way; opens its own phases)
+	s.b_leaf_linv_wanted = true; // (the inverse subset multiplies by inv(L_jj) of every column)
+	s.Enqueue_Sparse(p_values_dev, s.d_rhs.p(), true, s.n_dense_dim == 0);
+	s.Ensure_Leaf_Inverses();
+	s.Phase_Begin("marginals_inverse");
+	if(s.n_dense_dim) { // the top's inverse from a copy of its factor (the factor itself stays for solve_again)
+		SLAMPP_HIP_CHECK(hipMemcpyAsync(s.d_Zd_work.p(), s.d_dense.p(), size_t(s.n_dense_pad) * s.n_dense_pad * sizeof(double),
+			hipMemcpyDeviceToDevice, s.stream));
+		dense_top_clear_rhs_row(s.d_Zd_work.p(), s.n_dense_pad, s.stream);
+		dense_inverse_from_factor(s.d_Zd_work.p(), s.n_dense_pad, s.d_dense_invdiag.p(), s.d_Zd.p(), s.stream);
+	}
+	sparse_inverse_enqueue(*s.p_sinv, P, s.d_L.p(), s.d_Linv.p(), s.d_Z.p(), s.stream, s.d_Zd.p(), s.n_dense_pad);
+	s.Phase_End();
+	return SLAMPP_HIP_OK;
+}
+
+} // anonymous namespace
+
 int slampp_hip_marginals_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, double *p_block_diag_dev)
 {
 	return guarded(p_solver, [&]() -> int {
@@ -1006,56 +1069,10 @@ int slampp_hip_marginals_device_async(slampp_hip_solver *p_solver, const double 
 			return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, "marginals: block columns wider than 8 are factored in pieces: no covariance blocks in the caller's layout");
 		if(!p_values_dev || !p_block_diag_dev)
 			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginals: null pointer");
+		const int n_result = enqueue_sparse_inverse(p_solver, p_values_dev, "marginals");
+		if(n_result != SLAMPP_HIP_OK)
+			return n_result;
 		const Plan &P = s.plan;
-		if(!s.b_sinv_tried) {
-			s.b_sinv_tried = true;
-			s.p_sinv = sparse_inverse_setup(P, s.stream, true);
-			if(s.p_sinv) {
-				std::vector<int64_t> zoff(size_t(P.n));
-				for(int32_t c = 0; c < P.n; ++ c) {
-					const int32_t j = P.pinv[c];
-					zoff[c] = (P.dense_dim && P.dense_pos[j] >= 0)? -int64_t(P.dense_pos[j]) - 1 : P.loff[P.lptr[j]];
-				}
-				s.d_diag_zoff.Upload(zoff, s.stream);
-				if(!P.uniform_dim) { // mixed block sizes: where every caller's column's block goes, and how big it is
-					std::vector<int32_t> dims(size_t(P.n));
-					std::vector<int64_t> out_off(size_t(P.n));
-					int64_t n_at = 0;
-					for(int32_t c = 0; c < P.n; ++ c) {
-						dims[c] = int32_t(s.cumsum[c + 1] - s.cumsum[c]);
-						out_off[c] = n_at;
-						n_at += int64_t(dims[c]) * dims[c];
-					}
-					s.d_diag_dim.Upload(dims, s.stream);
-					s.d_diag_out_off.Upload(out_off, s.stream);
-				}
-				s.d_Z.Alloc(size_t(P.loff.back()));
-				if(s.n_dense_dim) {
-					s.d_Zd.Alloc(size_t(s.n_dense_pad) * s.n_dense_pad);
-					s.d_Zd_work.Alloc(size_t(s.n_dense_pad) * s.n_dense_pad);
-				}
-				SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream)); // zoff lives on this stack frame
-			}
-		}
-		if(!s.p_sinv)
-			return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, "marginals: mixed block sizes are taken without a dense top only (set the option dense_top_nb to 0), block sizes above 8 not at all");
-		// the fused forward substitution reads a right-hand side, and with a dense top it rides through that factorization
-		// as a row of the matrix: zeros (a NaN there would spread through 0 x NaN in the tile products)
-		s.d_rhs.Alloc(size_t(s.n_scalars));
-		SLAMPP_HIP_CHECK(hipMemsetAsync(s.d_rhs.p(), 0, size_t(s.n_scalars) * sizeof(double), s.stream));
-		// (with a dense top the whole factor + solve runs: the top is factored on the way; opens its own phases)
-		s.b_leaf_linv_wanted = true; // (the inverse subset multiplies by inv(L_jj) of every column)
-		s.Enqueue_Sparse(p_values_dev, s.d_rhs.p(), true, s.n_dense_dim == 0);
-		s.Ensure_Leaf_Inverses();
-		s.Phase_Begin("marginals_inverse");
-		if(s.n_dense_dim) { // the top's inverse from a copy of its factor (the factor itself stays for solve_again)
-			SLAMPP_HIP_CHECK(hipMemcpyAsync(s.d_Zd_work.p(), s.d_dense.p(), size_t(s.n_dense_pad) * s.n_dense_pad * sizeof(double),
-				hipMemcpyDeviceToDevice, s.stream));
-			dense_top_clear_rhs_row(s.d_Zd_work.p(), s.n_dense_pad, s.stream);
-			dense_inverse_from_factor(s.d_Zd_work.p(), s.n_dense_pad, s.d_dense_invdiag.p(), s.d_Zd.p(), s.stream);
-		}
-		sparse_inverse_enqueue(*s.p_sinv, P, s.d_L.p(), s.d_Linv.p(), s.d_Z.p(), s.stream, s.d_Zd.p(), s.n_dense_pad);
-		s.Phase_End();
 		if(P.uniform_dim)
 			inverse_diag_blocks_launch(P.n, P.max_dim, s.d_diag_zoff.p(), s.d_Z.p(), s.d_Zd.p(), s.n_dense_pad, p_block_diag_dev, s.stream);
 		else
@@ -1094,6 +1111,177 @@ int slampp_hip_marginals(slampp_hip_solver *p_solver, const double *p_values, do
 			SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
 			return SLAMPP_HIP_OK;
 		});
+	}
+	return n_result;
+}
+
+namespace {
+
+// the checks the covariance calls beyond the block diagonal share (inside guarded())
+int covariance_checks(slampp_hip_solver *p_solver, const char *p_s_name)
+{
+	slampp_hip_solver &s = *p_solver;
+	const std::string s_name(p_s_name);
+	if(!s.b_analyzed)
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, (s_name + ": analyze was not called").c_str());
+	if(s.n_mode != SLAMPP_HIP_MODE_SPARSE)
+		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, (s_name + ": sparse mode only (Schur mode: slampp_hip_schur_marginals)").c_str());
+	if(!s.group_devices.empty())
+		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, (s_name + ": not for a handle over several devices").c_str());
+	if(s.b_refined)
+		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, (s_name + ": block columns wider than 8 are factored in pieces: no covariance blocks in the caller's layout").c_str());
+	return SLAMPP_HIP_OK;
+}
+
+// n_cols distinct block columns in range; their scalar count in *p_k
+int columns_checks(slampp_hip_solver *p_solver, int n_cols, const int64_t *p_bcols, int64_t *p_k)
+{
+	slampp_hip_solver &s = *p_solver;
+	if(n_cols <= 0 || !p_bcols)
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_columns: no columns");
+	const int64_t n_bcols = int64_t(s.cumsum.size()) - 1;
+	std::vector<int64_t> sorted(p_bcols, p_bcols + n_cols);
+	std::sort(sorted.begin(), sorted.end());
+	if(sorted.front() < 0 || sorted.back() >= n_bcols)
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_columns: block column index out of range");
+	if(std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_columns: a block column is listed twice");
+	*p_k = 0;
+	for(int i = 0; i < n_cols; ++ i)
+		*p_k += s.cumsum[size_t(p_bcols[i] + 1)] - s.cumsum[size_t(p_bcols[i])];
+	return SLAMPP_HIP_OK;
+}
+
+} // anonymous namespace
+
+int slampp_hip_marginals_pattern_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, double *p_cov_dev)
+{
+	return guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		int n_result = covariance_checks(p_solver, "marginals_pattern");
+		if(n_result != SLAMPP_HIP_OK)
+			return n_result;
+		if(!p_values_dev || !p_cov_dev)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginals_pattern: null pointer");
+		n_result = enqueue_sparse_inverse(p_solver, p_values_dev, "marginals_pattern");
+		if(n_result != SLAMPP_HIP_OK)
+			return n_result;
+		covariance_pattern_enqueue(s, p_cov_dev);
+		s.b_factored = true; // the factor of these values is in place
+		return SLAMPP_HIP_OK;
+	});
+}
+
+int slampp_hip_marginals_pattern(slampp_hip_solver *p_solver, const double *p_values, double *p_cov)
+{
+	int n_result = guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		const int n_check = covariance_checks(p_solver, "marginals_pattern");
+		if(n_check != SLAMPP_HIP_OK)
+			return n_check;
+		if(!p_values || !p_cov)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginals_pattern: null pointer");
+		s.d_A.Alloc(size_t(s.n_values));
+		s.d_cov.Alloc(size_t(s.n_values));
+		Upload_Values_And_Join(s, p_values);
+		return SLAMPP_HIP_OK;
+	});
+	if(n_result != SLAMPP_HIP_OK)
+		return n_result;
+	slampp_hip_solver &s = *p_solver;
+	n_result = slampp_hip_marginals_pattern_device_async(p_solver, s.d_A.p(), s.d_cov.p());
+	if(n_result == SLAMPP_HIP_OK)
+		n_result = slampp_hip_sync(p_solver);
+	if(n_result == SLAMPP_HIP_OK) {
+		n_result = guarded(p_solver, [&]() -> int {
+			SLAMPP_HIP_CHECK(hipMemcpyAsync(p_cov, s.d_cov.p(), size_t(s.n_values) * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+			SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
+			return SLAMPP_HIP_OK;
+		});
+	}
+	return n_result;
+}
+
+int slampp_hip_marginal_columns_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, int n_cols,
+	const int64_t *p_bcols, double *p_out_dev)
+{
+	return guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		int n_result = covariance_checks(p_solver, "marginal_columns");
+		if(n_result != SLAMPP_HIP_OK)
+			return n_result;
+		if(!p_out_dev)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_columns: null pointer");
+		int64_t n_k = 0;
+		if((n_result = columns_checks(p_solver, n_cols, p_bcols, &n_k)) != SLAMPP_HIP_OK)
+			return n_result;
+		if(p_values_dev) { // factor these values (the fused forward substitution runs on zeros)
+			s.d_rhs.Alloc(size_t(s.n_scalars));
+			SLAMPP_HIP_CHECK(hipMemsetAsync(s.d_rhs.p(), 0, size_t(s.n_scalars) * sizeof(double), s.stream));
+			s.b_leaf_linv_wanted = true;
+			s.Enqueue_Sparse(p_values_dev, s.d_rhs.p(), true, s.n_dense_dim == 0);
+			s.b_factored = true;
+		} else if(!s.b_factored)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_columns: no valid factorization to reuse (values = NULL)");
+		s.Ensure_Leaf_Inverses(); // (the substitutions multiply by inv(L_jj) of every column)
+		covariance_columns_enqueue(s, n_cols, p_bcols, p_out_dev);
+		return SLAMPP_HIP_OK;
+	});
+}
+
+int slampp_hip_marginal_columns(slampp_hip_solver *p_solver, const double *p_values, int n_cols, const int64_t *p_bcols,
+	double *p_out)
+{
+	int64_t n_k = 0;
+	int n_result = guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		int n_check = covariance_checks(p_solver, "marginal_columns");
+		if(n_check != SLAMPP_HIP_OK)
+			return n_check;
+		if(!p_out)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_columns: null pointer");
+		if((n_check = columns_checks(p_solver, n_cols, p_bcols, &n_k)) != SLAMPP_HIP_OK)
+			return n_check;
+		if(!p_values && !s.b_factored)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_columns: no valid factorization to reuse (values = NULL)");
+		s.d_cov.Alloc(size_t(s.n_scalars) * COV_K_PASS);
+		if(p_values) {
+			s.d_A.Alloc(size_t(s.n_values));
+			Upload_Values_And_Join(s, p_values);
+		}
+		return SLAMPP_HIP_OK;
+	});
+	if(n_result != SLAMPP_HIP_OK)
+		return n_result;
+	// groups of whole block columns of at most COV_K_PASS scalar columns, each brought back behind its solve: the device
+	// holds n_scalars x COV_K_PASS of the result at a time, whatever k is
+	slampp_hip_solver &s = *p_solver;
+	const double *p_values_dev = p_values? s.d_A.p() : 0;
+	int64_t n_done = 0;
+	for(int i = 0; i < n_cols && n_result == SLAMPP_HIP_OK;) {
+		int n_group = 0;
+		int64_t n_group_k = 0;
+		while(i + n_group < n_cols) {
+			const int64_t c = p_bcols[i + n_group], d = s.cumsum[size_t(c + 1)] - s.cumsum[size_t(c)];
+			if(n_group && n_group_k + d > COV_K_PASS)
+				break;
+			n_group_k += d;
+			++ n_group;
+		}
+		n_result = slampp_hip_marginal_columns_device_async(p_solver, p_values_dev, n_group, p_bcols + i, s.d_cov.p());
+		p_values_dev = 0; // (the next groups reuse this factor)
+		if(n_result == SLAMPP_HIP_OK)
+			n_result = slampp_hip_sync(p_solver);
+		if(n_result == SLAMPP_HIP_OK) {
+			n_result = guarded(p_solver, [&]() -> int {
+				SLAMPP_HIP_CHECK(hipMemcpyAsync(p_out + size_t(n_done) * size_t(s.n_scalars), s.d_cov.p(), size_t(n_group_k) *
+					size_t(s.n_scalars) * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+				SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
+				return SLAMPP_HIP_OK;
+			});
+		}
+		n_done += n_group_k;
+		i += n_group;
 	}
 	return n_result;
 }

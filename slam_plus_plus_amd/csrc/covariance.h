@@ -1,0 +1,31 @@
+// covariance.h -- covariances beyond the block diagonal (covariance.hip): Lambda^-1 on Lambda's own block pattern, and
+// whole block columns of Lambda^-1 by multi-right-hand-side triangular solves with the factor in place
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+struct slampp_hip_solver;
+
+namespace slampp {
+
+struct CCovariance;
+
+// scalar columns of one pass of slampp_hip_marginal_columns: the workspace is n_scalars x COV_K_PASS doubles.  48 = eight
+// 6 x 6 block columns (or six 8 x 8 ones) in one pass; a lane of a wave per right-hand side, 48 of its 64 lanes busy
+enum { COV_K_PASS = 48 };
+
+void covariance_destroy(CCovariance *p);
+size_t covariance_bytes(const CCovariance *p);
+
+// Lambda^-1 at every stored (upper) block of Lambda, in the layout of Lambda's packed values, from the sparse inverse
+// subset Z (laid out like L) and -- with a dense top -- the dense inverse of the top's Schur complement Zd (lower
+// triangle and diagonal tiles valid, leading dimension s.n_dense_pad).  Builds its gather records at the first call
+// (Lambda's pattern lies inside the factor's: checked there, on the host).  Throws.
+void covariance_pattern_enqueue(slampp_hip_solver &s, double *p_out_dev);
+
+// block columns p_bcols[0 .. n_cols) (caller's order, distinct, in range: checked by the caller) of Lambda^-1 from the factor
+// in place (d_L, d_Linv of every column, the dense top's factor and inverted diagonal tiles): p_out_dev is n_scalars x k,
+// column-major, rows in the caller's scalar order, k = the sum of the columns' dimensions.  Throws.
+void covariance_columns_enqueue(slampp_hip_solver &s, int n_cols, const int64_t *p_bcols, double *p_out_dev);
+
+} // namespace slampp

@@ -1,0 +1,615 @@
+// covariance.hip -- covariances beyond the block diagonal: the reference's CMarginals parts other than mpart_Diagonal
+// (include/slam/IncrementalPolicy.h:366-372: mpart_LastBlock, mpart_Column, mpart_LastColumn, mpart_FullMatrix).
+//
+// Pattern gather.  The sparse inverse subset (sparse_inverse.hip) leaves Z = Lambda^-1 on the whole filled pattern of L,
+// the dense top's part in the dense inverse of its Schur complement.  Lambda's pattern lies inside L's for every ordering,
+// so Lambda^-1 at Lambda's stored blocks is a gather: one 16-byte record per upper block (r, c) says where block
+// (max, min) of the permuted pair lives in Z, whether it is read transposed, and where the block goes in the output.
+//
+// Block columns.  A block column J of Lambda^-1 solves L L^T X = P E_J.  The forward substitution is pruned: the
+// right-hand side is nonzero on J's rows only, so y is nonzero only on J's path to the root of the elimination tree (the
+// union of the paths for several columns).  The host lists those columns per pass, stage by stage, each with the row
+// entries L(j,c) whose c is on the paths too; one wave per task of a stage walks its listed columns with all k
+// right-hand sides at once (lane = right-hand side), each L block loaded once for the k of them.  The backward
+// substitution covers every column (x is dense), the factorization's stages in reverse, one wave per task, and scatters
+// x to the caller's order as each column is finished.  With a dense top, the listed dense-top columns only subtract
+// their rows' products from the right-hand side (into a buffer of their own, n_dense_pad x k); tile-by-tile k-column
+// triangular solves on the top's factor and its inverted diagonal tiles follow, the backward one writing the top's x
+// where the block columns below read it.
+//
+// Workspace X: n_scalars x k, interleaved -- the k values of a scalar row next to each other (X[row * k + c]): a lane per
+// right-hand side then reads and writes a block's rows as whole contiguous lines (d x k doubles), where a column stride of
+// n_scalars would make every lane of a wave touch a line of its own.  Rows of the permuted order (Plan::cs_new).  Which
+// rows the pruned forward wrote in this pass is told by a stamp per column (d_mark): the backward substitution reads y_j
+// only there, zero elsewhere -- no clearing of n_scalars x k doubles per pass.
+#include <hip/hip_runtime.h>
+#include "covariance.h"
+#include "solver.h"
+#include "sparse_inverse.h"
+
+#include <algorithm>
+#include <climits>
+
+namespace slampp {
+
+struct TCovGather { // 16 B
+	int64_t src; // >= 0: offset of the stored block of Z; < 0: -1 - (pos_r << 24 | pos_c), element-wise from the dense top's inverse
+	int64_t out; // output offset << 9 | d_r << 5 | d_c << 1 | read transposed
+};
+
+struct TCovFwd { // 40 B: one listed column of the pruned forward substitution
+	int64_t linv_off; // inv(L_jj)
+	int64_t e0;       // first of its filtered row entries
+	int32_t ne, dj;
+	int32_t ycs;      // scalar offset in the permuted workspace
+	int32_t bcol;     // right-hand side c of this pass has its 1 in row c - bcol of this column (if 0 <= c - bcol < dj)
+	int32_t dpos;     // dense top: position in the dense system (the column's reduced right-hand side goes there), else -1
+	int32_t s;        // schedule index (the stamp goes there)
+};
+
+struct CCovariance {
+	// pattern gather
+	bool b_gather = false;
+	int64_t n_gather = 0;
+	int n_gather_dim = 0; // 3 / 6 / 7: every block is D x D; 0: any sizes up to 8
+	CDevArray<TCovGather> d_gather;
+	// block columns
+	bool b_columns = false;
+	std::vector<int32_t> sched_pos;   // [n] schedule index of column j (new order), -1 in the dense top
+	std::vector<int32_t> sched_task;  // [n_sched] task of a schedule index
+	std::vector<int32_t> task_stage;  // [n_tasks]
+	std::vector<int32_t> host_mark, host_bcol;
+	int32_t n_host_stamp = 0;
+	CDevArray<double> d_X, d_Bd, d_Zb;
+	CDevArray<int32_t> d_mark;
+	int32_t n_stamp = 0;
+	// what one call lists: the uploads from these vectors are asynchronous, so a call refills them only once the previous
+	// call's uploads have completed (ev_lists, recorded behind them on the handle's stream)
+	hipEvent_t ev_lists = 0;
+	std::vector<TCovFwd> fwd;
+	std::vector<TRowEnt> ents;
+	std::vector<int32_t> seg; // segment b: fwd[seg[b] .. seg[b + 1]), the listed columns of one task
+	CDevArray<TCovFwd> d_fwd;
+	CDevArray<TRowEnt> d_ents;
+	CDevArray<int32_t> d_seg;
+	~CCovariance() { if(ev_lists) (void)hipEventDestroy(ev_lists); }
+};
+
+void covariance_destroy(CCovariance *p) { delete p; }
+
+size_t covariance_bytes(const CCovariance *p)
+{
+	return p? p->d_gather.n_Bytes() + p->d_X.n_Bytes() + p->d_Bd.n_Bytes() + p->d_Zb.n_Bytes() + p->d_mark.n_Bytes() +
+		p->d_fwd.n_Bytes() + p->d_ents.n_Bytes() + p->d_seg.n_Bytes() : 0;
+}
+
+// ---- pattern gather ----
+
+__device__ __forceinline__ double cov_gather_value(const TCovGather &g, int a, int b, int dr, int dc, const double *__restrict__ Z,
+	const double *__restrict__ Zd, int ld)
+{
+	if(g.src >= 0)
+		return (g.out & 1)? Z[g.src + b + int64_t(a) * dc] : Z[g.src + a + int64_t(b) * dr];
+	const int64_t code = -1 - g.src;
+	const int64_t pa = (code >> 24) + a, pb = (code & 0xffffff) + b;
+	return Zd[((pa > pb)? pa : pb) + ((pa > pb)? pb : pa) * int64_t(ld)];
+}
+
+// every block D x D: a thread per output element, the output streamed in order
+template <int D>
+__global__ void __launch_bounds__(256)
+cov_gather_kernel(int64_t n_blocks, const TCovGather *__restrict__ recs, const double *__restrict__ Z, const double *__restrict__ Zd,
+	int ld, double *__restrict__ out)
+{
+	const int64_t gid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+	if(gid >= n_blocks * (D * D))
+		return;
+	const int64_t blk = gid / (D * D);
+	const int e = int(gid - blk * (D * D)), a = e % D, b = e / D;
+	const TCovGather g = recs[blk];
+	out[gid] = cov_gather_value(g, a, b, D, D, Z, Zd, ld);
+}
+
+// any block sizes up to 8: a wave per block
+__global__ void __launch_bounds__(256)
+cov_gather_any_kernel(int64_t n_blocks, const TCovGather *__restrict__ recs, const double *__restrict__ Z, const double *__restrict__ Zd,
+	int ld, double *__restrict__ out)
+{
+	const int64_t blk = int64_t(blockIdx.x) * (blockDim.x / 64) + threadIdx.x / 64;
+	const int e = threadIdx.x & 63;
+	if(blk >= n_blocks)
+		return;
+	const TCovGather g = recs[blk];
+	const int dr = int(g.out >> 5) & 15, dc = int(g.out >> 1) & 15;
+	if(e < dr * dc)
+		out[(g.out >> 9) + e] = cov_gather_value(g, e % dr, e / dr, dr, dc, Z, Zd, ld);
+}
+
+static void Setup_Gather(slampp_hip_solver &s, CCovariance &cv)
+{
+	const Plan &P = s.plan;
+	const int64_t n_bcols = int64_t(s.cumsum.size()) - 1;
+	const int64_t n_blocks = s.bcol_ptr[size_t(n_bcols)];
+	std::vector<TCovGather> recs(static_cast<size_t>(n_blocks));
+	bool b_all_same = P.uniform_dim && (P.max_dim == 3 || P.max_dim == 6 || P.max_dim == 7);
+	int64_t n_out = 0;
+	for(int64_t C = 0; C < n_bcols; ++ C) {
+		const int32_t j = P.pinv[size_t(C)];
+		const int dc = int(s.cumsum[C + 1] - s.cumsum[C]);
+		for(int64_t b = s.bcol_ptr[size_t(C)]; b < s.bcol_ptr[size_t(C + 1)]; ++ b) {
+			const int32_t R = s.brow[size_t(b)], i = P.pinv[size_t(R)];
+			const int dr = int(s.cumsum[R + 1] - s.cumsum[R]);
+			TCovGather &g = recs[size_t(b)];
+			int64_t n_trans = 0;
+			if(P.dense_dim && P.dense_pos[i] >= 0 && P.dense_pos[j] >= 0)
+				g.src = -1 - ((int64_t(P.dense_pos[i]) << 24) | int64_t(P.dense_pos[j]));
+			else {
+				// Lambda's pattern lies inside the filled pattern of L, whatever the ordering: checked here, once
+				g.src = plan_block_offset(P, std::max(i, j), std::min(i, j));
+				if(g.src < 0)
+					throw std::logic_error("marginals_pattern: a block of Lambda is outside the pattern of its factor");
+				n_trans = i < j;
+			}
+			g.out = (n_out << 9) | (int64_t(dr) << 5) | (int64_t(dc) << 1) | n_trans;
+			n_out += int64_t(dr) * dc;
+		}
+	}
+	cv.d_gather.Upload(recs, s.stream);
+	SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream)); // recs lives in this scope
+	cv.n_gather = n_blocks;
+	cv.n_gather_dim = b_all_same? P.max_dim : 0;
+	cv.b_gather = true;
+}
+
+static CCovariance &Covariance_State(slampp_hip_solver &s)
+{
+	if(!s.p_cov)
+		s.p_cov = new CCovariance();
+	return *s.p_cov;
+}
+
+void covariance_pattern_enqueue(slampp_hip_solver &s, double *p_out_dev)
+{
+	CCovariance &cv = Covariance_State(s);
+	if(!cv.b_gather)
+		Setup_Gather(s, cv);
+	if(!cv.n_gather)
+		return;
+	const double *Z = s.d_Z.p(), *Zd = s.d_Zd.p();
+	const int ld = s.n_dense_pad;
+	switch(cv.n_gather_dim) {
+#define COV_GATHER(DD) case DD: hipLaunchKernelGGL(cov_gather_kernel<DD>, dim3(unsigned((cv.n_gather * (DD * DD) + 255) / 256)), dim3(256), 0, s.stream, \
+		cv.n_gather, cv.d_gather.p(), Z, Zd, ld, p_out_dev); break;
+	COV_GATHER(3)
+	COV_GATHER(6)
+	COV_GATHER(7)
+#undef COV_GATHER
+	default:
+		hipLaunchKernelGGL(cov_gather_any_kernel, dim3(unsigned((cv.n_gather + 3) / 4)), dim3(256), 0, s.stream, cv.n_gather,
+			cv.d_gather.p(), Z, Zd, ld, p_out_dev);
+	}
+	SLAMPP_HIP_CHECK(hipGetLastError());
+}
+
+// ---- block columns: pruned k-column forward substitution ----
+
+// one workgroup (one wave) per segment: the listed columns of one task, in order; lane c = right-hand side c
+template <int D>
+__global__ void __launch_bounds__(64)
+cov_forward_kernel(const int32_t *__restrict__ seg, int seg_begin, const TCovFwd *__restrict__ fwd, const TRowEnt *__restrict__ ents,
+	const double *__restrict__ L, const double *__restrict__ Linv, double *X, int kp, int32_t *mark, int32_t n_stamp,
+	double *Bd)
+{
+	constexpr int DM = D? D : 8;
+	const int c = threadIdx.x;
+	const bool b_act = c < kp;
+	const int sg = seg_begin + blockIdx.x;
+	for(int32_t f = seg[sg]; f < seg[sg + 1]; ++ f) {
+		const TCovFwd rec = fwd[f];
+		const int dj = D? D : rec.dj;
+		double acc[DM];
+		#pragma unroll
+		for(int r = 0; r < DM; ++ r)
+			acc[r] = (c - rec.bcol == r)? 1.0 : 0.0; // the right-hand side's block: P E_J
+		for(int64_t e = rec.e0; e < rec.e0 + rec.ne; ++ e) {
+			const TRowEnt t_e = ents[e];
+			const int dc = D? D : t_e.dc;
+			const double *Lb = L + t_e.off; // L(j,c): dj x dc
+			#pragma unroll
+			for(int t = 0; t < DM; ++ t) {
+				if(t < dc) {
+					const double yv = b_act? X[int64_t(t_e.ycs + t) * kp + c] : 0.0;
+					#pragma unroll
+					for(int r = 0; r < DM; ++ r) {
+						if(r < dj)
+							acc[r] -= Lb[r + t * dj] * yv;
+					}
+				}
+			}
+		}
+		if(rec.dpos >= 0) { // a dense-top column: its reduced right-hand side, for the dense solve
+			#pragma unroll
+			for(int r = 0; r < DM; ++ r) {
+				if(r < dj && b_act)
+					Bd[int64_t(rec.dpos + r) * kp + c] = acc[r];
+			}
+			continue;
+		}
+		const double *iL = Linv + rec.linv_off;
+		#pragma unroll
+		for(int r = 0; r < DM; ++ r) {
+			if(r < dj) {
+				double y = 0;
+				#pragma unroll
+				for(int t = 0; t < DM; ++ t) {
+					if(t < dj)
+						y += iL[r + t * dj] * acc[t];
+				}
+				if(b_act)
+					X[int64_t(rec.ycs + r) * kp + c] = y; // (read later by this very lane only: no barrier)
+			}
+		}
+		if(c == 0)
+			mark[rec.s] = n_stamp;
+	}
+}
+
+// ---- block columns: k-column backward substitution over all stages ----
+
+// one wave per task, its columns last to first (as backward_stage_kernel); x_j = inv(L_jj)^T (y_j - sum L(i,j)^T x_i)
+template <int D>
+__global__ void __launch_bounds__(64)
+cov_backward_kernel(const TColDesc *__restrict__ cols, const TBlkDesc *__restrict__ blks, const int64_t *__restrict__ task_ptr,
+	int task_begin, const double *__restrict__ L, const double *__restrict__ Linv, double *X, int kp,
+	const int32_t *__restrict__ mark, int32_t n_stamp, double *__restrict__ out, int64_t n_scalars, int col0)
+{
+	constexpr int DM = D? D : 8;
+	const int c = threadIdx.x;
+	const bool b_act = c < kp;
+	const int task = task_begin + blockIdx.x;
+	for(int64_t sc = task_ptr[task + 1] - 1; sc >= task_ptr[task]; -- sc) {
+		const TColDesc cd = cols[sc];
+		const int dj = D? D : cd.dj;
+		const bool b_y = mark[sc] == n_stamp; // the pruned forward substitution wrote y_j in this pass
+		double acc[DM];
+		#pragma unroll
+		for(int r = 0; r < DM; ++ r)
+			acc[r] = (r < dj && b_y && b_act)? X[(cd.cs_new + r) * kp + c] : 0.0;
+		for(int64_t b = cd.k0 + 1; b < cd.k0 + cd.nb; ++ b) {
+			const TBlkDesc bd = blks[b];
+			const int di = D? D : int(bd.np_di >> 24);
+			const double *Lb = L + bd.loff; // L(i,j): di x dj
+			#pragma unroll
+			for(int t = 0; t < DM; ++ t) {
+				if(t < di) {
+					const double xv = b_act? X[int64_t(bd.xcs + t) * kp + c] : 0.0;
+					#pragma unroll
+					for(int r = 0; r < DM; ++ r) {
+						if(r < dj)
+							acc[r] -= Lb[t + r * di] * xv;
+					}
+				}
+			}
+		}
+		const double *iL = Linv + cd.linv_off;
+		#pragma unroll
+		for(int r = 0; r < DM; ++ r) {
+			if(r < dj) {
+				double x = 0;
+				#pragma unroll
+				for(int t = 0; t < DM; ++ t) {
+					if(t < dj)
+						x += iL[t + r * dj] * acc[t];
+				}
+				if(b_act) {
+					X[(cd.cs_new + r) * kp + c] = x;
+					out[cd.cs_src + r + (int64_t(col0) + c) * n_scalars] = x;
+				}
+			}
+		}
+	}
+}
+
+// ---- block columns: the dense top, k columns, tile by tile ----
+
+enum { COV_NB = 64 };
+
+// forward step of tile column t: every workgroup forms z_t = inv(L_tt) b_t itself; workgroup 0 publishes it, workgroup
+// g > 0 subtracts L(t + g, t) z_t from b_{t + g}.  Positions >= n (padding, the right-hand side row of the factor) are zero.
+__global__ void __launch_bounds__(256)
+cov_dense_forward_kernel(const double *__restrict__ M, int ld, int n, int t, const double *__restrict__ invdiag, double *Bd,
+	double *Zb, int kp)
+{
+	__shared__ double s_b[COV_NB * COV_K_PASS], s_z[COV_NB * COV_K_PASS];
+	const int ne = COV_NB * kp, t0 = t * COV_NB;
+	for(int e = threadIdx.x; e < ne; e += blockDim.x) {
+		const int i = e / kp, c = e - i * kp;
+		s_b[e] = (t0 + i < n)? Bd[int64_t(t0 + i) * kp + c] : 0.0;
+	}
+	__syncthreads();
+	const double *iL = invdiag + size_t(t) * COV_NB * COV_NB;
+	for(int e = threadIdx.x; e < ne; e += blockDim.x) {
+		const int i = e / kp, c = e - i * kp;
+		double z = 0;
+		if(t0 + i < n) {
+			for(int q = 0; q <= i; ++ q)
+				z += iL[i + q * COV_NB] * s_b[q * kp + c];
+		}
+		s_z[e] = z;
+	}
+	__syncthreads();
+	if(blockIdx.x == 0) {
+		for(int e = threadIdx.x; e < ne; e += blockDim.x) {
+			const int i = e / kp, c = e - i * kp;
+			Zb[int64_t(t0 + i) * kp + c] = s_z[e];
+		}
+		return;
+	}
+	const int g0 = (t + int(blockIdx.x)) * COV_NB;
+	const int n_q = (n - t0 < COV_NB)? n - t0 : int(COV_NB);
+	for(int e = threadIdx.x; e < ne; e += blockDim.x) {
+		const int i = e / kp, c = e - i * kp;
+		if(g0 + i >= n)
+			continue;
+		const double *Mr = M + (g0 + i) + size_t(t0) * ld;
+		double acc = 0;
+		for(int q = 0; q < n_q; ++ q)
+			acc += Mr[size_t(q) * ld] * s_z[q * kp + c];
+		Bd[int64_t(g0 + i) * kp + c] -= acc;
+	}
+}
+
+// backward step of tile column t: every workgroup forms x_t = inv(L_tt)^T z_t itself; workgroup t stores it (into X at the
+// column's permuted rows, and into the output at the caller's), workgroup g < t subtracts L(t, g)^T x_t from z_g
+__global__ void __launch_bounds__(256)
+cov_dense_backward_kernel(const double *__restrict__ M, int ld, int n, int t, const double *__restrict__ invdiag, double *Zb, int kp,
+	const longlong2 *__restrict__ dst, double *X, double *out, int64_t n_scalars, int col0)
+{
+	__shared__ double s_z[COV_NB * COV_K_PASS], s_x[COV_NB * COV_K_PASS];
+	const int ne = COV_NB * kp, t0 = t * COV_NB;
+	const int n_q = (n - t0 < COV_NB)? n - t0 : int(COV_NB);
+	for(int e = threadIdx.x; e < ne; e += blockDim.x) {
+		const int i = e / kp, c = e - i * kp;
+		s_z[e] = (t0 + i < n)? Zb[int64_t(t0 + i) * kp + c] : 0.0;
+	}
+	__syncthreads();
+	const double *iL = invdiag + size_t(t) * COV_NB * COV_NB;
+	for(int e = threadIdx.x; e < ne; e += blockDim.x) {
+		const int i = e / kp, c = e - i * kp;
+		double x = 0;
+		for(int q = i; q < n_q; ++ q)
+			x += iL[q + i * COV_NB] * s_z[q * kp + c];
+		s_x[e] = x;
+	}
+	__syncthreads();
+	if(int(blockIdx.x) == t) {
+		for(int e = threadIdx.x; e < ne; e += blockDim.x) {
+			const int i = e / kp, c = e - i * kp;
+			if(t0 + i >= n)
+				continue;
+			const longlong2 d = dst[t0 + i];
+			if(d.x >= 0) {
+				X[d.x * kp + c] = s_x[e];
+				out[d.y + (int64_t(col0) + c) * n_scalars] = s_x[e];
+			}
+		}
+		return;
+	}
+	const int g0 = int(blockIdx.x) * COV_NB;
+	for(int e = threadIdx.x; e < ne; e += blockDim.x) {
+		const int i = e / kp, c = e - i * kp;
+		if(g0 + i >= n)
+			continue;
+		const double *Mc = M + t0 + size_t(g0 + i) * ld; // column g0 + i of L, rows t0 ..
+		double acc = 0;
+		for(int q = 0; q < n_q; ++ q)
+			acc += Mc[q] * s_x[q * kp + c];
+		Zb[int64_t(g0 + i) * kp + c] -= acc;
+	}
+}
+
+static void Setup_Columns(slampp_hip_solver &s, CCovariance &cv)
+{
+	const Plan &P = s.plan;
+	const int64_t n_sched = int64_t(P.task_cols.size());
+	const int n_tasks = int(P.task_ptr.size()) - 1, n_stages = int(P.stage_ptr.size()) - 1;
+	cv.sched_pos.assign(size_t(P.n), -1);
+	cv.sched_task.assign(size_t(n_sched), 0);
+	cv.task_stage.assign(size_t(std::max(n_tasks, 0)), 0);
+	for(int64_t sc = 0; sc < n_sched; ++ sc)
+		cv.sched_pos[size_t(P.task_cols[size_t(sc)])] = int32_t(sc);
+	for(int t = 0; t < n_tasks; ++ t) {
+		for(int64_t sc = P.task_ptr[size_t(t)]; sc < P.task_ptr[size_t(t + 1)]; ++ sc)
+			cv.sched_task[size_t(sc)] = t;
+	}
+	for(int st = 0; st < n_stages; ++ st) {
+		for(int t = P.stage_ptr[size_t(st)]; t < P.stage_ptr[size_t(st + 1)]; ++ t)
+			cv.task_stage[size_t(t)] = st;
+	}
+	cv.host_mark.assign(size_t(P.n), 0);
+	cv.host_bcol.assign(size_t(P.n), INT_MIN / 2);
+	cv.n_host_stamp = 0;
+	cv.d_X.Alloc(size_t(s.n_scalars) * COV_K_PASS);
+	cv.d_mark.Alloc(size_t(std::max<int64_t>(n_sched, 1)));
+	SLAMPP_HIP_CHECK(hipMemsetAsync(cv.d_mark.p(), 0, cv.d_mark.n_Bytes(), s.stream));
+	cv.n_stamp = 0;
+	if(s.n_dense_dim) {
+		cv.d_Bd.Alloc(size_t(s.n_dense_pad) * COV_K_PASS);
+		cv.d_Zb.Alloc(size_t(s.n_dense_pad) * COV_K_PASS);
+	}
+	cv.b_columns = true;
+}
+
+namespace {
+struct TCovLaunch {
+	int n_stage;       // -1: the dense-top columns
+	int seg0, seg1;
+};
+struct TCovPass {
+	int col0, kp;
+	std::vector<TCovLaunch> launches;
+};
+} // anonymous namespace
+
+void covariance_columns_enqueue(slampp_hip_solver &s, int n_cols, const int64_t *p_bcols, double *p_out_dev)
+{
+	const Plan &P = s.plan;
+	CCovariance &cv = Covariance_State(s);
+	if(!cv.b_columns)
+		Setup_Columns(s, cv);
+	int64_t k = 0;
+	std::vector<int64_t> col_off(size_t(n_cols) + 1, 0);
+	for(int i = 0; i < n_cols; ++ i) {
+		col_off[size_t(i)] = k;
+		k += s.cumsum[size_t(p_bcols[i] + 1)] - s.cumsum[size_t(p_bcols[i])];
+	}
+	col_off[size_t(n_cols)] = k;
+	if(k > int64_t(INT_MAX))
+		throw std::invalid_argument("marginal_columns: too many columns");
+	// the lists of every pass, built before anything is enqueued (one upload)
+	if(cv.ev_lists)
+		SLAMPP_HIP_CHECK(hipEventSynchronize(cv.ev_lists)); // (the previous call's uploads out of these vectors are over)
+	cv.fwd.clear();
+	cv.ents.clear();
+	cv.seg.assign(1, 0);
+	std::vector<TCovPass> passes;
+	std::vector<int32_t> reach, dense_reach;
+	for(int64_t col0 = 0; col0 < k; col0 += COV_K_PASS) {
+		TCovPass pass;
+		pass.col0 = int(col0);
+		pass.kp = int(std::min<int64_t>(COV_K_PASS, k - col0));
+		if(++ cv.n_host_stamp == INT_MAX) {
+			std::fill(cv.host_mark.begin(), cv.host_mark.end(), 0);
+			cv.n_host_stamp = 1;
+		}
+		const int32_t n_hs = cv.n_host_stamp;
+		reach.clear();
+		dense_reach.clear();
+		for(int i = 0; i < n_cols; ++ i) {
+			if(col_off[size_t(i) + 1] <= col0 || col_off[size_t(i)] >= col0 + pass.kp)
+				continue; // not in this pass
+			const int32_t j = P.pinv[size_t(p_bcols[i])];
+			cv.host_bcol[size_t(j)] = int32_t(col_off[size_t(i)] - col0);
+			for(int32_t x = j; x >= 0 && cv.host_mark[size_t(x)] != n_hs; x = P.parent[size_t(x)]) {
+				cv.host_mark[size_t(x)] = n_hs;
+				if(cv.sched_pos[size_t(x)] >= 0)
+					reach.push_back(x);
+				else
+					dense_reach.push_back(x);
+			}
+		}
+		std::sort(reach.begin(), reach.end(), [&](int32_t a, int32_t b) { return cv.sched_pos[size_t(a)] < cv.sched_pos[size_t(b)]; });
+		std::sort(dense_reach.begin(), dense_reach.end());
+		int n_cur_task = -1, n_cur_stage = -1;
+		for(int h = 0; h < 2; ++ h) { // the block-eliminated columns stage by stage, then the dense-top ones
+			const std::vector<int32_t> &r_list = h? dense_reach : reach;
+			for(size_t q = 0; q < r_list.size(); ++ q) {
+				const int32_t j = r_list[q];
+				const int32_t sc = cv.sched_pos[size_t(j)];
+				const int n_task = h? -2 - int(q) : cv.sched_task[size_t(sc)];
+				const int n_stage = h? -1 : cv.task_stage[size_t(n_task)];
+				if(n_task != n_cur_task) { // a segment of its own
+					if(n_cur_task != -1)
+						cv.seg.push_back(int32_t(cv.fwd.size()));
+					if(n_stage != n_cur_stage || pass.launches.empty()) {
+						TCovLaunch l = {n_stage, int(cv.seg.size()) - 1, int(cv.seg.size()) - 1};
+						pass.launches.push_back(l);
+					}
+					pass.launches.back().seg1 ++;
+					n_cur_task = n_task;
+					n_cur_stage = n_stage;
+				}
+				TCovFwd f;
+				f.linv_off = (sc >= 0)? P.linv_off[size_t(j)] : 0;
+				f.e0 = int64_t(cv.ents.size());
+				f.dj = P.dim[size_t(j)];
+				f.ycs = int32_t(P.cs_new[size_t(j)]);
+				f.bcol = cv.host_bcol[size_t(j)];
+				f.dpos = (sc >= 0)? -1 : P.dense_pos[size_t(j)];
+				f.s = std::max(sc, 0);
+				for(int64_t r = P.rptr[size_t(j)]; r < P.rptr[size_t(j) + 1]; ++ r) {
+					const int32_t b = P.rblk[size_t(r)], c = P.blk_col[size_t(b)];
+					if(cv.host_mark[size_t(c)] != n_hs || cv.sched_pos[size_t(c)] < 0)
+						continue; // y_c is zero in this pass, or c is in the dense top (its part is the dense solve's)
+					TRowEnt t_e;
+					t_e.off = P.loff[size_t(b)];
+					t_e.ycs = int32_t(P.cs_new[size_t(c)]);
+					t_e.dc = P.dim[size_t(c)];
+					cv.ents.push_back(t_e);
+				}
+				f.ne = int32_t(int64_t(cv.ents.size()) - f.e0);
+				cv.fwd.push_back(f);
+			}
+		}
+		if(n_cur_task != -1)
+			cv.seg.push_back(int32_t(cv.fwd.size()));
+		for(int i = 0; i < n_cols; ++ i)
+			cv.host_bcol[size_t(P.pinv[size_t(p_bcols[i])])] = INT_MIN / 2;
+		passes.push_back(pass);
+	}
+	if(cv.fwd.empty())
+		cv.fwd.resize(1); // (nothing listed: a record nobody reads, so that the uploads below have something to send)
+	if(cv.ents.empty())
+		cv.ents.resize(1);
+	cv.d_fwd.Upload(cv.fwd, s.stream);
+	cv.d_ents.Upload(cv.ents, s.stream);
+	cv.d_seg.Upload(cv.seg, s.stream);
+	if(!cv.ev_lists)
+		SLAMPP_HIP_CHECK(hipEventCreateWithFlags(&cv.ev_lists, hipEventDisableTiming));
+	SLAMPP_HIP_CHECK(hipEventRecord(cv.ev_lists, s.stream));
+	const int D = (P.uniform_dim && (P.max_dim == 3 || P.max_dim == 6 || P.max_dim == 7))? P.max_dim : 0;
+	const int n_stages = int(P.stage_ptr.size()) - 1;
+	const int ld = s.n_dense_pad, n_dense = s.n_dense_dim, n_tiles = ld / COV_NB;
+	s.Phase_Begin("marginal_columns");
+	for(size_t p = 0; p < passes.size(); ++ p) {
+		const TCovPass &pass = passes[p];
+		const int kp = pass.kp;
+		if(++ cv.n_stamp == INT_MAX) {
+			SLAMPP_HIP_CHECK(hipMemsetAsync(cv.d_mark.p(), 0, cv.d_mark.n_Bytes(), s.stream));
+			cv.n_stamp = 1;
+		}
+		if(n_dense)
+			SLAMPP_HIP_CHECK(hipMemsetAsync(cv.d_Bd.p(), 0, size_t(ld) * kp * sizeof(double), s.stream));
+		for(size_t q = 0; q < pass.launches.size(); ++ q) {
+			const TCovLaunch &l = pass.launches[q];
+			const int n_blocks = l.seg1 - l.seg0;
+			const int DL = (l.n_stage < 0)? 0 : D; // (the dense-top columns' dimensions: any)
+#define COV_FWD(DD) hipLaunchKernelGGL(cov_forward_kernel<DD>, dim3(n_blocks), dim3(64), 0, s.stream, cv.d_seg.p(), l.seg0, cv.d_fwd.p(), \
+				cv.d_ents.p(), s.d_L.p(), s.d_Linv.p(), cv.d_X.p(), kp, cv.d_mark.p(), cv.n_stamp, cv.d_Bd.p())
+			switch(DL) {
+			case 3: COV_FWD(3); break;
+			case 6: COV_FWD(6); break;
+			case 7: COV_FWD(7); break;
+			default: COV_FWD(0); break;
+			}
+#undef COV_FWD
+		}
+		if(n_dense) {
+			for(int t = 0; t < n_tiles; ++ t)
+				hipLaunchKernelGGL(cov_dense_forward_kernel, dim3(n_tiles - t), dim3(256), 0, s.stream, s.d_dense.p(), ld, n_dense, t,
+					s.d_dense_invdiag.p(), cv.d_Bd.p(), cv.d_Zb.p(), kp);
+			for(int t = n_tiles - 1; t >= 0; -- t)
+				hipLaunchKernelGGL(cov_dense_backward_kernel, dim3(t + 1), dim3(256), 0, s.stream, s.d_dense.p(), ld, n_dense, t,
+					s.d_dense_invdiag.p(), cv.d_Zb.p(), kp, s.d_dense_dst.p(), cv.d_X.p(), p_out_dev, s.n_scalars, pass.col0);
+		}
+		for(int st = n_stages - 1; st >= 0; -- st) {
+			const int n_tasks = P.stage_ptr[size_t(st + 1)] - P.stage_ptr[size_t(st)];
+			if(n_tasks <= 0)
+				continue;
+#define COV_BWD(DD) hipLaunchKernelGGL(cov_backward_kernel<DD>, dim3(n_tasks), dim3(64), 0, s.stream, s.dplan.cols, s.dplan.blks, \
+				s.dplan.task_ptr, P.stage_ptr[size_t(st)], s.d_L.p(), s.d_Linv.p(), cv.d_X.p(), kp, cv.d_mark.p(), cv.n_stamp, p_out_dev, \
+				s.n_scalars, pass.col0)
+			switch(D) {
+			case 3: COV_BWD(3); break;
+			case 6: COV_BWD(6); break;
+			case 7: COV_BWD(7); break;
+			default: COV_BWD(0); break;
+			}
+#undef COV_BWD
+		}
+	}
+	s.Phase_End();
+	SLAMPP_HIP_CHECK(hipGetLastError());
+}
+
+} // namespace slampp

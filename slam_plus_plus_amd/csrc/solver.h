@@ -144,6 +144,7 @@ struct CKeepDeviceMemory {
 struct CSchurState; // schur.hip
 struct CDeviceGroup; // group.hip
 struct CSparseInverse; // sparse_inverse.hip
+struct CCovariance; // covariance.hip
 struct CAssemblyState; // assembly.hip
 
 } // namespace slampp
@@ -277,6 +278,7 @@ struct slampp_hip_solver {
 	slampp::CDevArray<double> d_A, d_rhs, d_L, d_Linv, d_w, d_cov;
 	slampp::CSparseInverse *p_sinv = 0;    // sparse path: lists of the sparse inverse subset (slampp_hip_marginals), built on first use
 	bool b_sinv_tried = false;
+	slampp::CCovariance *p_cov = 0;       // sparse path: gather records of marginals_pattern and the workspaces of marginal_columns, built on first use
 	slampp::CDevArray<double> d_Z;         // laid out like d_L
 	slampp::CDevArray<double> d_Zd, d_Zd_work; // inverse of the dense top's Schur complement, and the copy of its factor that gets inverted
 	slampp::CDevArray<int64_t> d_diag_zoff; // offset of every block column's diagonal block in it, original order

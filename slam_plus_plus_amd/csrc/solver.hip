@@ -11,6 +11,7 @@
 #include <unordered_map>
 #include <sys/mman.h>
 #include "sparse_inverse.h"
+#include "covariance.h"
 
 #include <algorithm>
 #include <atomic>
@@ -185,6 +186,10 @@ void slampp_hip_solver::Free_Device()
 		p_sinv = 0;
 	}
 	b_sinv_tried = false;
+	if(p_cov) {
+		covariance_destroy(p_cov);
+		p_cov = 0;
+	}
 	d_Z.Free(); d_diag_zoff.Free(); d_diag_dim.Free(); d_diag_out_off.Free(); d_Zd.Free(); d_Zd_work.Free();
 	if(p_schur) {
 		schur_destroy(p_schur);
@@ -203,7 +208,7 @@ size_t slampp_hip_solver::n_Device_Bytes() const
 		d_simt_bwd_chunks.n_Bytes() + d_simt_bwd_prog.n_Bytes() + d_simt_bwd_tab.n_Bytes() +
 		d_panel_pkg.n_Bytes() + d_panel_off.n_Bytes() + d_panel_out_off.n_Bytes() + d_handup.n_Bytes() + d_panel_rest.n_Bytes() + d_panel_upd_slots.n_Bytes() + d_panel_upd_ents.n_Bytes() +
 		d_rhs.n_Bytes() + d_L.n_Bytes() + d_Linv.n_Bytes() + d_w.n_Bytes() + d_cov.n_Bytes() + d_flag.n_Bytes() +
-		d_Z.n_Bytes() + d_diag_zoff.n_Bytes() + d_Zd.n_Bytes() + d_Zd_work.n_Bytes() + sparse_inverse_bytes(p_sinv) +
+		d_Z.n_Bytes() + d_diag_zoff.n_Bytes() + d_Zd.n_Bytes() + d_Zd_work.n_Bytes() + sparse_inverse_bytes(p_sinv) + covariance_bytes(p_cov) +
 		(p_schur? schur_device_bytes(p_schur) : 0);
 }
 

@@ -122,6 +122,10 @@ ABI = {
     "slampp_hip_apply_damping_device_async": (C.c_int, [_P, _P, C.c_double, C.c_int64, C.c_int64]),
     "slampp_hip_marginals": (C.c_int, [_P, _P, _P]),
     "slampp_hip_marginals_device_async": (C.c_int, [_P, _P, _P]),
+    "slampp_hip_marginals_pattern": (C.c_int, [_P, _P, _P]),
+    "slampp_hip_marginals_pattern_device_async": (C.c_int, [_P, _P, _P]),
+    "slampp_hip_marginal_columns": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "slampp_hip_marginal_columns_device_async": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "slampp_hip_schur_marginals": (C.c_int, [_P, _P, _P, _P]),
     "slampp_hip_schur_marginals_device_async": (C.c_int, [_P, _P, _P, _P]),
     "slampp_hip_factor_solve_device_async": (C.c_int, [_P, _P, _P]),
@@ -564,6 +568,49 @@ def _block_diagonal_marginals(self, lam):
 
 
 CLinearSolver_HIP.Marginals = _block_diagonal_marginals
+
+
+def _pattern_marginals(self, lam) -> np.ndarray:
+    """Lambda^-1 at every stored block of Lambda: an array shaped like ``lam.values`` (same block order, each block
+    column-major), as CMarginals::Calculate_DenseMarginals_Recurrent_FBS gives it on a factor's pattern
+    (Marginals.h:1696) -- on Lambda's pattern here, which is the same under every ordering."""
+    if not self._analyzed or self._structure_key != self._key(lam):
+        self.SymbolicDecomposition_Blocky(lam)
+    vals = np.ascontiguousarray(lam.values, dtype=np.float64)
+    if vals.shape != (self._n_values,):
+        raise ValueError("lam.values does not match the block structure")
+    out = np.empty_like(vals)
+    if not self._check(self._lib.slampp_hip_marginals_pattern(self._h, _ptr(vals), _ptr(out))):
+        raise ArithmeticError("Marginals_Pattern: the system is not positive definite")
+    return out
+
+
+def _marginal_columns(self, lam, bcols, reuse_factor: bool = False) -> np.ndarray:
+    """Whole block columns ``bcols`` of Lambda^-1, shape (n_scalars, k), k = the sum of their dimensions, in the listed
+    order (the reference's mpart_Column / mpart_LastColumn, IncrementalPolicy.h:366-372).  ``reuse_factor``: the factor
+    the last solve or covariance call left in place is used, ``lam.values`` are not factored again."""
+    cols = np.ascontiguousarray(np.atleast_1d(np.asarray(bcols, dtype=np.int64)))
+    if reuse_factor:
+        if not self._analyzed or self._structure_key != self._key(lam):
+            raise ValueError("Marginal_Columns: there is no factorization of this structure to reuse")
+        vals = None
+    else:
+        if not self._analyzed or self._structure_key != self._key(lam):
+            self.SymbolicDecomposition_Blocky(lam)
+        vals = np.ascontiguousarray(lam.values, dtype=np.float64)
+        if vals.shape != (self._n_values,):
+            raise ValueError("lam.values does not match the block structure")
+    dims = np.diff(np.asarray(lam.cumsum, dtype=np.int64))
+    k = int(dims[cols].sum()) if cols.size and cols.min() >= 0 and cols.max() < len(dims) else 0
+    out = np.empty((max(k, 1), int(lam.cumsum[-1])), dtype=np.float64)   # column-major (n_scalars, k) = row-major (k, n_scalars)
+    if not self._check(self._lib.slampp_hip_marginal_columns(self._h, _ptr(vals) if vals is not None else None, int(cols.size),
+                                                             _ptr(cols), _ptr(out))):
+        raise ArithmeticError("Marginal_Columns: the system is not positive definite")
+    return out[:k].T
+
+
+CLinearSolver_HIP.Marginals_Pattern = _pattern_marginals
+CLinearSolver_HIP.Marginal_Columns = _marginal_columns
 
 
 class CLinearSolver_Schur_HIP(_SolverBase):
