@@ -1226,6 +1226,176 @@ public:
 		}
 		return true;
 	}
+
+	/**
+	 *	@brief calculates the requested parts of the covariance matrix (the inverse of lambda) of a BA system, the parts
+	 *		CLinearSolver_HIP::Marginals() takes (IncrementalPolicy.h:366-372).  The reference has no Schur path for them:
+	 *		after its Schur marginals it orders and factors the whole of lambda once more (NonlinearSolver_Lambda_LM.h:1362);
+	 *		here lambda's pattern comes from slampp_hip_schur_marginals_pattern and whole block columns from
+	 *		slampp_hip_schur_marginal_columns, which reuse the reduced camera system's factor of the first call
+	 *
+	 *	@param[out] r_marginals is filled with the union of the requested parts, upper triangle, in lambda's block order
+	 *	@param[in] r_lambda is the system matrix (symmetric layout, upper triangle stored)
+	 *	@param[in] n_part is a combination of mpart_Diagonal, mpart_LastBlock, mpart_LastColumn or mpart_FullMatrix (all block
+	 *		columns, in passes); mpart_Column does not say which column: with it set (other than as part of
+	 *		mpart_FullMatrix) this throws std::runtime_error (Marginal_Columns() names the columns)
+	 *	@param[in] b_structure_of_lambda adds every stored block of lambda
+	 *
+	 *	@return Returns true on success, false if lambda is not positive definite.
+	 *	@note A lambda without a landmark part goes to the sparse solver, with the same result.
+	 *	@note This function throws std::bad_alloc and std::runtime_error.
+	 */
+	bool Marginals(CUberBlockMatrix &r_marginals, const CUberBlockMatrix &r_lambda, EBlockMatrixPart n_part,
+		bool b_structure_of_lambda = false) // throw(std::bad_alloc, std::runtime_error)
+	{
+		const size_t n = r_lambda.n_BlockColumn_Num();
+		const bool b_full = (n_part & mpart_FullMatrix) == mpart_FullMatrix;
+		const bool b_last_col = b_full || (n_part & mpart_LastColumn) != 0;
+		const bool b_last_block = b_last_col || (n_part & mpart_LastBlock) != 0;
+		const bool b_diag = b_full || (n_part & mpart_Diagonal) != 0;
+		if((n_part & mpart_Column) && !b_full)
+			throw std::runtime_error("CLinearSolver_Schur_HIP::Marginals: mpart_Column does not say which column (use Marginal_Columns)");
+		if(!Gather_For_Covariances(r_lambda))
+			return m_sparse_fallback.Marginals(r_marginals, r_lambda, n_part, b_structure_of_lambda);
+		r_lambda.CopyLayoutTo(r_marginals);
+		bool b_have_factor = false;
+		if(b_structure_of_lambda || (b_diag && !b_full)) { // lambda's pattern (the diagonal is among it)
+			std::vector<double> v(m_n_value_num);
+			const int n_result = slampp_hip_schur_marginals_pattern(m_p_solver, m_p_values, v.empty()? 0 : &v[0]);
+			if(n_result == SLAMPP_HIP_NOT_POSDEF)
+				return false;
+			Throw_On_Error(n_result);
+			b_have_factor = true;
+			size_t n_at = 0;
+			for(size_t j = 0; j < n; ++ j) { // the library's block order
+				const size_t dj = size_t(m_cumsum[j + 1] - m_cumsum[j]);
+				for(int64_t k = m_bcol_ptr[j]; k < m_bcol_ptr[j + 1]; ++ k) {
+					const size_t i = size_t(m_brow[size_t(k)]), di = size_t(m_cumsum[i + 1] - m_cumsum[i]);
+					if(b_structure_of_lambda || i == j)
+						Put_Library_Block(r_marginals, i, j, di, dj, &v[n_at]);
+					n_at += di * dj;
+				}
+			}
+		}
+		std::vector<int64_t> cols;
+		if(b_full) {
+			for(size_t j = 0; j < n; ++ j)
+				cols.push_back(int64_t(j));
+		} else if(b_last_block)
+			cols.push_back(int64_t(n - 1));
+		for(size_t c0 = 0; c0 < cols.size();) { // at most 48 scalar columns at a time (one pass of the library)
+			size_t c1 = c0, n_k = 0;
+			while(c1 < cols.size() && (c1 == c0 || n_k + r_lambda.n_BlockColumn_Column_Num(size_t(cols[c1])) <= 48))
+				n_k += r_lambda.n_BlockColumn_Column_Num(size_t(cols[c1 ++]));
+			Eigen::MatrixXd X;
+			if(!Columns_Gathered(X, r_lambda, std::vector<int64_t>(cols.begin() + c0, cols.begin() + c1), b_have_factor))
+				return false;
+			b_have_factor = true;
+			size_t n_col = 0;
+			for(size_t q = c0; q < c1; ++ q) {
+				const size_t j = size_t(cols[q]), dj = r_lambda.n_BlockColumn_Column_Num(j);
+				for(size_t i = b_last_col? 0 : j; i <= j; ++ i) { // (mpart_LastBlock alone: the diagonal block only)
+					const size_t di = r_lambda.n_BlockColumn_Column_Num(i), b0 = r_lambda.n_BlockColumn_Base(i);
+					double *p_dest = r_marginals.p_GetBlock_Log(i, j, di, dj, true, false);
+					if(!p_dest)
+						throw std::runtime_error("CLinearSolver_Schur_HIP: cannot write the marginals");
+					for(size_t c = 0; c < dj; ++ c)
+						for(size_t r = 0; r < di; ++ r)
+							p_dest[r + c * di] = X(b0 + r, n_col + c);
+				}
+				n_col += dj;
+			}
+			c0 = c1;
+		}
+		return true;
+	}
+
+	/**
+	 *	@brief calculates whole block columns of the covariance matrix (the inverse of lambda) of a BA system: cameras and
+	 *		landmarks in any mix (slampp_hip_schur_marginal_columns)
+	 *
+	 *	@param[out] r_columns is filled with n_scalars x k values, k = the sum of the listed columns' widths, in the listed
+	 *		order, rows in lambda's scalar order
+	 *	@param[in] r_lambda is the system matrix (symmetric layout, upper triangle stored)
+	 *	@param[in] r_block_columns lists distinct block column indices of lambda
+	 *
+	 *	@return Returns true on success, false if lambda is not positive definite.
+	 *	@note A lambda without a landmark part goes to the sparse solver, with the same result.
+	 *	@note This function throws std::bad_alloc and std::runtime_error.
+	 */
+	bool Marginal_Columns(Eigen::MatrixXd &r_columns, const CUberBlockMatrix &r_lambda,
+		const std::vector<size_t> &r_block_columns) // throw(std::bad_alloc, std::runtime_error)
+	{
+		if(!Gather_For_Covariances(r_lambda))
+			return m_sparse_fallback.Marginal_Columns(r_columns, r_lambda, r_block_columns);
+		return Columns_Gathered(r_columns, r_lambda, std::vector<int64_t>(r_block_columns.begin(), r_block_columns.end()), false);
+	}
+
+protected:
+	/** @brief lambda's values into the staging; false if lambda has no landmark part (the sparse solver answers then) */
+	bool Gather_For_Covariances(const CUberBlockMatrix &r_lambda) // throw(std::bad_alloc, std::runtime_error)
+	{
+		if(m_n_matrix_cut == size_t(-1))
+			SymbolicDecomposition_Blocky(r_lambda, true);
+		if(m_n_matrix_cut == 0 || m_n_matrix_cut == r_lambda.n_BlockColumn_Num())
+			return false;
+		return Gather_Or_Reanalyze(r_lambda, [&]() { SymbolicDecomposition_Blocky(r_lambda, true); });
+	}
+
+	/**
+	 *	@brief block columns r_cols (lambda's indices) of the inverse, with the values Gather_For_Covariances() staged;
+	 *		b_reuse_factor: the reduced system's factor the previous covariance call left (no new factorization)
+	 */
+	bool Columns_Gathered(Eigen::MatrixXd &r_columns, const CUberBlockMatrix &r_lambda, const std::vector<int64_t> &r_cols,
+		bool b_reuse_factor) // throw(std::bad_alloc, std::runtime_error)
+	{
+		const size_t n = r_lambda.n_BlockColumn_Num();
+		std::vector<size_t> inv_order(m_order.size());
+		for(size_t i = 0; i < m_order.size(); ++ i)
+			inv_order[m_order[i]] = i;
+		std::vector<int64_t> lib_cols(r_cols.size());
+		size_t n_k = 0;
+		for(size_t i = 0; i < r_cols.size(); ++ i) {
+			if(r_cols[i] < 0 || size_t(r_cols[i]) >= n)
+				throw std::runtime_error("CLinearSolver_Schur_HIP::Marginal_Columns: block column index out of range");
+			lib_cols[i] = m_order.empty()? r_cols[i] : int64_t(inv_order[size_t(r_cols[i])]);
+			n_k += r_lambda.n_BlockColumn_Column_Num(size_t(r_cols[i]));
+		}
+		Eigen::MatrixXd X(r_lambda.n_Column_Num(), n_k); // (column-major, as the library writes it; rows in its order)
+		const int n_result = slampp_hip_schur_marginal_columns(m_p_solver, b_reuse_factor? 0 : m_p_values, int(lib_cols.size()),
+			lib_cols.empty()? 0 : &lib_cols[0], X.data());
+		if(n_result == SLAMPP_HIP_NOT_POSDEF)
+			return false;
+		Throw_On_Error(n_result);
+		if(m_order.empty())
+			r_columns.swap(X);
+		else { // rows back to lambda's scalar order
+			r_columns.resize(X.rows(), X.cols());
+			for(size_t i = 0; i < n; ++ i) {
+				const size_t n_dst = r_lambda.n_BlockColumn_Base(m_order[i]);
+				for(int64_t d = 0, w = m_cumsum[i + 1] - m_cumsum[i]; d < w; ++ d)
+					r_columns.row(int(n_dst + size_t(d))) = X.row(int(m_cumsum[i] + d));
+			}
+		}
+		return true;
+	}
+
+	/** @brief writes the di x dj column-major block (i, j) of the library's order into r_m at lambda's block position,
+	 *	transposed where the ordering turns the pair into a lower block */
+	void Put_Library_Block(CUberBlockMatrix &r_m, size_t i, size_t j, size_t di, size_t dj, const double *p_src) const
+	{
+		const size_t oi = m_order.empty()? i : m_order[i], oj = m_order.empty()? j : m_order[j];
+		const bool b_tr = oi > oj;
+		double *p_dest = (b_tr)? r_m.p_GetBlock_Log(oj, oi, dj, di, true, false) : r_m.p_GetBlock_Log(oi, oj, di, dj, true, false);
+		if(!p_dest)
+			throw std::runtime_error("CLinearSolver_Schur_HIP: cannot write the marginals");
+		for(size_t c = 0; c < dj; ++ c) {
+			for(size_t r = 0; r < di; ++ r)
+				p_dest[(b_tr)? c + r * dj : r + c * di] = p_src[r + c * di];
+		}
+	}
+
+public:
 };
 
 /**

@@ -323,6 +323,36 @@ int slampp_hip_schur_marginals(slampp_hip_solver *p_solver, const double *p_valu
 int slampp_hip_schur_marginals_device_async(slampp_hip_solver *p_solver, const double *p_values_dev,
 	double *p_cam_cov_dev, double *p_point_cov_dev);
 
+/* Schur mode: covariances beyond the block diagonal of a BA system.  The reference has none: after its Schur marginals
+ * (NonlinearSolver_Lambda_LM.h:1362, "could use fast Schur marginals but at the moment those only implement recovery of
+ * mpart_Diagonal") it orders and factors the whole of Lambda on the host and runs the recursive formula.  Here, with
+ * Lambda = [A U; U^T C], S = A - U C^-1 U^T, Z = S^-1, W_o = U_o C_p^-1:
+ *   camera blocks (a, b)     Z(a, b)
+ *   observation (c, p)       -sum over the cameras b observing p of Z(c, b) W_b
+ *   landmark p               C_p^-1 + W_p^T Z W_p
+ * slampp_hip_schur_marginals_pattern: p_cov has the length and layout of p_values and receives Lambda^-1 at every stored
+ * (upper) block -- camera blocks of A, every observation block (dc x dp), every landmark diagonal block -- each column-major.
+ * Its diagonal blocks are those of slampp_hip_schur_marginals.  Z comes from the dense inverse of S or from the sparse
+ * inverse subset on its factor, decided as slampp_hip_schur_marginals decides (options "schur_sparse", "marginals_dense").
+ * slampp_hip_schur_marginal_columns: whole block columns, cameras or landmarks in any mix, laid out as by
+ * slampp_hip_marginal_columns (n_scalars x k, column-major, listed order).  A camera column is Z E_c on the cameras and
+ * -W_p^T Z(cams(p), c) on every landmark p; a landmark column is -Z W E_p on the cameras, then the same per landmark plus
+ * C_p^-1 on its own block.  Passes of at most 48 scalar columns: the camera part is gathered from the dense inverse of S, or
+ * solved by multi-right-hand-side substitutions with S's sparse factor; the landmark rows follow per landmark.
+ * p_values = NULL (either call): the factor of S, C^-1 and W left by the previous call of these two on this handle are
+ * used; SLAMPP_HIP_ERR_INVALID if any other factorization ran since (a solve, schur_marginals, marginal poses, a batch) or if
+ * that one was not positive definite.  Both calls recompute C^-1 and W from the values given: a later incremental solve
+ * (slampp_hip_schur_set_changed_points) rebuilds the reduced system.  A handle whose Schur analysis went to the sparse
+ * path (option "schur_fallback") answers as slampp_hip_marginals_pattern / slampp_hip_marginal_columns (same layouts).
+ * Sparse mode, several devices, landmark shards: SLAMPP_HIP_ERR_UNSUPPORTED.  Bad column lists: SLAMPP_HIP_ERR_INVALID.
+ * Returns SLAMPP_HIP_NOT_POSDEF as the solve does. */
+int slampp_hip_schur_marginals_pattern(slampp_hip_solver *p_solver, const double *p_values, double *p_cov);
+int slampp_hip_schur_marginals_pattern_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, double *p_cov_dev);
+int slampp_hip_schur_marginal_columns(slampp_hip_solver *p_solver, const double *p_values, int n_cols, const int64_t *p_bcols,
+	double *p_out);
+int slampp_hip_schur_marginal_columns_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, int n_cols,
+	const int64_t *p_bcols, double *p_out_dev);
+
 /* enqueue-only variants for benchmarking / stream capture: no host synchronisation, no status
  * read-back; slampp_hip_sync() waits and returns OK / NOT_POSDEF / error for everything enqueued since the
  * previous slampp_hip_sync() (NOT_POSDEF if any of those factorizations was not positive definite) */

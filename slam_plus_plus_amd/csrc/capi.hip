@@ -537,6 +537,7 @@ int slampp_hip_set_structure(slampp_hip_solver *p_solver, int64_t n_bcols, const
 		s.b_has_structure = true;
 		s.b_analyzed = false;
 		s.b_factored = false;
+		++ s.n_factor_gen; // (what the Schur covariance calls left in place is stale now)
 		s.b_damp_valid = false;
 		s.n_uploaded = 0;
 		return SLAMPP_HIP_OK;
@@ -691,6 +692,7 @@ int slampp_hip_factor_solve_device_async(slampp_hip_solver *p_solver, const doub
 		else
 			schur_enqueue(s, p_values_dev, p_rhs_inout_dev);
 		s.b_factored = true;
+		++ s.n_factor_gen;
 		return SLAMPP_HIP_OK;
 	});
 }
@@ -721,6 +723,7 @@ int slampp_hip_sync(slampp_hip_solver *p_solver)
 		if(*s.p_host_flag) {
 			SLAMPP_HIP_CHECK(hipMemsetAsync(s.d_flag.p(), 0, sizeof(int), s.stream)); // (what was enqueued since the last sync has been answered for)
 			s.b_factored = false;
+			++ s.n_factor_gen;
 			schur_invalidate_previous(s.p_schur); // nothing to update from
 			return fail(p_solver, SLAMPP_HIP_NOT_POSDEF, "matrix is not positive definite");
 		}
@@ -773,6 +776,7 @@ int slampp_hip_factor_solve_batch_device_async(slampp_hip_solver *p_solver, int 
 			// the header promises "not touched": it is declared gone -- slampp_hip_solve_again and the covariance calls refuse
 			// until the next factorization -- rather than passed off as the handle's own (advisor, round 5).
 			s.b_factored = n_batch == 1;
+			++ s.n_factor_gen;
 			s.n_batch_owner_member = (n_batch == 1)? 0 : -1;
 			if(n_batch > 1)
 				schur_invalidate_previous(s.p_schur);
@@ -826,6 +830,7 @@ int slampp_hip_sync_batch(slampp_hip_solver *p_solver, int *p_status, int n_batc
 		}
 		if(s.n_batch_owner_member >= 0 && s.p_host_batch_flag && s.d_batch_flag.p() && s.p_host_batch_flag[s.n_batch_owner_member]) {
 			s.b_factored = false; // the member whose factor the handle kept failed: there is nothing to solve again from
+			++ s.n_factor_gen;
 			schur_invalidate_previous(s.p_schur);
 		}
 		s.n_batch_owner_member = -1;
@@ -991,6 +996,7 @@ int slampp_hip_solve_marginal_poses_device_async(slampp_hip_solver *p_solver, co
 			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_marginal_poses: null pointer");
 		schur_enqueue_marginal_poses(s, p_values_dev, p_rhs_inout_dev);
 		s.b_factored = false; // no factor of the reduced system comes out of this
+		++ s.n_factor_gen;
 		return SLAMPP_HIP_OK;
 	});
 }
@@ -1037,11 +1043,13 @@ int enqueue_sparse_inverse(slampp_hip_solver *p_solver, const double *p_values_d
 		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, (std::string(p_s_name) + ": mixed block sizes are taken without a dense top only (set the option dense_top_nb to 0), block sizes above 8 not at all").c_str());
 	// the fused forward substitution reads a right-hand side, and with a dense top it rides through that factorization
 	// as a row of the matrix: zeros (a NaN there would spread through 0 x NaN in the tile products)
-	s.d_rhs.Alloc(size_t(s.n_scalars));
-	SLAMPP_HIP_CHECK(hipMemsetAsync(s.d_rhs.p(), 0, size_t(s.n_scalars) * sizeof(double), s.stream));
-	// (with a dense top the whole factor + solve runs: the top is factored on the way; opens its own phases)
 	s.b_leaf_linv_wanted = true; // (the inverse subset multiplies by inv(L_jj) of every column)
-	s.Enqueue_Sparse(p_values_dev, s.d_rhs.p(), true, s.n_dense_dim == 0);
+	if(p_values_dev) { // (null: the factor in place -- the Schur covariance calls on a handle that went to this path)
+		s.d_rhs.Alloc(size_t(s.n_scalars));
+		SLAMPP_HIP_CHECK(hipMemsetAsync(s.d_rhs.p(), 0, size_t(s.n_scalars) * sizeof(double), s.stream));
+		// (with a dense top the whole factor + solve runs: the top is factored on the way; opens its own phases)
+		s.Enqueue_Sparse(p_values_dev, s.d_rhs.p(), true, s.n_dense_dim == 0);
+	}
 	s.Ensure_Leaf_Inverses();
 	s.Phase_Begin("marginals_inverse");
 	if(s.n_dense_dim) { // the top's inverse from a copy of its factor (the factor itself stays for solve_again)
@@ -1079,6 +1087,7 @@ int slampp_hip_marginals_device_async(slampp_hip_solver *p_solver, const double 
 			inverse_diag_blocks_any_launch(P.n, s.d_diag_dim.p(), s.d_diag_zoff.p(), s.d_diag_out_off.p(), s.d_Z.p(), p_block_diag_dev, s.stream);
 		SLAMPP_HIP_CHECK(hipGetLastError());
 		s.b_factored = true; // the factor of these values is in place
+		++ s.n_factor_gen;
 		return SLAMPP_HIP_OK;
 	});
 }
@@ -1168,6 +1177,7 @@ int slampp_hip_marginals_pattern_device_async(slampp_hip_solver *p_solver, const
 			return n_result;
 		covariance_pattern_enqueue(s, p_cov_dev);
 		s.b_factored = true; // the factor of these values is in place
+		++ s.n_factor_gen;
 		return SLAMPP_HIP_OK;
 	});
 }
@@ -1221,6 +1231,7 @@ int slampp_hip_marginal_columns_device_async(slampp_hip_solver *p_solver, const 
 			s.b_leaf_linv_wanted = true;
 			s.Enqueue_Sparse(p_values_dev, s.d_rhs.p(), true, s.n_dense_dim == 0);
 			s.b_factored = true;
+			++ s.n_factor_gen;
 		} else if(!s.b_factored)
 			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_columns: no valid factorization to reuse (values = NULL)");
 		s.Ensure_Leaf_Inverses(); // (the substitutions multiply by inv(L_jj) of every column)
@@ -1301,6 +1312,7 @@ int slampp_hip_schur_marginals_device_async(slampp_hip_solver *p_solver, const d
 			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "schur_marginals: null pointer");
 		schur_enqueue_marginals(s, p_values_dev, p_cam_cov_dev, p_point_cov_dev);
 		s.b_factored = false; // C^-1 and W were recomputed from these values: a kept factor may no longer match them
+		++ s.n_factor_gen;
 		return SLAMPP_HIP_OK;
 	});
 }
@@ -1344,6 +1356,186 @@ int slampp_hip_schur_marginals(slampp_hip_solver *p_solver, const double *p_valu
 			SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
 			return SLAMPP_HIP_OK;
 		});
+	}
+	return n_result;
+}
+
+namespace {
+
+// the checks of the Schur covariance calls beyond the block diagonal (inside guarded()); *p_b_fallback: the handle went to
+// the sparse path (its layouts are the same: the sparse calls answer).  b_reuse: values = NULL, which takes what the last
+// of these calls left only if no other factorization ran since and that one was positive definite
+int schur_cov_checks(slampp_hip_solver *p_solver, const char *p_s_name, bool b_reuse, bool *p_b_fallback)
+{
+	slampp_hip_solver &s = *p_solver;
+	const std::string s_name(p_s_name);
+	*p_b_fallback = false;
+	if(!s.b_analyzed)
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, (s_name + ": analyze was not called").c_str());
+	if(s.b_group_active || !s.group_devices.empty())
+		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, (s_name + ": not for a handle over several devices").c_str());
+	if(s.n_mode == SLAMPP_HIP_MODE_SPARSE && s.b_schur_fallback)
+		*p_b_fallback = true;
+	else if(s.n_mode != SLAMPP_HIP_MODE_SCHUR)
+		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, (s_name + ": needs the Schur mode (sparse mode: slampp_hip_marginals_pattern, slampp_hip_marginal_columns)").c_str());
+	else if(s.p_allreduce)
+		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, (s_name + ": not with landmark shards (an all-reduce callback is set)").c_str());
+	if(b_reuse && (!s.n_schur_cov_gen || s.n_schur_cov_gen != s.n_factor_gen))
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, (s_name + ": no factorization to reuse (values = NULL): none was left by a Schur covariance call, another factorization ran since, or it was not positive definite").c_str());
+	return SLAMPP_HIP_OK;
+}
+
+} // anonymous namespace
+
+int slampp_hip_schur_marginals_pattern_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, double *p_cov_dev)
+{
+	return guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		bool b_fallback = false;
+		int n_result = schur_cov_checks(p_solver, "schur_marginals_pattern", !p_values_dev, &b_fallback);
+		if(n_result != SLAMPP_HIP_OK)
+			return n_result;
+		if(!p_cov_dev)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "schur_marginals_pattern: null pointer");
+		if(b_fallback) { // what slampp_hip_marginals_pattern does
+			if((n_result = covariance_checks(p_solver, "schur_marginals_pattern")) != SLAMPP_HIP_OK ||
+			   (n_result = enqueue_sparse_inverse(p_solver, p_values_dev, "schur_marginals_pattern")) != SLAMPP_HIP_OK)
+				return n_result;
+			covariance_pattern_enqueue(s, p_cov_dev);
+			s.b_factored = true; // the factor of these values is in place
+		} else {
+			schur_cov_pattern_enqueue(s, p_values_dev, p_cov_dev);
+			s.b_factored = false; // C^-1 and W were recomputed from these values: a kept factor may no longer match them
+		}
+		if(p_values_dev)
+			++ s.n_factor_gen;
+		s.n_schur_cov_gen = s.n_factor_gen;
+		return SLAMPP_HIP_OK;
+	});
+}
+
+int slampp_hip_schur_marginals_pattern(slampp_hip_solver *p_solver, const double *p_values, double *p_cov)
+{
+	int n_result = guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		bool b_fallback = false;
+		const int n_check = schur_cov_checks(p_solver, "schur_marginals_pattern", !p_values, &b_fallback);
+		if(n_check != SLAMPP_HIP_OK)
+			return n_check;
+		if(!p_cov)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "schur_marginals_pattern: null pointer");
+		s.d_cov.Alloc(size_t(s.n_values));
+		if(p_values) {
+			s.d_A.Alloc(size_t(s.n_values));
+			Upload_Values_And_Join(s, p_values);
+		}
+		return SLAMPP_HIP_OK;
+	});
+	if(n_result != SLAMPP_HIP_OK)
+		return n_result;
+	slampp_hip_solver &s = *p_solver;
+	n_result = slampp_hip_schur_marginals_pattern_device_async(p_solver, p_values? s.d_A.p() : 0, s.d_cov.p());
+	if(n_result == SLAMPP_HIP_OK)
+		n_result = slampp_hip_sync(p_solver);
+	if(n_result == SLAMPP_HIP_OK) {
+		n_result = guarded(p_solver, [&]() -> int {
+			SLAMPP_HIP_CHECK(hipMemcpyAsync(p_cov, s.d_cov.p(), size_t(s.n_values) * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+			SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
+			return SLAMPP_HIP_OK;
+		});
+	}
+	return n_result;
+}
+
+int slampp_hip_schur_marginal_columns_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, int n_cols,
+	const int64_t *p_bcols, double *p_out_dev)
+{
+	return guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		bool b_fallback = false;
+		int n_result = schur_cov_checks(p_solver, "schur_marginal_columns", !p_values_dev, &b_fallback);
+		if(n_result != SLAMPP_HIP_OK)
+			return n_result;
+		if(!p_out_dev)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "schur_marginal_columns: null pointer");
+		int64_t n_k = 0;
+		if((n_result = columns_checks(p_solver, n_cols, p_bcols, &n_k)) != SLAMPP_HIP_OK)
+			return n_result;
+		if(b_fallback) { // what slampp_hip_marginal_columns does
+			if((n_result = covariance_checks(p_solver, "schur_marginal_columns")) != SLAMPP_HIP_OK)
+				return n_result;
+			if(p_values_dev) {
+				s.d_rhs.Alloc(size_t(s.n_scalars));
+				SLAMPP_HIP_CHECK(hipMemsetAsync(s.d_rhs.p(), 0, size_t(s.n_scalars) * sizeof(double), s.stream));
+				s.b_leaf_linv_wanted = true;
+				s.Enqueue_Sparse(p_values_dev, s.d_rhs.p(), true, s.n_dense_dim == 0);
+				s.b_factored = true;
+			}
+			s.Ensure_Leaf_Inverses();
+			covariance_columns_enqueue(s, n_cols, p_bcols, p_out_dev);
+		} else {
+			schur_cov_columns_enqueue(s, p_values_dev, n_cols, p_bcols, p_out_dev);
+			s.b_factored = false;
+		}
+		if(p_values_dev)
+			++ s.n_factor_gen;
+		s.n_schur_cov_gen = s.n_factor_gen;
+		return SLAMPP_HIP_OK;
+	});
+}
+
+int slampp_hip_schur_marginal_columns(slampp_hip_solver *p_solver, const double *p_values, int n_cols, const int64_t *p_bcols,
+	double *p_out)
+{
+	int64_t n_k = 0;
+	int n_result = guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		bool b_fallback = false;
+		int n_check = schur_cov_checks(p_solver, "schur_marginal_columns", !p_values, &b_fallback);
+		if(n_check != SLAMPP_HIP_OK)
+			return n_check;
+		if(!p_out)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "schur_marginal_columns: null pointer");
+		if((n_check = columns_checks(p_solver, n_cols, p_bcols, &n_k)) != SLAMPP_HIP_OK)
+			return n_check;
+		s.d_cov.Alloc(size_t(s.n_scalars) * COV_K_PASS);
+		if(p_values) {
+			s.d_A.Alloc(size_t(s.n_values));
+			Upload_Values_And_Join(s, p_values);
+		}
+		return SLAMPP_HIP_OK;
+	});
+	if(n_result != SLAMPP_HIP_OK)
+		return n_result;
+	// groups of whole block columns of at most COV_K_PASS scalar columns, each brought back behind its pass; the first
+	// factors the values, the others use that factor (values = NULL: the generation check lets them through)
+	slampp_hip_solver &s = *p_solver;
+	const double *p_values_dev = p_values? s.d_A.p() : 0;
+	int64_t n_done = 0;
+	for(int i = 0; i < n_cols && n_result == SLAMPP_HIP_OK;) {
+		int n_group = 0;
+		int64_t n_group_k = 0;
+		while(i + n_group < n_cols) {
+			const int64_t c = p_bcols[i + n_group], d = s.cumsum[size_t(c + 1)] - s.cumsum[size_t(c)];
+			if(n_group && n_group_k + d > COV_K_PASS)
+				break;
+			n_group_k += d;
+			++ n_group;
+		}
+		n_result = slampp_hip_schur_marginal_columns_device_async(p_solver, p_values_dev, n_group, p_bcols + i, s.d_cov.p());
+		p_values_dev = 0;
+		if(n_result == SLAMPP_HIP_OK)
+			n_result = slampp_hip_sync(p_solver);
+		if(n_result == SLAMPP_HIP_OK) {
+			n_result = guarded(p_solver, [&]() -> int {
+				SLAMPP_HIP_CHECK(hipMemcpyAsync(p_out + size_t(n_done) * size_t(s.n_scalars), s.d_cov.p(), size_t(n_group_k) *
+					size_t(s.n_scalars) * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+				SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
+				return SLAMPP_HIP_OK;
+			});
+		}
+		n_done += n_group_k;
+		i += n_group;
 	}
 	return n_result;
 }
@@ -1507,6 +1699,7 @@ int slampp_hip_factorize(slampp_hip_solver *p_solver, const double *p_values, do
 		SLAMPP_HIP_CHECK(hipMemsetAsync(s.d_rhs.p(), 0, size_t(s.n_scalars) * sizeof(double), s.stream)); // the fused forward substitution runs on zeros
 		s.Enqueue_Sparse(s.d_A.p(), s.d_rhs.p(), true, true); // (a dense top factors its columns on the matrix cores and hands them back into the block layout)
 		s.b_factored = s.n_dense_dim == 0; // (with a dense top the substitutions' vectors were not brought along: no solve_again from this)
+		++ s.n_factor_gen;
 		return SLAMPP_HIP_OK;
 	});
 	if(n_result != SLAMPP_HIP_OK)

@@ -28,4 +28,11 @@ void covariance_pattern_enqueue(slampp_hip_solver &s, double *p_out_dev);
 // column-major, rows in the caller's scalar order, k = the sum of the columns' dimensions.  Throws.
 void covariance_columns_enqueue(slampp_hip_solver &s, int n_cols, const int64_t *p_bcols, double *p_out_dev);
 
+// one pass of kp <= COV_K_PASS right-hand sides given whole: p_rhs_dev is n_scalars x kp in the factor's permuted row order,
+// interleaved (row * kp + column), nonzero on the rows of the block columns p_src_bcols[0 .. n_src) only (the pruned forward
+// substitution starts from their elimination-tree paths).  The solution goes to p_out_dev + n_col0 * n_ld_out, column-major,
+// rows in the caller's scalar order.  Throws.
+void covariance_columns_rhs_enqueue(slampp_hip_solver &s, int n_src, const int64_t *p_src_bcols, int kp, const double *p_rhs_dev,
+	double *p_out_dev, int64_t n_ld_out, int64_t n_col0);
+
 } // namespace slampp

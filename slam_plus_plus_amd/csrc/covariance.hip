@@ -193,12 +193,14 @@ void covariance_pattern_enqueue(slampp_hip_solver &s, double *p_out_dev)
 
 // ---- block columns: pruned k-column forward substitution ----
 
-// one workgroup (one wave) per segment: the listed columns of one task, in order; lane c = right-hand side c
-template <int D>
+// one workgroup (one wave) per segment: the listed columns of one task, in order; lane c = right-hand side c.  B_RHS: the
+// right-hand side is not P E_J but the dense block B (permuted rows, interleaved like X: B[row * kp + c]; nonzero on the
+// listed columns' own rows only) -- the landmark columns of the Schur path (schur_covariance.hip)
+template <int D, bool B_RHS = false>
 __global__ void __launch_bounds__(64)
 cov_forward_kernel(const int32_t *__restrict__ seg, int seg_begin, const TCovFwd *__restrict__ fwd, const TRowEnt *__restrict__ ents,
 	const double *__restrict__ L, const double *__restrict__ Linv, double *X, int kp, int32_t *mark, int32_t n_stamp,
-	double *Bd)
+	double *Bd, const double *__restrict__ B = 0)
 {
 	constexpr int DM = D? D : 8;
 	const int c = threadIdx.x;
@@ -209,8 +211,12 @@ cov_forward_kernel(const int32_t *__restrict__ seg, int seg_begin, const TCovFwd
 		const int dj = D? D : rec.dj;
 		double acc[DM];
 		#pragma unroll
-		for(int r = 0; r < DM; ++ r)
-			acc[r] = (c - rec.bcol == r)? 1.0 : 0.0; // the right-hand side's block: P E_J
+		for(int r = 0; r < DM; ++ r) {
+			if(B_RHS)
+				acc[r] = (r < dj && b_act)? B[int64_t(rec.ycs + r) * kp + c] : 0.0;
+			else
+				acc[r] = (c - rec.bcol == r)? 1.0 : 0.0; // the right-hand side's block: P E_J
+		}
 		for(int64_t e = rec.e0; e < rec.e0 + rec.ne; ++ e) {
 			const TRowEnt t_e = ents[e];
 			const int dc = D? D : t_e.dc;
@@ -451,7 +457,11 @@ struct TCovPass {
 };
 } // anonymous namespace
 
-void covariance_columns_enqueue(slampp_hip_solver &s, int n_cols, const int64_t *p_bcols, double *p_out_dev)
+// p_rhs = 0: the unit right-hand sides of the block columns p_bcols, in passes of COV_K_PASS; else one pass of n_rhs_k
+// right-hand sides read from p_rhs (see cov_forward_kernel), nonzero on the rows of the block columns p_bcols only.  The
+// result goes to p_out_dev + n_col0 * n_ld_out, column-major with leading dimension n_ld_out.
+static void columns_enqueue(slampp_hip_solver &s, int n_cols, const int64_t *p_bcols, const double *p_rhs, int n_rhs_k,
+	double *p_out_dev, int64_t n_ld_out, int64_t n_col0)
 {
 	const Plan &P = s.plan;
 	CCovariance &cv = Covariance_State(s);
@@ -460,8 +470,15 @@ void covariance_columns_enqueue(slampp_hip_solver &s, int n_cols, const int64_t 
 	int64_t k = 0;
 	std::vector<int64_t> col_off(size_t(n_cols) + 1, 0);
 	for(int i = 0; i < n_cols; ++ i) {
-		col_off[size_t(i)] = k;
+		col_off[size_t(i)] = (p_rhs)? 0 : k; // (one pass over all the sources)
 		k += s.cumsum[size_t(p_bcols[i] + 1)] - s.cumsum[size_t(p_bcols[i])];
+	}
+	if(p_rhs) {
+		if(n_rhs_k <= 0 || n_rhs_k > COV_K_PASS)
+			throw std::invalid_argument("marginal_columns: a right-hand side block of 1 .. COV_K_PASS columns");
+		k = n_rhs_k;
+		std::fill(col_off.begin(), col_off.end(), int64_t(0));
+		col_off[size_t(n_cols)] = k;
 	}
 	col_off[size_t(n_cols)] = k;
 	if(k > int64_t(INT_MAX))
@@ -486,10 +503,11 @@ void covariance_columns_enqueue(slampp_hip_solver &s, int n_cols, const int64_t 
 		reach.clear();
 		dense_reach.clear();
 		for(int i = 0; i < n_cols; ++ i) {
-			if(col_off[size_t(i) + 1] <= col0 || col_off[size_t(i)] >= col0 + pass.kp)
+			if(!p_rhs && (col_off[size_t(i) + 1] <= col0 || col_off[size_t(i)] >= col0 + pass.kp))
 				continue; // not in this pass
 			const int32_t j = P.pinv[size_t(p_bcols[i])];
-			cv.host_bcol[size_t(j)] = int32_t(col_off[size_t(i)] - col0);
+			if(!p_rhs)
+				cv.host_bcol[size_t(j)] = int32_t(col_off[size_t(i)] - col0);
 			for(int32_t x = j; x >= 0 && cv.host_mark[size_t(x)] != n_hs; x = P.parent[size_t(x)]) {
 				cv.host_mark[size_t(x)] = n_hs;
 				if(cv.sched_pos[size_t(x)] >= 0)
@@ -574,13 +592,22 @@ void covariance_columns_enqueue(slampp_hip_solver &s, int n_cols, const int64_t 
 			const TCovLaunch &l = pass.launches[q];
 			const int n_blocks = l.seg1 - l.seg0;
 			const int DL = (l.n_stage < 0)? 0 : D; // (the dense-top columns' dimensions: any)
-#define COV_FWD(DD) hipLaunchKernelGGL(cov_forward_kernel<DD>, dim3(n_blocks), dim3(64), 0, s.stream, cv.d_seg.p(), l.seg0, cv.d_fwd.p(), \
-				cv.d_ents.p(), s.d_L.p(), s.d_Linv.p(), cv.d_X.p(), kp, cv.d_mark.p(), cv.n_stamp, cv.d_Bd.p())
-			switch(DL) {
-			case 3: COV_FWD(3); break;
-			case 6: COV_FWD(6); break;
-			case 7: COV_FWD(7); break;
-			default: COV_FWD(0); break;
+#define COV_FWD(DD, BR) hipLaunchKernelGGL((cov_forward_kernel<DD, BR>), dim3(n_blocks), dim3(64), 0, s.stream, cv.d_seg.p(), l.seg0, \
+				cv.d_fwd.p(), cv.d_ents.p(), s.d_L.p(), s.d_Linv.p(), cv.d_X.p(), kp, cv.d_mark.p(), cv.n_stamp, cv.d_Bd.p(), p_rhs)
+			if(p_rhs) {
+				switch(DL) {
+				case 3: COV_FWD(3, true); break;
+				case 6: COV_FWD(6, true); break;
+				case 7: COV_FWD(7, true); break;
+				default: COV_FWD(0, true); break;
+				}
+			} else {
+				switch(DL) {
+				case 3: COV_FWD(3, false); break;
+				case 6: COV_FWD(6, false); break;
+				case 7: COV_FWD(7, false); break;
+				default: COV_FWD(0, false); break;
+				}
 			}
 #undef COV_FWD
 		}
@@ -590,7 +617,7 @@ void covariance_columns_enqueue(slampp_hip_solver &s, int n_cols, const int64_t 
 					s.d_dense_invdiag.p(), cv.d_Bd.p(), cv.d_Zb.p(), kp);
 			for(int t = n_tiles - 1; t >= 0; -- t)
 				hipLaunchKernelGGL(cov_dense_backward_kernel, dim3(t + 1), dim3(256), 0, s.stream, s.d_dense.p(), ld, n_dense, t,
-					s.d_dense_invdiag.p(), cv.d_Zb.p(), kp, s.d_dense_dst.p(), cv.d_X.p(), p_out_dev, s.n_scalars, pass.col0);
+					s.d_dense_invdiag.p(), cv.d_Zb.p(), kp, s.d_dense_dst.p(), cv.d_X.p(), p_out_dev, n_ld_out, int(n_col0 + pass.col0));
 		}
 		for(int st = n_stages - 1; st >= 0; -- st) {
 			const int n_tasks = P.stage_ptr[size_t(st + 1)] - P.stage_ptr[size_t(st)];
@@ -598,7 +625,7 @@ void covariance_columns_enqueue(slampp_hip_solver &s, int n_cols, const int64_t 
 				continue;
 #define COV_BWD(DD) hipLaunchKernelGGL(cov_backward_kernel<DD>, dim3(n_tasks), dim3(64), 0, s.stream, s.dplan.cols, s.dplan.blks, \
 				s.dplan.task_ptr, P.stage_ptr[size_t(st)], s.d_L.p(), s.d_Linv.p(), cv.d_X.p(), kp, cv.d_mark.p(), cv.n_stamp, p_out_dev, \
-				s.n_scalars, pass.col0)
+				n_ld_out, int(n_col0 + pass.col0))
 			switch(D) {
 			case 3: COV_BWD(3); break;
 			case 6: COV_BWD(6); break;
@@ -610,6 +637,17 @@ void covariance_columns_enqueue(slampp_hip_solver &s, int n_cols, const int64_t 
 	}
 	s.Phase_End();
 	SLAMPP_HIP_CHECK(hipGetLastError());
+}
+
+void covariance_columns_enqueue(slampp_hip_solver &s, int n_cols, const int64_t *p_bcols, double *p_out_dev)
+{
+	columns_enqueue(s, n_cols, p_bcols, 0, 0, p_out_dev, s.n_scalars, 0);
+}
+
+void covariance_columns_rhs_enqueue(slampp_hip_solver &s, int n_src, const int64_t *p_src_bcols, int kp, const double *p_rhs_dev,
+	double *p_out_dev, int64_t n_ld_out, int64_t n_col0)
+{
+	columns_enqueue(s, n_src, p_src_bcols, p_rhs_dev, kp, p_out_dev, n_ld_out, n_col0);
 }
 
 } // namespace slampp

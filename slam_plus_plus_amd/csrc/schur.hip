@@ -22,6 +22,7 @@
 #include "dense_chol.h"
 #include "sparse_inverse.h"
 #include "schur_tiles.h"
+#include "covariance.h"
 
 #include <algorithm>
 #include <chrono>
@@ -85,6 +86,16 @@ struct CSchurState {
 	CDevArray<int64_t> d_changed;              // landmarks named for the next solve
 	int64_t n_changed = -1;                    // -1: none named (full rebuild)
 	CSchurTiles tiles;                         // landmark-major assembly of S (schur_tiles.hip)
+	// covariances beyond the block diagonal (schur_covariance.hip): the reduced-system path the last of those calls took,
+	// whether the sparse inverse subset of its factor is in d_m_Zs, where A's blocks sit in it (offset * 2 + transposed)
+	// and every camera's rows in the inner solver's permuted vector, the column passes' right-hand sides, camera parts
+	// (interleaved) and column tables
+	bool b_cov_sparse = false, b_cov_z_valid = false;
+	CDevArray<int64_t> d_a_zent, d_cam_csn, d_cov_cols;
+	CDevArray<double> d_cov_B, d_cov_X;
+	std::vector<int64_t> h_cov_cols[2];        // the column tables of the last two calls (alternately)
+	hipEvent_t ev_cov_cols[2] = {0, 0};        // recorded behind the uploads out of them
+	int n_cov_call = 0;
 	CSchurState() :p_union_fn(0), p_union_context(0), b_union_dense(false), n_union(0), b_reduced_decided(false),
 		b_reduced_sparse(false), p_inner(0), n_in_blocks(0), p_sinv(0), b_sinv_tried(false) {}
 	~CSchurState();
@@ -94,6 +105,10 @@ CSchurState::~CSchurState()
 {
 	if(p_sinv)
 		sparse_inverse_destroy(p_sinv);
+	for(int i = 0; i < 2; ++ i) {
+		if(ev_cov_cols[i])
+			(void)hipEventDestroy(ev_cov_cols[i]);
+	}
 	if(p_inner) {
 		p_inner->stream = 0; // borrowed from the owning solver
 		delete p_inner;
@@ -112,7 +127,8 @@ size_t schur_device_bytes(const CSchurState *p)
 		p->d_m_invdiag.n_Bytes() + p->d_m_zero.n_Bytes() + p->d_m_Zs.n_Bytes() + p->d_cam_zoff.n_Bytes() +
 		p->d_pair_ptr.n_Bytes() + p->d_pair_tab.n_Bytes() + sparse_inverse_bytes(p->p_sinv) +
 		p->d_Cinv.n_Bytes() + p->d_t.n_Bytes() + p->d_invdiag.n_Bytes() + p->d_z.n_Bytes() + p->d_x.n_Bytes() +
-		p->d_A_prev.n_Bytes() + p->d_S_unf.n_Bytes() + p->d_changed.n_Bytes() + p->tiles.n_Bytes();
+		p->d_A_prev.n_Bytes() + p->d_S_unf.n_Bytes() + p->d_changed.n_Bytes() + p->tiles.n_Bytes() + p->d_a_zent.n_Bytes() +
+		p->d_cam_csn.n_Bytes() + p->d_cov_cols.n_Bytes() + p->d_cov_B.n_Bytes() + p->d_cov_X.n_Bytes();
 }
 
 void schur_invalidate_previous(CSchurState *p)
@@ -1208,6 +1224,9 @@ static void schur_try_sparse_reduced(slampp_hip_solver &s, CSchurState &S)
 		S.p_sinv = 0;
 	}
 	S.b_sinv_tried = false;
+	S.d_a_zent.Free(); // (the covariance tables point into the previous inner solver's factor: built again on first use)
+	S.d_cam_csn.Free();
+	S.b_cov_z_valid = false;
 	if(S.p_inner) {
 		S.p_inner->stream = 0;
 		delete S.p_inner;
@@ -1614,8 +1633,7 @@ static bool schur_setup_sparse_marginals(slampp_hip_solver &s, CSchurState &S)
 // inner solver's packed values, summed over the ranks), its factorization, then the blocks of S^-1 on the factor's
 // pattern (sparse_inverse.hip) instead of a dense inverse -- the cost of a second factorization, and no n^2 memory
 template <int DC, int DP>
-static void schur_enqueue_marginals_sparse_t(slampp_hip_solver &s, CSchurState &S, const double *A, double *cam_cov,
-	double *point_cov)
+static void schur_marginals_sparse_factor_t(slampp_hip_solver &s, CSchurState &S, const double *A)
 {
 	hipStream_t st = s.stream;
 	const int n = S.N;
@@ -1645,6 +1663,14 @@ static void schur_enqueue_marginals_sparse_t(slampp_hip_solver &s, CSchurState &
 	S.p_inner->Enqueue_Sparse(p_S, p_r, true, true); // numeric factorization only
 	S.p_inner->Ensure_Leaf_Inverses();
 	s.Phase_End();
+}
+
+template <int DC, int DP>
+static void schur_enqueue_marginals_sparse_t(slampp_hip_solver &s, CSchurState &S, const double *A, double *cam_cov,
+	double *point_cov)
+{
+	hipStream_t st = s.stream;
+	schur_marginals_sparse_factor_t<DC, DP>(s, S, A);
 	s.Phase_Begin("marginals_inverse");
 	sparse_inverse_enqueue(*S.p_sinv, S.p_inner->plan, S.p_inner->d_L.p(), S.p_inner->d_Linv.p(), S.d_m_Zs.p(), st);
 	s.Phase_End();
@@ -1655,20 +1681,12 @@ static void schur_enqueue_marginals_sparse_t(slampp_hip_solver &s, CSchurState &
 	SLAMPP_HIP_CHECK(hipGetLastError());
 }
 
+// the dense reduced system of the covariances assembled into d_m_S, factored, and inverted into d_m_Z
 template <int DC, int DP>
-static void schur_enqueue_marginals_t(slampp_hip_solver &s, CSchurState &S, const double *A, double *cam_cov, double *point_cov)
+static void schur_marginals_dense_inverse_t(slampp_hip_solver &s, CSchurState &S, const double *A)
 {
 	hipStream_t st = s.stream;
 	const int ld = S.Npad, n = S.N;
-	// decided as for a solve: with the sparse reduced system the covariances go through the sparse inverse subset
-	if(s.p_allreduce && (S.p_union_fn != s.p_allreduce || S.p_union_context != s.p_allreduce_context))
-		schur_agree_on_union(s, S);
-	if(!S.b_reduced_decided)
-		schur_setup_reduced(s, S);
-	if(S.b_reduced_sparse && s.n_marginals_dense == 0 && schur_setup_sparse_marginals(s, S)) {
-		schur_enqueue_marginals_sparse_t<DC, DP>(s, S, A, cam_cov, point_cov);
-		return;
-	}
 	if(!S.d_m_S.p()) {
 		S.d_m_S.Alloc(size_t(ld) * ld);
 		S.d_m_Z.Alloc(size_t(ld) * ld);
@@ -1702,6 +1720,23 @@ static void schur_enqueue_marginals_t(slampp_hip_solver &s, CSchurState &S, cons
 	s.Phase_Begin("marginals_inverse");
 	dense_inverse_from_factor(p_S, ld, S.d_m_invdiag.p(), S.d_m_Z.p(), st);
 	s.Phase_End();
+}
+
+template <int DC, int DP>
+static void schur_enqueue_marginals_t(slampp_hip_solver &s, CSchurState &S, const double *A, double *cam_cov, double *point_cov)
+{
+	hipStream_t st = s.stream;
+	const int ld = S.Npad;
+	// decided as for a solve: with the sparse reduced system the covariances go through the sparse inverse subset
+	if(s.p_allreduce && (S.p_union_fn != s.p_allreduce || S.p_union_context != s.p_allreduce_context))
+		schur_agree_on_union(s, S);
+	if(!S.b_reduced_decided)
+		schur_setup_reduced(s, S);
+	if(S.b_reduced_sparse && s.n_marginals_dense == 0 && schur_setup_sparse_marginals(s, S)) {
+		schur_enqueue_marginals_sparse_t<DC, DP>(s, S, A, cam_cov, point_cov);
+		return;
+	}
+	schur_marginals_dense_inverse_t<DC, DP>(s, S, A);
 	s.Phase_Begin("marginals_gather");
 	schur_marginals_launch(DC, DP, S.nc, S.np, S.d_ptr.p(), S.d_brow.p(), S.d_W.p(), S.d_Cinv.p(), S.d_m_Z.p(), ld,
 		cam_cov, point_cov, st);
@@ -1744,6 +1779,195 @@ void schur_enqueue(slampp_hip_solver &s, const double *p_values_dev, double *p_r
 		schur_enqueue_t<7, 3>(s, S, p_values_dev, p_rhs_dev);
 	else
 		schur_enqueue_t<3, 2>(s, S, p_values_dev, p_rhs_dev);
+}
+
+// ---- covariances beyond the block diagonal (schur_covariance.hip) ----
+
+void schur_cov_pattern_launch(int DC, int DP, int64_t nc, int64_t np, const int64_t *ptr, const int32_t *brow, int64_t ubase,
+	const int64_t *a_zent, const int64_t *pair_ptr, const int64_t *pair_tab, const double *W, const double *Cinv, const double *Z,
+	int ld, double *out, hipStream_t stream);
+void schur_cov_cols_cam_launch(int DC, int DP, int64_t nc, const int64_t *ptr, const int32_t *brow, const double *W,
+	const double *Z, int ld, const int64_t *cam_csn, const int64_t *col_src, int kp, double *B, double *X, double *out,
+	int64_t n_ld, int64_t n_col0, hipStream_t stream);
+void schur_cov_interleave_launch(int64_t n_rows, int kp, const double *out, int64_t n_ld, int64_t n_col0, double *X,
+	hipStream_t stream);
+void schur_cov_cols_point_launch(int DC, int DP, int64_t nc, int64_t np, const int64_t *ptr, const int32_t *brow, const double *W,
+	const double *Cinv, const int64_t *col_src, int kp, const double *X, double *out, int64_t n_ld, int64_t n_col0, hipStream_t stream);
+
+// the sparse path's extra tables: where Z(r, c) of every camera block of A sits in the inverse subset (A's blocks are blocks
+// of S, so of its factor), and every camera's first row in the inner solver's permuted vector
+static void schur_setup_cov_tables(slampp_hip_solver &s, CSchurState &S)
+{
+	if(S.d_cam_csn.p())
+		return;
+	const Plan &P = S.p_inner->plan;
+	const int64_t nc = S.nc, *ptr = s.bcol_ptr.data();
+	const int32_t *brow = s.brow.data();
+	std::vector<int64_t> a_zent(size_t(std::max<int64_t>(ptr[nc], 1)), int64_t(0)), cam_csn((size_t(nc)));
+	for(int64_t c = 0; c < nc; ++ c) {
+		const int32_t pc = P.pinv[size_t(c)];
+		cam_csn[size_t(c)] = P.cs_new[size_t(pc)];
+		for(int64_t k = ptr[c]; k < ptr[c + 1]; ++ k) {
+			const int32_t pr = P.pinv[size_t(brow[k])];
+			const int64_t off = plan_block_offset(P, std::max(pr, pc), std::min(pr, pc));
+			if(off < 0)
+				throw std::logic_error("covariances: a camera block of Lambda is not a block of the reduced system's factor");
+			a_zent[size_t(k)] = off * 2 + (pr < pc); // Z(r, c) is the stored block, or its transpose
+		}
+	}
+	S.d_a_zent.Upload(a_zent, s.stream);
+	S.d_cam_csn.Upload(cam_csn, s.stream);
+	SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream)); // the tables live on this stack frame
+}
+
+// C^-1, W and the factor of the reduced system from these values (A = 0: what the previous covariance call left), decided
+// as schur_marginals decides (options schur_sparse, marginals_dense); b_need_z: the inverse of the reduced system too
+template <int DC, int DP>
+static void schur_cov_factor_t(slampp_hip_solver &s, CSchurState &S, const double *A, bool b_need_z)
+{
+	if(A) {
+		if(!S.b_reduced_decided)
+			schur_setup_reduced(s, S);
+		S.b_cov_z_valid = false;
+		S.b_cov_sparse = S.b_reduced_sparse && s.n_marginals_dense == 0 && schur_setup_sparse_marginals(s, S);
+		if(S.b_cov_sparse)
+			schur_marginals_sparse_factor_t<DC, DP>(s, S, A); // (no inverse until one is asked for)
+		else {
+			schur_marginals_dense_inverse_t<DC, DP>(s, S, A); // (the columns are gathered from the dense inverse as well)
+			S.b_cov_z_valid = true;
+		}
+	}
+	if(S.b_cov_sparse) {
+		schur_setup_cov_tables(s, S);
+		if(b_need_z && !S.b_cov_z_valid) {
+			s.Phase_Begin("marginals_inverse");
+			sparse_inverse_enqueue(*S.p_sinv, S.p_inner->plan, S.p_inner->d_L.p(), S.p_inner->d_Linv.p(), S.d_m_Zs.p(), s.stream);
+			s.Phase_End();
+			S.b_cov_z_valid = true;
+		}
+	}
+}
+
+template <int DC, int DP>
+static void schur_cov_pattern_t(slampp_hip_solver &s, CSchurState &S, const double *A, double *out)
+{
+	schur_cov_factor_t<DC, DP>(s, S, A, true);
+	const int64_t ubase = S.n_ablocks * DC * DC;
+	s.Phase_Begin("pattern_gather");
+	if(S.b_cov_sparse)
+		schur_cov_pattern_launch(DC, DP, S.nc, S.np, S.d_ptr.p(), S.d_brow.p(), ubase, S.d_a_zent.p(), S.d_pair_ptr.p(),
+			S.d_pair_tab.p(), S.d_W.p(), S.d_Cinv.p(), S.d_m_Zs.p(), 0, out, s.stream);
+	else
+		schur_cov_pattern_launch(DC, DP, S.nc, S.np, S.d_ptr.p(), S.d_brow.p(), ubase, 0, 0, 0, S.d_W.p(), S.d_Cinv.p(),
+			S.d_m_Z.p(), S.Npad, out, s.stream);
+	s.Phase_End();
+	SLAMPP_HIP_CHECK(hipGetLastError());
+}
+
+void schur_cov_pattern_enqueue(slampp_hip_solver &s, const double *p_values_dev, double *p_cov_dev)
+{
+	CSchurState &S = *s.p_schur;
+	if(p_values_dev)
+		schur_invalidate_previous(&S); // C^-1, W (and the packed reduced system) are recomputed from these values
+	if(S.DC == 6 && S.DP == 3)
+		schur_cov_pattern_t<6, 3>(s, S, p_values_dev, p_cov_dev);
+	else if(S.DC == 7 && S.DP == 3)
+		schur_cov_pattern_t<7, 3>(s, S, p_values_dev, p_cov_dev);
+	else
+		schur_cov_pattern_t<3, 2>(s, S, p_values_dev, p_cov_dev);
+}
+
+// Whole block columns in passes of at most COV_K_PASS scalar columns (whole block columns each).  A pass's camera part:
+// dense reduced system -- gathered from its dense inverse (computed anyway: the factor's k-column substitutions would be a
+// dependent chain of tile solves per pass, the gather is one launch); sparse -- k-column substitutions with its factor
+// (covariance.hip), the right-hand sides E_c for a camera column and -W E_p for a landmark column.  Then the landmark rows.
+template <int DC, int DP>
+static void schur_cov_columns_t(slampp_hip_solver &s, CSchurState &S, const double *A, int n_cols, const int64_t *p_bcols,
+	double *out)
+{
+	hipStream_t st = s.stream;
+	schur_cov_factor_t<DC, DP>(s, S, A, false);
+	const int64_t nc = S.nc, n_ld = s.n_scalars;
+	const int64_t *ptr = s.bcol_ptr.data();
+	const int32_t *brow = s.brow.data();
+	// the column tables of every pass, one upload out of the host vector the call before the previous one used: its upload
+	// has long completed, so the host does not wait for the device here
+	const int n_buf = (S.n_cov_call ++) & 1;
+	std::vector<int64_t> &h_cols = S.h_cov_cols[n_buf];
+	if(S.ev_cov_cols[n_buf])
+		SLAMPP_HIP_CHECK(hipEventSynchronize(S.ev_cov_cols[n_buf]));
+	h_cols.clear();
+	std::vector<int> pass_first; // first listed column of every pass
+	int64_t n_pass_k = COV_K_PASS;
+	for(int i = 0; i < n_cols; ++ i) {
+		const int64_t c = p_bcols[i], d = (c < nc)? DC : DP;
+		if(n_pass_k + d > COV_K_PASS) {
+			pass_first.push_back(i);
+			n_pass_k = 0;
+		}
+		n_pass_k += d;
+		for(int64_t e = 0; e < d; ++ e)
+			h_cols.push_back((c < nc)? c * DC + e : -1 - ((c - nc) * DP + e));
+	}
+	pass_first.push_back(n_cols);
+	S.d_cov_cols.Upload(h_cols, st); // (stream-ordered behind the previous call's kernels, which read the old tables)
+	if(!S.ev_cov_cols[n_buf])
+		SLAMPP_HIP_CHECK(hipEventCreateWithFlags(&S.ev_cov_cols[n_buf], hipEventDisableTiming));
+	SLAMPP_HIP_CHECK(hipEventRecord(S.ev_cov_cols[n_buf], st));
+	S.d_cov_X.Alloc(size_t(nc * DC) * COV_K_PASS);
+	if(S.b_cov_sparse) {
+		S.d_cov_B.Alloc(size_t(nc * DC) * COV_K_PASS);
+		S.p_inner->Ensure_Leaf_Inverses(); // (the substitutions multiply by inv(L_jj) of every column)
+	}
+	s.Phase_Begin("marginal_columns");
+	std::vector<int64_t> srcs;
+	int64_t col0 = 0;
+	for(size_t p = 0; p + 1 < pass_first.size(); ++ p) {
+		int kp = 0;
+		srcs.clear();
+		for(int i = pass_first[p]; i < pass_first[p + 1]; ++ i) {
+			const int64_t c = p_bcols[i];
+			if(c < nc) {
+				kp += DC;
+				srcs.push_back(c);
+			} else {
+				kp += DP;
+				for(int64_t k = ptr[c]; k < ptr[c + 1] - 1; ++ k)
+					srcs.push_back(brow[k]); // the cameras observing the landmark
+			}
+		}
+		const int64_t *p_cols = S.d_cov_cols.p() + col0;
+		if(S.b_cov_sparse) {
+			std::sort(srcs.begin(), srcs.end());
+			srcs.erase(std::unique(srcs.begin(), srcs.end()), srcs.end());
+			SLAMPP_HIP_CHECK(hipMemsetAsync(S.d_cov_B.p(), 0, size_t(nc * DC) * kp * sizeof(double), st));
+			schur_cov_cols_cam_launch(DC, DP, nc, S.d_ptr.p(), S.d_brow.p(), S.d_W.p(), 0, 0, S.d_cam_csn.p(), p_cols, kp,
+				S.d_cov_B.p(), 0, 0, 0, 0, st);
+			covariance_columns_rhs_enqueue(*S.p_inner, int(srcs.size()), srcs.data(), kp, S.d_cov_B.p(), out, n_ld, col0);
+			schur_cov_interleave_launch(nc * DC, kp, out, n_ld, col0, S.d_cov_X.p(), st);
+		} else {
+			schur_cov_cols_cam_launch(DC, DP, nc, S.d_ptr.p(), S.d_brow.p(), S.d_W.p(), S.d_m_Z.p(), S.Npad, 0, p_cols, kp, 0,
+				S.d_cov_X.p(), out, n_ld, col0, st);
+		}
+		schur_cov_cols_point_launch(DC, DP, nc, S.np, S.d_ptr.p(), S.d_brow.p(), S.d_W.p(), S.d_Cinv.p(), p_cols, kp,
+			S.d_cov_X.p(), out, n_ld, col0, st);
+		col0 += kp;
+	}
+	s.Phase_End();
+	SLAMPP_HIP_CHECK(hipGetLastError());
+}
+
+void schur_cov_columns_enqueue(slampp_hip_solver &s, const double *p_values_dev, int n_cols, const int64_t *p_bcols, double *p_out_dev)
+{
+	CSchurState &S = *s.p_schur;
+	if(p_values_dev)
+		schur_invalidate_previous(&S);
+	if(S.DC == 6 && S.DP == 3)
+		schur_cov_columns_t<6, 3>(s, S, p_values_dev, n_cols, p_bcols, p_out_dev);
+	else if(S.DC == 7 && S.DP == 3)
+		schur_cov_columns_t<7, 3>(s, S, p_values_dev, n_cols, p_bcols, p_out_dev);
+	else
+		schur_cov_columns_t<3, 2>(s, S, p_values_dev, n_cols, p_bcols, p_out_dev);
 }
 
 } // namespace slampp

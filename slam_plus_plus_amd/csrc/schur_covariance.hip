@@ -1,0 +1,410 @@
+// schur_covariance.hip -- covariances of a BA system beyond the block diagonal, from its Schur complement.
+//   Lambda = | A  U |   S = A - U C^-1 U^T,  Z = S^-1,  W = U C^-1 (W_o = U_o C_p^-1 per observation o of landmark p)
+//            | U' C |
+//   Lambda^-1 = | Z          -Z W            |
+//               | -W^T Z     C^-1 + W^T Z W  |
+// Pattern (Lambda^-1 at every stored upper block of Lambda):
+//   camera blocks (a, b) of A           Z(a, b)
+//   observation (c, p)                  -T_c,  T_a = sum over the cameras b observing p of Z(a, b) W_b
+//   landmark diagonal p                 C_p^-1 + sum over the cameras a observing p of W_a^T T_a
+// so one pass over the k^2 camera pairs of a landmark gives its k cross-covariances and its diagonal block.
+// Columns: the camera part X of a pass (Z E_c for a camera column, -Z W E_p for a landmark column) comes from the dense
+// inverse or from k-column substitutions with the reduced system's sparse factor (covariance.hip); the landmark rows
+// are then -W_q^T X(cams(q)) per landmark q, plus C_p^-1 on a landmark column's own block.
+// Z is read either from the dense inverse (dense_inverse.hip: lower triangle and diagonal 64 x 64 tiles valid, element
+// (i, j) read as (max, min)) or from the sparse inverse subset on the reduced system's factor pattern (sparse_inverse.hip:
+// where a block sits and whether it is stored transposed comes from host-built tables, schur.hip).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace slampp {
+
+// N contiguous doubles, 16-byte loads where the address allows it
+template <int N>
+__device__ __forceinline__ void cov_load(double (&r_dst)[N], const double *__restrict__ p_src)
+{
+	typedef double v2f64 __attribute__((ext_vector_type(2)));
+	if((reinterpret_cast<uintptr_t>(p_src) & 15) == 0) {
+		#pragma unroll
+		for(int i = 0; i + 1 < N; i += 2) {
+			const v2f64 v = *reinterpret_cast<const v2f64*>(p_src + i);
+			r_dst[i] = v.x;
+			r_dst[i + 1] = v.y;
+		}
+		if(N & 1)
+			r_dst[N - 1] = p_src[N - 1];
+	} else {
+		#pragma unroll
+		for(int i = 0; i < N; ++ i)
+			r_dst[i] = p_src[i];
+	}
+}
+
+// t += Z(a, b) w, Z(a, b)[r, q] = p_z[r + q * n_cs] (stored as it is) or p_z[q + r * n_cs] (stored transposed); the loads
+// are contiguous runs of DC either way
+template <int DC, int DP>
+__device__ __forceinline__ void cov_zw_acc(double (&t)[DC * DP], const double *__restrict__ p_z, int64_t n_cs, bool b_tr,
+	const double (&w)[DC * DP])
+{
+	if(!b_tr) {
+		#pragma unroll
+		for(int q = 0; q < DC; ++ q) {
+			double zc[DC];
+			cov_load<DC>(zc, p_z + q * n_cs);
+			#pragma unroll
+			for(int r = 0; r < DC; ++ r) {
+				#pragma unroll
+				for(int j = 0; j < DP; ++ j)
+					t[r + j * DC] += zc[r] * w[q + j * DC];
+			}
+		}
+	} else {
+		#pragma unroll
+		for(int r = 0; r < DC; ++ r) {
+			double zr[DC];
+			cov_load<DC>(zr, p_z + r * n_cs);
+			#pragma unroll
+			for(int j = 0; j < DP; ++ j) {
+				double sum = 0;
+				#pragma unroll
+				for(int q = 0; q < DC; ++ q)
+					sum += zr[q] * w[q + j * DC];
+				t[r + j * DC] += sum;
+			}
+		}
+	}
+}
+
+// ---- pattern: the camera blocks of A (diagonal and off-diagonal), one thread per element ----
+// a_zent = 0: Z dense (leading dimension ld); else Z is the sparse inverse subset and a_zent[k] = offset * 2 + transposed of
+// block k's Z(r, c)
+template <int DC>
+__global__ void __launch_bounds__(256)
+schur_cov_cam_pattern_kernel(int64_t nc, const int64_t *__restrict__ ptr, const int32_t *__restrict__ brow,
+	const int64_t *__restrict__ a_zent, const double *__restrict__ Z, int ld, double *out)
+{
+	const int64_t gid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+	if(gid >= ptr[nc] * (DC * DC))
+		return;
+	const int64_t k = gid / (DC * DC);
+	const int e = int(gid - k * (DC * DC)), rr = e % DC, q = e / DC; // element (rr, q) of block k = Lambda^-1(r, c)
+	if(a_zent) {
+		const int64_t ent = a_zent[k], off = ent >> 1;
+		out[gid] = (ent & 1)? Z[off + q + rr * DC] : Z[off + rr + q * DC];
+		return;
+	}
+	int64_t lo = 0, hi = nc; // column of block k
+	while(hi - lo > 1) {
+		const int64_t mid = (lo + hi) >> 1;
+		if(ptr[mid] <= k) lo = mid; else hi = mid;
+	}
+	const int64_t i = int64_t(brow[k]) * DC + rr, j = lo * DC + q;
+	out[gid] = Z[size_t(i > j? i : j) + size_t(i > j? j : i) * ld];
+}
+
+// ---- pattern: the observation blocks and the diagonal block of every landmark ----
+// COV_G lanes per landmark, lane l takes the observing cameras a = l, l + COV_G, ...: T_a over all k cameras b, then its
+// cross-covariance block and its share of the diagonal; the group sums the shares by lane shuffles.  Lanes past k idle.
+enum { COV_G = 8 };
+
+template <int DC, int DP, bool SPARSE>
+__global__ void __launch_bounds__(256)
+schur_cov_point_pattern_kernel(const int64_t *__restrict__ ptr, const int32_t *__restrict__ brow, int64_t nc, int64_t np,
+	int64_t ubase, const int64_t *__restrict__ pair_ptr, const int64_t *__restrict__ pair_tab, const double *__restrict__ W,
+	const double *__restrict__ Cinv, const double *__restrict__ Z, int ld, double *out)
+{
+	const int64_t gid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+	const int64_t pt = gid / COV_G;
+	const int l = int(gid % COV_G);
+	const bool b_pt = pt < np;
+	int64_t k0 = 0, k = 0, o0 = 0;
+	if(b_pt) {
+		k0 = ptr[nc + pt];
+		k = ptr[nc + pt + 1] - k0 - 1; // the last block of the column is C_p itself
+		o0 = k0 - ptr[nc] - pt;
+	}
+	double cov[DP * DP];
+	#pragma unroll
+	for(int i = 0; i < DP * DP; ++ i)
+		cov[i] = 0;
+	for(int64_t a = l; a < k; a += COV_G) {
+		const int64_t ca = brow[k0 + a];
+		double t[DC * DP];
+		#pragma unroll
+		for(int i = 0; i < DC * DP; ++ i)
+			t[i] = 0;
+		for(int64_t b = 0; b < k; ++ b) {
+			double wb[DC * DP];
+			cov_load<DC * DP>(wb, W + (o0 + b) * (DC * DP));
+			if(SPARSE) {
+				const int64_t *tab = pair_tab + pair_ptr[pt];
+				const int64_t hi = (a > b)? a : b, lo = (a > b)? b : a;
+				const int64_t ent = tab[hi * (hi + 1) / 2 + lo]; // Z(cam_hi, cam_lo): offset * 2 + stored transposed
+				const bool b_tr = ((ent & 1) != 0) != (a < b);
+				cov_zw_acc<DC, DP>(t, Z + (ent >> 1), DC, b_tr, wb);
+			} else {
+				const int64_t cb = brow[k0 + b];
+				if(ca > cb)
+					cov_zw_acc<DC, DP>(t, Z + size_t(ca * DC) + size_t(cb * DC) * ld, ld, false, wb);
+				else if(ca < cb)
+					cov_zw_acc<DC, DP>(t, Z + size_t(cb * DC) + size_t(ca * DC) * ld, ld, true, wb);
+				else { // the diagonal block: (max, min) element by element
+					#pragma unroll
+					for(int q = 0; q < DC; ++ q) {
+						#pragma unroll
+						for(int r = 0; r < DC; ++ r) {
+							const int h = (r > q)? r : q, m = (r > q)? q : r;
+							const double z = Z[size_t(ca * DC + h) + size_t(ca * DC + m) * ld];
+							#pragma unroll
+							for(int j = 0; j < DP; ++ j)
+								t[r + j * DC] += z * wb[q + j * DC];
+						}
+					}
+				}
+			}
+		}
+		double *p_obs = out + ubase + (o0 + a) * (DC * DP) + pt * (DP * DP); // observation block (c_a, p), DC x DP
+		#pragma unroll
+		for(int i = 0; i < DC * DP; ++ i)
+			p_obs[i] = -t[i];
+		double wa[DC * DP];
+		cov_load<DC * DP>(wa, W + (o0 + a) * (DC * DP));
+		#pragma unroll
+		for(int j = 0; j < DP; ++ j) {
+			#pragma unroll
+			for(int i = 0; i < DP; ++ i) {
+				double sum = 0;
+				#pragma unroll
+				for(int r = 0; r < DC; ++ r)
+					sum += wa[r + i * DC] * t[r + j * DC];
+				cov[i + j * DP] += sum;
+			}
+		}
+	}
+	#pragma unroll
+	for(int i = 0; i < DP * DP; ++ i) {
+		#pragma unroll
+		for(int m = COV_G / 2; m > 0; m >>= 1)
+			cov[i] += __shfl_xor(cov[i], m, COV_G);
+	}
+	if(b_pt && l == 0) {
+		double *p_diag = out + ubase + (o0 + k) * (DC * DP) + pt * (DP * DP);
+		#pragma unroll
+		for(int i = 0; i < DP * DP; ++ i)
+			p_diag[i] = cov[i] + Cinv[pt * (DP * DP) + i];
+	}
+}
+
+// ---- columns ----
+// a pass's columns are described by col_src[j]: >= 0 the scalar column c * DC + s of camera c, < 0 -1 - (p * DP + s),
+// scalar column s of landmark p
+
+// dense Z: the camera part of a pass, one thread per (row i, column j); into the output (column-major, leading dimension
+// n_ld, column n_col0 + j) and into X, interleaved (X[i * kp + j]) for the landmark rows
+template <int DC, int DP>
+__global__ void __launch_bounds__(256)
+schur_cov_cols_dense_kernel(int64_t nc, const int64_t *__restrict__ ptr, const int32_t *__restrict__ brow,
+	const double *__restrict__ W, const double *__restrict__ Z, int ld, const int64_t *__restrict__ col_src, int kp,
+	double *X, double *out, int64_t n_ld, int64_t n_col0)
+{
+	const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+	const int j = blockIdx.y;
+	if(i >= nc * DC)
+		return;
+	const int64_t src = col_src[j];
+	double x;
+	if(src >= 0)
+		x = Z[size_t(i > src? i : src) + size_t(i > src? src : i) * ld];
+	else {
+		const int64_t v = -1 - src, p = v / DP, s = v - p * DP;
+		const int64_t k0 = ptr[nc + p], k = ptr[nc + p + 1] - k0 - 1, o0 = k0 - ptr[nc] - p;
+		x = 0;
+		for(int64_t a = 0; a < k; ++ a) {
+			const int64_t c0 = int64_t(brow[k0 + a]) * DC;
+			const double *w = W + (o0 + a) * (DC * DP) + s * DC;
+			#pragma unroll
+			for(int t = 0; t < DC; ++ t) {
+				const int64_t jj = c0 + t;
+				x -= Z[size_t(i > jj? i : jj) + size_t(i > jj? jj : i) * ld] * w[t];
+			}
+		}
+	}
+	X[i * kp + j] = x;
+	out[i + (n_col0 + j) * n_ld] = x;
+}
+
+// sparse factor: the right-hand sides of a pass in the factor's permuted rows, interleaved (B was zeroed); one
+// workgroup per column j
+template <int DC, int DP>
+__global__ void __launch_bounds__(64)
+schur_cov_rhs_kernel(int64_t nc, const int64_t *__restrict__ ptr, const int32_t *__restrict__ brow, const double *__restrict__ W,
+	const int64_t *__restrict__ cam_csn, const int64_t *__restrict__ col_src, int kp, double *B)
+{
+	const int j = blockIdx.x;
+	const int64_t src = col_src[j];
+	if(src >= 0) {
+		if(threadIdx.x == 0) {
+			const int64_t c = src / DC;
+			B[(cam_csn[c] + (src - c * DC)) * kp + j] = 1.0;
+		}
+		return;
+	}
+	const int64_t v = -1 - src, p = v / DP, s = v - p * DP;
+	const int64_t k0 = ptr[nc + p], k = ptr[nc + p + 1] - k0 - 1, o0 = k0 - ptr[nc] - p;
+	for(int64_t e = threadIdx.x; e < k * DC; e += blockDim.x) {
+		const int64_t a = e / DC, t = e - a * DC;
+		B[(cam_csn[brow[k0 + a]] + t) * kp + j] = -W[(o0 + a) * (DC * DP) + t + s * DC];
+	}
+}
+
+// the camera part of a pass as the substitutions left it in the output, interleaved into X
+__global__ void __launch_bounds__(256)
+schur_cov_interleave_kernel(int64_t n_rows, int kp, const double *__restrict__ out, int64_t n_ld, int64_t n_col0, double *X)
+{
+	const int64_t gid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+	if(gid >= n_rows * kp)
+		return;
+	const int64_t i = gid / kp;
+	const int j = int(gid - i * kp);
+	X[gid] = out[i + (n_col0 + j) * n_ld];
+}
+
+// the landmark rows of a pass: n_g lanes per landmark q (the power of two from kp up), lane j = column j -- a wave takes
+// 64 / n_g landmarks, so a pass of one block column does not leave most of a wave idle; the W blocks are the same address
+// for the lanes of a landmark, the camera rows of X are read as contiguous runs of kp doubles
+template <int DC, int DP>
+__global__ void __launch_bounds__(256)
+schur_cov_point_rows_kernel(int64_t nc, int64_t np, const int64_t *__restrict__ ptr, const int32_t *__restrict__ brow,
+	const double *__restrict__ W, const double *__restrict__ Cinv, const int64_t *__restrict__ col_src, int kp, int n_g,
+	const double *__restrict__ X, double *out, int64_t n_ld, int64_t n_col0)
+{
+	const int64_t gid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+	const int64_t q = gid / n_g;
+	const int j = int(gid % n_g);
+	if(q >= np || j >= kp)
+		return;
+	const int64_t k0 = ptr[nc + q], k = ptr[nc + q + 1] - k0 - 1, o0 = k0 - ptr[nc] - q;
+	double acc[DP];
+	#pragma unroll
+	for(int r = 0; r < DP; ++ r)
+		acc[r] = 0;
+	for(int64_t a = 0; a < k; ++ a) {
+		const int64_t c0 = int64_t(brow[k0 + a]) * DC;
+		double w[DC * DP], x[DC];
+		cov_load<DC * DP>(w, W + (o0 + a) * (DC * DP));
+		#pragma unroll
+		for(int t = 0; t < DC; ++ t)
+			x[t] = X[(c0 + t) * kp + j];
+		#pragma unroll
+		for(int r = 0; r < DP; ++ r) {
+			#pragma unroll
+			for(int t = 0; t < DC; ++ t)
+				acc[r] -= w[t + r * DC] * x[t];
+		}
+	}
+	const int64_t src = col_src[j];
+	if(src < 0) {
+		const int64_t v = -1 - src, p = v / DP, s = v - p * DP;
+		if(p == q) {
+			#pragma unroll
+			for(int r = 0; r < DP; ++ r)
+				acc[r] += Cinv[q * (DP * DP) + r + s * DP];
+		}
+	}
+	double *p_out = out + nc * DC + q * DP + (n_col0 + j) * n_ld;
+	#pragma unroll
+	for(int r = 0; r < DP; ++ r)
+		p_out[r] = acc[r];
+}
+
+// ---- launches ----
+
+template <int DC, int DP>
+static void pattern_t(int64_t nc, int64_t np, const int64_t *ptr, const int32_t *brow, int64_t ubase, const int64_t *a_zent,
+	const int64_t *pair_ptr, const int64_t *pair_tab, const double *W, const double *Cinv, const double *Z, int ld, double *out,
+	hipStream_t stream)
+{
+	const int64_t n_cam_elems = ubase; // (the camera blocks come first in the values: ptr[nc] blocks of DC x DC)
+	if(n_cam_elems)
+		hipLaunchKernelGGL((schur_cov_cam_pattern_kernel<DC>), dim3(unsigned((n_cam_elems + 255) / 256)), dim3(256), 0, stream,
+			nc, ptr, brow, a_zent, Z, ld, out);
+	if(np) {
+		const dim3 grid(unsigned((np * COV_G + 255) / 256));
+		if(pair_tab)
+			hipLaunchKernelGGL((schur_cov_point_pattern_kernel<DC, DP, true>), grid, dim3(256), 0, stream,
+				ptr, brow, nc, np, ubase, pair_ptr, pair_tab, W, Cinv, Z, ld, out);
+		else
+			hipLaunchKernelGGL((schur_cov_point_pattern_kernel<DC, DP, false>), grid, dim3(256), 0, stream,
+				ptr, brow, nc, np, ubase, pair_ptr, pair_tab, W, Cinv, Z, ld, out);
+	}
+}
+
+void schur_cov_pattern_launch(int DC, int DP, int64_t nc, int64_t np, const int64_t *ptr, const int32_t *brow, int64_t ubase,
+	const int64_t *a_zent, const int64_t *pair_ptr, const int64_t *pair_tab, const double *W, const double *Cinv, const double *Z,
+	int ld, double *out, hipStream_t stream)
+{
+	if(DC == 6 && DP == 3)
+		pattern_t<6, 3>(nc, np, ptr, brow, ubase, a_zent, pair_ptr, pair_tab, W, Cinv, Z, ld, out, stream);
+	else if(DC == 7 && DP == 3)
+		pattern_t<7, 3>(nc, np, ptr, brow, ubase, a_zent, pair_ptr, pair_tab, W, Cinv, Z, ld, out, stream);
+	else
+		pattern_t<3, 2>(nc, np, ptr, brow, ubase, a_zent, pair_ptr, pair_tab, W, Cinv, Z, ld, out, stream);
+}
+
+template <int DC, int DP>
+static void cols_cam_t(int64_t nc, const int64_t *ptr, const int32_t *brow, const double *W, const double *Z, int ld,
+	const int64_t *cam_csn, const int64_t *col_src, int kp, double *B, double *X, double *out, int64_t n_ld, int64_t n_col0,
+	hipStream_t stream)
+{
+	if(Z)
+		hipLaunchKernelGGL((schur_cov_cols_dense_kernel<DC, DP>), dim3(unsigned((nc * DC + 255) / 256), unsigned(kp)), dim3(256), 0,
+			stream, nc, ptr, brow, W, Z, ld, col_src, kp, X, out, n_ld, n_col0);
+	else
+		hipLaunchKernelGGL((schur_cov_rhs_kernel<DC, DP>), dim3(unsigned(kp)), dim3(64), 0, stream, nc, ptr, brow, W, cam_csn, col_src,
+			kp, B);
+}
+
+// Z given: the camera part of a pass from the dense inverse, into out and X; else the right-hand sides into B
+void schur_cov_cols_cam_launch(int DC, int DP, int64_t nc, const int64_t *ptr, const int32_t *brow, const double *W,
+	const double *Z, int ld, const int64_t *cam_csn, const int64_t *col_src, int kp, double *B, double *X, double *out,
+	int64_t n_ld, int64_t n_col0, hipStream_t stream)
+{
+	if(DC == 6 && DP == 3)
+		cols_cam_t<6, 3>(nc, ptr, brow, W, Z, ld, cam_csn, col_src, kp, B, X, out, n_ld, n_col0, stream);
+	else if(DC == 7 && DP == 3)
+		cols_cam_t<7, 3>(nc, ptr, brow, W, Z, ld, cam_csn, col_src, kp, B, X, out, n_ld, n_col0, stream);
+	else
+		cols_cam_t<3, 2>(nc, ptr, brow, W, Z, ld, cam_csn, col_src, kp, B, X, out, n_ld, n_col0, stream);
+}
+
+void schur_cov_interleave_launch(int64_t n_rows, int kp, const double *out, int64_t n_ld, int64_t n_col0, double *X,
+	hipStream_t stream)
+{
+	hipLaunchKernelGGL(schur_cov_interleave_kernel, dim3(unsigned((n_rows * kp + 255) / 256)), dim3(256), 0, stream,
+		n_rows, kp, out, n_ld, n_col0, X);
+}
+
+template <int DC, int DP>
+static void cols_point_t(int64_t nc, int64_t np, const int64_t *ptr, const int32_t *brow, const double *W, const double *Cinv,
+	const int64_t *col_src, int kp, const double *X, double *out, int64_t n_ld, int64_t n_col0, hipStream_t stream)
+{
+	int n_g = 1;
+	while(n_g < kp)
+		n_g *= 2; // (kp <= 48: n_g <= 64)
+	if(np)
+		hipLaunchKernelGGL((schur_cov_point_rows_kernel<DC, DP>), dim3(unsigned((np * n_g + 255) / 256)), dim3(256), 0, stream,
+			nc, np, ptr, brow, W, Cinv, col_src, kp, n_g, X, out, n_ld, n_col0);
+}
+
+void schur_cov_cols_point_launch(int DC, int DP, int64_t nc, int64_t np, const int64_t *ptr, const int32_t *brow, const double *W,
+	const double *Cinv, const int64_t *col_src, int kp, const double *X, double *out, int64_t n_ld, int64_t n_col0, hipStream_t stream)
+{
+	if(DC == 6 && DP == 3)
+		cols_point_t<6, 3>(nc, np, ptr, brow, W, Cinv, col_src, kp, X, out, n_ld, n_col0, stream);
+	else if(DC == 7 && DP == 3)
+		cols_point_t<7, 3>(nc, np, ptr, brow, W, Cinv, col_src, kp, X, out, n_ld, n_col0, stream);
+	else
+		cols_point_t<3, 2>(nc, np, ptr, brow, W, Cinv, col_src, kp, X, out, n_ld, n_col0, stream);
+}
+
+} // namespace slampp

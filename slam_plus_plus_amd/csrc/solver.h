@@ -171,6 +171,10 @@ struct slampp_hip_solver {
 
 	// Lambda structure as given
 	bool b_has_structure, b_analyzed, b_factored;
+	// generation of whatever factorization the handle holds: every call that factors (or fails to) counts it up.  The Schur
+	// covariance calls (slampp_hip_schur_marginals_pattern / _marginal_columns) record the generation they left, and a call
+	// with values = NULL reuses their reduced-system factor, C^-1 and W only while nothing else has run since
+	uint64_t n_factor_gen = 0, n_schur_cov_gen = 0; // (0: none)
 	int n_mode;
 	int64_t n_matrix_cut;
 	std::vector<int64_t> cumsum, bcol_ptr;
@@ -398,6 +402,10 @@ void schur_marginals_sparse_launch(int DC, int DP, int64_t nc, int64_t np, const
 void damping_enqueue(const int64_t *p_off_dim_dev, int64_t n_first, int64_t n_last, double f_alpha, double *p_values_dev,
 	hipStream_t stream); // assembly.hip
 void schur_enqueue_marginals(slampp_hip_solver &s, const double *p_values_dev, double *p_cam_cov_dev, double *p_point_cov_dev); // throws
+// Lambda^-1 on Lambda's pattern and whole block columns of it (schur_covariance.hip); p_values_dev = 0: from what the previous
+// of these calls left in place (the caller checks that it is still valid).  Throw.
+void schur_cov_pattern_enqueue(slampp_hip_solver &s, const double *p_values_dev, double *p_cov_dev);
+void schur_cov_columns_enqueue(slampp_hip_solver &s, const double *p_values_dev, int n_cols, const int64_t *p_bcols, double *p_out_dev);
 size_t schur_device_bytes(const CSchurState *p);
 void schur_invalidate_previous(CSchurState *p); // the kept reduced system no longer matches what the caller last solved
 void schur_set_changed_points(slampp_hip_solver &s, const int64_t *p_points, int64_t n_points); // throws

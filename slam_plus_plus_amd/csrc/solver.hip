@@ -197,6 +197,7 @@ void slampp_hip_solver::Free_Device()
 	}
 	b_analyzed = false;
 	b_factored = false;
+	++ n_factor_gen;
 }
 
 size_t slampp_hip_solver::n_Device_Bytes() const

@@ -128,6 +128,10 @@ ABI = {
     "slampp_hip_marginal_columns_device_async": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "slampp_hip_schur_marginals": (C.c_int, [_P, _P, _P, _P]),
     "slampp_hip_schur_marginals_device_async": (C.c_int, [_P, _P, _P, _P]),
+    "slampp_hip_schur_marginals_pattern": (C.c_int, [_P, _P, _P]),
+    "slampp_hip_schur_marginals_pattern_device_async": (C.c_int, [_P, _P, _P]),
+    "slampp_hip_schur_marginal_columns": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "slampp_hip_schur_marginal_columns_device_async": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "slampp_hip_factor_solve_device_async": (C.c_int, [_P, _P, _P]),
     "slampp_hip_sync": (C.c_int, [_P]),
     "slampp_hip_factor_solve_batch_device_async": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64]),
@@ -685,6 +689,49 @@ class CLinearSolver_Schur_HIP(_SolverBase):
     def schur_marginals_device_async(self, values_ptr: int, cam_cov_ptr: int, point_cov_ptr: int) -> None:
         self._check(self._lib.slampp_hip_schur_marginals_device_async(self._h, values_ptr, cam_cov_ptr or None,
                                                                       point_cov_ptr or None))
+
+    def Marginals_Pattern(self, lam, reuse_factor: bool = False) -> np.ndarray:
+        """Lambda^-1 at every stored block of Lambda (camera blocks, camera-landmark observation blocks, landmark
+        diagonal blocks): an array shaped like ``lam.values``, each block column-major.  ``reuse_factor``: the reduced
+        system's factor, C^-1 and W the previous Marginals_Pattern / Marginal_Columns call left are used (ValueError
+        if anything else factored since)."""
+        if reuse_factor:
+            if not self._analyzed or self._structure_key != self._key(lam):
+                raise ValueError("Marginals_Pattern: there is no factorization of this structure to reuse")
+            vals = None
+        else:
+            if not self._analyzed or self._structure_key != self._key(lam):
+                self.SymbolicDecomposition_Blocky(lam, True)
+            vals = np.ascontiguousarray(lam.values, dtype=np.float64)
+            if vals.shape != (self._n_values,):
+                raise ValueError("lam.values does not match the block structure")
+        out = np.empty(self._n_values, dtype=np.float64)
+        if not self._check(self._lib.slampp_hip_schur_marginals_pattern(self._h, _ptr(vals) if vals is not None else None,
+                                                                        _ptr(out))):
+            raise ArithmeticError("Marginals_Pattern: the system is not positive definite")
+        return out
+
+    def Marginal_Columns(self, lam, bcols, reuse_factor: bool = False) -> np.ndarray:
+        """Whole block columns ``bcols`` (cameras and landmarks in any mix) of Lambda^-1, shape (n_scalars, k), in the
+        listed order.  ``reuse_factor``: what the previous Marginals_Pattern / Marginal_Columns call left is used."""
+        cols = np.ascontiguousarray(np.atleast_1d(np.asarray(bcols, dtype=np.int64)))
+        if reuse_factor:
+            if not self._analyzed or self._structure_key != self._key(lam):
+                raise ValueError("Marginal_Columns: there is no factorization of this structure to reuse")
+            vals = None
+        else:
+            if not self._analyzed or self._structure_key != self._key(lam):
+                self.SymbolicDecomposition_Blocky(lam, True)
+            vals = np.ascontiguousarray(lam.values, dtype=np.float64)
+            if vals.shape != (self._n_values,):
+                raise ValueError("lam.values does not match the block structure")
+        dims = np.diff(np.asarray(lam.cumsum, dtype=np.int64))
+        k = int(dims[cols].sum()) if cols.size and cols.min() >= 0 and cols.max() < len(dims) else 0
+        out = np.empty((max(k, 1), int(lam.cumsum[-1])), dtype=np.float64)   # column-major (n_scalars, k)
+        if not self._check(self._lib.slampp_hip_schur_marginal_columns(self._h, _ptr(vals) if vals is not None else None,
+                                                                      int(cols.size), _ptr(cols), _ptr(out))):
+            raise ArithmeticError("Marginal_Columns: the system is not positive definite")
+        return out[:k].T
 
 
 class CLambdaAssembly_HIP:
