@@ -10,6 +10,7 @@ are in DESIGN.md, never here.
 
   python bench.py --gpus 1 --steps 20 --warmup 3            # default workload: C3, 100k-pose SE(3)
   python bench.py --workload ba                             # C4: 1k cams x 500k points, Schur path
+  python bench.py --full                                    # every leg, baseline and split beside the headline (minutes)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Multi-GPU (N > 1): the headline is STRONG scaling of one fixed BA system -- BASELINE config 5, 2 000 cameras x
@@ -18,6 +19,16 @@ Multi-GPU (N > 1): the headline is STRONG scaling of one fixed BA system -- BASE
 packed blocks of the reduced camera system per step; "scaling": "strong".  The N = 1 line carries the same two systems
 on one GPU (`ba_c5`, `ba_1k_1m`), so the curve has its first point.  The pose-graph factorization does not shard (one
 elimination tree): at N > 1 it runs as N independent replicas and is reported beside the headline (`pose_graph_replicas`).
+
+A plain run does what the headline needs and nothing else: it builds the headline's system, warms up, times the steps,
+checks the last solution's residual and prints the line.  With --dump-outputs every timed leg runs (its timed steps alone),
+so that the files are those of every leg, as --full writes them.  `--full` adds everything else the
+benchmark measures: the cold analyses in a process of their own, the other workloads, sizes and visibility models (C1,
+C2, C4 band / uniform / Venice-like, C5, 1k x 1M), the CPU and reference baselines, the per-kernel split and the
+rooflines it feeds (extra untimed steps), host paths, marginals, assembly, replicas, the scaling model and, at N > 1,
+the north star's system, the pose-graph replicas and the one-process device group.  A plain run's `roofline` is null (the
+time-dominant kernel is known only from the split); `roofline_leaf_kernel` and `roofline_whole_step` come from the timed
+region and stay.
 
 One JSON line on stdout (rank 0).  `value` = algorithmic GFLOP/s of the whole job; `ms_per_step` =
 wall-clock per Lambda solve; `roofline` = dominant kernel against HBM peak, timed with HIP events
@@ -115,7 +126,10 @@ def main():
     ap.add_argument("--group-reps", type=int, default=3, help="warm solves of the in-library device group leg (--gpus N, N > 1)")
     ap.add_argument("--no-group-leg", action="store_true", help="leave out the one-process device group leg at N > 1")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
-                    help="after the timed steps, write what each timed leg computed in its last step to DIR/<name>.npy (float64, 64 MB at most)")
+                    help="after the timed steps, write what each timed leg computed in its last step to DIR/<name>.npy (float64, 64 MB at most); "
+                         "without --full every timed leg then runs, its timed steps alone")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline's timed steps, run every other leg, baseline and split as well (see the module docstring)")
     ap.add_argument("--no-cold-process", action="store_true", help="leave out the cold analyses in a process of their own (bench_legs/cold.py): analyze_ms_cold is then the in-process number")
     args = ap.parse_args()
 
@@ -137,8 +151,11 @@ def main():
         local_rank = 0
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     legs = [m for m in args.ba_legs.split(",") if m]
+    # --dump-outputs asks for what EVERY timed leg computed: without --full those legs run too, as their timed steps and
+    # nothing beside them (no split, baseline or side leg); a plain run without it is the headline's leg alone
+    every_leg = args.full or args.dump_outputs is not None
     cold_res, cold_specs = None, {}
-    if world == 1 and args.workload == "all" and not args.ba_solve_only and not args.c3_solve_only and not args.no_cold_process:
+    if args.full and world == 1 and args.workload == "all" and not args.ba_solve_only and not args.c3_solve_only and not args.no_cold_process:
         # the cold analyses first, in a process of their own, while this one holds nothing yet (bench_legs/cold.py: beside a parent
         # that held the bench's systems and tensors the child measured C5 at 73-83 ms, on its own at 52-58)
         from bench_legs import cold
@@ -187,6 +204,8 @@ def main():
         # graph (does not shard) as N replicas, reported but not the headline
         strong = [(key, c, p) for key, c, p in (("ba_c5", args.c5_cams, args.c5_points), ("ba_1k_1m", args.target_cams, args.target_points))
                   if args.workload in ("all", "ba")]
+        if not every_leg:       # the headline's system alone
+            strong = strong[:1]
         for i, (key, c, p) in enumerate(strong):
             leg = run_ba(args, rank, world, local_rank, dist, mode=args.c5_mode, extras=False, cams=c, points=p,
                          label="C5" if key == "ba_c5" else "north-star target")
@@ -194,7 +213,7 @@ def main():
                 if out is None:
                     out = promote(leg, "strong")
                 out[key] = leg
-        if args.workload in ("all", "c3"):
+        if args.workload == "c3" or (args.workload == "all" and every_leg):
             c3 = run_c3(args, rank, world, local_rank, dist)
             if rank == 0:
                 if out is None:
@@ -205,26 +224,27 @@ def main():
         if args.workload in ("all", "c3"):
             out = run_c3(args, rank, world, local_rank, dist)
         if args.workload == "small":
-            small = run_small_configs(args, local_rank)
+            which = [k_ for k_ in args.small_configs.split(",") if k_]
+            small = run_small_configs(args, local_rank, which=which if every_leg else sorted(which)[-1:])
             first = small[sorted(small)[-1]]
             out = {"metric": "Lambda solve ms (numeric factor + 2 substitutions)", "value": first["ms_per_solve"], "unit": "ms",
                    "n_gpus": 1, "steps": 20, "warmup": 1, "ms_per_step": first["ms_per_solve"], "higher_is_better": False,
                    "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
                    "config": {"workload": first["workload"]}, "roofline": first.get("roofline"), "other_configs": small}
-        if args.workload in ("all", "ba"):
+        if args.workload == "ba" or (args.workload == "all" and every_leg):
             # BASELINE config 4 is "Venice-style": that leg is `ba_schur`; band and uniform visibility (SURVEY.md section 8d:
             # "band (sparse S) or uniformly (dense S -- report both)") ride beside it
             first = legs[0]
-            ba = run_ba(args, rank, world, local_rank, dist, mode=first, extras=not args.ba_solve_only)
+            ba = run_ba(args, rank, world, local_rank, dist, mode=first, extras=args.full and not args.ba_solve_only)
             if out is None:   # BA only: promote it to the headline
                 out = promote(ba, "weak")
             out["ba_schur"] = ba
             if args.workload == "all":
                 out["other_configs"] = run_small_configs(args, local_rank)
             for key, mode in (("ba_schur_band", "band"), ("ba_schur_uniform_dense_S", "uniform"), ("ba_schur_venice", "venice")):
-                if mode in legs[1:]:
+                if every_leg and mode in legs[1:]:
                     out[key] = run_ba(args, rank, world, local_rank, dist, mode=mode, extras=False)
-            if args.workload == "all" and not args.ba_solve_only:
+            if args.workload == "all" and not args.ba_solve_only:     # (`all` reaches here with every leg only)
                 # the N = 1 points of the strong-scaling curves `bench.py --gpus N` reports
                 out["ba_c5"] = run_ba(args, rank, world, local_rank, dist, mode=args.c5_mode, extras=False, cams=args.c5_cams,
                                       points=args.c5_points, label="C5")
@@ -237,7 +257,7 @@ def main():
                                             "ms_per_step": out["ba_c5"].get("ms_per_step"),
                                             "workload": out["ba_c5"].get("workload"),
                                             "note": "the N = 1 point of the curve bench.py --gpus N (N > 1) reports as `value`"}
-    if rank == 0 and world == 1 and out is not None and out.get("ba_c5"):
+    if args.full and rank == 0 and world == 1 and out is not None and out.get("ba_c5"):
         # both strong-scaling systems, device-resident and from host arrays
         out["scaling_model"] = {key: scaling_model(out[key], out[key].get("n_values"), out[key].get("n_scalars"),
                                                    out[key].get("n_exchange_doubles"))
@@ -272,7 +292,7 @@ def main():
         dist.destroy_process_group()
     if rank != 0:
         return
-    if world > 1 and out is not None and args.workload in ("all", "ba") and not args.no_group_leg:
+    if args.full and world > 1 and out is not None and args.workload in ("all", "ba") and not args.no_group_leg:
         # the same fixed C5 system through ONE handle over the N devices (what SLAMPP_HIP_DEVICES gives an unchanged SLAM++
         # binary), after the process group is gone: the other ranks have left their devices
         time.sleep(1.0)

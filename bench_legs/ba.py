@@ -204,19 +204,23 @@ def run_ba(args, rank, world, local_rank, dist, schur_sparse=-1, mode="band", ex
     if not ok:
         raise SystemExit("BA solve failed: not positive definite")
     prof = {k_: v[1] / max(v[0], 1) for k_, v in solver.profile().items()}   # timed region: the roofline kernels' phases
-    # the other phases from three extra, untimed steps with every phase bracketed (an event pair costs microseconds);
-    # every rank runs them: the solve holds a collective
-    solver.set_option("profile", 1)
-    solver.profile(reset=True)
-    extra_rhs = [torch.from_numpy(lam.rhs).to(dev) for _ in range(3)]
-    torch.cuda.synchronize()
-    for t_ in extra_rhs:
-        solver.factor_solve_device_async(vals.data_ptr(), t_.data_ptr())
-    solver.sync()
-    del extra_rhs
-    prof = dict({k_: v[1] / max(v[0], 1) for k_, v in solver.profile().items()}, **prof)
-    # ... and the same three steps under the names the reference prints with __SCHUR_PROFILING (LinearSolver_Schur.h:1895-1912)
-    prof_ref_names = {k_: v[1] / max(v[0], 1) for k_, v in solver.profile_reference_names().items()}
+    full = getattr(args, "full", True)
+    prof_ref_names = None
+    if full:
+        # the other phases from three extra, untimed steps with every phase bracketed (an event pair costs microseconds);
+        # every rank runs them: the solve holds a collective.  Without --full the phases are the timed region's alone, and
+        # the rooflines that need the others (all of the assembly, the reduced system, the time-dominant phase) are left out
+        solver.set_option("profile", 1)
+        solver.profile(reset=True)
+        extra_rhs = [torch.from_numpy(lam.rhs).to(dev) for _ in range(3)]
+        torch.cuda.synchronize()
+        for t_ in extra_rhs:
+            solver.factor_solve_device_async(vals.data_ptr(), t_.data_ptr())
+        solver.sync()
+        del extra_rhs
+        prof = dict({k_: v[1] / max(v[0], 1) for k_, v in solver.profile().items()}, **prof)
+        # ... and the same three steps under the names the reference prints with __SCHUR_PROFILING (LinearSolver_Schur.h:1895-1912)
+        prof_ref_names = {k_: v[1] / max(v[0], 1) for k_, v in solver.profile_reference_names().items()}
     solver.profile(reset=True)
     red = solver.reduced_stats()
     x_local = bufs[-1].cpu().numpy()
@@ -311,20 +315,21 @@ def run_ba(args, rank, world, local_rank, dist, schur_sparse=-1, mode="band", ex
             "traffic_source": traffic_file,
             "traffic_measured_in": "builder's rocprofv3 --pmc run (replayed from the committed file)" if traffic_file else None,
             "algorithmic_bytes_per_step": nbytes, "ms_per_step": prof["schur_tiles"]}
-        # ... and over EVERY assembly kernel of the step (run / tile / reduce kernels + what the contribution lists of the
-        # landmarks in no run or tile cost: C^-1, W, gather, right-hand side), on the same algorithmic bytes: what the
-        # reference's steps a13-a18 (LinearSolver_Schur.h:1743-1767) cost here as a whole
-        asm_ms = sum(prof.get(k_, 0.0) for k_ in ("schur_tiles", "schur_gather", "schur_points", "schur_rhs", "schur_init"))
-        tr_all = None
-        if traffic:
-            parts = [kernel_traffic_sum(traffic, k_) for k_ in ("schur_run_kernel", "schur_tile_kernel", "schur_tile_reduce_kernel", "schur_gather_S_kernel",
-                                                                "schur_obs_W_kernel", "schur_rhs_kernel", "schur_point_inverse_kernel", "schur_scatter_A_kernel",
-                                                                "schur_wide_kernel")]
-            tr_all = sum(p for p in parts if p) or None
-        out["roofline_schur_assembly_all"] = {
-            "bound": "hbm", "kernel": "every kernel of the assembly of S and r (landmark-major runs / tiles / reduction + contribution lists)",
-            "achieved": nbytes / (asm_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": nbytes / (asm_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-            "traffic": tr_all, "traffic_source": traffic_file, "algorithmic_bytes_per_step": nbytes, "ms_per_step": asm_ms}
+        if full:      # (needs the phases of the extra steps)
+            # ... and over EVERY assembly kernel of the step (run / tile / reduce kernels + what the contribution lists of the
+            # landmarks in no run or tile cost: C^-1, W, gather, right-hand side), on the same algorithmic bytes: what the
+            # reference's steps a13-a18 (LinearSolver_Schur.h:1743-1767) cost here as a whole
+            asm_ms = sum(prof.get(k_, 0.0) for k_ in ("schur_tiles", "schur_gather", "schur_points", "schur_rhs", "schur_init"))
+            tr_all = None
+            if traffic:
+                parts = [kernel_traffic_sum(traffic, k_) for k_ in ("schur_run_kernel", "schur_tile_kernel", "schur_tile_reduce_kernel", "schur_gather_S_kernel",
+                                                                    "schur_obs_W_kernel", "schur_rhs_kernel", "schur_point_inverse_kernel", "schur_scatter_A_kernel",
+                                                                    "schur_wide_kernel")]
+                tr_all = sum(p for p in parts if p) or None
+            out["roofline_schur_assembly_all"] = {
+                "bound": "hbm", "kernel": "every kernel of the assembly of S and r (landmark-major runs / tiles / reduction + contribution lists)",
+                "achieved": nbytes / (asm_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": nbytes / (asm_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                "traffic": tr_all, "traffic_source": traffic_file, "algorithmic_bytes_per_step": nbytes, "ms_per_step": asm_ms}
     if "schur_gather" in prof and prof["schur_gather"] > 0.02 and "schur_tiles" not in prof:
         gb = (288.0 * st["n_update_pairs"] + 2 * 8.0 * 36 * st["l_blocks"]) / (prof["schur_gather"] * 1e-3) / 1e9
         out["roofline_schur_gather"] = {"bound": "hbm", "kernel": "schur_gather_S_kernel", "achieved": gb, "peak": HBM_PEAK_GBS,
@@ -356,7 +361,7 @@ def run_ba(args, rank, world, local_rank, dist, schur_sparse=-1, mode="band", ex
                 "roofline_schur_gather": prof.get("schur_gather", 0.0),
                 "roofline_reduced_sparse": prof.get("reduced_sparse", 0.0)}
     present = [k_ for k_ in phase_ms if k_ in out]
-    if present:
+    if present and full:
         k_dom = max(present, key=lambda k_: phase_ms[k_])
         out["roofline"] = dict(out[k_dom], name=k_dom, phase_ms=phase_ms[k_dom], share_of_step=phase_ms[k_dom] / ms,
                                other_phases_ms={k_: phase_ms[k_] for k_ in present if k_ != k_dom})

@@ -302,18 +302,21 @@ def run_c3(args, rank, world, local_rank, dist):
     resid = float(np.abs(lam.to_scipy() @ x - lam.rhs).max() / np.abs(lam.rhs).max())
     ms_per_step = dt / args.steps * 1e3
     prof = solver.profile()          # timed region: one event pair, around the leaf kernel (option profile = 3)
-    # the split of the table below comes from a few extra, untimed steps: every event pair between two kernels costs
-    # microseconds of stream time, and the timed region carries only the one the roofline needs
-    solver.set_option("profile", 2)
-    solver.profile(reset=True)
-    extra = [rhs0.clone() for _ in range(5)]
-    for t_ in extra:
-        solver.factor_solve_device_async(vals.data_ptr(), t_.data_ptr())
-    solver.sync()
-    prof_fine = solver.profile()
-    solver.set_option("profile", 3)
-    solver.profile(reset=True)
-    prof = dict(prof_fine, **{k_: v_ for k_, v_ in prof.items() if k_ in ("factor_leaves",)})
+    full = getattr(args, "full", True)
+    if full:
+        # the split of the table below comes from a few extra, untimed steps: every event pair between two kernels costs
+        # microseconds of stream time, and the timed region carries only the one the roofline needs.  Without --full the
+        # table holds the leaf kernel alone, and the time-dominant kernel's `roofline` is not known
+        solver.set_option("profile", 2)
+        solver.profile(reset=True)
+        extra = [rhs0.clone() for _ in range(5)]
+        for t_ in extra:
+            solver.factor_solve_device_async(vals.data_ptr(), t_.data_ptr())
+        solver.sync()
+        prof_fine = solver.profile()
+        solver.set_option("profile", 3)
+        solver.profile(reset=True)
+        prof = dict(prof_fine, **{k_: v_ for k_, v_ in prof.items() if k_ in ("factor_leaves",)})
     n_stages, n_bottom = stats["n_stages"], stats["n_bottom_stages"]
     kb = per_kernel_bytes_sparse(solver.plan(), n_bottom)
     # the separator stages are one launch each -- the tasks as panels in LDS, next to them the updates the NEXT stage's blocks
@@ -344,7 +347,7 @@ def run_c3(args, rank, world, local_rank, dist):
     kernels.sort(key=lambda k: -k["ms_per_step"])
     gpu_ms = sum(k["ms_per_step"] for k in kernels)
     for k in kernels:
-        k["share_of_step_time"] = k["ms_per_step"] / gpu_ms if gpu_ms > 0 else None
+        k["share_of_step_time"] = k["ms_per_step"] / gpu_ms if full and gpu_ms > 0 else None
     # two roofline objects: `roofline` is for the kernel the step spends most of its time in (since round 3 the panel kernel of
     # the separator slices: a chain of launches of 0.1-4 MB each, bound by dependent latency, and priced as what it is);
     # `roofline_leaf_kernel` for the one that moves the step's bytes -- the leaf kernel reads nearly all of Lambda and writes
@@ -373,14 +376,14 @@ def run_c3(args, rank, world, local_rank, dist):
                         "solve_bytes": counts["solve_bytes"], "source": counts["source"]},
         "own_ordering": {"l_nnz": stats["l_nnz"], "factor_flops": stats["factor_flops"], "n_stages": n_stages,
                          "n_tasks": stats["n_tasks"], "analyze_ms_cold": analyze_ms},
-        "roofline": roofline_of(dom), "roofline_leaf_kernel": roofline_of(leaf),
+        "roofline": roofline_of(dom) if full else None, "roofline_leaf_kernel": roofline_of(leaf),
         "kernels": kernels,
         "roofline_whole_step": {"bound": "hbm", "achieved": (counts["factor_bytes"] + counts["solve_bytes"]) / (dt / args.steps) / 1e9,
                                 "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                 "frac": (counts["factor_bytes"] + counts["solve_bytes"]) / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
-                                "launches_per_step": int(sum(k["launches_per_step"] for k in kernels))},
+                                "launches_per_step": int(sum(k["launches_per_step"] for k in kernels)) if full else None},
     }
-    if args.c3_solve_only:     # (the profiling passes: per-kernel averages of the solve alone)
+    if args.c3_solve_only or not full:     # (the profiling passes: per-kernel averages of the solve alone)
         return out
     out["assembly"] = assembly_leg(solver, lam, dev)
     if world == 1:

@@ -17,17 +17,20 @@ from .c3 import *  # noqa: F401,F403
 __all__ = ['run_small_configs']
 
 
-def run_small_configs(args, local_rank):
+def run_small_configs(args, local_rank, which=None):
     """BASELINE.json configs[0] and configs[1] (parity-test cases, not the benchmark workload): the Manhattan3500 SE(2)
     and Sphere2500 SE(3) look-alikes, warm numeric factor + solve on the GPU next to the reference's CHOLMOD on the
-    host.  Reported as extra objects of the JSON line; N = 1 only."""
+    host.  Reported as extra objects of the JSON line; N = 1 only.  `which`: the configs to run (default
+    --small-configs); the split of the step, its rooflines and the reference's times only under --full."""
     import torch
     from slam_plus_plus_amd import synth
     from slam_plus_plus_amd.hip_solver import CLinearSolver_HIP
     from oracle import oracle_lib as O
     dev = torch.device(f"cuda:{local_rank}")
     out = {}
-    which = [k_ for k_ in args.small_configs.split(",") if k_]
+    if which is None:
+        which = [k_ for k_ in args.small_configs.split(",") if k_]
+    full = getattr(args, "full", True)
     for key, name, make in (("C1", "Manhattan3500 SE(2) look-alike, 3x3 blocks", lambda: synth.manhattan(3500)),
                             ("C2", "Sphere2500 SE(3) look-alike, 6x6 blocks", lambda: synth.sphere(50, 50))):
         if key not in which:
@@ -52,6 +55,9 @@ def run_small_configs(args, local_rank):
         rec = {"workload": f"{name}, n={lam.n_scalars}", "ms_per_solve": ms, "analyze_ms_cold": analyze_ms,
                "dense_top_dim": st["schur_dim"], "n_stages": st["n_stages"],
                "solve_residual_rel_inf": float(np.abs(lam.to_scipy() @ x - lam.rhs).max() / np.abs(lam.rhs).max())}
+        if not full:
+            out[key] = rec
+            continue
         # the split of the step (five extra solves with every phase bracketed by events) and its roofline: the big separators
         # of a 2-D-like graph are factored as one dense matrix on the matrix cores (the "dense top": the flops of its columns
         # under our ordering, sum of squared column counts, against the fp64 MFMA peak); the block-by-block part below it is

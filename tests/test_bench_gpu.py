@@ -1,5 +1,6 @@
 """bench.py itself, at toy sizes: the one JSON line with its roofline objects, and the two-rank path (two processes on one GPU
-over gloo: SLAMPP_BENCH_ONE_DEVICE) -- every rank has to walk through the same solves, the BA solve holds a collective."""
+over gloo: SLAMPP_BENCH_ONE_DEVICE) -- every rank has to walk through the same solves, the BA solve holds a collective.  What
+sits beside the headline (other legs, baselines, the per-kernel split, the device group) runs under --full only."""
 import json
 import os
 import socket
@@ -10,6 +11,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FULL = ["--full"]
 SMALL = ["--poses", "3000", "--ba-cams", "60", "--ba-points", "4000", "--steps", "3", "--warmup", "1", "--ba-steps", "2",
          "--no-cpu-baseline", "--ba-legs", "band", "--c5-cams", "60", "--c5-points", "6000", "--target-cams", "40", "--target-points", "3000"]
 
@@ -33,8 +35,8 @@ def last_json(text, full=True):
 
 
 @pytest.mark.parametrize("workload", ["c3", "ba"])
-def test_bench_line(workload):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--full-json", f"gpurun_out/test_bench_{workload}.json"] + SMALL,
+def test_bench_line(workload, tmp_path):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--full-json", str(tmp_path / "full.json")] + FULL + SMALL,
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = last_json(r.stdout, full=False)
@@ -67,6 +69,44 @@ def test_bench_dump_outputs_are_the_last_step_solutions(workload, tmp_path):
     assert np.abs(lam.to_scipy() @ x - lam.rhs).max() / np.abs(lam.rhs).max() < 1e-9
 
 
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full: the headline's steps, its residual check and the line -- no other leg, no baseline, no per-kernel
+    split (the time-dominant kernel's `roofline` comes from that split: null here)."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full-json", str(tmp_path / "full.json")] + SMALL,
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = last_json(r.stdout, full=False)
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["higher_is_better"] and line["dtype"] == "f64" and "C3" in line["config"]["workload"]
+    assert line["roofline"] is None and line["cpu_baseline"] is None and "legs" not in line
+    assert line["roofline_leaf_kernel"]["frac"] > 0 and line["roofline_whole_step"]["frac"] > 0
+    d = last_json(r.stdout)
+    assert d["solve_residual_rel_inf"] < 1e-9
+    for key in ("ba_schur", "ba_c5", "other_configs", "assembly", "replicas_one_gpu", "marginals", "host_path", "scaling_model"):
+        assert key not in d, key
+    assert [k["timed_in"] for k in d["kernels"]] == ["timed region"]
+
+
+def test_bench_dump_outputs_without_full_writes_every_timed_leg(tmp_path):
+    """--dump-outputs without --full: every timed leg runs (its timed steps alone), so the files are the same set --full
+    writes; nothing beside the timed steps (baselines, split, side legs) runs."""
+    import numpy as np
+    from slam_plus_plus_amd import synth
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full-json", str(tmp_path / "full.json"),
+                        "--dump-outputs", str(tmp_path / "out")] + SMALL, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert sorted(os.listdir(tmp_path / "out")) == ["C1_x.npy", "C2_x.npy", "ba_40x3000_band_x.npy", "ba_60x4000_band_x.npy",
+                                                    "ba_60x6000_band_x.npy", "c3_x.npy"]
+    line = last_json(r.stdout, full=False)
+    assert line["roofline"] is None and line["cpu_baseline"] is None and "scaling_model" not in line
+    d = last_json(r.stdout)
+    for key in ("assembly", "replicas_one_gpu", "marginals", "host_path"):
+        assert key not in d and key not in d["ba_schur"], key
+    for name, lam in (("c3_x", synth.pose_chain(n=3000)), ("ba_60x6000_band_x", synth.ba(60, 6000, k=4, mode="band", seed=777))):
+        x = np.load(tmp_path / "out" / f"{name}.npy")
+        assert np.abs(lam.to_scipy() @ x - lam.rhs).max() / np.abs(lam.rhs).max() < 1e-9, name
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -74,13 +114,13 @@ def _free_port():
 
 
 @pytest.mark.parametrize("world", [2, 3])
-def test_bench_ranks_on_one_device_strong_scaling(world):
+def test_bench_ranks_on_one_device_strong_scaling(world, tmp_path):
     """`--gpus N`: one fixed BA system cut into N landmark shards (strong scaling), every rank's phases with the all-reduce in
     them, and the residual of the FULL system assembled from the ranks' pieces -- the parity guard of the sharded solve."""
     env = dict(os.environ, SLAMPP_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--full-json",
-           f"gpurun_out/test_bench_ranks{world}.json"] + SMALL
+           str(tmp_path / "full.json")] + FULL + SMALL
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = last_json(r.stdout, full=False)
@@ -98,8 +138,8 @@ def test_bench_ranks_on_one_device_strong_scaling(world):
     assert d["pose_graph_replicas"]["scaling"] == "weak"
 
 
-def test_bench_default_run_carries_the_n1_points_of_the_scaling_curves():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full-json", "gpurun_out/test_bench_default.json"] + SMALL,
+def test_bench_default_run_carries_the_n1_points_of_the_scaling_curves(tmp_path):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full-json", str(tmp_path / "full.json")] + FULL + SMALL,
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = last_json(r.stdout, full=False)
@@ -126,14 +166,14 @@ def test_bench_default_run_carries_the_n1_points_of_the_scaling_curves():
     assert d["own_ordering"]["analyze_ms_cold_in_bench_process"] > 0 and "analyze_ms_cold_process" not in d
 
 
-def test_bench_c3_with_the_reference_prints_conditioning_beside_the_error():
+def test_bench_c3_with_the_reference_prints_conditioning_beside_the_error(tmp_path):
     """"the acceptance report must print cond-proxy + inter-oracle spread beside our error" -- and the
     three like-for-like ratios that replaced round 4's single speed-up figure."""
     from oracle import oracle_lib as O
     if not O.have_reference():
         pytest.skip("oracle/_ref/ref_harness not built")
     args = [a for a in SMALL if a != "--no-cpu-baseline"] + ["--workload", "c3"]
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full-json", "gpurun_out/test_bench_c3_ref.json"] + args,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full-json", str(tmp_path / "full.json")] + FULL + args,
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = last_json(r.stdout, full=False)
@@ -141,14 +181,14 @@ def test_bench_c3_with_the_reference_prints_conditioning_beside_the_error():
     assert "numeric_phases_device_resident" in line["speedup_vs_reference"]
 
 
-def test_bench_gpus_2_without_a_launcher_starts_two_ranks():
+def test_bench_gpus_2_without_a_launcher_starts_two_ranks(tmp_path):
     """`python bench.py --gpus 2` by itself: the ranks are started by bench.py (here both on device 0: SLAMPP_BENCH_ONE_DEVICE), the
     line says n_gpus 2 -- never a silent one-GPU run."""
     env = dict(os.environ, SLAMPP_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "ba", "--full-json",
-                        "gpurun_out/test_bench_spawn2.json"] + SMALL, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        str(tmp_path / "full.json")] + FULL + SMALL, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = last_json(r.stdout, full=False)
     assert line["n_gpus"] == 2 and line["scaling"] == "strong"

@@ -56,6 +56,12 @@ def test_gpus_n_without_devices_fails_loudly():
     assert r.returncode != 0 and not [l for l in r.stdout.splitlines() if l.startswith("{")]
 
 
+def test_full_is_an_option_off_by_default():
+    """Everything beside the headline's steps sits behind --full; a plain run leaves it out."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0 and "[--full]" in r.stdout
+
+
 def test_dump_outputs_stays_in_budget_and_samples_the_same_entries(tmp_path):
     """--dump-outputs: float64 .npy files, 64 MB at most in all; an array over its share is a fixed sample, the same every run."""
     import numpy as np

@@ -11,12 +11,12 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # leg name -> bench.py arguments (the solve alone: no host-path / marginals / assembly legs launching the same kernels)
 declare -A LEG
-LEG[c3]="--workload c3 --steps 20 --warmup 3 --no-cpu-baseline --c3-solve-only"
-LEG[ba_venice]="--workload ba --ba-legs venice --ba-steps 5 --no-cpu-baseline --ba-solve-only"
-LEG[ba_band]="--workload ba --ba-legs band --ba-steps 5 --no-cpu-baseline --ba-solve-only"
-LEG[ba_uniform]="--workload ba --ba-legs uniform --ba-steps 5 --no-cpu-baseline --ba-solve-only"
-LEG[c2]="--workload small --small-configs C2 --no-cpu-baseline"
-LEG[c1]="--workload small --small-configs C1 --no-cpu-baseline"
+LEG[c3]="--full --workload c3 --steps 20 --warmup 3 --no-cpu-baseline --c3-solve-only"
+LEG[ba_venice]="--full --workload ba --ba-legs venice --ba-steps 5 --no-cpu-baseline --ba-solve-only"
+LEG[ba_band]="--full --workload ba --ba-legs band --ba-steps 5 --no-cpu-baseline --ba-solve-only"
+LEG[ba_uniform]="--full --workload ba --ba-legs uniform --ba-steps 5 --no-cpu-baseline --ba-solve-only"
+LEG[c2]="--full --workload small --small-configs C2 --no-cpu-baseline"
+LEG[c1]="--full --workload small --small-configs C1 --no-cpu-baseline"
 for L in c3 ba_venice ba_band ba_uniform c2 c1; do
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${L}_trace -- python3 $R/bench.py ${LEG[$L]} --full-json gpurun_out/$TAG/${L}_bench_full_under_rocprof.json > $OUT/${L}_bench_under_rocprof.json 2> $OUT/${L}_trace.err
   f=$(find $OUT/${L}_trace -name "*kernel_stats.csv" | head -1)

@@ -1,7 +1,8 @@
 #!/bin/bash
-python bench.py --full-json gpurun_out/r06_bench_full.json > gpurun_out/r06_bench.json 2> gpurun_out/r06_bench.err
+# usage: tools/round_numbers.sh <full record .json> <bench line .json>
+python bench.py --full --full-json "${1:?full record path}" > "${2:?bench line path}" 2> "$2.err"
 echo "bench rc=$?"
-wc -c gpurun_out/r06_bench.json
+wc -c "$2"
 export SLAMPP_HIP_DEV=1
 SETTLE_MS=30 REPS=5 python3 tools/cold_path.py c1 c2 c3 venice band c5 uniform 1kx1m 2>/dev/null > gpurun_out/r06_cold_path.txt
 cat gpurun_out/r06_cold_path.txt
