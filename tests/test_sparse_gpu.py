@@ -533,7 +533,7 @@ def _damped(lam, alpha):
 
 
 BATCH_CASES = {
-    "chain6": (lambda: synth.pose_chain(n=3000, d=6, seed=41), {}),                    # lane-per-task leaves, slices of the tree as panels
+    "chain6": (lambda: synth.pose_chain(n=3000, d=6, seed=41), {}),                    # ~375 leaf tasks: a wave per leaf subtree, slices of the tree as 8-wave panels
     "chain3": (lambda: synth.pose_chain(n=2500, d=3, seed=42), {}),
     "chain7_columns": (lambda: synth.pose_chain(n=1200, d=7, seed=43), {"panel": 0}),  # separators column by column
     "chain6_waves": (lambda: synth.pose_chain(n=2000, d=6, seed=44), {"simt": 0}),     # a wave per leaf subtree
