@@ -131,7 +131,7 @@ void slampp_hip_destroy(slampp_hip_solver *p_solver);
 int slampp_hip_free_memory(slampp_hip_solver *p_solver);
 const char *slampp_hip_last_error(const slampp_hip_solver *p_solver);
 
-/* Options (19).  All but the ones marked (*) take effect at the next slampp_hip_analyze.
+/* Options (20).  All but the ones marked (*) take effect at the next slampp_hip_analyze.
  *
  * ordering / schedule of the sparse block path
  *   "natural_order"      0 / 1: keep the caller's block order instead of nested dissection (default 0; what
@@ -155,6 +155,8 @@ const char *slampp_hip_last_error(const slampp_hip_solver *p_solver);
  *                        runs and tiles wherever possible / tiles only / runs of any length
  *   "schur_incremental"  0 / 1 / 2: keep the assembled S for slampp_hip_schur_set_changed_points; 1 = a solve with a list of
  *                        changed landmarks updates it when that is the shorter way, 2 = whenever a list is given
+ *   "schur_keep"         0 (default) / 1: every solve also stores W = U C^-1 and leaves the factor of S valid for another
+ *                        right-hand side (slampp_hip_solve_again, slampp_hip_solve_again_device_async, slampp_hip_refine)
  *   "schur_fallback"     default 1: a structure the Schur kernels do not take (no landmark part, landmark-landmark blocks,
  *                        block sizes other than (6,3), (7,3), (3,2)) is solved by the sparse block path, as the reference
  *                        solves it (LinearSolver_Schur.h:1635-1638, 1721-1726); 0 = slampp_hip_analyze reports
@@ -174,7 +176,7 @@ const char *slampp_hip_last_error(const slampp_hip_solver *p_solver);
  *   "profile"            (*) 0 / 1 / 2 / 3, see slampp_hip_get_profile
  *
  * Anything else set_option knows ("panel", "panel_rows", "panel_handup", "simt", "simt_width", "simt_stages",
- * "simt_backward", "wide_min_tasks", "nd_balance", "dense_nb", "dense_top_tiles", "schur_distributed", "group_fail_member")
+ * "simt_backward", "wide_min_tasks", "nd_balance", "dense_nb", "dense_top_tiles", "schur_distributed", "group_fail_member", "multiply_long_row")
  * is a development option: an alternative the defaults were measured against, or a test hook.  They are refused with
  * SLAMPP_HIP_ERR_INVALID unless the process runs with SLAMPP_HIP_DEV=1, and are described where they are implemented
  * (csrc/solver.h). */
@@ -224,6 +226,69 @@ int slampp_hip_factor_solve_device(slampp_hip_solver *p_solver, const double *p_
 /* another right-hand side with the factor of the last factor_solve
  * (reference: cholmod_solve / cs_lsolve+cs_ltsolve on a kept factor, LinearSolver_CholMod.cpp:322-347) */
 int slampp_hip_solve_again(slampp_hip_solver *p_solver, double *p_rhs_inout);
+
+/* ... and the same with the vector resident in device memory, enqueue-only on the solver's stream, in both modes.
+ * Sparse mode: the two substitutions with the kept factor; SLAMPP_HIP_ERR_INVALID without one (nothing factored yet, a
+ * factorization that was not positive definite, a batch that went through the handle's factor arrays).
+ * Schur mode: a BA solve keeps the factor of the reduced camera system S and C^-1, and with the option "schur_keep" (or
+ * "schur_incremental") also W = U C^-1; the re-solve is CHOLMOD's kept-factor solve inside the reference's Schur steps
+ * (LinearSolver_CholMod.cpp:322-347 within LinearSolver_Schur.h:1830-1886), without reading Lambda's values again:
+ *   r = eta_c - sum_p W_p eta_p   (per camera over its observations, fixed order),   S dx = r   (the dense factor's or the
+ *   inner sparse solver's substitutions),   dl_p = C_p^-1 eta_p - sum over the cameras c of p of W_(c,p)^T dx_c.
+ * Valid after a solve with "schur_keep" = 1 or "schur_incremental" >= 1 that was positive definite, or after
+ * slampp_hip_schur_marginals_pattern / _schur_marginal_columns (which leave W, C^-1 and the factor of S -- or, where they
+ * inverted the dense S in place of its factor, that inverse, which is then multiplied with); anything that factors, or fails
+ * to, since (another solve without the option, slampp_hip_schur_marginals, marginal poses, a batch, set_structure, analyze, a
+ * slampp_hip_sync that reports SLAMPP_HIP_NOT_POSDEF) ends it: SLAMPP_HIP_ERR_INVALID, and slampp_hip_last_error names the
+ * option.  Landmark shards (an all-reduce callback, a handle over several devices): SLAMPP_HIP_ERR_UNSUPPORTED.  A Schur
+ * handle whose analysis went to the sparse path ("schur_fallback") answers as the sparse path does.
+ * The host slampp_hip_solve_again takes the same route in Schur mode when such a factor is valid; without one it answers as
+ * before (SLAMPP_HIP_ERR_UNSUPPORTED after a plain Schur solve). */
+int slampp_hip_solve_again_device_async(slampp_hip_solver *p_solver, double *p_rhs_inout_dev);
+
+/* y = alpha Lambda x + beta y with Lambda's packed values as slampp_hip_factor_solve_device reads them -- what the
+ * reference's LM and dog-leg solvers compute on the host after every linear solve: the gain ratio's dx^T (alpha dx + eta)
+ * and the Cauchy step's g^T Lambda g (include/slam/NonlinearSolver_Lambda_LM.h:207, NonlinearSolver_Lambda_DL.h:1175-1177 and 1270:
+ * CUberBlockMatrix::PostMultiply_Add and PreMultiply_Add on the upper triangle).  Lambda is the symmetric matrix whose
+ * upper blocks are stored: a stored block (r, c), r < c, contributes B x_c to y_r and B^T x_r to y_c; diagonal blocks are read
+ * as the full d x d blocks the solver reads.  Needs slampp_hip_set_structure only (no analysis, either mode); the caller's
+ * structure is used as given, block columns wider than 8 go through a generic (slow) kernel.  No atomics: every entry of y is
+ * summed in a fixed order (ascending block column; rows with more than SLAMPP_HIP_MULTIPLY_LONG_ROW blocks in chunks of
+ * SLAMPP_HIP_MULTIPLY_CHUNK whose partial sums are added in chunk order), two calls give the same bits.  beta = 0 does not
+ * read y (it may hold NaN).  x == y: SLAMPP_HIP_ERR_INVALID; a handle solving with landmark shards: SLAMPP_HIP_ERR_UNSUPPORTED.
+ * Enqueue-only on the solver's stream, but for the first call after a set_structure: that one builds the row lists on the
+ * host and, where lists of an earlier structure exist, waits for the stream before it frees them.  The lists live until
+ * the next set_structure (slampp_hip_analyze leaves them; slampp_hip_free_memory frees them).
+ * slampp_hip_multiply: host arrays, the values through the staging of slampp_hip_host_staging. */
+#define SLAMPP_HIP_MULTIPLY_LONG_ROW 256
+#define SLAMPP_HIP_MULTIPLY_CHUNK 256
+int slampp_hip_multiply_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, const double *p_x_dev,
+	double *p_y_dev, double f_alpha, double f_beta);
+int slampp_hip_multiply(slampp_hip_solver *p_solver, const double *p_values, const double *p_x, double *p_y,
+	double f_alpha, double f_beta);
+
+/* *p_out_dev = sum a_i b_i over n device-resident entries, in two passes of a fixed shape (it depends on n alone): bit-
+ * reproducible like the product.  With it the scalars of the LM / dog-leg step control (Eigen's dot products in
+ * NonlinearSolver_Lambda_LM.h:207, NonlinearSolver_Lambda_DL.h:1270, 1510) stay on the device.  Enqueue-only; any handle. */
+int slampp_hip_dot_device_async(slampp_hip_solver *p_solver, const double *p_a_dev, const double *p_b_dev, int64_t n,
+	double *p_out_dev);
+
+/* Iterative refinement of a solution x of Lambda x = eta with the kept factor: n_steps (1 .. 8) times r = eta - Lambda x,
+ * d = solve_again(r), x += d -- the classical loop around cholmod_solve (LinearSolver_CholMod.cpp:322-347; the reference
+ * itself does not refine).  A step stands only if it at least halves max |eta - Lambda x| (the test LAPACK's xPORFS
+ * continues on: below that the fp64 residual is its own rounding noise); otherwise x is put back as it was and the steps
+ * after it change nothing, so the call never returns an x with a larger residual norm than it was given.  All of it is
+ * decided on the device.  p_resid_inf_dev (n_steps + 1 doubles, or NULL): entry k = max |eta - Lambda x_k| of the x held
+ * before step k, the last one that of the x returned (a fixed-order max; the entries never grow).  Needs what
+ * slampp_hip_solve_again_device_async needs (SLAMPP_HIP_ERR_INVALID otherwise) and the values the factor was made of; one
+ * workspace of 2 n_scalars doubles (the residual and the x to go back to), allocated once; enqueue-only.  The residual is
+ * computed in plain fp64 (with fused multiply-adds), not in extended precision: the steps lower the backward error of x
+ * towards that of the residual's own rounding, they do not promise a smaller forward error where cond(Lambda) * eps is
+ * near 1.  slampp_hip_refine: host arrays. */
+int slampp_hip_refine_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, const double *p_eta_dev,
+	double *p_x_inout_dev, int n_steps, double *p_resid_inf_dev);
+int slampp_hip_refine(slampp_hip_solver *p_solver, const double *p_values, const double *p_eta, double *p_x_inout, int n_steps,
+	double *p_resid_inf);
 
 /* Numeric factorization only, the factor handed back to the host -- for CLinearSolverTag-style callers that keep
  * the factor themselves (the reference's Factorize_PosDef_Blocky, LinearSolver_CholMod.cpp:362-544, used by its

@@ -9,6 +9,7 @@
 #include "solver.h"
 #include "sparse_inverse.h"
 #include "covariance.h"
+#include "multiply.h"
 
 #include <algorithm>
 #include <atomic>
@@ -333,7 +334,8 @@ static int set_option_checked(slampp_hip_solver *p_solver, const char *p_s_name,
 		// defaults were measured against, test hooks --: they keep kernels and plan branches reachable for A/B timing and
 		// for the parity tests of those branches, and are refused unless the process runs with SLAMPP_HIP_DEV=1 (plan.h).
 		static const char *p_dev_options[] = {"nd_balance", "dense_nb", "dense_top_tiles", "simt", "simt_width", "simt_stages",
-			"simt_backward", "wide_min_tasks", "panel", "panel_handup", "panel_rows", "group_fail_member", "schur_distributed"};
+			"simt_backward", "wide_min_tasks", "panel", "panel_handup", "panel_rows", "group_fail_member", "schur_distributed",
+			"multiply_long_row"};
 		for(const char *p_s_dev : p_dev_options) {
 			if(s == p_s_dev && !dev_knobs_on())
 				return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "development option: set SLAMPP_HIP_DEV=1 in the environment to use it");
@@ -402,6 +404,12 @@ static int set_option_checked(slampp_hip_solver *p_solver, const char *p_s_name,
 		p_solver->n_schur_tiles = int(n_value);
 	else if(s == "schur_incremental" && n_value >= 0 && n_value <= 2)
 		p_solver->n_schur_incremental = int(n_value);
+	else if(s == "schur_keep" && n_value >= 0 && n_value <= 1)
+		p_solver->n_schur_keep = int(n_value);
+	else if(s == "multiply_long_row" && n_value >= 1 && n_value <= (1 << 30)) {
+		p_solver->n_multiply_long_row = int(n_value); // block rows of slampp_hip_multiply with more blocks than this are cut into chunks (multiply.h)
+		return SLAMPP_HIP_OK; // read by the next product: does not invalidate the analysis
+	}
 	else if(s == "dense_top_tiles" && n_value >= -1 && n_value <= 1) {
 		p_solver->n_dense_top_tiles = int(n_value);
 		p_solver->opt.dense_top_align = n_value? 64 : 0; // the alignment padding only serves the tile schedule
@@ -539,6 +547,7 @@ int slampp_hip_set_structure(slampp_hip_solver *p_solver, int64_t n_bcols, const
 		s.b_factored = false;
 		++ s.n_factor_gen; // (what the Schur covariance calls left in place is stale now)
 		s.b_damp_valid = false;
+		s.b_mul_valid = false; // (the row lists of slampp_hip_multiply belong to the previous structure)
 		s.n_uploaded = 0;
 		return SLAMPP_HIP_OK;
 	}, false); // (host arrays only)
@@ -594,7 +603,7 @@ int slampp_hip_analyze(slampp_hip_solver *p_solver, int n_mode, int64_t n_matrix
 			if(s.copy_stream)
 				SLAMPP_HIP_CHECK(hipStreamSynchronize(s.copy_stream));
 			CKeepDeviceMemory t_keep; // (a re-analysis: the arrays cease to exist, their memory waits for the new plan's)
-			s.Free_Device();
+			s.Free_Device(true);
 		}
 		s.b_group_active = false;
 		s.b_schur_fallback = false;
@@ -654,7 +663,7 @@ int slampp_hip_analyze(slampp_hip_solver *p_solver, int n_mode, int64_t n_matrix
 				(void)hipSetDevice(s.n_device);
 				if(t_staging_thread.t.joinable())
 					t_staging_thread.t.join(); // (it allocates the device arrays Free_Device() is about to free)
-				s.Free_Device();
+				s.Free_Device(true);
 				s.b_group_active = false;
 				s.b_schur_fallback = true;
 				s.n_mode = SLAMPP_HIP_MODE_SPARSE; // from here on this is a sparse-mode handle that remembers why
@@ -693,6 +702,8 @@ int slampp_hip_factor_solve_device_async(slampp_hip_solver *p_solver, const doub
 			schur_enqueue(s, p_values_dev, p_rhs_inout_dev);
 		s.b_factored = true;
 		++ s.n_factor_gen;
+		if(s.n_mode == SLAMPP_HIP_MODE_SCHUR && schur_keeps_for_resolve(s))
+			s.n_schur_keep_gen = s.n_factor_gen; // W, C^-1 and the reduced system's factor stay for slampp_hip_solve_again
 		return SLAMPP_HIP_OK;
 	});
 }
@@ -1745,20 +1756,256 @@ int slampp_hip_factorize(slampp_hip_solver *p_solver, const double *p_values, do
 	});
 }
 
+namespace {
+
+// Schur mode: which kept state another right-hand side can be solved from (inside guarded()).  0 = none; 1 = what a solve
+// with "schur_keep" / "schur_incremental" left; 2 = what a Schur covariance call left.  Both are generations of
+// n_factor_gen: whatever installs or drops a factor since (a solve, a batch, marginals, a factorization that turns out not
+// positive definite at slampp_hip_sync, set_structure, analyze) counts it up and thereby ends them.
+int schur_resolve_source(const slampp_hip_solver &s)
+{
+	if(!s.p_schur || !s.n_factor_gen)
+		return 0;
+	if(s.n_schur_keep_gen == s.n_factor_gen)
+		return 1;
+	if(s.n_schur_cov_gen == s.n_factor_gen)
+		return 2;
+	return 0;
+}
+
+// the checks of slampp_hip_solve_again_device_async / slampp_hip_refine (inside guarded()): SLAMPP_HIP_OK, and how to solve
+int resolve_checks(slampp_hip_solver *p_solver, const char *p_s_name, int *p_n_schur_source)
+{
+	slampp_hip_solver &s = *p_solver;
+	const std::string s_name(p_s_name);
+	*p_n_schur_source = 0;
+	if(s.b_group_active || (s.n_mode == SLAMPP_HIP_MODE_SCHUR && s.p_allreduce))
+		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, (s_name + ": not for a handle that solves with landmark shards or over several devices").c_str());
+	if(!s.b_analyzed)
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, (s_name + ": no valid factorization (analyze was not called)").c_str());
+	if(s.n_mode == SLAMPP_HIP_MODE_SPARSE) {
+		if(!s.b_factored)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, (s_name + ": no valid factorization").c_str());
+		return SLAMPP_HIP_OK;
+	}
+	if(!(*p_n_schur_source = schur_resolve_source(s)))
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, (s_name + ": no kept factor of the reduced camera system: set the option schur_keep (or "
+			"schur_incremental) before analyze and solve, or call a Schur covariance entry point; anything that factors or fails "
+			"to since ends its validity").c_str());
+	return SLAMPP_HIP_OK;
+}
+
+// the substitutions themselves, enqueue-only
+void resolve_enqueue(slampp_hip_solver &s, double *p_rhs_dev, int n_schur_source)
+{
+	if(s.n_mode == SLAMPP_HIP_MODE_SPARSE)
+		s.Enqueue_Sparse(0, p_rhs_dev, false);
+	else
+		schur_resolve_enqueue(s, p_rhs_dev, n_schur_source == 2);
+}
+
+} // anonymous namespace
+
+int slampp_hip_solve_again_device_async(slampp_hip_solver *p_solver, double *p_rhs_inout_dev)
+{
+	return guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		int n_source = 0;
+		const int n_check = resolve_checks(p_solver, "solve_again", &n_source);
+		if(n_check != SLAMPP_HIP_OK)
+			return n_check;
+		if(!p_rhs_inout_dev)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_again: null pointer");
+		resolve_enqueue(s, p_rhs_inout_dev, n_source);
+		return SLAMPP_HIP_OK;
+	});
+}
+
 int slampp_hip_solve_again(slampp_hip_solver *p_solver, double *p_rhs_inout)
 {
 	return guarded(p_solver, [&]() -> int {
 		slampp_hip_solver &s = *p_solver;
-		if(!s.b_factored)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_again: no valid factorization");
-		if(s.n_mode != SLAMPP_HIP_MODE_SPARSE)
-			return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, "solve_again: only the sparse path keeps its factor");
+		int n_source = 0;
+		if(s.n_mode != SLAMPP_HIP_MODE_SPARSE && s.b_analyzed && !s.b_group_active && (n_source = schur_resolve_source(s))) {
+			// Schur mode with W, C^-1 and the reduced system's factor kept: the same route as the device entry point
+			const int n_check = resolve_checks(p_solver, "solve_again", &n_source);
+			if(n_check != SLAMPP_HIP_OK)
+				return n_check;
+		} else {
+			if(!s.b_factored)
+				return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_again: no valid factorization");
+			if(s.n_mode != SLAMPP_HIP_MODE_SPARSE)
+				return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, "solve_again: only the sparse path keeps its factor");
+		}
 		if(!p_rhs_inout)
 			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_again: null pointer");
 		s.d_rhs.Alloc(size_t(s.n_scalars));
 		SLAMPP_HIP_CHECK(hipMemcpyAsync(s.d_rhs.p(), p_rhs_inout, size_t(s.n_scalars) * sizeof(double), hipMemcpyHostToDevice, s.stream));
-		s.Enqueue_Sparse(0, s.d_rhs.p(), false);
+		resolve_enqueue(s, s.d_rhs.p(), n_source);
 		SLAMPP_HIP_CHECK(hipMemcpyAsync(p_rhs_inout, s.d_rhs.p(), size_t(s.n_scalars) * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+		SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
+		return SLAMPP_HIP_OK;
+	});
+}
+
+// ---- y = alpha Lambda x + beta y, dot products, iterative refinement (multiply.hip) ----
+
+namespace {
+
+int multiply_checks(slampp_hip_solver *p_solver, const char *p_s_name)
+{
+	slampp_hip_solver &s = *p_solver;
+	const std::string s_name(p_s_name);
+	if(!s.b_has_structure)
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, (s_name + ": set_structure was not called").c_str());
+	if(s.b_group_active)
+		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, (s_name + ": this handle solves with landmark shards on several devices").c_str());
+	return SLAMPP_HIP_OK;
+}
+
+} // anonymous namespace
+
+int slampp_hip_multiply_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, const double *p_x_dev,
+	double *p_y_dev, double f_alpha, double f_beta)
+{
+	return guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		const int n_check = multiply_checks(p_solver, "multiply");
+		if(n_check != SLAMPP_HIP_OK)
+			return n_check;
+		if(!p_values_dev || !p_x_dev || !p_y_dev)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "multiply: null pointer");
+		if(p_x_dev == p_y_dev)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "multiply: x and y must be different vectors (every row of y reads all of x)");
+		s.Require_Multiply();
+		multiply_enqueue(*s.p_mul, p_values_dev, p_x_dev, p_y_dev, f_alpha, f_beta, s.stream);
+		return SLAMPP_HIP_OK;
+	});
+}
+
+int slampp_hip_multiply(slampp_hip_solver *p_solver, const double *p_values, const double *p_x, double *p_y, double f_alpha,
+	double f_beta)
+{
+	int n_result = guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		const int n_check = multiply_checks(p_solver, "multiply");
+		if(n_check != SLAMPP_HIP_OK)
+			return n_check;
+		if(!p_values || !p_x || !p_y)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "multiply: null pointer");
+		if(p_x == p_y)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "multiply: x and y must be different vectors (every row of y reads all of x)");
+		const size_t n_bytes = size_t(s.n_scalars) * sizeof(double);
+		s.d_A.Alloc(size_t(s.n_values));
+		s.d_mul_x.Alloc(size_t(s.n_scalars));
+		s.d_mul_y.Alloc(size_t(s.n_scalars));
+		Upload_Values_And_Join(s, p_values);
+		SLAMPP_HIP_CHECK(hipMemcpyAsync(s.d_mul_x.p(), p_x, n_bytes, hipMemcpyHostToDevice, s.stream));
+		if(f_beta != 0)
+			SLAMPP_HIP_CHECK(hipMemcpyAsync(s.d_mul_y.p(), p_y, n_bytes, hipMemcpyHostToDevice, s.stream));
+		return SLAMPP_HIP_OK;
+	});
+	if(n_result != SLAMPP_HIP_OK)
+		return n_result;
+	slampp_hip_solver &s = *p_solver;
+	n_result = slampp_hip_multiply_device_async(p_solver, s.d_A.p(), s.d_mul_x.p(), s.d_mul_y.p(), f_alpha, f_beta);
+	if(n_result != SLAMPP_HIP_OK)
+		return n_result;
+	return guarded(p_solver, [&]() -> int {
+		SLAMPP_HIP_CHECK(hipMemcpyAsync(p_y, s.d_mul_y.p(), size_t(s.n_scalars) * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+		SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
+		return SLAMPP_HIP_OK;
+	});
+}
+
+int slampp_hip_dot_device_async(slampp_hip_solver *p_solver, const double *p_a_dev, const double *p_b_dev, int64_t n,
+	double *p_out_dev)
+{
+	return guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		if(!p_a_dev || !p_b_dev || !p_out_dev || n < 0)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "dot: null pointer or negative length");
+		if(s.b_group_active)
+			return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, "dot: this handle solves with landmark shards on several devices");
+		s.d_reduce.Alloc(reduce_MAX_PARTIALS);
+		dot_enqueue(p_a_dev, p_b_dev, n, s.d_reduce.p(), p_out_dev, s.stream);
+		return SLAMPP_HIP_OK;
+	});
+}
+
+int slampp_hip_refine_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, const double *p_eta_dev,
+	double *p_x_inout_dev, int n_steps, double *p_resid_inf_dev)
+{
+	return guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		int n_check = multiply_checks(p_solver, "refine"), n_source = 0;
+		if(n_check != SLAMPP_HIP_OK || (n_check = resolve_checks(p_solver, "refine", &n_source)) != SLAMPP_HIP_OK)
+			return n_check;
+		if(!p_values_dev || !p_eta_dev || !p_x_inout_dev)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "refine: null pointer");
+		if(n_steps < 1 || n_steps > 8)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "refine: between 1 and 8 steps");
+		if(p_eta_dev == p_x_inout_dev)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "refine: eta and x must be different vectors");
+		s.Require_Multiply();
+		s.d_refine_r.Alloc(2 * size_t(s.n_scalars)); // the one workspace: the residual, then the correction | the x before the step
+		s.d_reduce.Alloc(reduce_MAX_PARTIALS);
+		s.d_refine_resid.Alloc(refine_SCALARS);
+		double *p_r = s.d_refine_r.p(), *p_keep = p_r + s.n_scalars;
+		double *p_norm = (p_resid_inf_dev)? p_resid_inf_dev : s.d_refine_resid.p(); // (the norms decide, asked for or not)
+		double *p_trial = s.d_refine_resid.p() + refine_TRIAL, *p_stop = s.d_refine_resid.p() + refine_STOP;
+		const size_t n_bytes = size_t(s.n_scalars) * sizeof(double);
+		SLAMPP_HIP_CHECK(hipMemsetAsync(p_stop, 0, sizeof(double), s.stream));
+		for(int k = 0; k <= n_steps; ++ k) {
+			SLAMPP_HIP_CHECK(hipMemcpyAsync(p_r, p_eta_dev, n_bytes, hipMemcpyDeviceToDevice, s.stream));
+			multiply_enqueue(*s.p_mul, p_values_dev, p_x_inout_dev, p_r, -1.0, 1.0, s.stream); // r = eta - Lambda x
+			norm_inf_enqueue(p_r, s.n_scalars, s.d_reduce.p(), (k)? p_trial : p_norm, s.stream);
+			if(k) { // was step k - 1 worth taking? if not, x is put back and the steps after it add nothing
+				refine_accept_enqueue(p_x_inout_dev, p_keep, s.n_scalars, p_norm + (k - 1), p_trial, p_norm + k, p_stop,
+					s.stream);
+			}
+			if(k == n_steps)
+				break;
+			resolve_enqueue(s, p_r, n_source); // d = Lambda^-1 r with the kept factor
+			refine_step_enqueue(p_x_inout_dev, p_keep, p_r, s.n_scalars, p_stop, s.stream);
+		}
+		return SLAMPP_HIP_OK;
+	});
+}
+
+int slampp_hip_refine(slampp_hip_solver *p_solver, const double *p_values, const double *p_eta, double *p_x_inout, int n_steps,
+	double *p_resid_inf)
+{
+	int n_result = guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		int n_check = multiply_checks(p_solver, "refine"), n_source = 0;
+		if(n_check != SLAMPP_HIP_OK || (n_check = resolve_checks(p_solver, "refine", &n_source)) != SLAMPP_HIP_OK)
+			return n_check;
+		if(!p_values || !p_eta || !p_x_inout)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "refine: null pointer");
+		if(n_steps < 1 || n_steps > 8)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "refine: between 1 and 8 steps");
+		const size_t n_bytes = size_t(s.n_scalars) * sizeof(double);
+		s.d_A.Alloc(size_t(s.n_values));
+		s.d_mul_x.Alloc(size_t(s.n_scalars));
+		s.d_mul_y.Alloc(size_t(s.n_scalars));
+		s.d_refine_resid.Alloc(refine_SCALARS);
+		Upload_Values_And_Join(s, p_values);
+		SLAMPP_HIP_CHECK(hipMemcpyAsync(s.d_mul_y.p(), p_eta, n_bytes, hipMemcpyHostToDevice, s.stream));
+		SLAMPP_HIP_CHECK(hipMemcpyAsync(s.d_mul_x.p(), p_x_inout, n_bytes, hipMemcpyHostToDevice, s.stream));
+		return SLAMPP_HIP_OK;
+	});
+	if(n_result != SLAMPP_HIP_OK)
+		return n_result;
+	slampp_hip_solver &s = *p_solver;
+	n_result = slampp_hip_refine_device_async(p_solver, s.d_A.p(), s.d_mul_y.p(), s.d_mul_x.p(), n_steps,
+		p_resid_inf? s.d_refine_resid.p() : 0);
+	if(n_result != SLAMPP_HIP_OK)
+		return n_result;
+	return guarded(p_solver, [&]() -> int {
+		SLAMPP_HIP_CHECK(hipMemcpyAsync(p_x_inout, s.d_mul_x.p(), size_t(s.n_scalars) * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+		if(p_resid_inf)
+			SLAMPP_HIP_CHECK(hipMemcpyAsync(p_resid_inf, s.d_refine_resid.p(), size_t(n_steps + 1) * sizeof(double), hipMemcpyDeviceToHost, s.stream));
 		SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
 		return SLAMPP_HIP_OK;
 	});

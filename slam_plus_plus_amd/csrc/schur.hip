@@ -1412,6 +1412,8 @@ static void schur_enqueue_t(slampp_hip_solver &s, CSchurState &S, const double *
 	// option "schur_incremental": what this solve assembles is kept (the dense system in a buffer of its own: the
 	// factorization works in place), and a solve that names the changed landmarks updates it instead of rebuilding it
 	const bool b_keep = s.n_schur_incremental != 0 && !s.p_allreduce && s.b_shard_primary;
+	// option "schur_keep": W is stored as well, so that slampp_hip_solve_again can substitute with what this solve leaves
+	const bool b_store_W = b_keep || schur_keeps_for_resolve(s);
 	// ... when that is the shorter way (option value 1; 2 = whenever a list is given): the update exchanges the listed
 	// landmarks' contributions with atomic adds (C4: 0.44 ms a solve at 500 landmarks, 0.46 at 5 000, 0.51 at 15 000, 0.69
 	// at 50 000) and rebuilds the reduced right-hand side; the landmark-major assembly rebuilds everything (0.55 ms a
@@ -1454,7 +1456,7 @@ static void schur_enqueue_t(slampp_hip_solver &s, CSchurState &S, const double *
 		SLAMPP_HIP_CHECK(hipMemcpyAsync(S.d_A_prev.p(), A, size_t(S.n_ablocks) * DC * DC * sizeof(double), hipMemcpyDeviceToDevice, st));
 	s.Phase_End();
 
-	schur_assemble_t<DC, DP>(s, S, A, rhs, p_S, ld, p_sb_dst, p_r, b_keep);
+	schur_assemble_t<DC, DP>(s, S, A, rhs, p_S, ld, p_sb_dst, p_r, b_store_W);
 	}
 	S.b_prev_valid = b_keep; // (a solve that turns out not positive definite takes it back: slampp_hip_sync)
 	S.n_changed = -1;        // the list serves one solve
@@ -1779,6 +1781,77 @@ void schur_enqueue(slampp_hip_solver &s, const double *p_values_dev, double *p_r
 		schur_enqueue_t<7, 3>(s, S, p_values_dev, p_rhs_dev);
 	else
 		schur_enqueue_t<3, 2>(s, S, p_values_dev, p_rhs_dev);
+}
+
+// ---- another right-hand side with the kept factor (schur_resolve.hip) ----
+
+void schur_resolve_init_launch(const double *eta, int n, double *S, int ld, double *p_r, hipStream_t stream);
+void schur_resolve_symv_launch(const double *Z, int ld, int n, const double *r, double *dx, hipStream_t stream);
+void schur_resolve_points_launch(int DC, int DP, const int64_t *ptr, const int32_t *brow, int64_t nc, int64_t np, int n,
+	const double *Cinv, const double *W, const double *dx, double *out, hipStream_t stream);
+
+// a solve of this handle stores W and leaves the reduced system's factor for slampp_hip_solve_again (options "schur_keep",
+// "schur_incremental"; never with landmark shards: the factor is of the summed system, W and C^-1 of this rank's landmarks)
+bool schur_keeps_for_resolve(const slampp_hip_solver &s)
+{
+	return (s.n_schur_keep != 0 || s.n_schur_incremental != 0) && !s.p_allreduce && s.b_shard_primary;
+}
+
+template <int DC, int DP>
+static void schur_resolve_t(slampp_hip_solver &s, CSchurState &S, double *rhs, bool b_from_covariance)
+{
+	hipStream_t st = s.stream;
+	const int ld = S.Npad, n = S.N;
+	// where the factor is: the inner sparse solver's, the dense one in d_S, or -- after a covariance call on the dense reduced
+	// system, whose inversion overwrites the factor -- the dense inverse in d_m_Z
+	const bool b_sparse = b_from_covariance? S.b_cov_sparse : S.b_reduced_sparse;
+	const bool b_inverse = b_from_covariance && !S.b_cov_sparse;
+	double *p_r = 0;
+	if(b_sparse)
+		p_r = S.d_in_buf.p() + size_t(S.n_in_blocks) * DC * DC;
+	else if(b_inverse) {
+		S.d_z.Alloc(size_t(ld));
+		S.d_x.Alloc(size_t(ld));
+		p_r = S.d_z.p();
+	}
+	s.Phase_Begin("resolve_rhs");
+	schur_resolve_init_launch(rhs, n, S.d_S.p(), ld, p_r, st);
+	hipLaunchKernelGGL((schur_rhs_kernel<DC, DP>), dim3(unsigned(S.nc)), dim3(64), 0, st,
+		S.d_cam_ptr.p(), S.d_cam_obs.p(), S.d_obs_pt.p(), n, S.d_W.p(), rhs, S.d_S.p(), ld, p_r);
+	s.Phase_End();
+	const double *p_dx;
+	if(b_sparse) {
+		s.Phase_Begin("reduced_sparse");
+		S.p_inner->p_flag_shared = s.d_flag.p();
+		S.p_inner->Enqueue_Sparse(0, p_r, false);
+		s.Phase_End();
+		p_dx = p_r;
+	} else {
+		s.Phase_Begin("dense_solve");
+		if(b_inverse)
+			schur_resolve_symv_launch(S.d_m_Z.p(), ld, n, p_r, S.d_x.p(), st);
+		else {
+			dense_forwardsolve(S.d_S.p(), ld, S.d_invdiag.p(), st);
+			dense_backsolve(S.d_S.p(), ld, n, S.d_invdiag.p(), S.d_z.p(), S.d_x.p(), st);
+		}
+		s.Phase_End();
+		p_dx = S.d_x.p();
+	}
+	s.Phase_Begin("backsubst");
+	schur_resolve_points_launch(DC, DP, S.d_ptr.p(), S.d_brow.p(), S.nc, S.np, n, S.d_Cinv.p(), S.d_W.p(), p_dx, rhs, st);
+	s.Phase_End();
+	SLAMPP_HIP_CHECK(hipGetLastError());
+}
+
+void schur_resolve_enqueue(slampp_hip_solver &s, double *p_rhs_dev, bool b_from_covariance)
+{
+	CSchurState &S = *s.p_schur;
+	if(S.DC == 6 && S.DP == 3)
+		schur_resolve_t<6, 3>(s, S, p_rhs_dev, b_from_covariance);
+	else if(S.DC == 7 && S.DP == 3)
+		schur_resolve_t<7, 3>(s, S, p_rhs_dev, b_from_covariance);
+	else
+		schur_resolve_t<3, 2>(s, S, p_rhs_dev, b_from_covariance);
 }
 
 // ---- covariances beyond the block diagonal (schur_covariance.hip) ----

@@ -146,6 +146,7 @@ struct CDeviceGroup; // group.hip
 struct CSparseInverse; // sparse_inverse.hip
 struct CCovariance; // covariance.hip
 struct CAssemblyState; // assembly.hip
+struct CMultiplyState; // multiply.hip
 
 } // namespace slampp
 
@@ -167,6 +168,7 @@ struct slampp_hip_solver {
 	int n_assembly_groups = 1 << 20; // option "assembly_groups": most vertices a group of the Lambda assembly takes (0: no groups, the one-wave kernels for everything)
 	int n_schur_tiles = -1; // option "schur_tiles": landmark-major assembly of S: -1 = where it pays, 0 = never, 1 = wherever possible
 	int n_schur_incremental = 0; // option "schur_incremental": keep the assembled reduced system for slampp_hip_schur_set_changed_points
+	int n_schur_keep = 0; // option "schur_keep": a solve stores W = U C^-1 and leaves the reduced system's factor for slampp_hip_solve_again
 	int n_schur_sparse; // reduced camera system: -1 = sparse path when few of its blocks are nonzero, 0 = always dense, 1 = always sparse
 
 	// Lambda structure as given
@@ -175,6 +177,18 @@ struct slampp_hip_solver {
 	// covariance calls (slampp_hip_schur_marginals_pattern / _marginal_columns) record the generation they left, and a call
 	// with values = NULL reuses their reduced-system factor, C^-1 and W only while nothing else has run since
 	uint64_t n_factor_gen = 0, n_schur_cov_gen = 0; // (0: none)
+	// ... and so does a Schur solve that kept W and the reduced factor (options "schur_keep", "schur_incremental"): what
+	// slampp_hip_solve_again works from in Schur mode is valid while this equals n_factor_gen -- every path that installs or
+	// drops a factor counts n_factor_gen up, so none of them can leave it standing (n_batch_owner_member)
+	uint64_t n_schur_keep_gen = 0;
+	// y = alpha Lambda x + beta y (multiply.hip): the row lists of the structure, built at the first product after a
+	// set_structure; the split threshold of its long rows (development option "multiply_long_row"); workspaces of the
+	// reductions, of slampp_hip_refine and of the host entry points
+	slampp::CMultiplyState *p_mul = 0;
+	bool b_mul_valid = false;
+	int n_multiply_long_row = SLAMPP_HIP_MULTIPLY_LONG_ROW;
+	slampp::CDevArray<double> d_reduce, d_refine_r, d_mul_x, d_mul_y, d_refine_resid;
+	void Require_Multiply(); // throws
 	int n_mode;
 	int64_t n_matrix_cut;
 	std::vector<int64_t> cumsum, bcol_ptr;
@@ -382,7 +396,7 @@ struct slampp_hip_solver {
 
 	slampp_hip_solver();
 	~slampp_hip_solver();
-	void Free_Device();
+	void Free_Device(bool b_keep_multiply = false); // b_keep_multiply: a re-analysis, which leaves the product's row lists (they depend on the structure alone)
 	size_t n_Device_Bytes() const;
 	void Analyze_Sparse();
 	void Enqueue_Sparse(const double *p_values_dev, double *p_rhs_dev, bool b_factor, bool b_factor_only = false);
@@ -395,6 +409,10 @@ namespace slampp {
 void schur_destroy(CSchurState *p);
 CSchurState *schur_analyze(slampp_hip_solver &s); // throws
 void schur_enqueue(slampp_hip_solver &s, const double *p_values_dev, double *p_rhs_dev); // throws
+bool schur_keeps_for_resolve(const slampp_hip_solver &s); // a solve of this handle leaves W, C^-1 and the factor of S for another right-hand side
+// another right-hand side with W, C^-1 and the reduced system's factor in place (the caller checks that they are valid);
+// b_from_covariance: the ones a Schur covariance call left (schur_resolve.hip).  Throws.
+void schur_resolve_enqueue(slampp_hip_solver &s, double *p_rhs_dev, bool b_from_covariance);
 void schur_enqueue_marginal_poses(slampp_hip_solver &s, const double *p_values_dev, double *p_rhs_dev); // throws
 void schur_marginals_sparse_launch(int DC, int DP, int64_t nc, int64_t np, const int64_t *ptr, const int64_t *cam_zoff,
 	const int64_t *pair_ptr, const int64_t *pair_tab, const double *W, const double *Cinv, const double *Z, double *cam_cov,

@@ -12,6 +12,7 @@
 #include <sys/mman.h>
 #include "sparse_inverse.h"
 #include "covariance.h"
+#include "multiply.h"
 
 #include <algorithm>
 #include <atomic>
@@ -161,7 +162,7 @@ slampp_hip_solver::~slampp_hip_solver()
 		(void)hipStreamDestroy(stream);
 }
 
-void slampp_hip_solver::Free_Device()
+void slampp_hip_solver::Free_Device(bool b_keep_multiply)
 {
 	d_cols.Free(); d_blks.Free(); d_rents.Free(); d_pairs.Free(); d_task_ptr.Free(); d_task_pkg.Free(); d_pkg.Free();
 	d_simt_chunks.Free(); d_simt_prog.Free(); d_simt_rest.Free(); d_simt_tab.Free();
@@ -195,6 +196,12 @@ void slampp_hip_solver::Free_Device()
 		schur_destroy(p_schur);
 		p_schur = 0;
 	}
+	if(p_mul && !b_keep_multiply) {
+		multiply_destroy(p_mul);
+		p_mul = 0;
+		b_mul_valid = false;
+	}
+	d_reduce.Free(); d_refine_r.Free(); d_mul_x.Free(); d_mul_y.Free(); d_refine_resid.Free();
 	b_analyzed = false;
 	b_factored = false;
 	++ n_factor_gen;
@@ -210,7 +217,8 @@ size_t slampp_hip_solver::n_Device_Bytes() const
 		d_panel_pkg.n_Bytes() + d_panel_off.n_Bytes() + d_panel_out_off.n_Bytes() + d_handup.n_Bytes() + d_panel_rest.n_Bytes() + d_panel_upd_slots.n_Bytes() + d_panel_upd_ents.n_Bytes() +
 		d_rhs.n_Bytes() + d_L.n_Bytes() + d_Linv.n_Bytes() + d_w.n_Bytes() + d_cov.n_Bytes() + d_flag.n_Bytes() +
 		d_Z.n_Bytes() + d_diag_zoff.n_Bytes() + d_Zd.n_Bytes() + d_Zd_work.n_Bytes() + sparse_inverse_bytes(p_sinv) + covariance_bytes(p_cov) +
-		(p_schur? schur_device_bytes(p_schur) : 0);
+		(p_schur? schur_device_bytes(p_schur) : 0) + multiply_device_bytes(p_mul) + d_reduce.n_Bytes() + d_refine_r.n_Bytes() +
+		d_mul_x.n_Bytes() + d_mul_y.n_Bytes() + d_refine_resid.n_Bytes();
 }
 
 void slampp_hip_solver::Phase_Begin(const char *p_s_label)

@@ -33,6 +33,9 @@ LIB_PATH = os.path.join(_HERE, "libslampp_hip.so")
 OK, NOT_POSDEF = 0, 1
 ERR_INVALID, ERR_ALLOC, ERR_DEVICE, ERR_UNSUPPORTED = -1, -2, -3, -4
 MODE_SPARSE, MODE_SCHUR = 0, 1
+# slampp_hip_multiply: block rows with more blocks than MULTIPLY_LONG_ROW are cut into chunks of MULTIPLY_CHUNK
+# (SLAMPP_HIP_MULTIPLY_* in include/slampp_hip.h; the development option "multiply_long_row" lowers the threshold)
+MULTIPLY_LONG_ROW, MULTIPLY_CHUNK = 256, 256
 
 
 def _hash_array(a: np.ndarray) -> int:
@@ -114,6 +117,12 @@ ABI = {
     "slampp_hip_host_staging": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "slampp_hip_upload_values_async": (C.c_int, [_P, C.c_int64, C.c_int64]),
     "slampp_hip_solve_again": (C.c_int, [_P, _P]),
+    "slampp_hip_solve_again_device_async": (C.c_int, [_P, _P]),
+    "slampp_hip_multiply_device_async": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double]),
+    "slampp_hip_multiply": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double]),
+    "slampp_hip_dot_device_async": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
+    "slampp_hip_refine_device_async": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
+    "slampp_hip_refine": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
     "slampp_hip_factorize": (C.c_int, [_P, _P, _P]),
     "slampp_hip_factor_structure": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P, _P, _P, _P, _P]),
     "slampp_hip_schur_set_changed_points": (C.c_int, [_P, _P, C.c_int64]),
@@ -417,13 +426,59 @@ class _SolverBase:
 
     def Solve_Again(self, eta: np.ndarray) -> bool:
         """Another right-hand side with the factor the last solve left behind (cholmod_solve on a kept factor,
-        LinearSolver_CholMod.cpp:322-347)."""
+        LinearSolver_CholMod.cpp:322-347).  Schur mode: needs the option ``schur_keep=1`` (or a Schur covariance call
+        before it), which keeps W, C^-1 and the reduced system's factor; NotImplementedError without."""
         if self._structure_key is None or not self._analyzed:
             raise ValueError("Solve_Again: there is no factorization")
         n_scalars = self._structure_key[2]
         if eta.dtype != np.float64 or not eta.flags.c_contiguous or eta.shape != (n_scalars,):
             raise ValueError("eta must be a contiguous float64 vector of the system's dimension")
         return self._check(self._lib.slampp_hip_solve_again(self._h, _ptr(eta)))
+
+    def _set_structure(self, lam) -> None:
+        """The block structure alone (slampp_hip_set_structure): what the product needs; a solve analyzes it later."""
+        cs = np.ascontiguousarray(lam.cumsum, dtype=np.int64)
+        bp = np.ascontiguousarray(lam.bcol_ptr, dtype=np.int64)
+        br = np.ascontiguousarray(lam.brow_idx, dtype=np.int32)
+        self._check(self._lib.slampp_hip_set_structure(self._h, lam.n_bcols, _ptr(cs), _ptr(bp), _ptr(br)))
+        self._structure_key = self._key(lam)
+        self._n_values = int(lam.values.shape[0])
+        self._analyzed = False
+
+    def Multiply(self, lam, x: np.ndarray, y: np.ndarray = None, alpha: float = 1.0, beta: float = 0.0) -> np.ndarray:
+        """y = alpha Lambda x + beta y for the symmetric Lambda whose upper blocks ``lam`` stores (slampp_hip_multiply);
+        returns y (a new vector where none is given, which needs beta = 0).  No analysis is needed."""
+        if self._structure_key is None or self._structure_key != self._key(lam):
+            self._set_structure(lam)
+        n = int(lam.cumsum[-1])
+        if y is None:
+            if beta != 0:
+                raise ValueError("Multiply: beta != 0 needs a y")
+            y = np.empty(n, dtype=np.float64)
+        for v in (x, y):
+            if v.dtype != np.float64 or not v.flags.c_contiguous or v.shape != (n,):
+                raise ValueError("x and y must be contiguous float64 vectors of the system's dimension")
+        vals = np.ascontiguousarray(lam.values, dtype=np.float64)
+        if vals.shape != (self._n_values,):
+            raise ValueError("lam.values does not match the block structure")
+        self._check(self._lib.slampp_hip_multiply(self._h, _ptr(vals), _ptr(x), _ptr(y), float(alpha), float(beta)))
+        return y
+
+    def Refine(self, lam, eta: np.ndarray, x: np.ndarray, n_steps: int = 2) -> np.ndarray:
+        """``n_steps`` of iterative refinement of ``x`` (in place) with the kept factor (slampp_hip_refine): r = eta - Lambda x,
+        d = Solve_Again(r), x += d, where a step that does not at least halve max|eta - Lambda x| is taken back and ends the
+        refinement.  Returns the n_steps + 1 residual norms max|eta - Lambda x_k| of the x held before every step and of
+        the x returned; they never grow.  ValueError without a valid kept factor (Schur mode: option ``schur_keep=1``)."""
+        n = int(lam.cumsum[-1])
+        for v in (eta, x):
+            if v.dtype != np.float64 or not v.flags.c_contiguous or v.shape != (n,):
+                raise ValueError("eta and x must be contiguous float64 vectors of the system's dimension")
+        vals = np.ascontiguousarray(lam.values, dtype=np.float64)
+        if self._structure_key is None or self._structure_key != self._key(lam) or vals.shape != (self._n_values,):
+            raise ValueError("Refine: lam is not the system this handle factorized")
+        resid = np.zeros(max(int(n_steps), 0) + 1, dtype=np.float64)
+        self._check(self._lib.slampp_hip_refine(self._h, _ptr(vals), _ptr(eta), _ptr(x), int(n_steps), _ptr(resid)))
+        return resid
 
     def host_staging(self):
         """(values, rhs): numpy views of the library's pinned staging for the current structure -- filling these and
@@ -516,6 +571,25 @@ class _SolverBase:
 
     def sync(self) -> bool:
         return self._check(self._lib.slampp_hip_sync(self._h))
+
+    def solve_again_device(self, rhs_ptr: int) -> None:
+        """Another right-hand side with the kept factor, device-resident and enqueue-only, in both modes
+        (slampp_hip_solve_again_device_async; Schur mode: option ``schur_keep=1``)."""
+        self._check(self._lib.slampp_hip_solve_again_device_async(self._h, rhs_ptr))
+
+    def multiply_device(self, values_ptr: int, x_ptr: int, y_ptr: int, alpha: float = 1.0, beta: float = 0.0) -> None:
+        """y = alpha Lambda x + beta y on device-resident arrays, enqueue-only (slampp_hip_multiply_device_async); the
+        structure is the one last given to the handle."""
+        self._check(self._lib.slampp_hip_multiply_device_async(self._h, values_ptr, x_ptr, y_ptr, float(alpha), float(beta)))
+
+    def dot_device(self, a_ptr: int, b_ptr: int, n: int, out_ptr: int) -> None:
+        """*out = a . b over n device-resident doubles, in a fixed order (slampp_hip_dot_device_async)."""
+        self._check(self._lib.slampp_hip_dot_device_async(self._h, a_ptr, b_ptr, int(n), out_ptr))
+
+    def refine_device(self, values_ptr: int, eta_ptr: int, x_ptr: int, n_steps: int, resid_ptr: int = 0) -> None:
+        """Iterative refinement on device-resident arrays, enqueue-only (slampp_hip_refine_device_async); ``resid_ptr``:
+        n_steps + 1 doubles, or 0."""
+        self._check(self._lib.slampp_hip_refine_device_async(self._h, values_ptr, eta_ptr, x_ptr, int(n_steps), resid_ptr or None))
 
     def apply_damping_device_async(self, values_ptr: int, f_alpha: float, n_first_vertex: int, n_last_vertex: int) -> None:
         """ApplyDamping of the reference's LM solver (NonlinearSolver_Lambda_LM.h:228-239) on device-resident values."""
