@@ -1,15 +1,14 @@
 // capi.hip -- C ABI of libslampp_hip.so (include/slampp_hip.h): argument checks, error mapping, orchestration
 // (one of the translation units solver.hip was split into in round 5: solver.hip the handle and its device memory,
 // staging.hip pinned staging and uploads, sparse_setup.hip the analysis of the sparse block path, sparse_enqueue.hip its launches,
-// capi.hip the C ABI of include/slampp_hip.h)
+// capi.hip the C ABI of include/slampp_hip.h).  This file: the handle's life cycle, options, structure, analysis, solve, sync,
+// batch, staging, statistics, plan views and assembly; capi_covariance.hip: the covariance entry points; capi_resolve.hip:
+// the factor handed out, re-solves, products and refinement; capi_util.h: what the three share
 #include <execinfo.h>
 #include <signal.h>
 #include <unistd.h>
 #include <pthread.h>
-#include "solver.h"
-#include "sparse_inverse.h"
-#include "covariance.h"
-#include "multiply.h"
+#include "capi_util.h"
 
 #include <algorithm>
 #include <atomic>
@@ -25,50 +24,12 @@
 #include <sys/mman.h>
 
 #include "preload.h"
-#include <atomic>
 
 using namespace slampp;
 
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-
-namespace {
-
-// runs f, maps exceptions to status codes, records the message
-template <class F>
-int guarded(slampp_hip_solver *p, F f, bool b_join_bringup = true /* false: the entry point waits for the handle's streams itself, or needs none */)
-{
-	if(!p)
-		return SLAMPP_HIP_ERR_INVALID;
-	try {
-		if(b_join_bringup)
-			p->Join_Bringup();
-		if(hipSetDevice(p->n_device) != hipSuccess)
-			throw CDeviceError("hipSetDevice failed");
-		return f();
-	} catch(std::bad_alloc&) {
-		p->s_error = "out of memory";
-		return SLAMPP_HIP_ERR_ALLOC;
-	} catch(CDeviceError &e) {
-		p->s_error = e.what();
-		return SLAMPP_HIP_ERR_DEVICE;
-	} catch(std::domain_error &e) {
-		p->s_error = e.what();
-		return SLAMPP_HIP_ERR_UNSUPPORTED;
-	} catch(std::exception &e) {
-		p->s_error = e.what();
-		return SLAMPP_HIP_ERR_INVALID;
-	}
-}
-
-int fail(slampp_hip_solver *p, int n_code, const char *p_s_msg)
-{
-	p->s_error = p_s_msg;
-	return n_code;
-}
-
-} // anonymous namespace
 
 extern "C" {
 
@@ -544,8 +505,7 @@ int slampp_hip_set_structure(slampp_hip_solver *p_solver, int64_t n_bcols, const
 		s.n_scalars = s.cumsum[n_bcols];
 		s.b_has_structure = true;
 		s.b_analyzed = false;
-		s.b_factored = false;
-		++ s.n_factor_gen; // (what the Schur covariance calls left in place is stale now)
+		s.Factor_Dropped(); // (what the Schur covariance calls left in place is stale now)
 		s.b_damp_valid = false;
 		s.b_mul_valid = false; // (the row lists of slampp_hip_multiply belong to the previous structure)
 		s.n_uploaded = 0;
@@ -700,10 +660,9 @@ int slampp_hip_factor_solve_device_async(slampp_hip_solver *p_solver, const doub
 			s.Enqueue_Sparse(p_values_dev, p_rhs_inout_dev, true);
 		else
 			schur_enqueue(s, p_values_dev, p_rhs_inout_dev);
-		s.b_factored = true;
-		++ s.n_factor_gen;
+		s.Factor_Installed();
 		if(s.n_mode == SLAMPP_HIP_MODE_SCHUR && schur_keeps_for_resolve(s))
-			s.n_schur_keep_gen = s.n_factor_gen; // W, C^-1 and the reduced system's factor stay for slampp_hip_solve_again
+			s.Schur_Kept(); // W, C^-1 and the reduced system's factor stay for slampp_hip_solve_again
 		return SLAMPP_HIP_OK;
 	});
 }
@@ -733,8 +692,7 @@ int slampp_hip_sync(slampp_hip_solver *p_solver)
 		}
 		if(*s.p_host_flag) {
 			SLAMPP_HIP_CHECK(hipMemsetAsync(s.d_flag.p(), 0, sizeof(int), s.stream)); // (what was enqueued since the last sync has been answered for)
-			s.b_factored = false;
-			++ s.n_factor_gen;
+			s.Factor_Dropped();
 			schur_invalidate_previous(s.p_schur); // nothing to update from
 			return fail(p_solver, SLAMPP_HIP_NOT_POSDEF, "matrix is not positive definite");
 		}
@@ -786,8 +744,7 @@ int slampp_hip_factor_solve_batch_device_async(slampp_hip_solver *p_solver, int 
 			// finds the member not positive definite.  After more than one member the handle holds the last member's factor where
 			// the header promises "not touched": it is declared gone -- slampp_hip_solve_again and the covariance calls refuse
 			// until the next factorization -- rather than passed off as the handle's own (advisor, round 5).
-			s.b_factored = n_batch == 1;
-			++ s.n_factor_gen;
+			s.Factor_Installed(n_batch == 1);
 			s.n_batch_owner_member = (n_batch == 1)? 0 : -1;
 			if(n_batch > 1)
 				schur_invalidate_previous(s.p_schur);
@@ -840,8 +797,7 @@ int slampp_hip_sync_batch(slampp_hip_solver *p_solver, int *p_status, int n_batc
 			b_any = b_any || p_status[k] != SLAMPP_HIP_OK;
 		}
 		if(s.n_batch_owner_member >= 0 && s.p_host_batch_flag && s.d_batch_flag.p() && s.p_host_batch_flag[s.n_batch_owner_member]) {
-			s.b_factored = false; // the member whose factor the handle kept failed: there is nothing to solve again from
-			++ s.n_factor_gen;
+			s.Factor_Dropped(); // the member whose factor the handle kept failed: there is nothing to solve again from
 			schur_invalidate_previous(s.p_schur);
 		}
 		s.n_batch_owner_member = -1;
@@ -988,1025 +944,6 @@ int slampp_hip_schur_set_changed_points(slampp_hip_solver *p_solver, const int64
 			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "schur_set_changed_points: null list");
 		SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream)); // (the previous list may still be read)
 		schur_set_changed_points(s, p_points, n_points);
-		return SLAMPP_HIP_OK;
-	});
-}
-
-int slampp_hip_solve_marginal_poses_device_async(slampp_hip_solver *p_solver, const double *p_values_dev,
-	double *p_rhs_inout_dev)
-{
-	return guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		if(!s.b_analyzed)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_marginal_poses: analyze was not called");
-		if(s.n_mode != SLAMPP_HIP_MODE_SCHUR)
-			return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, "solve_marginal_poses: needs the Schur mode (cameras and landmarks)");
-		if(s.b_group_active)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_marginal_poses_device: this handle solves with landmark shards on several devices: host entry points only");
-		if(!p_values_dev || !p_rhs_inout_dev)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_marginal_poses: null pointer");
-		schur_enqueue_marginal_poses(s, p_values_dev, p_rhs_inout_dev);
-		s.b_factored = false; // no factor of the reduced system comes out of this
-		++ s.n_factor_gen;
-		return SLAMPP_HIP_OK;
-	});
-}
-
-namespace {
-
-// what slampp_hip_marginals and slampp_hip_marginals_pattern share: the numeric factorization and the sparse inverse
-// subset Z on the factor's pattern (d_Z; the dense top's part in d_Zd).  Inside guarded(), behind the caller's checks.
-int enqueue_sparse_inverse(slampp_hip_solver *p_solver, const double *p_values_dev, const char *p_s_name)
-{
-	slampp_hip_solver &s = *p_solver;
-	const Plan &P = s.plan;
-	if(!s.b_sinv_tried) {
-		s.b_sinv_tried = true;
-		s.p_sinv = sparse_inverse_setup(P, s.stream, true);
-		if(s.p_sinv) {
-			std::vector<int64_t> zoff(size_t(P.n));
-			for(int32_t c = 0; c < P.n; ++ c) {
-				const int32_t j = P.pinv[c];
-				zoff[c] = (P.dense_dim && P.dense_pos[j] >= 0)? -int64_t(P.dense_pos[j]) - 1 : P.loff[P.lptr[j]];
-			}
-			s.d_diag_zoff.Upload(zoff, s.stream);
-			if(!P.uniform_dim) { // mixed block sizes: where every caller's column's block goes, and how big it is
-				std::vector<int32_t> dims(size_t(P.n));
-				std::vector<int64_t> out_off(size_t(P.n));
-				int64_t n_at = 0;
-				for(int32_t c = 0; c < P.n; ++ c) {
-					dims[c] = int32_t(s.cumsum[c + 1] - s.cumsum[c]);
-					out_off[c] = n_at;
-					n_at += int64_t(dims[c]) * dims[c];
-				}
-				s.d_diag_dim.Upload(dims, s.stream);
-				s.d_diag_out_off.Upload(out_off, s.stream);
-			}
-			s.d_Z.Alloc(size_t(P.loff.back()));
-			if(s.n_dense_dim) {
-				s.d_Zd.Alloc(size_t(s.n_dense_pad) * s.n_dense_pad);
-				s.d_Zd_work.Alloc(size_t(s.n_dense_pad) * s.n_dense_pad);
-			}
-			SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream)); // zoff lives on this stack frame
-		}
-	}
-	if(!s.p_sinv)
-		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, (std::string(p_s_name) + ": mixed block sizes are taken without a dense top only (set the option dense_top_nb to 0), block sizes above 8 not at all").c_str());
-	// the fused forward substitution reads a right-hand side, and with a dense top it rides through that factorization
-	// as a row of the matrix: zeros (a NaN there would spread through 0 x NaN in the tile products)
-	s.b_leaf_linv_wanted = true; // (the inverse subset multiplies by inv(L_jj) of every column)
-	if(p_values_dev) { // (null: the factor in place -- the Schur covariance calls on a handle that went to this path)
-		s.d_rhs.Alloc(size_t(s.n_scalars));
-		SLAMPP_HIP_CHECK(hipMemsetAsync(s.d_rhs.p(), 0, size_t(s.n_scalars) * sizeof(double), s.stream));
-		// (with a dense top the whole factor + solve runs: the top is factored on the way; opens its own phases)
-		s.Enqueue_Sparse(p_values_dev, s.d_rhs.p(), true, s.n_dense_dim == 0);
-	}
-	s.Ensure_Leaf_Inverses();
-	s.Phase_Begin("marginals_inverse");
-	if(s.n_dense_dim) { // the top's inverse from a copy of its factor (the factor itself stays for solve_again)
-		SLAMPP_HIP_CHECK(hipMemcpyAsync(s.d_Zd_work.p(), s.d_dense.p(), size_t(s.n_dense_pad) * s.n_dense_pad * sizeof(double),
-			hipMemcpyDeviceToDevice, s.stream));
-		dense_top_clear_rhs_row(s.d_Zd_work.p(), s.n_dense_pad, s.stream);
-		dense_inverse_from_factor(s.d_Zd_work.p(), s.n_dense_pad, s.d_dense_invdiag.p(), s.d_Zd.p(), s.stream);
-	}
-	sparse_inverse_enqueue(*s.p_sinv, P, s.d_L.p(), s.d_Linv.p(), s.d_Z.p(), s.stream, s.d_Zd.p(), s.n_dense_pad);
-	s.Phase_End();
-	return SLAMPP_HIP_OK;
-}
-
-} // anonymous namespace
-
-int slampp_hip_marginals_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, double *p_block_diag_dev)
-{
-	return guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		if(!s.b_analyzed)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginals: analyze was not called");
-		if(s.n_mode != SLAMPP_HIP_MODE_SPARSE)
-			return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, "marginals: sparse mode only (Schur mode: slampp_hip_schur_marginals)");
-		if(s.b_refined)
-			return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, "marginals: block columns wider than 8 are factored in pieces: no covariance blocks in the caller's layout");
-		if(!p_values_dev || !p_block_diag_dev)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginals: null pointer");
-		const int n_result = enqueue_sparse_inverse(p_solver, p_values_dev, "marginals");
-		if(n_result != SLAMPP_HIP_OK)
-			return n_result;
-		const Plan &P = s.plan;
-		if(P.uniform_dim)
-			inverse_diag_blocks_launch(P.n, P.max_dim, s.d_diag_zoff.p(), s.d_Z.p(), s.d_Zd.p(), s.n_dense_pad, p_block_diag_dev, s.stream);
-		else
-			inverse_diag_blocks_any_launch(P.n, s.d_diag_dim.p(), s.d_diag_zoff.p(), s.d_diag_out_off.p(), s.d_Z.p(), p_block_diag_dev, s.stream);
-		SLAMPP_HIP_CHECK(hipGetLastError());
-		s.b_factored = true; // the factor of these values is in place
-		++ s.n_factor_gen;
-		return SLAMPP_HIP_OK;
-	});
-}
-
-int slampp_hip_marginals(slampp_hip_solver *p_solver, const double *p_values, double *p_block_diag)
-{
-	size_t n_out = 0;
-	int n_result = guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		if(!s.b_analyzed)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginals: analyze was not called");
-		if(!p_values || !p_block_diag)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginals: null pointer");
-		for(size_t c = 0; c + 1 < s.cumsum.size(); ++ c)
-			n_out += size_t((s.cumsum[c + 1] - s.cumsum[c]) * (s.cumsum[c + 1] - s.cumsum[c]));
-		s.d_A.Alloc(size_t(s.n_values));
-		s.d_cov.Alloc(n_out);
-		Upload_Values_And_Join(s, p_values);
-		return SLAMPP_HIP_OK;
-	});
-	if(n_result != SLAMPP_HIP_OK)
-		return n_result;
-	slampp_hip_solver &s = *p_solver;
-	n_result = slampp_hip_marginals_device_async(p_solver, s.d_A.p(), s.d_cov.p());
-	if(n_result == SLAMPP_HIP_OK)
-		n_result = slampp_hip_sync(p_solver);
-	if(n_result == SLAMPP_HIP_OK) {
-		n_result = guarded(p_solver, [&]() -> int {
-			SLAMPP_HIP_CHECK(hipMemcpyAsync(p_block_diag, s.d_cov.p(), n_out * sizeof(double), hipMemcpyDeviceToHost, s.stream));
-			SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
-			return SLAMPP_HIP_OK;
-		});
-	}
-	return n_result;
-}
-
-namespace {
-
-// the checks the covariance calls beyond the block diagonal share (inside guarded())
-int covariance_checks(slampp_hip_solver *p_solver, const char *p_s_name)
-{
-	slampp_hip_solver &s = *p_solver;
-	const std::string s_name(p_s_name);
-	if(!s.b_analyzed)
-		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, (s_name + ": analyze was not called").c_str());
-	if(s.n_mode != SLAMPP_HIP_MODE_SPARSE)
-		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, (s_name + ": sparse mode only (Schur mode: slampp_hip_schur_marginals)").c_str());
-	if(!s.group_devices.empty())
-		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, (s_name + ": not for a handle over several devices").c_str());
-	if(s.b_refined)
-		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, (s_name + ": block columns wider than 8 are factored in pieces: no covariance blocks in the caller's layout").c_str());
-	return SLAMPP_HIP_OK;
-}
-
-// n_cols distinct block columns in range; their scalar count in *p_k
-int columns_checks(slampp_hip_solver *p_solver, int n_cols, const int64_t *p_bcols, int64_t *p_k)
-{
-	slampp_hip_solver &s = *p_solver;
-	if(n_cols <= 0 || !p_bcols)
-		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_columns: no columns");
-	const int64_t n_bcols = int64_t(s.cumsum.size()) - 1;
-	std::vector<int64_t> sorted(p_bcols, p_bcols + n_cols);
-	std::sort(sorted.begin(), sorted.end());
-	if(sorted.front() < 0 || sorted.back() >= n_bcols)
-		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_columns: block column index out of range");
-	if(std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
-		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_columns: a block column is listed twice");
-	*p_k = 0;
-	for(int i = 0; i < n_cols; ++ i)
-		*p_k += s.cumsum[size_t(p_bcols[i] + 1)] - s.cumsum[size_t(p_bcols[i])];
-	return SLAMPP_HIP_OK;
-}
-
-} // anonymous namespace
-
-int slampp_hip_marginals_pattern_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, double *p_cov_dev)
-{
-	return guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		int n_result = covariance_checks(p_solver, "marginals_pattern");
-		if(n_result != SLAMPP_HIP_OK)
-			return n_result;
-		if(!p_values_dev || !p_cov_dev)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginals_pattern: null pointer");
-		n_result = enqueue_sparse_inverse(p_solver, p_values_dev, "marginals_pattern");
-		if(n_result != SLAMPP_HIP_OK)
-			return n_result;
-		covariance_pattern_enqueue(s, p_cov_dev);
-		s.b_factored = true; // the factor of these values is in place
-		++ s.n_factor_gen;
-		return SLAMPP_HIP_OK;
-	});
-}
-
-int slampp_hip_marginals_pattern(slampp_hip_solver *p_solver, const double *p_values, double *p_cov)
-{
-	int n_result = guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		const int n_check = covariance_checks(p_solver, "marginals_pattern");
-		if(n_check != SLAMPP_HIP_OK)
-			return n_check;
-		if(!p_values || !p_cov)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginals_pattern: null pointer");
-		s.d_A.Alloc(size_t(s.n_values));
-		s.d_cov.Alloc(size_t(s.n_values));
-		Upload_Values_And_Join(s, p_values);
-		return SLAMPP_HIP_OK;
-	});
-	if(n_result != SLAMPP_HIP_OK)
-		return n_result;
-	slampp_hip_solver &s = *p_solver;
-	n_result = slampp_hip_marginals_pattern_device_async(p_solver, s.d_A.p(), s.d_cov.p());
-	if(n_result == SLAMPP_HIP_OK)
-		n_result = slampp_hip_sync(p_solver);
-	if(n_result == SLAMPP_HIP_OK) {
-		n_result = guarded(p_solver, [&]() -> int {
-			SLAMPP_HIP_CHECK(hipMemcpyAsync(p_cov, s.d_cov.p(), size_t(s.n_values) * sizeof(double), hipMemcpyDeviceToHost, s.stream));
-			SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
-			return SLAMPP_HIP_OK;
-		});
-	}
-	return n_result;
-}
-
-int slampp_hip_marginal_columns_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, int n_cols,
-	const int64_t *p_bcols, double *p_out_dev)
-{
-	return guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		int n_result = covariance_checks(p_solver, "marginal_columns");
-		if(n_result != SLAMPP_HIP_OK)
-			return n_result;
-		if(!p_out_dev)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_columns: null pointer");
-		int64_t n_k = 0;
-		if((n_result = columns_checks(p_solver, n_cols, p_bcols, &n_k)) != SLAMPP_HIP_OK)
-			return n_result;
-		if(p_values_dev) { // factor these values (the fused forward substitution runs on zeros)
-			s.d_rhs.Alloc(size_t(s.n_scalars));
-			SLAMPP_HIP_CHECK(hipMemsetAsync(s.d_rhs.p(), 0, size_t(s.n_scalars) * sizeof(double), s.stream));
-			s.b_leaf_linv_wanted = true;
-			s.Enqueue_Sparse(p_values_dev, s.d_rhs.p(), true, s.n_dense_dim == 0);
-			s.b_factored = true;
-			++ s.n_factor_gen;
-		} else if(!s.b_factored)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_columns: no valid factorization to reuse (values = NULL)");
-		s.Ensure_Leaf_Inverses(); // (the substitutions multiply by inv(L_jj) of every column)
-		covariance_columns_enqueue(s, n_cols, p_bcols, p_out_dev);
-		return SLAMPP_HIP_OK;
-	});
-}
-
-int slampp_hip_marginal_columns(slampp_hip_solver *p_solver, const double *p_values, int n_cols, const int64_t *p_bcols,
-	double *p_out)
-{
-	int64_t n_k = 0;
-	int n_result = guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		int n_check = covariance_checks(p_solver, "marginal_columns");
-		if(n_check != SLAMPP_HIP_OK)
-			return n_check;
-		if(!p_out)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_columns: null pointer");
-		if((n_check = columns_checks(p_solver, n_cols, p_bcols, &n_k)) != SLAMPP_HIP_OK)
-			return n_check;
-		if(!p_values && !s.b_factored)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_columns: no valid factorization to reuse (values = NULL)");
-		s.d_cov.Alloc(size_t(s.n_scalars) * COV_K_PASS);
-		if(p_values) {
-			s.d_A.Alloc(size_t(s.n_values));
-			Upload_Values_And_Join(s, p_values);
-		}
-		return SLAMPP_HIP_OK;
-	});
-	if(n_result != SLAMPP_HIP_OK)
-		return n_result;
-	// groups of whole block columns of at most COV_K_PASS scalar columns, each brought back behind its solve: the device
-	// holds n_scalars x COV_K_PASS of the result at a time, whatever k is
-	slampp_hip_solver &s = *p_solver;
-	const double *p_values_dev = p_values? s.d_A.p() : 0;
-	int64_t n_done = 0;
-	for(int i = 0; i < n_cols && n_result == SLAMPP_HIP_OK;) {
-		int n_group = 0;
-		int64_t n_group_k = 0;
-		while(i + n_group < n_cols) {
-			const int64_t c = p_bcols[i + n_group], d = s.cumsum[size_t(c + 1)] - s.cumsum[size_t(c)];
-			if(n_group && n_group_k + d > COV_K_PASS)
-				break;
-			n_group_k += d;
-			++ n_group;
-		}
-		n_result = slampp_hip_marginal_columns_device_async(p_solver, p_values_dev, n_group, p_bcols + i, s.d_cov.p());
-		p_values_dev = 0; // (the next groups reuse this factor)
-		if(n_result == SLAMPP_HIP_OK)
-			n_result = slampp_hip_sync(p_solver);
-		if(n_result == SLAMPP_HIP_OK) {
-			n_result = guarded(p_solver, [&]() -> int {
-				SLAMPP_HIP_CHECK(hipMemcpyAsync(p_out + size_t(n_done) * size_t(s.n_scalars), s.d_cov.p(), size_t(n_group_k) *
-					size_t(s.n_scalars) * sizeof(double), hipMemcpyDeviceToHost, s.stream));
-				SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
-				return SLAMPP_HIP_OK;
-			});
-		}
-		n_done += n_group_k;
-		i += n_group;
-	}
-	return n_result;
-}
-
-int slampp_hip_schur_marginals_device_async(slampp_hip_solver *p_solver, const double *p_values_dev,
-	double *p_cam_cov_dev, double *p_point_cov_dev)
-{
-	return guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		if(!s.b_analyzed)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "schur_marginals: analyze was not called");
-		if(s.n_mode != SLAMPP_HIP_MODE_SCHUR)
-			return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, "schur_marginals: needs the Schur mode (cameras and landmarks)");
-		if(s.b_group_active)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "schur_marginals_device: this handle solves with landmark shards on several devices: host entry points only");
-		if(!p_values_dev || (!p_cam_cov_dev && !p_point_cov_dev))
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "schur_marginals: null pointer");
-		schur_enqueue_marginals(s, p_values_dev, p_cam_cov_dev, p_point_cov_dev);
-		s.b_factored = false; // C^-1 and W were recomputed from these values: a kept factor may no longer match them
-		++ s.n_factor_gen;
-		return SLAMPP_HIP_OK;
-	});
-}
-
-int slampp_hip_schur_marginals(slampp_hip_solver *p_solver, const double *p_values, double *p_cam_cov, double *p_point_cov)
-{
-	size_t n_cam_doubles = 0, n_point_doubles = 0;
-	int n_result = guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		if(!s.b_analyzed)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "schur_marginals: analyze was not called");
-		if(s.n_mode != SLAMPP_HIP_MODE_SCHUR)
-			return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, "schur_marginals: needs the Schur mode (cameras and landmarks)");
-		if(!p_values || (!p_cam_cov && !p_point_cov))
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "schur_marginals: null pointer");
-		if(s.b_group_active)
-			return group_schur_marginals(s, p_values, p_cam_cov, p_point_cov);
-		const int64_t nc = s.n_matrix_cut, np = int64_t(s.cumsum.size()) - 1 - nc;
-		const int64_t dc = s.cumsum[1] - s.cumsum[0], dp = s.cumsum[nc + 1] - s.cumsum[nc];
-		n_cam_doubles = size_t(nc * dc * dc);
-		n_point_doubles = size_t(np * dp * dp);
-		s.d_A.Alloc(size_t(s.n_values));
-		s.d_cov.Alloc(n_cam_doubles + n_point_doubles);
-		Upload_Values_And_Join(s, p_values);
-		return SLAMPP_HIP_OK;
-	});
-	if(n_result != SLAMPP_HIP_OK || p_solver->b_group_active)
-		return n_result;
-	slampp_hip_solver &s = *p_solver;
-	n_result = slampp_hip_schur_marginals_device_async(p_solver, s.d_A.p(), p_cam_cov? s.d_cov.p() : 0,
-		p_point_cov? s.d_cov.p() + n_cam_doubles : 0);
-	if(n_result == SLAMPP_HIP_OK)
-		n_result = slampp_hip_sync(p_solver);
-	if(n_result == SLAMPP_HIP_OK) {
-		n_result = guarded(p_solver, [&]() -> int {
-			if(p_cam_cov)
-				SLAMPP_HIP_CHECK(hipMemcpyAsync(p_cam_cov, s.d_cov.p(), n_cam_doubles * sizeof(double), hipMemcpyDeviceToHost, s.stream));
-			if(p_point_cov)
-				SLAMPP_HIP_CHECK(hipMemcpyAsync(p_point_cov, s.d_cov.p() + n_cam_doubles, n_point_doubles * sizeof(double),
-					hipMemcpyDeviceToHost, s.stream));
-			SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
-			return SLAMPP_HIP_OK;
-		});
-	}
-	return n_result;
-}
-
-namespace {
-
-// the checks of the Schur covariance calls beyond the block diagonal (inside guarded()); *p_b_fallback: the handle went to
-// the sparse path (its layouts are the same: the sparse calls answer).  b_reuse: values = NULL, which takes what the last
-// of these calls left only if no other factorization ran since and that one was positive definite
-int schur_cov_checks(slampp_hip_solver *p_solver, const char *p_s_name, bool b_reuse, bool *p_b_fallback)
-{
-	slampp_hip_solver &s = *p_solver;
-	const std::string s_name(p_s_name);
-	*p_b_fallback = false;
-	if(!s.b_analyzed)
-		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, (s_name + ": analyze was not called").c_str());
-	if(s.b_group_active || !s.group_devices.empty())
-		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, (s_name + ": not for a handle over several devices").c_str());
-	if(s.n_mode == SLAMPP_HIP_MODE_SPARSE && s.b_schur_fallback)
-		*p_b_fallback = true;
-	else if(s.n_mode != SLAMPP_HIP_MODE_SCHUR)
-		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, (s_name + ": needs the Schur mode (sparse mode: slampp_hip_marginals_pattern, slampp_hip_marginal_columns)").c_str());
-	else if(s.p_allreduce)
-		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, (s_name + ": not with landmark shards (an all-reduce callback is set)").c_str());
-	if(b_reuse && (!s.n_schur_cov_gen || s.n_schur_cov_gen != s.n_factor_gen))
-		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, (s_name + ": no factorization to reuse (values = NULL): none was left by a Schur covariance call, another factorization ran since, or it was not positive definite").c_str());
-	return SLAMPP_HIP_OK;
-}
-
-} // anonymous namespace
-
-int slampp_hip_schur_marginals_pattern_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, double *p_cov_dev)
-{
-	return guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		bool b_fallback = false;
-		int n_result = schur_cov_checks(p_solver, "schur_marginals_pattern", !p_values_dev, &b_fallback);
-		if(n_result != SLAMPP_HIP_OK)
-			return n_result;
-		if(!p_cov_dev)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "schur_marginals_pattern: null pointer");
-		if(b_fallback) { // what slampp_hip_marginals_pattern does
-			if((n_result = covariance_checks(p_solver, "schur_marginals_pattern")) != SLAMPP_HIP_OK ||
-			   (n_result = enqueue_sparse_inverse(p_solver, p_values_dev, "schur_marginals_pattern")) != SLAMPP_HIP_OK)
-				return n_result;
-			covariance_pattern_enqueue(s, p_cov_dev);
-			s.b_factored = true; // the factor of these values is in place
-		} else {
-			schur_cov_pattern_enqueue(s, p_values_dev, p_cov_dev);
-			s.b_factored = false; // C^-1 and W were recomputed from these values: a kept factor may no longer match them
-		}
-		if(p_values_dev)
-			++ s.n_factor_gen;
-		s.n_schur_cov_gen = s.n_factor_gen;
-		return SLAMPP_HIP_OK;
-	});
-}
-
-int slampp_hip_schur_marginals_pattern(slampp_hip_solver *p_solver, const double *p_values, double *p_cov)
-{
-	int n_result = guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		bool b_fallback = false;
-		const int n_check = schur_cov_checks(p_solver, "schur_marginals_pattern", !p_values, &b_fallback);
-		if(n_check != SLAMPP_HIP_OK)
-			return n_check;
-		if(!p_cov)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "schur_marginals_pattern: null pointer");
-		s.d_cov.Alloc(size_t(s.n_values));
-		if(p_values) {
-			s.d_A.Alloc(size_t(s.n_values));
-			Upload_Values_And_Join(s, p_values);
-		}
-		return SLAMPP_HIP_OK;
-	});
-	if(n_result != SLAMPP_HIP_OK)
-		return n_result;
-	slampp_hip_solver &s = *p_solver;
-	n_result = slampp_hip_schur_marginals_pattern_device_async(p_solver, p_values? s.d_A.p() : 0, s.d_cov.p());
-	if(n_result == SLAMPP_HIP_OK)
-		n_result = slampp_hip_sync(p_solver);
-	if(n_result == SLAMPP_HIP_OK) {
-		n_result = guarded(p_solver, [&]() -> int {
-			SLAMPP_HIP_CHECK(hipMemcpyAsync(p_cov, s.d_cov.p(), size_t(s.n_values) * sizeof(double), hipMemcpyDeviceToHost, s.stream));
-			SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
-			return SLAMPP_HIP_OK;
-		});
-	}
-	return n_result;
-}
-
-int slampp_hip_schur_marginal_columns_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, int n_cols,
-	const int64_t *p_bcols, double *p_out_dev)
-{
-	return guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		bool b_fallback = false;
-		int n_result = schur_cov_checks(p_solver, "schur_marginal_columns", !p_values_dev, &b_fallback);
-		if(n_result != SLAMPP_HIP_OK)
-			return n_result;
-		if(!p_out_dev)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "schur_marginal_columns: null pointer");
-		int64_t n_k = 0;
-		if((n_result = columns_checks(p_solver, n_cols, p_bcols, &n_k)) != SLAMPP_HIP_OK)
-			return n_result;
-		if(b_fallback) { // what slampp_hip_marginal_columns does
-			if((n_result = covariance_checks(p_solver, "schur_marginal_columns")) != SLAMPP_HIP_OK)
-				return n_result;
-			if(p_values_dev) {
-				s.d_rhs.Alloc(size_t(s.n_scalars));
-				SLAMPP_HIP_CHECK(hipMemsetAsync(s.d_rhs.p(), 0, size_t(s.n_scalars) * sizeof(double), s.stream));
-				s.b_leaf_linv_wanted = true;
-				s.Enqueue_Sparse(p_values_dev, s.d_rhs.p(), true, s.n_dense_dim == 0);
-				s.b_factored = true;
-			}
-			s.Ensure_Leaf_Inverses();
-			covariance_columns_enqueue(s, n_cols, p_bcols, p_out_dev);
-		} else {
-			schur_cov_columns_enqueue(s, p_values_dev, n_cols, p_bcols, p_out_dev);
-			s.b_factored = false;
-		}
-		if(p_values_dev)
-			++ s.n_factor_gen;
-		s.n_schur_cov_gen = s.n_factor_gen;
-		return SLAMPP_HIP_OK;
-	});
-}
-
-int slampp_hip_schur_marginal_columns(slampp_hip_solver *p_solver, const double *p_values, int n_cols, const int64_t *p_bcols,
-	double *p_out)
-{
-	int64_t n_k = 0;
-	int n_result = guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		bool b_fallback = false;
-		int n_check = schur_cov_checks(p_solver, "schur_marginal_columns", !p_values, &b_fallback);
-		if(n_check != SLAMPP_HIP_OK)
-			return n_check;
-		if(!p_out)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "schur_marginal_columns: null pointer");
-		if((n_check = columns_checks(p_solver, n_cols, p_bcols, &n_k)) != SLAMPP_HIP_OK)
-			return n_check;
-		s.d_cov.Alloc(size_t(s.n_scalars) * COV_K_PASS);
-		if(p_values) {
-			s.d_A.Alloc(size_t(s.n_values));
-			Upload_Values_And_Join(s, p_values);
-		}
-		return SLAMPP_HIP_OK;
-	});
-	if(n_result != SLAMPP_HIP_OK)
-		return n_result;
-	// groups of whole block columns of at most COV_K_PASS scalar columns, each brought back behind its pass; the first
-	// factors the values, the others use that factor (values = NULL: the generation check lets them through)
-	slampp_hip_solver &s = *p_solver;
-	const double *p_values_dev = p_values? s.d_A.p() : 0;
-	int64_t n_done = 0;
-	for(int i = 0; i < n_cols && n_result == SLAMPP_HIP_OK;) {
-		int n_group = 0;
-		int64_t n_group_k = 0;
-		while(i + n_group < n_cols) {
-			const int64_t c = p_bcols[i + n_group], d = s.cumsum[size_t(c + 1)] - s.cumsum[size_t(c)];
-			if(n_group && n_group_k + d > COV_K_PASS)
-				break;
-			n_group_k += d;
-			++ n_group;
-		}
-		n_result = slampp_hip_schur_marginal_columns_device_async(p_solver, p_values_dev, n_group, p_bcols + i, s.d_cov.p());
-		p_values_dev = 0;
-		if(n_result == SLAMPP_HIP_OK)
-			n_result = slampp_hip_sync(p_solver);
-		if(n_result == SLAMPP_HIP_OK) {
-			n_result = guarded(p_solver, [&]() -> int {
-				SLAMPP_HIP_CHECK(hipMemcpyAsync(p_out + size_t(n_done) * size_t(s.n_scalars), s.d_cov.p(), size_t(n_group_k) *
-					size_t(s.n_scalars) * sizeof(double), hipMemcpyDeviceToHost, s.stream));
-				SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
-				return SLAMPP_HIP_OK;
-			});
-		}
-		n_done += n_group_k;
-		i += n_group;
-	}
-	return n_result;
-}
-
-int slampp_hip_solve_marginal_poses(slampp_hip_solver *p_solver, const double *p_values, double *p_rhs_inout)
-{
-	int n_result = guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		if(!s.b_analyzed)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_marginal_poses: analyze was not called");
-		if(!p_values || !p_rhs_inout)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_marginal_poses: null pointer");
-		if(s.b_group_active)
-			return group_solve_marginal_poses(s, p_values, p_rhs_inout);
-		s.d_A.Alloc(size_t(s.n_values));
-		s.d_rhs.Alloc(size_t(s.n_scalars));
-		s.Upload_Values(p_values);
-		Upload_Rhs_And_Join(s, p_rhs_inout);
-		return SLAMPP_HIP_OK;
-	});
-	if(n_result != SLAMPP_HIP_OK || p_solver->b_group_active)
-		return n_result;
-	slampp_hip_solver &s = *p_solver;
-	n_result = slampp_hip_solve_marginal_poses_device_async(p_solver, s.d_A.p(), s.d_rhs.p());
-	if(n_result == SLAMPP_HIP_OK)
-		n_result = slampp_hip_sync(p_solver);
-	if(n_result == SLAMPP_HIP_OK) {
-		n_result = guarded(p_solver, [&]() -> int {
-			SLAMPP_HIP_CHECK(hipMemcpyAsync(p_rhs_inout, s.d_rhs.p(), size_t(s.n_scalars) * sizeof(double), hipMemcpyDeviceToHost, s.stream));
-			SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
-			return SLAMPP_HIP_OK;
-		});
-	}
-	return n_result;
-}
-
-// The factor's block structure in the CALLER's block columns (what slampp_hip_factorize fills).  Without wide columns that is
-// the plan's own; where block columns wider than 8 were cut into pieces (Refine_Structure) the pieces are put together
-// again: block (I, J) of the caller's columns exists where any of its pieces does.  Needs the pieces of a column next to
-// each other and in order, which the caller's own order (option natural_order; what Factorize_PosDef_Blocky asks for:
-// the matrix comes pre-ordered, LinearSolver_CholMod.cpp:362-544) guarantees.
-namespace {
-
-struct TCoarseFactor {
-	std::vector<int32_t> perm, dim, lrow;
-	std::vector<int64_t> lptr, loff; // loff[l_blocks] = number of values
-	std::vector<int32_t> piece_col, piece_off; // refined column -> caller's column, scalar offset inside it
-};
-
-bool coarse_factor_structure(const slampp_hip_solver &s, TCoarseFactor &r_out, std::string &r_s_why)
-{
-	const Plan &P = s.plan;
-	const int64_t n = int64_t(s.cumsum.size()) - 1, n_refined = int64_t(s.refined_cumsum.size()) - 1;
-	r_out.piece_col.assign(size_t(n_refined), 0);
-	r_out.piece_off.assign(size_t(n_refined), 0);
-	{
-		int64_t c = 0;
-		for(int64_t p = 0; p < n_refined; ++ p) {
-			while(s.refined_cumsum[p] >= s.cumsum[c + 1])
-				++ c;
-			r_out.piece_col[p] = int32_t(c);
-			r_out.piece_off[p] = int32_t(s.refined_cumsum[p] - s.cumsum[c]);
-		}
-	}
-	for(int64_t p = 0; p < n_refined; ++ p) {
-		if(P.perm[p] != p) {
-			r_s_why = "factorize: block columns wider than 8 are factored in pieces: the factor has the caller's block layout only in the caller's own order (option natural_order = 1)";
-			return false;
-		}
-	}
-	r_out.perm.resize(size_t(n));
-	r_out.dim.resize(size_t(n));
-	for(int64_t c = 0; c < n; ++ c) {
-		r_out.perm[c] = int32_t(c);
-		r_out.dim[c] = int32_t(s.cumsum[c + 1] - s.cumsum[c]);
-	}
-	r_out.lptr.assign(1, 0);
-	r_out.lrow.clear();
-	r_out.loff.clear();
-	std::vector<int32_t> rows;
-	int64_t n_off = 0, p = 0;
-	for(int64_t c = 0; c < n; ++ c) {
-		rows.clear();
-		for(; p < n_refined && r_out.piece_col[p] == c; ++ p) {
-			for(int64_t k = P.lptr[p]; k < P.lptr[p + 1]; ++ k)
-				rows.push_back(r_out.piece_col[P.lrow[k]]);
-		}
-		std::sort(rows.begin(), rows.end());
-		rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
-		for(size_t i = 0; i < rows.size(); ++ i) { // (ascending: the diagonal block first)
-			r_out.lrow.push_back(rows[i]);
-			r_out.loff.push_back(n_off);
-			n_off += int64_t(r_out.dim[rows[i]]) * r_out.dim[c];
-		}
-		r_out.lptr.push_back(int64_t(r_out.lrow.size()));
-	}
-	r_out.loff.push_back(n_off);
-	return true;
-}
-
-} // anonymous namespace
-
-int slampp_hip_factor_structure(const slampp_hip_solver *p_solver, int64_t *p_n_bcols, int64_t *p_l_blocks, int64_t *p_l_values,
-	int32_t *p_perm, int32_t *p_dim, int64_t *p_lptr, int32_t *p_lrow, int64_t *p_loff)
-{
-	if(!p_solver || !p_solver->b_analyzed || p_solver->n_mode != SLAMPP_HIP_MODE_SPARSE)
-		return SLAMPP_HIP_ERR_INVALID;
-	const slampp_hip_solver &s = *p_solver;
-	const Plan &P = s.plan;
-	try {
-		if(!s.b_refined) {
-			if(p_n_bcols) *p_n_bcols = P.n;
-			if(p_l_blocks) *p_l_blocks = int64_t(P.lrow.size());
-			if(p_l_values) *p_l_values = P.loff[P.lrow.size()];
-			if(p_perm) std::copy(P.perm.begin(), P.perm.end(), p_perm);
-			if(p_dim) std::copy(P.dim.begin(), P.dim.end(), p_dim);
-			if(p_lptr) std::copy(P.lptr.begin(), P.lptr.end(), p_lptr);
-			if(p_lrow) std::copy(P.lrow.begin(), P.lrow.end(), p_lrow);
-			if(p_loff) std::copy(P.loff.begin(), P.loff.begin() + P.lrow.size(), p_loff);
-			return SLAMPP_HIP_OK;
-		}
-		TCoarseFactor t;
-		std::string s_why;
-		if(!coarse_factor_structure(s, t, s_why)) {
-			const_cast<slampp_hip_solver*>(p_solver)->s_error = s_why;
-			return SLAMPP_HIP_ERR_UNSUPPORTED;
-		}
-		if(p_n_bcols) *p_n_bcols = int64_t(t.dim.size());
-		if(p_l_blocks) *p_l_blocks = int64_t(t.lrow.size());
-		if(p_l_values) *p_l_values = t.loff.back();
-		if(p_perm) std::copy(t.perm.begin(), t.perm.end(), p_perm);
-		if(p_dim) std::copy(t.dim.begin(), t.dim.end(), p_dim);
-		if(p_lptr) std::copy(t.lptr.begin(), t.lptr.end(), p_lptr);
-		if(p_lrow) std::copy(t.lrow.begin(), t.lrow.end(), p_lrow);
-		if(p_loff) std::copy(t.loff.begin(), t.loff.end() - 1, p_loff);
-		return SLAMPP_HIP_OK;
-	} catch(std::bad_alloc&) {
-		return SLAMPP_HIP_ERR_ALLOC;
-	}
-}
-
-int slampp_hip_factorize(slampp_hip_solver *p_solver, const double *p_values, double *p_factor_out)
-{
-	int n_result = guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		if(!s.b_analyzed)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "factorize: analyze was not called");
-		if(s.n_mode != SLAMPP_HIP_MODE_SPARSE)
-			return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, "factorize: the sparse mode only");
-		if(!p_values || !p_factor_out)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "factorize: null pointer");
-		if(s.b_refined) {
-			for(size_t p = 0; p < s.plan.perm.size(); ++ p) {
-				if(s.plan.perm[p] != int32_t(p))
-					return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, "factorize: block columns wider than 8 are factored in pieces: the factor has the caller's block layout only in the caller's own order (option natural_order = 1)");
-			}
-		}
-		s.d_A.Alloc(size_t(s.n_values));
-		s.d_rhs.Alloc(size_t(s.n_scalars));
-		Upload_Values_And_Join(s, p_values);
-		SLAMPP_HIP_CHECK(hipMemsetAsync(s.d_rhs.p(), 0, size_t(s.n_scalars) * sizeof(double), s.stream)); // the fused forward substitution runs on zeros
-		s.Enqueue_Sparse(s.d_A.p(), s.d_rhs.p(), true, true); // (a dense top factors its columns on the matrix cores and hands them back into the block layout)
-		s.b_factored = s.n_dense_dim == 0; // (with a dense top the substitutions' vectors were not brought along: no solve_again from this)
-		++ s.n_factor_gen;
-		return SLAMPP_HIP_OK;
-	});
-	if(n_result != SLAMPP_HIP_OK)
-		return n_result;
-	n_result = slampp_hip_sync(p_solver);
-	if(n_result != SLAMPP_HIP_OK)
-		return n_result;
-	return guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		const Plan &P = s.plan;
-		const size_t n_l_values = size_t(P.loff[P.lrow.size()]);
-		if(!s.b_refined) {
-			SLAMPP_HIP_CHECK(hipMemcpyAsync(p_factor_out, s.d_L.p(), n_l_values * sizeof(double), hipMemcpyDeviceToHost, s.stream));
-			SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
-			return SLAMPP_HIP_OK;
-		}
-		// the pieces of the wide columns put together again: piece block (pi, pj) is a sub-block of the caller's block (I, J)
-		TCoarseFactor t;
-		std::string s_why;
-		if(!coarse_factor_structure(s, t, s_why))
-			return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, s_why.c_str());
-		std::vector<double> pieces(n_l_values);
-		SLAMPP_HIP_CHECK(hipMemcpyAsync(pieces.data(), s.d_L.p(), n_l_values * sizeof(double), hipMemcpyDeviceToHost, s.stream));
-		SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
-		std::fill(p_factor_out, p_factor_out + t.loff.back(), 0.0);
-		for(int64_t pj = 0; pj < int64_t(P.n); ++ pj) {
-			const int32_t J = t.piece_col[pj];
-			const int n_col0 = t.piece_off[pj], w = P.dim[pj];
-			for(int64_t k = P.lptr[pj]; k < P.lptr[pj + 1]; ++ k) {
-				const int32_t pi = P.lrow[k], I = t.piece_col[pi];
-				const int n_row0 = t.piece_off[pi], h = P.dim[pi], H = t.dim[I];
-				const int32_t *p_first = &t.lrow[size_t(t.lptr[J])], *p_last = &t.lrow[size_t(t.lptr[J + 1])];
-				const int64_t n_blk = t.lptr[J] + (std::lower_bound(p_first, p_last, I) - p_first);
-				double *p_dst = p_factor_out + t.loff[size_t(n_blk)];
-				const double *p_src = &pieces[size_t(P.loff[k])];
-				for(int b = 0; b < w; ++ b) {
-					for(int a = 0; a < h; ++ a)
-						p_dst[(n_row0 + a) + size_t(n_col0 + b) * H] = p_src[a + size_t(b) * h];
-				}
-			}
-		}
-		return SLAMPP_HIP_OK;
-	});
-}
-
-namespace {
-
-// Schur mode: which kept state another right-hand side can be solved from (inside guarded()).  0 = none; 1 = what a solve
-// with "schur_keep" / "schur_incremental" left; 2 = what a Schur covariance call left.  Both are generations of
-// n_factor_gen: whatever installs or drops a factor since (a solve, a batch, marginals, a factorization that turns out not
-// positive definite at slampp_hip_sync, set_structure, analyze) counts it up and thereby ends them.
-int schur_resolve_source(const slampp_hip_solver &s)
-{
-	if(!s.p_schur || !s.n_factor_gen)
-		return 0;
-	if(s.n_schur_keep_gen == s.n_factor_gen)
-		return 1;
-	if(s.n_schur_cov_gen == s.n_factor_gen)
-		return 2;
-	return 0;
-}
-
-// the checks of slampp_hip_solve_again_device_async / slampp_hip_refine (inside guarded()): SLAMPP_HIP_OK, and how to solve
-int resolve_checks(slampp_hip_solver *p_solver, const char *p_s_name, int *p_n_schur_source)
-{
-	slampp_hip_solver &s = *p_solver;
-	const std::string s_name(p_s_name);
-	*p_n_schur_source = 0;
-	if(s.b_group_active || (s.n_mode == SLAMPP_HIP_MODE_SCHUR && s.p_allreduce))
-		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, (s_name + ": not for a handle that solves with landmark shards or over several devices").c_str());
-	if(!s.b_analyzed)
-		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, (s_name + ": no valid factorization (analyze was not called)").c_str());
-	if(s.n_mode == SLAMPP_HIP_MODE_SPARSE) {
-		if(!s.b_factored)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, (s_name + ": no valid factorization").c_str());
-		return SLAMPP_HIP_OK;
-	}
-	if(!(*p_n_schur_source = schur_resolve_source(s)))
-		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, (s_name + ": no kept factor of the reduced camera system: set the option schur_keep (or "
-			"schur_incremental) before analyze and solve, or call a Schur covariance entry point; anything that factors or fails "
-			"to since ends its validity").c_str());
-	return SLAMPP_HIP_OK;
-}
-
-// the substitutions themselves, enqueue-only
-void resolve_enqueue(slampp_hip_solver &s, double *p_rhs_dev, int n_schur_source)
-{
-	if(s.n_mode == SLAMPP_HIP_MODE_SPARSE)
-		s.Enqueue_Sparse(0, p_rhs_dev, false);
-	else
-		schur_resolve_enqueue(s, p_rhs_dev, n_schur_source == 2);
-}
-
-} // anonymous namespace
-
-int slampp_hip_solve_again_device_async(slampp_hip_solver *p_solver, double *p_rhs_inout_dev)
-{
-	return guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		int n_source = 0;
-		const int n_check = resolve_checks(p_solver, "solve_again", &n_source);
-		if(n_check != SLAMPP_HIP_OK)
-			return n_check;
-		if(!p_rhs_inout_dev)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_again: null pointer");
-		resolve_enqueue(s, p_rhs_inout_dev, n_source);
-		return SLAMPP_HIP_OK;
-	});
-}
-
-int slampp_hip_solve_again(slampp_hip_solver *p_solver, double *p_rhs_inout)
-{
-	return guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		int n_source = 0;
-		if(s.n_mode != SLAMPP_HIP_MODE_SPARSE && s.b_analyzed && !s.b_group_active && (n_source = schur_resolve_source(s))) {
-			// Schur mode with W, C^-1 and the reduced system's factor kept: the same route as the device entry point
-			const int n_check = resolve_checks(p_solver, "solve_again", &n_source);
-			if(n_check != SLAMPP_HIP_OK)
-				return n_check;
-		} else {
-			if(!s.b_factored)
-				return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_again: no valid factorization");
-			if(s.n_mode != SLAMPP_HIP_MODE_SPARSE)
-				return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, "solve_again: only the sparse path keeps its factor");
-		}
-		if(!p_rhs_inout)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_again: null pointer");
-		s.d_rhs.Alloc(size_t(s.n_scalars));
-		SLAMPP_HIP_CHECK(hipMemcpyAsync(s.d_rhs.p(), p_rhs_inout, size_t(s.n_scalars) * sizeof(double), hipMemcpyHostToDevice, s.stream));
-		resolve_enqueue(s, s.d_rhs.p(), n_source);
-		SLAMPP_HIP_CHECK(hipMemcpyAsync(p_rhs_inout, s.d_rhs.p(), size_t(s.n_scalars) * sizeof(double), hipMemcpyDeviceToHost, s.stream));
-		SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
-		return SLAMPP_HIP_OK;
-	});
-}
-
-// ---- y = alpha Lambda x + beta y, dot products, iterative refinement (multiply.hip) ----
-
-namespace {
-
-int multiply_checks(slampp_hip_solver *p_solver, const char *p_s_name)
-{
-	slampp_hip_solver &s = *p_solver;
-	const std::string s_name(p_s_name);
-	if(!s.b_has_structure)
-		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, (s_name + ": set_structure was not called").c_str());
-	if(s.b_group_active)
-		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, (s_name + ": this handle solves with landmark shards on several devices").c_str());
-	return SLAMPP_HIP_OK;
-}
-
-} // anonymous namespace
-
-int slampp_hip_multiply_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, const double *p_x_dev,
-	double *p_y_dev, double f_alpha, double f_beta)
-{
-	return guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		const int n_check = multiply_checks(p_solver, "multiply");
-		if(n_check != SLAMPP_HIP_OK)
-			return n_check;
-		if(!p_values_dev || !p_x_dev || !p_y_dev)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "multiply: null pointer");
-		if(p_x_dev == p_y_dev)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "multiply: x and y must be different vectors (every row of y reads all of x)");
-		s.Require_Multiply();
-		multiply_enqueue(*s.p_mul, p_values_dev, p_x_dev, p_y_dev, f_alpha, f_beta, s.stream);
-		return SLAMPP_HIP_OK;
-	});
-}
-
-int slampp_hip_multiply(slampp_hip_solver *p_solver, const double *p_values, const double *p_x, double *p_y, double f_alpha,
-	double f_beta)
-{
-	int n_result = guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		const int n_check = multiply_checks(p_solver, "multiply");
-		if(n_check != SLAMPP_HIP_OK)
-			return n_check;
-		if(!p_values || !p_x || !p_y)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "multiply: null pointer");
-		if(p_x == p_y)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "multiply: x and y must be different vectors (every row of y reads all of x)");
-		const size_t n_bytes = size_t(s.n_scalars) * sizeof(double);
-		s.d_A.Alloc(size_t(s.n_values));
-		s.d_mul_x.Alloc(size_t(s.n_scalars));
-		s.d_mul_y.Alloc(size_t(s.n_scalars));
-		Upload_Values_And_Join(s, p_values);
-		SLAMPP_HIP_CHECK(hipMemcpyAsync(s.d_mul_x.p(), p_x, n_bytes, hipMemcpyHostToDevice, s.stream));
-		if(f_beta != 0)
-			SLAMPP_HIP_CHECK(hipMemcpyAsync(s.d_mul_y.p(), p_y, n_bytes, hipMemcpyHostToDevice, s.stream));
-		return SLAMPP_HIP_OK;
-	});
-	if(n_result != SLAMPP_HIP_OK)
-		return n_result;
-	slampp_hip_solver &s = *p_solver;
-	n_result = slampp_hip_multiply_device_async(p_solver, s.d_A.p(), s.d_mul_x.p(), s.d_mul_y.p(), f_alpha, f_beta);
-	if(n_result != SLAMPP_HIP_OK)
-		return n_result;
-	return guarded(p_solver, [&]() -> int {
-		SLAMPP_HIP_CHECK(hipMemcpyAsync(p_y, s.d_mul_y.p(), size_t(s.n_scalars) * sizeof(double), hipMemcpyDeviceToHost, s.stream));
-		SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
-		return SLAMPP_HIP_OK;
-	});
-}
-
-int slampp_hip_dot_device_async(slampp_hip_solver *p_solver, const double *p_a_dev, const double *p_b_dev, int64_t n,
-	double *p_out_dev)
-{
-	return guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		if(!p_a_dev || !p_b_dev || !p_out_dev || n < 0)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "dot: null pointer or negative length");
-		if(s.b_group_active)
-			return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, "dot: this handle solves with landmark shards on several devices");
-		s.d_reduce.Alloc(reduce_MAX_PARTIALS);
-		dot_enqueue(p_a_dev, p_b_dev, n, s.d_reduce.p(), p_out_dev, s.stream);
-		return SLAMPP_HIP_OK;
-	});
-}
-
-int slampp_hip_refine_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, const double *p_eta_dev,
-	double *p_x_inout_dev, int n_steps, double *p_resid_inf_dev)
-{
-	return guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		int n_check = multiply_checks(p_solver, "refine"), n_source = 0;
-		if(n_check != SLAMPP_HIP_OK || (n_check = resolve_checks(p_solver, "refine", &n_source)) != SLAMPP_HIP_OK)
-			return n_check;
-		if(!p_values_dev || !p_eta_dev || !p_x_inout_dev)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "refine: null pointer");
-		if(n_steps < 1 || n_steps > 8)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "refine: between 1 and 8 steps");
-		if(p_eta_dev == p_x_inout_dev)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "refine: eta and x must be different vectors");
-		s.Require_Multiply();
-		s.d_refine_r.Alloc(2 * size_t(s.n_scalars)); // the one workspace: the residual, then the correction | the x before the step
-		s.d_reduce.Alloc(reduce_MAX_PARTIALS);
-		s.d_refine_resid.Alloc(refine_SCALARS);
-		double *p_r = s.d_refine_r.p(), *p_keep = p_r + s.n_scalars;
-		double *p_norm = (p_resid_inf_dev)? p_resid_inf_dev : s.d_refine_resid.p(); // (the norms decide, asked for or not)
-		double *p_trial = s.d_refine_resid.p() + refine_TRIAL, *p_stop = s.d_refine_resid.p() + refine_STOP;
-		const size_t n_bytes = size_t(s.n_scalars) * sizeof(double);
-		SLAMPP_HIP_CHECK(hipMemsetAsync(p_stop, 0, sizeof(double), s.stream));
-		for(int k = 0; k <= n_steps; ++ k) {
-			SLAMPP_HIP_CHECK(hipMemcpyAsync(p_r, p_eta_dev, n_bytes, hipMemcpyDeviceToDevice, s.stream));
-			multiply_enqueue(*s.p_mul, p_values_dev, p_x_inout_dev, p_r, -1.0, 1.0, s.stream); // r = eta - Lambda x
-			norm_inf_enqueue(p_r, s.n_scalars, s.d_reduce.p(), (k)? p_trial : p_norm, s.stream);
-			if(k) { // was step k - 1 worth taking? if not, x is put back and the steps after it add nothing
-				refine_accept_enqueue(p_x_inout_dev, p_keep, s.n_scalars, p_norm + (k - 1), p_trial, p_norm + k, p_stop,
-					s.stream);
-			}
-			if(k == n_steps)
-				break;
-			resolve_enqueue(s, p_r, n_source); // d = Lambda^-1 r with the kept factor
-			refine_step_enqueue(p_x_inout_dev, p_keep, p_r, s.n_scalars, p_stop, s.stream);
-		}
-		return SLAMPP_HIP_OK;
-	});
-}
-
-int slampp_hip_refine(slampp_hip_solver *p_solver, const double *p_values, const double *p_eta, double *p_x_inout, int n_steps,
-	double *p_resid_inf)
-{
-	int n_result = guarded(p_solver, [&]() -> int {
-		slampp_hip_solver &s = *p_solver;
-		int n_check = multiply_checks(p_solver, "refine"), n_source = 0;
-		if(n_check != SLAMPP_HIP_OK || (n_check = resolve_checks(p_solver, "refine", &n_source)) != SLAMPP_HIP_OK)
-			return n_check;
-		if(!p_values || !p_eta || !p_x_inout)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "refine: null pointer");
-		if(n_steps < 1 || n_steps > 8)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "refine: between 1 and 8 steps");
-		const size_t n_bytes = size_t(s.n_scalars) * sizeof(double);
-		s.d_A.Alloc(size_t(s.n_values));
-		s.d_mul_x.Alloc(size_t(s.n_scalars));
-		s.d_mul_y.Alloc(size_t(s.n_scalars));
-		s.d_refine_resid.Alloc(refine_SCALARS);
-		Upload_Values_And_Join(s, p_values);
-		SLAMPP_HIP_CHECK(hipMemcpyAsync(s.d_mul_y.p(), p_eta, n_bytes, hipMemcpyHostToDevice, s.stream));
-		SLAMPP_HIP_CHECK(hipMemcpyAsync(s.d_mul_x.p(), p_x_inout, n_bytes, hipMemcpyHostToDevice, s.stream));
-		return SLAMPP_HIP_OK;
-	});
-	if(n_result != SLAMPP_HIP_OK)
-		return n_result;
-	slampp_hip_solver &s = *p_solver;
-	n_result = slampp_hip_refine_device_async(p_solver, s.d_A.p(), s.d_mul_y.p(), s.d_mul_x.p(), n_steps,
-		p_resid_inf? s.d_refine_resid.p() : 0);
-	if(n_result != SLAMPP_HIP_OK)
-		return n_result;
-	return guarded(p_solver, [&]() -> int {
-		SLAMPP_HIP_CHECK(hipMemcpyAsync(p_x_inout, s.d_mul_x.p(), size_t(s.n_scalars) * sizeof(double), hipMemcpyDeviceToHost, s.stream));
-		if(p_resid_inf)
-			SLAMPP_HIP_CHECK(hipMemcpyAsync(p_resid_inf, s.d_refine_resid.p(), size_t(n_steps + 1) * sizeof(double), hipMemcpyDeviceToHost, s.stream));
-		SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream));
 		return SLAMPP_HIP_OK;
 	});
 }

@@ -178,9 +178,15 @@ struct slampp_hip_solver {
 	// with values = NULL reuses their reduced-system factor, C^-1 and W only while nothing else has run since
 	uint64_t n_factor_gen = 0, n_schur_cov_gen = 0; // (0: none)
 	// ... and so does a Schur solve that kept W and the reduced factor (options "schur_keep", "schur_incremental"): what
-	// slampp_hip_solve_again works from in Schur mode is valid while this equals n_factor_gen -- every path that installs or
-	// drops a factor counts n_factor_gen up, so none of them can leave it standing (n_batch_owner_member)
+	// slampp_hip_solve_again works from in Schur mode is valid while this equals n_factor_gen
 	uint64_t n_schur_keep_gen = 0;
+	// The rule: every path that installs or drops a factor counts n_factor_gen up, so none of them can leave what an earlier
+	// factorization kept standing (n_batch_owner_member).  These four are the only writers of b_factored (the
+	// handle's initialisation aside) and of the three generations.
+	void Factor_Installed(bool b_resolvable = true) { b_factored = b_resolvable; ++ n_factor_gen; } // b_resolvable: slampp_hip_solve_again can work from it
+	void Factor_Dropped() { Factor_Installed(false); }
+	void Schur_Kept() { n_schur_keep_gen = n_factor_gen; } // the factorization just counted kept W, C^-1 and the reduced system's factor
+	void Schur_Cov_Left() { n_schur_cov_gen = n_factor_gen; } // a Schur covariance call left (or found: values = NULL) its state with this generation
 	// y = alpha Lambda x + beta y (multiply.hip): the row lists of the structure, built at the first product after a
 	// set_structure; the split threshold of its long rows (development option "multiply_long_row"); workspaces of the
 	// reductions, of slampp_hip_refine and of the host entry points

@@ -203,8 +203,7 @@ void slampp_hip_solver::Free_Device(bool b_keep_multiply)
 	}
 	d_reduce.Free(); d_refine_r.Free(); d_mul_x.Free(); d_mul_y.Free(); d_refine_resid.Free();
 	b_analyzed = false;
-	b_factored = false;
-	++ n_factor_gen;
+	Factor_Dropped();
 }
 
 size_t slampp_hip_solver::n_Device_Bytes() const

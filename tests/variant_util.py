@@ -394,8 +394,8 @@ def reach_subtree_v1(r):
 
 
 def reach_batch(r):
-    """Gate 5, capi.hip:763-765: K > 1 members in one pass of launches (blockIdx.y) needs no dense top, no regrouped values and
-    aligned bases / even strides; the test passes those."""
+    """Gate 5, capi.hip: slampp_hip_factor_solve_batch_device_async: K > 1 members in one pass of launches (blockIdx.y) needs no
+    dense top, no regrouped values and aligned bases / even strides; the test passes those."""
     assert r.plan["dense_dim"] == 0 and int(r.sysrec.dims.max()) <= 8
 
 
