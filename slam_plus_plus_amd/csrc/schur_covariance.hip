@@ -13,9 +13,13 @@
 // are then -W_q^T X(cams(q)) per landmark q, plus C_p^-1 on a landmark column's own block.
 // Z is read either from the dense inverse (dense_inverse.hip: lower triangle and diagonal 64 x 64 tiles valid, element
 // (i, j) read as (max, min)) or from the sparse inverse subset on the reduced system's factor pattern (sparse_inverse.hip:
-// where a block sits and whether it is stored transposed comes from host-built tables, schur.hip).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+// where a block sits and whether it is stored transposed comes from host-built tables, schur_setup.hip).
+// This file holds the kernels, their launches (functions of the state, one dispatch on the block sizes each) and the two
+// entry points that drive them behind the reduced system's factorization: schur_cov_pattern_enqueue, schur_cov_columns_enqueue.
+#include "schur_state.h"
+#include "covariance.h"
+
+#include <algorithm>
 
 namespace slampp {
 
@@ -317,94 +321,187 @@ schur_cov_point_rows_kernel(int64_t nc, int64_t np, const int64_t *__restrict__ 
 		p_out[r] = acc[r];
 }
 
-// ---- launches ----
+// ---- launches: Z is the sparse inverse subset in d_m_Zs (S.b_cov_sparse) or the dense inverse in d_m_Z ----
 
-template <int DC, int DP>
-static void pattern_t(int64_t nc, int64_t np, const int64_t *ptr, const int32_t *brow, int64_t ubase, const int64_t *a_zent,
-	const int64_t *pair_ptr, const int64_t *pair_tab, const double *W, const double *Cinv, const double *Z, int ld, double *out,
+static void schur_cov_pattern_gather(CSchurState &S, double *out, hipStream_t stream)
+{
+	schur_dispatch(S.DC, S.DP, [&](auto dc, auto dp) {
+		constexpr int DC = dc(), DP = dp();
+		const int64_t ubase = S.n_ablocks * DC * DC; // (the camera blocks come first in the values: ptr[nc] blocks of DC x DC)
+		const bool b_sparse = S.b_cov_sparse;
+		const double *Z = b_sparse? S.d_m_Zs.p() : S.d_m_Z.p();
+		const int ld = b_sparse? 0 : S.Npad;
+		const int64_t *pair_ptr = b_sparse? S.d_pair_ptr.p() : 0, *pair_tab = b_sparse? S.d_pair_tab.p() : 0;
+		if(ubase)
+			hipLaunchKernelGGL((schur_cov_cam_pattern_kernel<DC>), dim3(unsigned((ubase + 255) / 256)), dim3(256), 0, stream,
+				S.nc, S.d_ptr.p(), S.d_brow.p(), b_sparse? S.d_a_zent.p() : (const int64_t*)0, Z, ld, out);
+		if(S.np) {
+			const dim3 grid(unsigned((S.np * COV_G + 255) / 256));
+			if(b_sparse)
+				hipLaunchKernelGGL((schur_cov_point_pattern_kernel<DC, DP, true>), grid, dim3(256), 0, stream,
+					S.d_ptr.p(), S.d_brow.p(), S.nc, S.np, ubase, pair_ptr, pair_tab, S.d_W.p(), S.d_Cinv.p(), Z, ld, out);
+			else
+				hipLaunchKernelGGL((schur_cov_point_pattern_kernel<DC, DP, false>), grid, dim3(256), 0, stream,
+					S.d_ptr.p(), S.d_brow.p(), S.nc, S.np, ubase, pair_ptr, pair_tab, S.d_W.p(), S.d_Cinv.p(), Z, ld, out);
+		}
+	});
+}
+
+// one pass of kp scalar columns, p_cols their sources, col0 the first one's place in out (leading dimension n_ld): the
+// camera part from the dense inverse, into out and d_cov_X -- or (S.b_cov_sparse) its right-hand sides into the zeroed d_cov_B
+static void schur_cov_cols_cam_launch(CSchurState &S, const int64_t *p_cols, int kp, int64_t col0, double *out, int64_t n_ld,
 	hipStream_t stream)
 {
-	const int64_t n_cam_elems = ubase; // (the camera blocks come first in the values: ptr[nc] blocks of DC x DC)
-	if(n_cam_elems)
-		hipLaunchKernelGGL((schur_cov_cam_pattern_kernel<DC>), dim3(unsigned((n_cam_elems + 255) / 256)), dim3(256), 0, stream,
-			nc, ptr, brow, a_zent, Z, ld, out);
-	if(np) {
-		const dim3 grid(unsigned((np * COV_G + 255) / 256));
-		if(pair_tab)
-			hipLaunchKernelGGL((schur_cov_point_pattern_kernel<DC, DP, true>), grid, dim3(256), 0, stream,
-				ptr, brow, nc, np, ubase, pair_ptr, pair_tab, W, Cinv, Z, ld, out);
+	schur_dispatch(S.DC, S.DP, [&](auto dc, auto dp) {
+		constexpr int DC = dc(), DP = dp();
+		if(!S.b_cov_sparse)
+			hipLaunchKernelGGL((schur_cov_cols_dense_kernel<DC, DP>), dim3(unsigned((S.nc * DC + 255) / 256), unsigned(kp)), dim3(256), 0,
+				stream, S.nc, S.d_ptr.p(), S.d_brow.p(), S.d_W.p(), S.d_m_Z.p(), S.Npad, p_cols, kp, S.d_cov_X.p(), out, n_ld, col0);
 		else
-			hipLaunchKernelGGL((schur_cov_point_pattern_kernel<DC, DP, false>), grid, dim3(256), 0, stream,
-				ptr, brow, nc, np, ubase, pair_ptr, pair_tab, W, Cinv, Z, ld, out);
-	}
+			hipLaunchKernelGGL((schur_cov_rhs_kernel<DC, DP>), dim3(unsigned(kp)), dim3(64), 0, stream, S.nc, S.d_ptr.p(), S.d_brow.p(),
+				S.d_W.p(), S.d_cam_csn.p(), p_cols, kp, S.d_cov_B.p());
+	});
 }
 
-void schur_cov_pattern_launch(int DC, int DP, int64_t nc, int64_t np, const int64_t *ptr, const int32_t *brow, int64_t ubase,
-	const int64_t *a_zent, const int64_t *pair_ptr, const int64_t *pair_tab, const double *W, const double *Cinv, const double *Z,
-	int ld, double *out, hipStream_t stream)
+// ... the camera part as the substitutions left it in out, interleaved into d_cov_X
+static void schur_cov_cols_interleave_launch(CSchurState &S, int kp, int64_t col0, const double *out, int64_t n_ld, hipStream_t stream)
 {
-	if(DC == 6 && DP == 3)
-		pattern_t<6, 3>(nc, np, ptr, brow, ubase, a_zent, pair_ptr, pair_tab, W, Cinv, Z, ld, out, stream);
-	else if(DC == 7 && DP == 3)
-		pattern_t<7, 3>(nc, np, ptr, brow, ubase, a_zent, pair_ptr, pair_tab, W, Cinv, Z, ld, out, stream);
-	else
-		pattern_t<3, 2>(nc, np, ptr, brow, ubase, a_zent, pair_ptr, pair_tab, W, Cinv, Z, ld, out, stream);
-}
-
-template <int DC, int DP>
-static void cols_cam_t(int64_t nc, const int64_t *ptr, const int32_t *brow, const double *W, const double *Z, int ld,
-	const int64_t *cam_csn, const int64_t *col_src, int kp, double *B, double *X, double *out, int64_t n_ld, int64_t n_col0,
-	hipStream_t stream)
-{
-	if(Z)
-		hipLaunchKernelGGL((schur_cov_cols_dense_kernel<DC, DP>), dim3(unsigned((nc * DC + 255) / 256), unsigned(kp)), dim3(256), 0,
-			stream, nc, ptr, brow, W, Z, ld, col_src, kp, X, out, n_ld, n_col0);
-	else
-		hipLaunchKernelGGL((schur_cov_rhs_kernel<DC, DP>), dim3(unsigned(kp)), dim3(64), 0, stream, nc, ptr, brow, W, cam_csn, col_src,
-			kp, B);
-}
-
-// Z given: the camera part of a pass from the dense inverse, into out and X; else the right-hand sides into B
-void schur_cov_cols_cam_launch(int DC, int DP, int64_t nc, const int64_t *ptr, const int32_t *brow, const double *W,
-	const double *Z, int ld, const int64_t *cam_csn, const int64_t *col_src, int kp, double *B, double *X, double *out,
-	int64_t n_ld, int64_t n_col0, hipStream_t stream)
-{
-	if(DC == 6 && DP == 3)
-		cols_cam_t<6, 3>(nc, ptr, brow, W, Z, ld, cam_csn, col_src, kp, B, X, out, n_ld, n_col0, stream);
-	else if(DC == 7 && DP == 3)
-		cols_cam_t<7, 3>(nc, ptr, brow, W, Z, ld, cam_csn, col_src, kp, B, X, out, n_ld, n_col0, stream);
-	else
-		cols_cam_t<3, 2>(nc, ptr, brow, W, Z, ld, cam_csn, col_src, kp, B, X, out, n_ld, n_col0, stream);
-}
-
-void schur_cov_interleave_launch(int64_t n_rows, int kp, const double *out, int64_t n_ld, int64_t n_col0, double *X,
-	hipStream_t stream)
-{
+	const int64_t n_rows = S.nc * S.DC;
 	hipLaunchKernelGGL(schur_cov_interleave_kernel, dim3(unsigned((n_rows * kp + 255) / 256)), dim3(256), 0, stream,
-		n_rows, kp, out, n_ld, n_col0, X);
+		n_rows, kp, out, n_ld, col0, S.d_cov_X.p());
 }
 
-template <int DC, int DP>
-static void cols_point_t(int64_t nc, int64_t np, const int64_t *ptr, const int32_t *brow, const double *W, const double *Cinv,
-	const int64_t *col_src, int kp, const double *X, double *out, int64_t n_ld, int64_t n_col0, hipStream_t stream)
+// ... and the landmark rows from d_cov_X
+static void schur_cov_cols_point_launch(CSchurState &S, const int64_t *p_cols, int kp, int64_t col0, double *out, int64_t n_ld,
+	hipStream_t stream)
 {
 	int n_g = 1;
 	while(n_g < kp)
 		n_g *= 2; // (kp <= 48: n_g <= 64)
-	if(np)
-		hipLaunchKernelGGL((schur_cov_point_rows_kernel<DC, DP>), dim3(unsigned((np * n_g + 255) / 256)), dim3(256), 0, stream,
-			nc, np, ptr, brow, W, Cinv, col_src, kp, n_g, X, out, n_ld, n_col0);
+	if(S.np)
+		schur_dispatch(S.DC, S.DP, [&](auto dc, auto dp) {
+			hipLaunchKernelGGL((schur_cov_point_rows_kernel<dc(), dp()>), dim3(unsigned((S.np * n_g + 255) / 256)), dim3(256), 0, stream,
+				S.nc, S.np, S.d_ptr.p(), S.d_brow.p(), S.d_W.p(), S.d_Cinv.p(), p_cols, kp, n_g, S.d_cov_X.p(), out, n_ld, col0);
+		});
 }
 
-void schur_cov_cols_point_launch(int DC, int DP, int64_t nc, int64_t np, const int64_t *ptr, const int32_t *brow, const double *W,
-	const double *Cinv, const int64_t *col_src, int kp, const double *X, double *out, int64_t n_ld, int64_t n_col0, hipStream_t stream)
+// ---- the entry points ----
+
+// C^-1, W and the factor of the reduced system from these values (A = 0: what the previous covariance call left), decided
+// as schur_marginals decides (options schur_sparse, marginals_dense); b_need_z: the inverse of the reduced system too
+static void schur_cov_factor(slampp_hip_solver &s, CSchurState &S, const double *A, bool b_need_z)
 {
-	if(DC == 6 && DP == 3)
-		cols_point_t<6, 3>(nc, np, ptr, brow, W, Cinv, col_src, kp, X, out, n_ld, n_col0, stream);
-	else if(DC == 7 && DP == 3)
-		cols_point_t<7, 3>(nc, np, ptr, brow, W, Cinv, col_src, kp, X, out, n_ld, n_col0, stream);
-	else
-		cols_point_t<3, 2>(nc, np, ptr, brow, W, Cinv, col_src, kp, X, out, n_ld, n_col0, stream);
+	if(A) {
+		if(!S.b_reduced_decided)
+			schur_setup_reduced(s, S);
+		S.b_cov_z_valid = false;
+		S.b_cov_sparse = S.b_reduced_sparse && s.n_marginals_dense == 0 && schur_setup_sparse_marginals(s, S);
+		if(S.b_cov_sparse)
+			schur_marginals_sparse_factor(s, S, A); // (no inverse until one is asked for)
+		else {
+			schur_marginals_dense_inverse(s, S, A); // (the columns are gathered from the dense inverse as well)
+			S.b_cov_z_valid = true;
+		}
+	}
+	if(S.b_cov_sparse) {
+		schur_setup_cov_tables(s, S);
+		if(b_need_z && !S.b_cov_z_valid) {
+			s.Phase_Begin("marginals_inverse");
+			sparse_inverse_enqueue(*S.p_sinv, S.p_inner->plan, S.p_inner->d_L.p(), S.p_inner->d_Linv.p(), S.d_m_Zs.p(), s.stream);
+			s.Phase_End();
+			S.b_cov_z_valid = true;
+		}
+	}
+}
+
+void schur_cov_pattern_enqueue(slampp_hip_solver &s, const double *p_values_dev, double *p_cov_dev)
+{
+	CSchurState &S = *s.p_schur;
+	if(p_values_dev)
+		schur_invalidate_previous(&S); // C^-1, W (and the packed reduced system) are recomputed from these values
+	schur_cov_factor(s, S, p_values_dev, true);
+	s.Phase_Begin("pattern_gather");
+	schur_cov_pattern_gather(S, p_cov_dev, s.stream);
+	s.Phase_End();
+	SLAMPP_HIP_CHECK(hipGetLastError());
+}
+
+// Whole block columns in passes of at most COV_K_PASS scalar columns (whole block columns each).  A pass's camera part:
+// dense reduced system -- gathered from its dense inverse (computed anyway: the factor's k-column substitutions would be a
+// dependent chain of tile solves per pass, the gather is one launch); sparse -- k-column substitutions with its factor
+// (covariance.hip), the right-hand sides E_c for a camera column and -W E_p for a landmark column.  Then the landmark rows.
+void schur_cov_columns_enqueue(slampp_hip_solver &s, const double *A, int n_cols, const int64_t *p_bcols, double *out)
+{
+	CSchurState &S = *s.p_schur;
+	if(A)
+		schur_invalidate_previous(&S);
+	hipStream_t st = s.stream;
+	schur_cov_factor(s, S, A, false);
+	const int DC = S.DC, DP = S.DP;
+	const int64_t nc = S.nc, n_ld = s.n_scalars;
+	const int64_t *ptr = s.bcol_ptr.data();
+	const int32_t *brow = s.brow.data();
+	// the column tables of every pass, one upload out of the host vector the call before the previous one used: its upload
+	// has long completed, so the host does not wait for the device here
+	const int n_buf = (S.n_cov_call ++) & 1;
+	std::vector<int64_t> &h_cols = S.h_cov_cols[n_buf];
+	if(S.ev_cov_cols[n_buf])
+		SLAMPP_HIP_CHECK(hipEventSynchronize(S.ev_cov_cols[n_buf]));
+	h_cols.clear();
+	std::vector<int> pass_first; // first listed column of every pass
+	int64_t n_pass_k = COV_K_PASS;
+	for(int i = 0; i < n_cols; ++ i) {
+		const int64_t c = p_bcols[i], d = (c < nc)? DC : DP;
+		if(n_pass_k + d > COV_K_PASS) {
+			pass_first.push_back(i);
+			n_pass_k = 0;
+		}
+		n_pass_k += d;
+		for(int64_t e = 0; e < d; ++ e)
+			h_cols.push_back((c < nc)? c * DC + e : -1 - ((c - nc) * DP + e));
+	}
+	pass_first.push_back(n_cols);
+	S.d_cov_cols.Upload(h_cols, st); // (stream-ordered behind the previous call's kernels, which read the old tables)
+	if(!S.ev_cov_cols[n_buf])
+		SLAMPP_HIP_CHECK(hipEventCreateWithFlags(&S.ev_cov_cols[n_buf], hipEventDisableTiming));
+	SLAMPP_HIP_CHECK(hipEventRecord(S.ev_cov_cols[n_buf], st));
+	S.d_cov_X.Alloc(size_t(nc * DC) * COV_K_PASS);
+	if(S.b_cov_sparse) {
+		S.d_cov_B.Alloc(size_t(nc * DC) * COV_K_PASS);
+		S.p_inner->Ensure_Leaf_Inverses(); // (the substitutions multiply by inv(L_jj) of every column)
+	}
+	s.Phase_Begin("marginal_columns");
+	std::vector<int64_t> srcs;
+	int64_t col0 = 0;
+	for(size_t p = 0; p + 1 < pass_first.size(); ++ p) {
+		int kp = 0;
+		srcs.clear();
+		for(int i = pass_first[p]; i < pass_first[p + 1]; ++ i) {
+			const int64_t c = p_bcols[i];
+			if(c < nc) {
+				kp += DC;
+				srcs.push_back(c);
+			} else {
+				kp += DP;
+				for(int64_t k = ptr[c]; k < ptr[c + 1] - 1; ++ k)
+					srcs.push_back(brow[k]); // the cameras observing the landmark
+			}
+		}
+		const int64_t *p_cols = S.d_cov_cols.p() + col0;
+		if(S.b_cov_sparse) {
+			std::sort(srcs.begin(), srcs.end());
+			srcs.erase(std::unique(srcs.begin(), srcs.end()), srcs.end());
+			SLAMPP_HIP_CHECK(hipMemsetAsync(S.d_cov_B.p(), 0, size_t(nc * DC) * kp * sizeof(double), st));
+			schur_cov_cols_cam_launch(S, p_cols, kp, col0, out, n_ld, st);
+			covariance_columns_rhs_enqueue(*S.p_inner, int(srcs.size()), srcs.data(), kp, S.d_cov_B.p(), out, n_ld, col0);
+			schur_cov_cols_interleave_launch(S, kp, col0, out, n_ld, st);
+		} else
+			schur_cov_cols_cam_launch(S, p_cols, kp, col0, out, n_ld, st);
+		schur_cov_cols_point_launch(S, p_cols, kp, col0, out, n_ld, st);
+		col0 += kp;
+	}
+	s.Phase_End();
+	SLAMPP_HIP_CHECK(hipGetLastError());
 }
 
 } // namespace slampp

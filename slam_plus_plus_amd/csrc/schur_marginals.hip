@@ -7,8 +7,10 @@
 // and the whole of its diagonal 64 x 64 tiles are valid, element (i, j) is read as (max, min).
 // The landmark kernel is a gather: k (k + 1) / 2 blocks of Z per landmark with k observations, DC column segments
 // each; neighbouring landmarks see neighbouring cameras, so most of them come out of L2.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+// With the reduced system factored by the sparse block path, Z is the sparse inverse subset on its factor's pattern instead.
+// This file holds the gather kernels and schur_enqueue_marginals, which drives them behind the reduced system's
+// factorization (schur.hip: schur_marginals_sparse_factor, schur_marginals_dense_inverse).
+#include "schur_state.h"
 
 namespace slampp {
 
@@ -180,52 +182,54 @@ schur_point_cov_sparse_kernel(const int64_t *__restrict__ ptr, int64_t nc, int64
 		out[pt * (DP * DP) + i] = cov[i];
 }
 
-template <int DC, int DP>
-static void launch_sparse_t(int64_t nc, int64_t np, const int64_t *ptr, const int64_t *cam_zoff, const int64_t *pair_ptr,
-	const int64_t *pair_tab, const double *W, const double *Cinv, const double *Z, double *cam_cov, double *point_cov,
-	hipStream_t stream)
+// the block diagonal gathered from the inverse subset in d_m_Zs (S.b_cov_sparse) or from the dense inverse in d_m_Z; either
+// output may be null
+static void schur_marginals_gather(CSchurState &S, double *cam_cov, double *point_cov, hipStream_t stream)
 {
-	if(cam_cov)
-		hipLaunchKernelGGL((schur_cam_cov_sparse_kernel<DC>), dim3(unsigned((nc * DC * DC + 255) / 256)), dim3(256), 0, stream,
-			nc, cam_zoff, Z, cam_cov);
-	if(point_cov)
-		hipLaunchKernelGGL((schur_point_cov_sparse_kernel<DC, DP>), dim3(unsigned((np + 127) / 128)), dim3(128), 0, stream,
-			ptr, nc, np, pair_ptr, pair_tab, W, Cinv, Z, point_cov);
+	schur_dispatch(S.DC, S.DP, [&](auto dc, auto dp) {
+		constexpr int DC = dc(), DP = dp();
+		const dim3 cam_grid(unsigned((S.nc * DC * DC + 255) / 256)), point_grid(unsigned((S.np + 127) / 128));
+		if(cam_cov && S.b_cov_sparse)
+			hipLaunchKernelGGL((schur_cam_cov_sparse_kernel<DC>), cam_grid, dim3(256), 0, stream,
+				S.nc, S.d_cam_zoff.p(), S.d_m_Zs.p(), cam_cov);
+		else if(cam_cov)
+			hipLaunchKernelGGL((schur_cam_cov_kernel<DC>), cam_grid, dim3(256), 0, stream, S.nc, S.d_m_Z.p(), S.Npad, cam_cov);
+		if(point_cov && S.b_cov_sparse)
+			hipLaunchKernelGGL((schur_point_cov_sparse_kernel<DC, DP>), point_grid, dim3(128), 0, stream,
+				S.d_ptr.p(), S.nc, S.np, S.d_pair_ptr.p(), S.d_pair_tab.p(), S.d_W.p(), S.d_Cinv.p(), S.d_m_Zs.p(), point_cov);
+		else if(point_cov)
+			hipLaunchKernelGGL((schur_point_cov_kernel<DC, DP>), point_grid, dim3(128), 0, stream,
+				S.d_ptr.p(), S.d_brow.p(), S.nc, S.np, S.d_W.p(), S.d_Cinv.p(), S.d_m_Z.p(), S.Npad, point_cov);
+	});
 }
 
-void schur_marginals_sparse_launch(int DC, int DP, int64_t nc, int64_t np, const int64_t *ptr, const int64_t *cam_zoff,
-	const int64_t *pair_ptr, const int64_t *pair_tab, const double *W, const double *Cinv, const double *Z, double *cam_cov,
-	double *point_cov, hipStream_t stream)
+// Block diagonal of Lambda^-1: the reduced system is assembled into a dense buffer of its own whatever way the solves
+// factor it, factored, inverted on the matrix cores, then gathered per landmark -- or, where the solves factor it by the
+// sparse block path, assembled and factored there, and the blocks of S^-1 on the factor's pattern are gathered
+// (sparse_inverse.hip).  Landmark shards: S is summed over the ranks; every rank then writes the covariances of its own
+// landmarks.
+void schur_enqueue_marginals(slampp_hip_solver &s, const double *p_values_dev, double *p_cam_cov_dev, double *p_point_cov_dev)
 {
-	if(DC == 6 && DP == 3)
-		launch_sparse_t<6, 3>(nc, np, ptr, cam_zoff, pair_ptr, pair_tab, W, Cinv, Z, cam_cov, point_cov, stream);
-	else if(DC == 7 && DP == 3)
-		launch_sparse_t<7, 3>(nc, np, ptr, cam_zoff, pair_ptr, pair_tab, W, Cinv, Z, cam_cov, point_cov, stream);
-	else
-		launch_sparse_t<3, 2>(nc, np, ptr, cam_zoff, pair_ptr, pair_tab, W, Cinv, Z, cam_cov, point_cov, stream);
-}
-
-template <int DC, int DP>
-static void launch_t(int64_t nc, int64_t np, const int64_t *ptr, const int32_t *brow, const double *W, const double *Cinv,
-	const double *Z, int ld, double *cam_cov, double *point_cov, hipStream_t stream)
-{
-	if(cam_cov)
-		hipLaunchKernelGGL((schur_cam_cov_kernel<DC>), dim3(unsigned((nc * DC * DC + 255) / 256)), dim3(256), 0, stream,
-			nc, Z, ld, cam_cov);
-	if(point_cov)
-		hipLaunchKernelGGL((schur_point_cov_kernel<DC, DP>), dim3(unsigned((np + 127) / 128)), dim3(128), 0, stream,
-			ptr, brow, nc, np, W, Cinv, Z, ld, point_cov);
-}
-
-void schur_marginals_launch(int DC, int DP, int64_t nc, int64_t np, const int64_t *ptr, const int32_t *brow, const double *W,
-	const double *Cinv, const double *Z, int ld, double *cam_cov, double *point_cov, hipStream_t stream)
-{
-	if(DC == 6 && DP == 3)
-		launch_t<6, 3>(nc, np, ptr, brow, W, Cinv, Z, ld, cam_cov, point_cov, stream);
-	else if(DC == 7 && DP == 3)
-		launch_t<7, 3>(nc, np, ptr, brow, W, Cinv, Z, ld, cam_cov, point_cov, stream);
-	else
-		launch_t<3, 2>(nc, np, ptr, brow, W, Cinv, Z, ld, cam_cov, point_cov, stream);
+	schur_invalidate_previous(s.p_schur); // C^-1, W (and the packed reduced system) are recomputed from these values
+	CSchurState &S = *s.p_schur;
+	// decided as for a solve: with the sparse reduced system the covariances go through the sparse inverse subset
+	if(s.p_allreduce && (S.p_union_fn != s.p_allreduce || S.p_union_context != s.p_allreduce_context))
+		schur_agree_on_union(s, S);
+	if(!S.b_reduced_decided)
+		schur_setup_reduced(s, S);
+	S.b_cov_sparse = S.b_reduced_sparse && s.n_marginals_dense == 0 && schur_setup_sparse_marginals(s, S);
+	if(S.b_cov_sparse) {
+		schur_marginals_sparse_factor(s, S, p_values_dev);
+		s.Phase_Begin("marginals_inverse");
+		sparse_inverse_enqueue(*S.p_sinv, S.p_inner->plan, S.p_inner->d_L.p(), S.p_inner->d_Linv.p(), S.d_m_Zs.p(), s.stream);
+		s.Phase_End();
+	} else
+		schur_marginals_dense_inverse(s, S, p_values_dev);
+	S.b_cov_z_valid = true; // (either way the inverse is of these values)
+	s.Phase_Begin("marginals_gather");
+	schur_marginals_gather(S, p_cam_cov_dev, p_point_cov_dev, s.stream);
+	s.Phase_End();
+	SLAMPP_HIP_CHECK(hipGetLastError());
 }
 
 } // namespace slampp

@@ -1,5 +1,5 @@
 // schur_resolve.hip -- another right-hand side with what a Schur solve left on the device (slampp_hip_solve_again in Schur
-// mode; the orchestration is schur_resolve_enqueue in schur.hip).  With W_o = U_o C_p^-1, C^-1 and the factor of S kept:
+// mode): its kernels and schur_resolve_enqueue, which drives them.  With W_o = U_o C_p^-1, C^-1 and the factor of S kept:
 //   r    = eta_c - sum over the observations o of camera c of W_o eta_p(o)      (schur_rhs_kernel of schur.hip, after
 //                                                                                schur_resolve_init_kernel has put eta_c in place)
 //   dx   = S^-1 r       the dense or the sparse factor's substitutions, or -- after a covariance call that inverted the dense
@@ -8,7 +8,8 @@
 // Lambda's values are not read: the reference's counterpart is cholmod_solve on a kept factor
 // (LinearSolver_CholMod.cpp:322-347) inside CLinearSolver_Schur's steps 8-13 (LinearSolver_Schur.h:1830-1886).
 // Every sum runs in a fixed order.
-#include "solver.h"
+#include "schur_state.h"
+#include "dense_chol.h"
 
 #include <algorithm>
 
@@ -84,26 +85,52 @@ schur_resolve_points_kernel(const int64_t *__restrict__ ptr, const int32_t *__re
 		out[gid] = dx[gid];
 }
 
-void schur_resolve_init_launch(const double *eta, int n, double *S, int ld, double *p_r, hipStream_t stream)
+void schur_resolve_enqueue(slampp_hip_solver &s, double *rhs, bool b_from_covariance)
 {
-	hipLaunchKernelGGL(schur_resolve_init_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, stream, eta, n, S, ld, p_r);
-}
-
-void schur_resolve_symv_launch(const double *Z, int ld, int n, const double *r, double *dx, hipStream_t stream)
-{
-	hipLaunchKernelGGL(schur_resolve_symv_kernel, dim3(unsigned(n)), dim3(64), 0, stream, Z, ld, n, r, dx);
-}
-
-void schur_resolve_points_launch(int DC, int DP, const int64_t *ptr, const int32_t *brow, int64_t nc, int64_t np, int n,
-	const double *Cinv, const double *W, const double *dx, double *out, hipStream_t stream)
-{
-	const dim3 grid(unsigned((std::max<int64_t>(np, n) + 255) / 256)), block(256);
-	if(DC == 6 && DP == 3)
-		hipLaunchKernelGGL((schur_resolve_points_kernel<6, 3>), grid, block, 0, stream, ptr, brow, nc, np, n, Cinv, W, dx, out);
-	else if(DC == 7 && DP == 3)
-		hipLaunchKernelGGL((schur_resolve_points_kernel<7, 3>), grid, block, 0, stream, ptr, brow, nc, np, n, Cinv, W, dx, out);
-	else
-		hipLaunchKernelGGL((schur_resolve_points_kernel<3, 2>), grid, block, 0, stream, ptr, brow, nc, np, n, Cinv, W, dx, out);
+	CSchurState &S = *s.p_schur;
+	hipStream_t st = s.stream;
+	const int ld = S.Npad, n = S.N;
+	// where the factor is: the inner sparse solver's, the dense one in d_S, or -- after a covariance call on the dense reduced
+	// system, whose inversion overwrites the factor -- the dense inverse in d_m_Z
+	const bool b_sparse = b_from_covariance? S.b_cov_sparse : S.b_reduced_sparse;
+	const bool b_inverse = b_from_covariance && !S.b_cov_sparse;
+	double *p_r = 0;
+	if(b_sparse)
+		p_r = S.d_in_buf.p() + size_t(S.n_in_blocks) * S.DC * S.DC;
+	else if(b_inverse) {
+		S.d_z.Alloc(size_t(ld));
+		S.d_x.Alloc(size_t(ld));
+		p_r = S.d_z.p();
+	}
+	s.Phase_Begin("resolve_rhs");
+	hipLaunchKernelGGL(schur_resolve_init_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, st, rhs, n, S.d_S.p(), ld, p_r);
+	schur_reduced_rhs_launch(S, rhs, S.d_S.p(), p_r, st);
+	s.Phase_End();
+	const double *p_dx;
+	if(b_sparse) {
+		s.Phase_Begin("reduced_sparse");
+		S.p_inner->p_flag_shared = s.d_flag.p();
+		S.p_inner->Enqueue_Sparse(0, p_r, false);
+		s.Phase_End();
+		p_dx = p_r;
+	} else {
+		s.Phase_Begin("dense_solve");
+		if(b_inverse)
+			hipLaunchKernelGGL(schur_resolve_symv_kernel, dim3(unsigned(n)), dim3(64), 0, st, S.d_m_Z.p(), ld, n, p_r, S.d_x.p());
+		else {
+			dense_forwardsolve(S.d_S.p(), ld, S.d_invdiag.p(), st);
+			dense_backsolve(S.d_S.p(), ld, n, S.d_invdiag.p(), S.d_z.p(), S.d_x.p(), st);
+		}
+		s.Phase_End();
+		p_dx = S.d_x.p();
+	}
+	s.Phase_Begin("backsubst");
+	schur_dispatch(S.DC, S.DP, [&](auto dc, auto dp) {
+		hipLaunchKernelGGL((schur_resolve_points_kernel<dc(), dp()>), dim3(unsigned((std::max<int64_t>(S.np, n) + 255) / 256)), dim3(256),
+			0, st, S.d_ptr.p(), S.d_brow.p(), S.nc, S.np, n, S.d_Cinv.p(), S.d_W.p(), p_dx, rhs);
+	});
+	s.Phase_End();
+	SLAMPP_HIP_CHECK(hipGetLastError());
 }
 
 } // namespace slampp

@@ -17,6 +17,7 @@
 // (fewer than three contributions per block: random visibility), stay with the contribution lists.
 // SLAMPP_HIP_DEV_TILE_POINTS / SLAMPP_HIP_DEV_RUN_PIECE (environment, with SLAMPP_HIP_DEV=1: plan.h) are development knobs for the landmarks per tile / per run piece.
 #include "schur_tiles.h"
+#include "schur_state.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -735,12 +736,9 @@ void schur_tiles_enqueue(const CSchurTiles &T, int DC, int DP, const int64_t *pt
 	const double *eta, int n, double *Cinv, double *p_W, bool b_store, const int32_t *sb_row, const int32_t *sb_col,
 	double *S, int ld, const int64_t *p_dst, double *p_r, int *p_flag, hipStream_t stream)
 {
-	if(DC == 6 && DP == 3)
-		tiles_enqueue_t<6, 3>(T, ptr, nc, ubase, A, eta, n, Cinv, p_W, b_store, sb_row, sb_col, S, ld, p_dst, p_r, p_flag, stream);
-	else if(DC == 7 && DP == 3)
-		tiles_enqueue_t<7, 3>(T, ptr, nc, ubase, A, eta, n, Cinv, p_W, b_store, sb_row, sb_col, S, ld, p_dst, p_r, p_flag, stream);
-	else
-		tiles_enqueue_t<3, 2>(T, ptr, nc, ubase, A, eta, n, Cinv, p_W, b_store, sb_row, sb_col, S, ld, p_dst, p_r, p_flag, stream);
+	schur_dispatch(DC, DP, [&](auto dc, auto dp) {
+		tiles_enqueue_t<dc(), dp()>(T, ptr, nc, ubase, A, eta, n, Cinv, p_W, b_store, sb_row, sb_col, S, ld, p_dst, p_r, p_flag, stream);
+	});
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1609,7 +1607,7 @@ void schur_tiles_build(CSchurTiles &T, int n_mode, int DC, int DP, int64_t nc, i
 			Upload_Runs(); // (a small system: a thread's start-up is what it would save)
 	}
 	for(size_t i = 0; i < trash.size(); ++ i)
-		T.trash.emplace_back(std::move(trash[i])); // (the caller frees them behind the analysis: schur.hip)
+		T.trash.emplace_back(std::move(trash[i])); // (the caller frees them behind the analysis: schur_setup.hip)
 	trash.clear();
 	const size_t n_run_jobs_all = T.p_run_upload->jobs.size();
 	T.n_tiles = n_tiles;

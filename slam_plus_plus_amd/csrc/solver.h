@@ -141,7 +141,7 @@ struct CKeepDeviceMemory {
 	~CKeepDeviceMemory() { g_b_keep_device_memory = b_before; }
 };
 
-struct CSchurState; // schur.hip
+struct CSchurState; // schur_state.h
 struct CDeviceGroup; // group.hip
 struct CSparseInverse; // sparse_inverse.hip
 struct CCovariance; // covariance.hip
@@ -411,7 +411,7 @@ struct slampp_hip_solver {
 
 namespace slampp {
 
-// Schur path entry points (schur.hip)
+// Schur path entry points (schur*.hip; what those units call in each other: schur_state.h)
 void schur_destroy(CSchurState *p);
 CSchurState *schur_analyze(slampp_hip_solver &s); // throws
 void schur_enqueue(slampp_hip_solver &s, const double *p_values_dev, double *p_rhs_dev); // throws
@@ -420,9 +420,6 @@ bool schur_keeps_for_resolve(const slampp_hip_solver &s); // a solve of this han
 // b_from_covariance: the ones a Schur covariance call left (schur_resolve.hip).  Throws.
 void schur_resolve_enqueue(slampp_hip_solver &s, double *p_rhs_dev, bool b_from_covariance);
 void schur_enqueue_marginal_poses(slampp_hip_solver &s, const double *p_values_dev, double *p_rhs_dev); // throws
-void schur_marginals_sparse_launch(int DC, int DP, int64_t nc, int64_t np, const int64_t *ptr, const int64_t *cam_zoff,
-	const int64_t *pair_ptr, const int64_t *pair_tab, const double *W, const double *Cinv, const double *Z, double *cam_cov,
-	double *point_cov, hipStream_t stream); // schur_marginals.hip
 void damping_enqueue(const int64_t *p_off_dim_dev, int64_t n_first, int64_t n_last, double f_alpha, double *p_values_dev,
 	hipStream_t stream); // assembly.hip
 void schur_enqueue_marginals(slampp_hip_solver &s, const double *p_values_dev, double *p_cam_cov_dev, double *p_point_cov_dev); // throws
