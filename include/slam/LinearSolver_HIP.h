@@ -963,6 +963,93 @@ public:
 		return Columns(r_columns, r_lambda, std::vector<int64_t>(r_block_columns.begin(), r_block_columns.end()), false);
 	}
 
+	/**
+	 *	@brief calculates blocks of the covariance matrix (the inverse of lambda) at arbitrary pairs of block columns, inside
+	 *		lambda's pattern or outside it (slampp_hip_marginal_blocks: forward substitutions only, no whole columns)
+	 *
+	 *	@param[out] r_blocks is filled with one block per pair, in the listed order: block k has the rows of block column
+	 *		r_pairs[k].first and the columns of block column r_pairs[k].second
+	 *	@param[in] r_lambda is the system matrix (symmetric layout, upper triangle stored)
+	 *	@param[in] r_pairs lists the pairs (any order, first < second or not, repeats allowed)
+	 *
+	 *	@return Returns true on success, false if lambda is not positive definite.
+	 *	@note This function throws std::bad_alloc and std::runtime_error.
+	 */
+	bool Marginal_Blocks(std::vector<Eigen::MatrixXd> &r_blocks, const CUberBlockMatrix &r_lambda,
+		const std::vector<std::pair<size_t, size_t> > &r_pairs) // throw(std::bad_alloc, std::runtime_error)
+	{
+		Gather_Or_Reanalyze(r_lambda, [&]() { SymbolicDecomposition_Blocky(r_lambda); });
+		if(!m_order.empty())
+			throw std::runtime_error("CLinearSolver_HIP::Marginal_Blocks: a reordered structure");
+		std::vector<int64_t> rows(r_pairs.size()), cols(r_pairs.size());
+		size_t n_out = 0;
+		for(size_t k = 0; k < r_pairs.size(); ++ k) {
+			if(r_pairs[k].first >= r_lambda.n_BlockColumn_Num() || r_pairs[k].second >= r_lambda.n_BlockColumn_Num())
+				throw std::runtime_error("CLinearSolver_HIP::Marginal_Blocks: block column index out of range");
+			rows[k] = int64_t(r_pairs[k].first);
+			cols[k] = int64_t(r_pairs[k].second);
+			n_out += r_lambda.n_BlockColumn_Column_Num(r_pairs[k].first) * r_lambda.n_BlockColumn_Column_Num(r_pairs[k].second);
+		}
+		std::vector<double> flat(std::max(n_out, size_t(1)));
+		const int n_result = slampp_hip_marginal_blocks(m_p_solver, m_p_values, int64_t(r_pairs.size()),
+			rows.empty()? 0 : &rows[0], cols.empty()? 0 : &cols[0], &flat[0]);
+		if(n_result == SLAMPP_HIP_NOT_POSDEF)
+			return false;
+		Throw_On_Error(n_result);
+		r_blocks.resize(r_pairs.size());
+		const double *p_src = &flat[0];
+		for(size_t k = 0; k < r_pairs.size(); ++ k) {
+			const size_t dr = r_lambda.n_BlockColumn_Column_Num(r_pairs[k].first), dc = r_lambda.n_BlockColumn_Column_Num(r_pairs[k].second);
+			r_blocks[k] = Eigen::Map<const Eigen::MatrixXd>(p_src, dr, dc); // (column-major, as the library writes it)
+			p_src += dr * dc;
+		}
+		return true;
+	}
+
+	/**
+	 *	@brief calculates the joint marginal covariance of a set of block columns: the dense symmetric matrix of the blocks
+	 *		of the inverse of lambda at every pair of them (the upper pairs are computed and mirrored)
+	 *
+	 *	@param[out] r_joint is filled with k x k values, k = the sum of the listed columns' widths, in the listed order
+	 *	@param[in] r_lambda is the system matrix (symmetric layout, upper triangle stored)
+	 *	@param[in] r_block_columns lists distinct block column indices (at least one)
+	 *
+	 *	@return Returns true on success, false if lambda is not positive definite.
+	 *	@note This function throws std::bad_alloc and std::runtime_error.
+	 */
+	bool Joint_Marginal(Eigen::MatrixXd &r_joint, const CUberBlockMatrix &r_lambda,
+		const std::vector<size_t> &r_block_columns) // throw(std::bad_alloc, std::runtime_error)
+	{
+		std::vector<size_t> sorted(r_block_columns);
+		std::sort(sorted.begin(), sorted.end());
+		if(sorted.empty() || std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+			throw std::runtime_error("CLinearSolver_HIP::Joint_Marginal: an empty set of block columns, or one listed twice");
+		std::vector<std::pair<size_t, size_t> > pairs;
+		for(size_t b = 0; b < r_block_columns.size(); ++ b) {
+			for(size_t a = 0; a <= b; ++ a)
+				pairs.push_back(std::make_pair(r_block_columns[a], r_block_columns[b]));
+		}
+		std::vector<Eigen::MatrixXd> blocks;
+		if(!Marginal_Blocks(blocks, r_lambda, pairs))
+			return false;
+		std::vector<size_t> off(r_block_columns.size() + 1, 0);
+		for(size_t a = 0; a < r_block_columns.size(); ++ a)
+			off[a + 1] = off[a] + r_lambda.n_BlockColumn_Column_Num(r_block_columns[a]);
+		r_joint.resize(off.back(), off.back());
+		for(size_t b = 0, k = 0; b < r_block_columns.size(); ++ b) {
+			for(size_t a = 0; a <= b; ++ a, ++ k) {
+				r_joint.block(off[a], off[b], off[a + 1] - off[a], off[b + 1] - off[b]) = blocks[k];
+				if(a != b)
+					r_joint.block(off[b], off[a], off[b + 1] - off[b], off[a + 1] - off[a]) = blocks[k].transpose();
+			}
+		}
+		for(size_t c = 0; c < size_t(r_joint.cols()); ++ c) { // (the diagonal blocks: the upper triangle mirrored, symmetric bit for bit)
+			for(size_t r = c + 1; r < size_t(r_joint.rows()); ++ r)
+				r_joint(r, c) = r_joint(c, r);
+		}
+		return true;
+	}
+
 protected:
 	/** @brief block columns of the inverse; b_reuse_factor: the factor the last call left in place (no new factorization) */
 	bool Columns(Eigen::MatrixXd &r_columns, const CUberBlockMatrix &r_lambda, const std::vector<int64_t> &r_cols,

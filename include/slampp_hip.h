@@ -371,6 +371,30 @@ int slampp_hip_marginal_columns(slampp_hip_solver *p_solver, const double *p_val
 int slampp_hip_marginal_columns_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, int n_cols,
 	const int64_t *p_bcols, double *p_out_dev);
 
+/* Sparse mode: blocks of Lambda^-1 at arbitrary pairs of block columns -- what a front end asks for when it gates loop
+ * closures or tests joint compatibility (Sigma_ii, Sigma_jj, Sigma_ij of candidate pairs that are not edges yet; g2o's
+ * computeMarginals(spinv, blockIndices), GTSAM's jointMarginalCovariance).  p_brows, p_bcols (host): n_pairs block column
+ * indices each; pair k gives the d_r x d_c block Lambda^-1[rows of block column p_brows[k], columns of block column
+ * p_bcols[k]], column-major, and the blocks follow each other in p_out in the listed order.  With Lambda = P^T L L^T P,
+ *   Lambda^-1(r, c) = (L^-1 P E_r)^T (L^-1 P E_c) = Y_r^T Y_c,
+ * and Y_j is nonzero only on the path of j to the root of the elimination tree: the pruned forward substitution of
+ * slampp_hip_marginal_columns gives all of it, in passes of at most 48 scalar right-hand sides (both columns of a pair in one
+ * pass, pairs taken in the listed order until the next would not fit); there is no backward substitution and no
+ * n_scalars x k result.  A Gram kernel then sums, per pair, over the rows both paths share -- from their lowest common
+ * ancestor to the root, the dense top included -- in a fixed order without atomics: the same call gives the same bits.
+ * Nothing is refused about the pairs themselves: r < c, r > c (the block as it stands in the symmetric inverse) and r == c,
+ * inside Lambda's pattern or outside it, a column in any number of pairs, a pair listed twice (each listing is computed).
+ * p_values = NULL: the factor in place, by the rule of slampp_hip_marginal_columns (SLAMPP_HIP_ERR_INVALID without one);
+ * otherwise these values are factored first and the factor stays in place.  n_pairs <= 0, a null pointer, an index out of
+ * range: SLAMPP_HIP_ERR_INVALID; Schur mode, several devices, landmark shards, block columns wider than 8:
+ * SLAMPP_HIP_ERR_UNSUPPORTED (a Schur handle whose analysis went to the sparse path answers).  Returns
+ * SLAMPP_HIP_NOT_POSDEF as the solve does, and leaves no factor then.  The device version only enqueues, once its lists
+ * are built on the host; the host version brings the blocks back in one copy. */
+int slampp_hip_marginal_blocks(slampp_hip_solver *p_solver, const double *p_values, int64_t n_pairs, const int64_t *p_brows,
+	const int64_t *p_bcols, double *p_out);
+int slampp_hip_marginal_blocks_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, int64_t n_pairs,
+	const int64_t *p_brows, const int64_t *p_bcols, double *p_out_dev);
+
 /* Schur mode only: block diagonal of the covariance matrix Lambda^-1 -- the reference's
  * CSchurComplement_Marginals::Schur_Marginals (include/slam/BAMarginals.h:579-806, called from
  * NonlinearSolver_Lambda_LM.h:1326 and NonlinearSolver_Lambda_DL.h:1640 with the Cholesky factor of the Schur

@@ -1,5 +1,6 @@
 // capi_covariance.hip -- the covariance entry points of the C ABI (include/slampp_hip.h): block-diagonal marginals, Lambda^-1 on
-// Lambda's pattern and whole block columns of it, in the sparse mode and in the Schur mode, and the landmark-only solve
+// Lambda's pattern, whole block columns of it and its blocks at arbitrary pairs, in the sparse mode and (but for the pairs)
+// in the Schur mode, and the landmark-only solve
 #include "capi_util.h"
 #include "sparse_inverse.h"
 #include "covariance.h"
@@ -207,6 +208,39 @@ int columns_checks(slampp_hip_solver *p_solver, int n_cols, const int64_t *p_bco
 	return SLAMPP_HIP_OK;
 }
 
+// n_pairs pairs of block columns in range; the doubles of their blocks in *p_n_out
+int pairs_checks(slampp_hip_solver *p_solver, int64_t n_pairs, const int64_t *p_brows, const int64_t *p_bcols, size_t *p_n_out)
+{
+	slampp_hip_solver &s = *p_solver;
+	if(n_pairs <= 0 || !p_brows || !p_bcols)
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_blocks: no pairs");
+	const int64_t n_bcols = int64_t(s.cumsum.size()) - 1;
+	*p_n_out = 0;
+	for(int64_t k = 0; k < n_pairs; ++ k) {
+		const int64_t r = p_brows[k], c = p_bcols[k];
+		if(r < 0 || r >= n_bcols || c < 0 || c >= n_bcols)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_blocks: block column index out of range");
+		*p_n_out += size_t((s.cumsum[size_t(r + 1)] - s.cumsum[size_t(r)]) * (s.cumsum[size_t(c + 1)] - s.cumsum[size_t(c)]));
+	}
+	return SLAMPP_HIP_OK;
+}
+
+// what the two marginal_blocks entry points check (inside guarded())
+int marginal_blocks_checks(slampp_hip_solver *p_solver, bool b_values, int64_t n_pairs, const int64_t *p_brows,
+	const int64_t *p_bcols, const double *p_out, size_t *p_n_out)
+{
+	int n_result = covariance_checks(p_solver, "marginal_blocks");
+	if(n_result != SLAMPP_HIP_OK)
+		return n_result;
+	if(!p_out)
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_blocks: null pointer");
+	if((n_result = pairs_checks(p_solver, n_pairs, p_brows, p_bcols, p_n_out)) != SLAMPP_HIP_OK)
+		return n_result;
+	if(!b_values && !p_solver->b_factored)
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_blocks: no valid factorization to reuse (values = NULL)");
+	return SLAMPP_HIP_OK;
+}
+
 // what slampp_hip_marginals_pattern_device_async does behind its checks (inside guarded()); p_values_dev = 0, which only
 // the Schur covariance calls of a handle that went to the sparse path pass: the factor in place
 int marginals_pattern_enqueue(slampp_hip_solver *p_solver, const double *p_values_dev, double *p_cov_dev, const char *p_s_name)
@@ -221,15 +255,21 @@ int marginals_pattern_enqueue(slampp_hip_solver *p_solver, const double *p_value
 	return SLAMPP_HIP_OK;
 }
 
-// what slampp_hip_marginal_columns_device_async does behind its checks (inside guarded()); p_values_dev = 0: the factor in
-// place, which the caller has found valid
-void marginal_columns_enqueue(slampp_hip_solver &s, const double *p_values_dev, int n_cols, const int64_t *p_bcols, double *p_out_dev)
+// the factor the substitutions of marginal_columns and marginal_blocks work from (inside guarded()); p_values_dev = 0: the
+// factor in place, which the caller has found valid
+void substitution_factor_enqueue(slampp_hip_solver &s, const double *p_values_dev)
 {
 	if(p_values_dev) { // factor these values (the fused forward substitution runs on zeros)
 		factor_on_zeros(s, p_values_dev);
 		s.Factor_Installed();
 	}
 	s.Ensure_Leaf_Inverses(); // (the substitutions multiply by inv(L_jj) of every column)
+}
+
+// what slampp_hip_marginal_columns_device_async does behind its checks (inside guarded())
+void marginal_columns_enqueue(slampp_hip_solver &s, const double *p_values_dev, int n_cols, const int64_t *p_bcols, double *p_out_dev)
+{
+	substitution_factor_enqueue(s, p_values_dev);
 	covariance_columns_enqueue(s, n_cols, p_bcols, p_out_dev);
 }
 
@@ -346,6 +386,43 @@ int slampp_hip_marginal_columns(slampp_hip_solver *p_solver, const double *p_val
 	if(n_result != SLAMPP_HIP_OK)
 		return n_result;
 	return marginal_columns_in_groups(p_solver, p_values != 0, n_cols, p_bcols, p_out, slampp_hip_marginal_columns_device_async);
+}
+
+int slampp_hip_marginal_blocks_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, int64_t n_pairs,
+	const int64_t *p_brows, const int64_t *p_bcols, double *p_out_dev)
+{
+	return guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		size_t n_out = 0;
+		const int n_result = marginal_blocks_checks(p_solver, p_values_dev != 0, n_pairs, p_brows, p_bcols, p_out_dev, &n_out);
+		if(n_result != SLAMPP_HIP_OK)
+			return n_result;
+		substitution_factor_enqueue(s, p_values_dev);
+		covariance_pairs_enqueue(s, n_pairs, p_brows, p_bcols, p_out_dev);
+		return SLAMPP_HIP_OK;
+	});
+}
+
+int slampp_hip_marginal_blocks(slampp_hip_solver *p_solver, const double *p_values, int64_t n_pairs, const int64_t *p_brows,
+	const int64_t *p_bcols, double *p_out)
+{
+	size_t n_out = 0;
+	return host_round_trip(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		const int n_check = marginal_blocks_checks(p_solver, p_values != 0, n_pairs, p_brows, p_bcols, p_out, &n_out);
+		if(n_check != SLAMPP_HIP_OK)
+			return n_check;
+		s.d_cov.Alloc(n_out);
+		if(p_values) {
+			s.d_A.Alloc(size_t(s.n_values));
+			Upload_Values_And_Join(s, p_values);
+		}
+		return SLAMPP_HIP_OK;
+	}, [&](slampp_hip_solver &s) {
+		return slampp_hip_marginal_blocks_device_async(p_solver, p_values? s.d_A.p() : 0, n_pairs, p_brows, p_bcols, s.d_cov.p());
+	}, true, [&](slampp_hip_solver &s) {
+		SLAMPP_HIP_CHECK(hipMemcpyAsync(p_out, s.d_cov.p(), n_out * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+	});
 }
 
 int slampp_hip_schur_marginals_device_async(slampp_hip_solver *p_solver, const double *p_values_dev,

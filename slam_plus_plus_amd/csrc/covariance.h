@@ -28,6 +28,12 @@ void covariance_pattern_enqueue(slampp_hip_solver &s, double *p_out_dev);
 // column-major, rows in the caller's scalar order, k = the sum of the columns' dimensions.  Throws.
 void covariance_columns_enqueue(slampp_hip_solver &s, int n_cols, const int64_t *p_bcols, double *p_out_dev);
 
+// blocks (p_brows[k], p_bcols[k]) of Lambda^-1, k = 0 .. n_pairs (caller's block columns, in range: checked by the caller; any
+// order, repeats allowed), from the factor in place: Y_r^T Y_c from the pruned forward substitution alone, summed over the
+// rows the two elimination-tree paths share (pair_plan.h) in a fixed order.  p_out_dev: the d_r x d_c blocks, column-major,
+// one after the other in the listed order.  Throws.
+void covariance_pairs_enqueue(slampp_hip_solver &s, int64_t n_pairs, const int64_t *p_brows, const int64_t *p_bcols, double *p_out_dev);
+
 // one pass of kp <= COV_K_PASS right-hand sides given whole: p_rhs_dev is n_scalars x kp in the factor's permuted row order,
 // interleaved (row * kp + column), nonzero on the rows of the block columns p_src_bcols[0 .. n_src) only (the pruned forward
 // substitution starts from their elimination-tree paths).  The solution goes to p_out_dev + n_col0 * n_ld_out, column-major,

@@ -17,6 +17,11 @@
 // triangular solves on the top's factor and its inverted diagonal tiles follow, the backward one writing the top's x
 // where the block columns below read it.
 //
+// Blocks at arbitrary pairs.  Lambda^-1(r, c) = Y_r^T Y_c with Y_j = L^-1 P E_j, the pruned forward substitution's result:
+// no backward substitution and no n_scalars x k output.  The pairs are grouped into passes (pair_plan.cpp); a pass runs the
+// forward half above for its distinct columns, then one Gram kernel sums, for every pair, the products of the two columns'
+// lanes over the rows both paths share (the path from their lowest common ancestor to the root) and over the dense top.
+//
 // Workspace X: n_scalars x k, interleaved -- the k values of a scalar row next to each other (X[row * k + c]): a lane per
 // right-hand side then reads and writes a block's rows as whole contiguous lines (d x k doubles), where a column stride of
 // n_scalars would make every lane of a wave touch a line of its own.  Rows of the permuted order (Plan::cs_new).  Which
@@ -26,6 +31,7 @@
 #include "covariance.h"
 #include "solver.h"
 #include "sparse_inverse.h"
+#include "pair_plan.h"
 
 #include <algorithm>
 #include <climits>
@@ -72,6 +78,13 @@ struct CCovariance {
 	CDevArray<TCovFwd> d_fwd;
 	CDevArray<TRowEnt> d_ents;
 	CDevArray<int32_t> d_seg;
+	std::vector<int32_t> reach, dense_reach; // (List_Pass's scratch)
+	// blocks at arbitrary pairs (slampp_hip_marginal_blocks): the records of every pass of one call, uploaded with the lists above
+	PairPlan pair_plan;
+	std::vector<TPairRec> pairs;
+	std::vector<TPairRow> pair_rows;
+	CDevArray<TPairRec> d_pairs;
+	CDevArray<TPairRow> d_pair_rows;
 	~CCovariance() { if(ev_lists) (void)hipEventDestroy(ev_lists); }
 };
 
@@ -80,7 +93,7 @@ void covariance_destroy(CCovariance *p) { delete p; }
 size_t covariance_bytes(const CCovariance *p)
 {
 	return p? p->d_gather.n_Bytes() + p->d_X.n_Bytes() + p->d_Bd.n_Bytes() + p->d_Zb.n_Bytes() + p->d_mark.n_Bytes() +
-		p->d_fwd.n_Bytes() + p->d_ents.n_Bytes() + p->d_seg.n_Bytes() : 0;
+		p->d_fwd.n_Bytes() + p->d_ents.n_Bytes() + p->d_seg.n_Bytes() + p->d_pairs.n_Bytes() + p->d_pair_rows.n_Bytes() : 0;
 }
 
 // ---- pattern gather ----
@@ -457,6 +470,193 @@ struct TCovPass {
 };
 } // anonymous namespace
 
+// The lists of one call are built before anything is enqueued and go up in one set of uploads: Lists_Begin(), List_Pass()
+// per pass, Lists_Upload().
+static void Lists_Begin(CCovariance &cv)
+{
+	if(cv.ev_lists)
+		SLAMPP_HIP_CHECK(hipEventSynchronize(cv.ev_lists)); // (the previous call's uploads out of these vectors are over)
+	cv.fwd.clear();
+	cv.ents.clear();
+	cv.seg.assign(1, 0);
+	cv.pairs.clear();
+	cv.pair_rows.clear();
+}
+
+// lists the pruned forward substitution of one pass: the union of the paths of the columns p_src[0 .. n_src) (new order) to
+// the root, stage by stage.  p_lane[i]: where the unit right-hand sides of column p_src[i] start among the pass's lanes
+// (negative where the column begins in the pass before); p_lane = 0: the right-hand sides are given whole
+static void List_Pass(CCovariance &cv, const Plan &P, int n_src, const int32_t *p_src, const int32_t *p_lane, TCovPass &pass)
+{
+	if(++ cv.n_host_stamp == INT_MAX) {
+		std::fill(cv.host_mark.begin(), cv.host_mark.end(), 0);
+		cv.n_host_stamp = 1;
+	}
+	const int32_t n_hs = cv.n_host_stamp;
+	std::vector<int32_t> &reach = cv.reach, &dense_reach = cv.dense_reach;
+	reach.clear();
+	dense_reach.clear();
+	for(int i = 0; i < n_src; ++ i) {
+		const int32_t j = p_src[i];
+		if(p_lane)
+			cv.host_bcol[size_t(j)] = p_lane[i];
+		for(int32_t x = j; x >= 0 && cv.host_mark[size_t(x)] != n_hs; x = P.parent[size_t(x)]) {
+			cv.host_mark[size_t(x)] = n_hs;
+			if(cv.sched_pos[size_t(x)] >= 0)
+				reach.push_back(x);
+			else
+				dense_reach.push_back(x);
+		}
+	}
+	std::sort(reach.begin(), reach.end(), [&](int32_t a, int32_t b) { return cv.sched_pos[size_t(a)] < cv.sched_pos[size_t(b)]; });
+	std::sort(dense_reach.begin(), dense_reach.end());
+	int n_cur_task = -1, n_cur_stage = -1;
+	for(int h = 0; h < 2; ++ h) { // the block-eliminated columns stage by stage, then the dense-top ones
+		const std::vector<int32_t> &r_list = h? dense_reach : reach;
+		for(size_t q = 0; q < r_list.size(); ++ q) {
+			const int32_t j = r_list[q];
+			const int32_t sc = cv.sched_pos[size_t(j)];
+			const int n_task = h? -2 - int(q) : cv.sched_task[size_t(sc)];
+			const int n_stage = h? -1 : cv.task_stage[size_t(n_task)];
+			if(n_task != n_cur_task) { // a segment of its own
+				if(n_cur_task != -1)
+					cv.seg.push_back(int32_t(cv.fwd.size()));
+				if(n_stage != n_cur_stage || pass.launches.empty()) {
+					TCovLaunch l = {n_stage, int(cv.seg.size()) - 1, int(cv.seg.size()) - 1};
+					pass.launches.push_back(l);
+				}
+				pass.launches.back().seg1 ++;
+				n_cur_task = n_task;
+				n_cur_stage = n_stage;
+			}
+			TCovFwd f;
+			f.linv_off = (sc >= 0)? P.linv_off[size_t(j)] : 0;
+			f.e0 = int64_t(cv.ents.size());
+			f.dj = P.dim[size_t(j)];
+			f.ycs = int32_t(P.cs_new[size_t(j)]);
+			f.bcol = cv.host_bcol[size_t(j)];
+			f.dpos = (sc >= 0)? -1 : P.dense_pos[size_t(j)];
+			f.s = std::max(sc, 0);
+			for(int64_t r = P.rptr[size_t(j)]; r < P.rptr[size_t(j) + 1]; ++ r) {
+				const int32_t b = P.rblk[size_t(r)], c = P.blk_col[size_t(b)];
+				if(cv.host_mark[size_t(c)] != n_hs || cv.sched_pos[size_t(c)] < 0)
+					continue; // y_c is zero in this pass, or c is in the dense top (its part is the dense solve's)
+				TRowEnt t_e;
+				t_e.off = P.loff[size_t(b)];
+				t_e.ycs = int32_t(P.cs_new[size_t(c)]);
+				t_e.dc = P.dim[size_t(c)];
+				cv.ents.push_back(t_e);
+			}
+			f.ne = int32_t(int64_t(cv.ents.size()) - f.e0);
+			cv.fwd.push_back(f);
+		}
+	}
+	if(n_cur_task != -1)
+		cv.seg.push_back(int32_t(cv.fwd.size()));
+	for(int i = 0; i < n_src; ++ i)
+		cv.host_bcol[size_t(p_src[i])] = INT_MIN / 2;
+}
+
+static void Lists_Upload(slampp_hip_solver &s, CCovariance &cv)
+{
+	if(cv.fwd.empty())
+		cv.fwd.resize(1); // (nothing listed: a record nobody reads, so that the uploads below have something to send)
+	if(cv.ents.empty())
+		cv.ents.resize(1);
+	cv.d_fwd.Upload(cv.fwd, s.stream);
+	cv.d_ents.Upload(cv.ents, s.stream);
+	cv.d_seg.Upload(cv.seg, s.stream);
+	if(!cv.pairs.empty()) { // (slampp_hip_marginal_blocks)
+		if(cv.pair_rows.empty())
+			cv.pair_rows.resize(1);
+		cv.d_pairs.Upload(cv.pairs, s.stream);
+		cv.d_pair_rows.Upload(cv.pair_rows, s.stream);
+	}
+	if(!cv.ev_lists)
+		SLAMPP_HIP_CHECK(hipEventCreateWithFlags(&cv.ev_lists, hipEventDisableTiming));
+	SLAMPP_HIP_CHECK(hipEventRecord(cv.ev_lists, s.stream));
+}
+
+static int Unrolled_Dim(const Plan &P)
+{
+	return (P.uniform_dim && (P.max_dim == 3 || P.max_dim == 6 || P.max_dim == 7))? P.max_dim : 0;
+}
+
+// the forward half of one pass: a new stamp, the pruned forward substitution into d_X (and the dense-top columns' reduced
+// right-hand sides into d_Bd), then -- b_dense_top -- the dense tiles' forward substitution into d_Zb
+static void Forward_Enqueue(slampp_hip_solver &s, CCovariance &cv, const TCovPass &pass, const double *p_rhs, bool b_dense_top)
+{
+	const int D = Unrolled_Dim(s.plan);
+	const int ld = s.n_dense_pad, n_dense = s.n_dense_dim, n_tiles = ld / COV_NB;
+	const int kp = pass.kp;
+	if(++ cv.n_stamp == INT_MAX) {
+		SLAMPP_HIP_CHECK(hipMemsetAsync(cv.d_mark.p(), 0, cv.d_mark.n_Bytes(), s.stream));
+		cv.n_stamp = 1;
+	}
+	if(n_dense)
+		SLAMPP_HIP_CHECK(hipMemsetAsync(cv.d_Bd.p(), 0, size_t(ld) * kp * sizeof(double), s.stream));
+	for(size_t q = 0; q < pass.launches.size(); ++ q) {
+		const TCovLaunch &l = pass.launches[q];
+		const int n_blocks = l.seg1 - l.seg0;
+		const int DL = (l.n_stage < 0)? 0 : D; // (the dense-top columns' dimensions: any)
+#define COV_FWD(DD, BR) hipLaunchKernelGGL((cov_forward_kernel<DD, BR>), dim3(n_blocks), dim3(64), 0, s.stream, cv.d_seg.p(), l.seg0, \
+			cv.d_fwd.p(), cv.d_ents.p(), s.d_L.p(), s.d_Linv.p(), cv.d_X.p(), kp, cv.d_mark.p(), cv.n_stamp, cv.d_Bd.p(), p_rhs)
+		if(p_rhs) {
+			switch(DL) {
+			case 3: COV_FWD(3, true); break;
+			case 6: COV_FWD(6, true); break;
+			case 7: COV_FWD(7, true); break;
+			default: COV_FWD(0, true); break;
+			}
+		} else {
+			switch(DL) {
+			case 3: COV_FWD(3, false); break;
+			case 6: COV_FWD(6, false); break;
+			case 7: COV_FWD(7, false); break;
+			default: COV_FWD(0, false); break;
+			}
+		}
+#undef COV_FWD
+	}
+	if(n_dense && b_dense_top) {
+		for(int t = 0; t < n_tiles; ++ t)
+			hipLaunchKernelGGL(cov_dense_forward_kernel, dim3(n_tiles - t), dim3(256), 0, s.stream, s.d_dense.p(), ld, n_dense, t,
+				s.d_dense_invdiag.p(), cv.d_Bd.p(), cv.d_Zb.p(), kp);
+	}
+}
+
+// the backward half: the dense tiles' backward substitution, then every stage's, last to first; x goes to
+// p_out_dev + n_col0 * n_ld_out as each column is finished
+static void Backward_Enqueue(slampp_hip_solver &s, CCovariance &cv, const TCovPass &pass, double *p_out_dev, int64_t n_ld_out,
+	int64_t n_col0)
+{
+	const Plan &P = s.plan;
+	const int D = Unrolled_Dim(P);
+	const int n_stages = int(P.stage_ptr.size()) - 1;
+	const int ld = s.n_dense_pad, n_dense = s.n_dense_dim, n_tiles = ld / COV_NB;
+	const int kp = pass.kp;
+	if(n_dense) {
+		for(int t = n_tiles - 1; t >= 0; -- t)
+			hipLaunchKernelGGL(cov_dense_backward_kernel, dim3(t + 1), dim3(256), 0, s.stream, s.d_dense.p(), ld, n_dense, t,
+				s.d_dense_invdiag.p(), cv.d_Zb.p(), kp, s.d_dense_dst.p(), cv.d_X.p(), p_out_dev, n_ld_out, int(n_col0 + pass.col0));
+	}
+	for(int st = n_stages - 1; st >= 0; -- st) {
+		const int n_tasks = P.stage_ptr[size_t(st + 1)] - P.stage_ptr[size_t(st)];
+		if(n_tasks <= 0)
+			continue;
+#define COV_BWD(DD) hipLaunchKernelGGL(cov_backward_kernel<DD>, dim3(n_tasks), dim3(64), 0, s.stream, s.dplan.cols, s.dplan.blks, \
+			s.dplan.task_ptr, P.stage_ptr[size_t(st)], s.d_L.p(), s.d_Linv.p(), cv.d_X.p(), kp, cv.d_mark.p(), cv.n_stamp, p_out_dev, \
+			n_ld_out, int(n_col0 + pass.col0))
+		switch(D) {
+		case 3: COV_BWD(3); break;
+		case 6: COV_BWD(6); break;
+		case 7: COV_BWD(7); break;
+		default: COV_BWD(0); break;
+		}
+#undef COV_BWD
+	}
+}
+
 // p_rhs = 0: the unit right-hand sides of the block columns p_bcols, in passes of COV_K_PASS; else one pass of n_rhs_k
 // right-hand sides read from p_rhs (see cov_forward_kernel), nonzero on the rows of the block columns p_bcols only.  The
 // result goes to p_out_dev + n_col0 * n_ld_out, column-major with leading dimension n_ld_out.
@@ -483,157 +683,101 @@ static void columns_enqueue(slampp_hip_solver &s, int n_cols, const int64_t *p_b
 	col_off[size_t(n_cols)] = k;
 	if(k > int64_t(INT_MAX))
 		throw std::invalid_argument("marginal_columns: too many columns");
-	// the lists of every pass, built before anything is enqueued (one upload)
-	if(cv.ev_lists)
-		SLAMPP_HIP_CHECK(hipEventSynchronize(cv.ev_lists)); // (the previous call's uploads out of these vectors are over)
-	cv.fwd.clear();
-	cv.ents.clear();
-	cv.seg.assign(1, 0);
+	Lists_Begin(cv);
 	std::vector<TCovPass> passes;
-	std::vector<int32_t> reach, dense_reach;
+	std::vector<int32_t> src, lane;
 	for(int64_t col0 = 0; col0 < k; col0 += COV_K_PASS) {
 		TCovPass pass;
 		pass.col0 = int(col0);
 		pass.kp = int(std::min<int64_t>(COV_K_PASS, k - col0));
-		if(++ cv.n_host_stamp == INT_MAX) {
-			std::fill(cv.host_mark.begin(), cv.host_mark.end(), 0);
-			cv.n_host_stamp = 1;
-		}
-		const int32_t n_hs = cv.n_host_stamp;
-		reach.clear();
-		dense_reach.clear();
+		src.clear();
+		lane.clear();
 		for(int i = 0; i < n_cols; ++ i) {
 			if(!p_rhs && (col_off[size_t(i) + 1] <= col0 || col_off[size_t(i)] >= col0 + pass.kp))
 				continue; // not in this pass
-			const int32_t j = P.pinv[size_t(p_bcols[i])];
-			if(!p_rhs)
-				cv.host_bcol[size_t(j)] = int32_t(col_off[size_t(i)] - col0);
-			for(int32_t x = j; x >= 0 && cv.host_mark[size_t(x)] != n_hs; x = P.parent[size_t(x)]) {
-				cv.host_mark[size_t(x)] = n_hs;
-				if(cv.sched_pos[size_t(x)] >= 0)
-					reach.push_back(x);
-				else
-					dense_reach.push_back(x);
-			}
+			src.push_back(P.pinv[size_t(p_bcols[i])]);
+			lane.push_back(int32_t(col_off[size_t(i)] - col0));
 		}
-		std::sort(reach.begin(), reach.end(), [&](int32_t a, int32_t b) { return cv.sched_pos[size_t(a)] < cv.sched_pos[size_t(b)]; });
-		std::sort(dense_reach.begin(), dense_reach.end());
-		int n_cur_task = -1, n_cur_stage = -1;
-		for(int h = 0; h < 2; ++ h) { // the block-eliminated columns stage by stage, then the dense-top ones
-			const std::vector<int32_t> &r_list = h? dense_reach : reach;
-			for(size_t q = 0; q < r_list.size(); ++ q) {
-				const int32_t j = r_list[q];
-				const int32_t sc = cv.sched_pos[size_t(j)];
-				const int n_task = h? -2 - int(q) : cv.sched_task[size_t(sc)];
-				const int n_stage = h? -1 : cv.task_stage[size_t(n_task)];
-				if(n_task != n_cur_task) { // a segment of its own
-					if(n_cur_task != -1)
-						cv.seg.push_back(int32_t(cv.fwd.size()));
-					if(n_stage != n_cur_stage || pass.launches.empty()) {
-						TCovLaunch l = {n_stage, int(cv.seg.size()) - 1, int(cv.seg.size()) - 1};
-						pass.launches.push_back(l);
-					}
-					pass.launches.back().seg1 ++;
-					n_cur_task = n_task;
-					n_cur_stage = n_stage;
-				}
-				TCovFwd f;
-				f.linv_off = (sc >= 0)? P.linv_off[size_t(j)] : 0;
-				f.e0 = int64_t(cv.ents.size());
-				f.dj = P.dim[size_t(j)];
-				f.ycs = int32_t(P.cs_new[size_t(j)]);
-				f.bcol = cv.host_bcol[size_t(j)];
-				f.dpos = (sc >= 0)? -1 : P.dense_pos[size_t(j)];
-				f.s = std::max(sc, 0);
-				for(int64_t r = P.rptr[size_t(j)]; r < P.rptr[size_t(j) + 1]; ++ r) {
-					const int32_t b = P.rblk[size_t(r)], c = P.blk_col[size_t(b)];
-					if(cv.host_mark[size_t(c)] != n_hs || cv.sched_pos[size_t(c)] < 0)
-						continue; // y_c is zero in this pass, or c is in the dense top (its part is the dense solve's)
-					TRowEnt t_e;
-					t_e.off = P.loff[size_t(b)];
-					t_e.ycs = int32_t(P.cs_new[size_t(c)]);
-					t_e.dc = P.dim[size_t(c)];
-					cv.ents.push_back(t_e);
-				}
-				f.ne = int32_t(int64_t(cv.ents.size()) - f.e0);
-				cv.fwd.push_back(f);
-			}
-		}
-		if(n_cur_task != -1)
-			cv.seg.push_back(int32_t(cv.fwd.size()));
-		for(int i = 0; i < n_cols; ++ i)
-			cv.host_bcol[size_t(P.pinv[size_t(p_bcols[i])])] = INT_MIN / 2;
+		List_Pass(cv, P, int(src.size()), src.data(), p_rhs? 0 : lane.data(), pass);
 		passes.push_back(pass);
 	}
-	if(cv.fwd.empty())
-		cv.fwd.resize(1); // (nothing listed: a record nobody reads, so that the uploads below have something to send)
-	if(cv.ents.empty())
-		cv.ents.resize(1);
-	cv.d_fwd.Upload(cv.fwd, s.stream);
-	cv.d_ents.Upload(cv.ents, s.stream);
-	cv.d_seg.Upload(cv.seg, s.stream);
-	if(!cv.ev_lists)
-		SLAMPP_HIP_CHECK(hipEventCreateWithFlags(&cv.ev_lists, hipEventDisableTiming));
-	SLAMPP_HIP_CHECK(hipEventRecord(cv.ev_lists, s.stream));
-	const int D = (P.uniform_dim && (P.max_dim == 3 || P.max_dim == 6 || P.max_dim == 7))? P.max_dim : 0;
-	const int n_stages = int(P.stage_ptr.size()) - 1;
-	const int ld = s.n_dense_pad, n_dense = s.n_dense_dim, n_tiles = ld / COV_NB;
+	Lists_Upload(s, cv);
 	s.Phase_Begin("marginal_columns");
 	for(size_t p = 0; p < passes.size(); ++ p) {
-		const TCovPass &pass = passes[p];
-		const int kp = pass.kp;
-		if(++ cv.n_stamp == INT_MAX) {
-			SLAMPP_HIP_CHECK(hipMemsetAsync(cv.d_mark.p(), 0, cv.d_mark.n_Bytes(), s.stream));
-			cv.n_stamp = 1;
-		}
-		if(n_dense)
-			SLAMPP_HIP_CHECK(hipMemsetAsync(cv.d_Bd.p(), 0, size_t(ld) * kp * sizeof(double), s.stream));
-		for(size_t q = 0; q < pass.launches.size(); ++ q) {
-			const TCovLaunch &l = pass.launches[q];
-			const int n_blocks = l.seg1 - l.seg0;
-			const int DL = (l.n_stage < 0)? 0 : D; // (the dense-top columns' dimensions: any)
-#define COV_FWD(DD, BR) hipLaunchKernelGGL((cov_forward_kernel<DD, BR>), dim3(n_blocks), dim3(64), 0, s.stream, cv.d_seg.p(), l.seg0, \
-				cv.d_fwd.p(), cv.d_ents.p(), s.d_L.p(), s.d_Linv.p(), cv.d_X.p(), kp, cv.d_mark.p(), cv.n_stamp, cv.d_Bd.p(), p_rhs)
-			if(p_rhs) {
-				switch(DL) {
-				case 3: COV_FWD(3, true); break;
-				case 6: COV_FWD(6, true); break;
-				case 7: COV_FWD(7, true); break;
-				default: COV_FWD(0, true); break;
-				}
-			} else {
-				switch(DL) {
-				case 3: COV_FWD(3, false); break;
-				case 6: COV_FWD(6, false); break;
-				case 7: COV_FWD(7, false); break;
-				default: COV_FWD(0, false); break;
-				}
-			}
-#undef COV_FWD
-		}
-		if(n_dense) {
-			for(int t = 0; t < n_tiles; ++ t)
-				hipLaunchKernelGGL(cov_dense_forward_kernel, dim3(n_tiles - t), dim3(256), 0, s.stream, s.d_dense.p(), ld, n_dense, t,
-					s.d_dense_invdiag.p(), cv.d_Bd.p(), cv.d_Zb.p(), kp);
-			for(int t = n_tiles - 1; t >= 0; -- t)
-				hipLaunchKernelGGL(cov_dense_backward_kernel, dim3(t + 1), dim3(256), 0, s.stream, s.d_dense.p(), ld, n_dense, t,
-					s.d_dense_invdiag.p(), cv.d_Zb.p(), kp, s.d_dense_dst.p(), cv.d_X.p(), p_out_dev, n_ld_out, int(n_col0 + pass.col0));
-		}
-		for(int st = n_stages - 1; st >= 0; -- st) {
-			const int n_tasks = P.stage_ptr[size_t(st + 1)] - P.stage_ptr[size_t(st)];
-			if(n_tasks <= 0)
-				continue;
-#define COV_BWD(DD) hipLaunchKernelGGL(cov_backward_kernel<DD>, dim3(n_tasks), dim3(64), 0, s.stream, s.dplan.cols, s.dplan.blks, \
-				s.dplan.task_ptr, P.stage_ptr[size_t(st)], s.d_L.p(), s.d_Linv.p(), cv.d_X.p(), kp, cv.d_mark.p(), cv.n_stamp, p_out_dev, \
-				n_ld_out, int(n_col0 + pass.col0))
-			switch(D) {
-			case 3: COV_BWD(3); break;
-			case 6: COV_BWD(6); break;
-			case 7: COV_BWD(7); break;
-			default: COV_BWD(0); break;
-			}
-#undef COV_BWD
-		}
+		Forward_Enqueue(s, cv, passes[p], p_rhs, true);
+		Backward_Enqueue(s, cv, passes[p], p_out_dev, n_ld_out, n_col0);
+	}
+	s.Phase_End();
+	SLAMPP_HIP_CHECK(hipGetLastError());
+}
+
+// ---- blocks at arbitrary pairs: Y_r^T Y_c over the rows the two paths share ----
+
+enum { COV_GRAM_WAVES = 4 };
+
+// One workgroup of COV_GRAM_WAVES waves per pair, lane e of every wave = output entry (a, b) = (e % dr, e / dr), at most 64.
+// Wave w sums the listed columns w, w + COV_GRAM_WAVES, .. (each with its dim rows in order) and the w-th of COV_GRAM_WAVES
+// contiguous chunks of the dense top's rows; the partial sums meet in LDS and are added in wave order: no atomics, every
+// entry in one fixed order.  Reads rows of this pass's reach only (the listed ones; all of Zb is written in every pass
+// that runs the dense tiles' forward substitution): X holds stale values elsewhere.
+__global__ void __launch_bounds__(64 * COV_GRAM_WAVES)
+cov_gram_kernel(const TPairRec *__restrict__ pairs, int64_t pair0, const TPairRow *__restrict__ rows, const double *__restrict__ X,
+	const double *__restrict__ Zb, int n_dense, int kp, double *__restrict__ out)
+{
+	__shared__ double s_part[COV_GRAM_WAVES][64];
+	const TPairRec rec = pairs[pair0 + blockIdx.x];
+	const int e = threadIdx.x & 63, w = threadIdx.x >> 6;
+	const bool b_act = e < rec.dr * rec.dc;
+	const int la = b_act? rec.lane_r + e % rec.dr : 0, lb = b_act? rec.lane_c + e / rec.dr : 0; // (lanes < kp)
+	double acc = 0;
+	for(int q = w; q < rec.n_rows; q += COV_GRAM_WAVES) {
+		const TPairRow row = rows[rec.row0 + q];
+		const double *Xr = X + int64_t(row.cs) * kp;
+		for(int t = 0; t < row.dim; ++ t)
+			acc += Xr[t * kp + la] * Xr[t * kp + lb];
+	}
+	if(rec.dense) {
+		const int n_chunk = (n_dense + COV_GRAM_WAVES - 1) / COV_GRAM_WAVES;
+		const int i1 = (n_chunk * (w + 1) < n_dense)? n_chunk * (w + 1) : n_dense;
+		#pragma unroll 4
+		for(int i = n_chunk * w; i < i1; ++ i)
+			acc += Zb[int64_t(i) * kp + la] * Zb[int64_t(i) * kp + lb];
+	}
+	s_part[w][e] = acc;
+	__syncthreads();
+	if(w == 0 && b_act) {
+		double sum = s_part[0][e];
+		#pragma unroll
+		for(int v = 1; v < COV_GRAM_WAVES; ++ v)
+			sum += s_part[v][e];
+		out[rec.out + e] = sum;
+	}
+}
+
+void covariance_pairs_enqueue(slampp_hip_solver &s, int64_t n_pairs, const int64_t *p_brows, const int64_t *p_bcols, double *p_out_dev)
+{
+	const Plan &P = s.plan;
+	CCovariance &cv = Covariance_State(s);
+	if(!cv.b_columns)
+		Setup_Columns(s, cv);
+	Lists_Begin(cv); // (before the pair records are touched: the previous call's uploads read them)
+	plan_pairs(P, cv.sched_pos, n_pairs, p_brows, p_bcols, COV_K_PASS, cv.pair_plan);
+	const PairPlan &pp = cv.pair_plan;
+	cv.pairs = pp.pairs;
+	cv.pair_rows = pp.rows;
+	std::vector<TCovPass> passes(pp.passes.size());
+	for(size_t p = 0; p < pp.passes.size(); ++ p) {
+		passes[p].col0 = 0;
+		passes[p].kp = pp.passes[p].kp;
+		List_Pass(cv, P, int(pp.passes[p].cols.size()), pp.passes[p].cols.data(), pp.passes[p].lanes.data(), passes[p]);
+	}
+	Lists_Upload(s, cv);
+	s.Phase_Begin("marginal_blocks");
+	for(size_t p = 0; p < passes.size(); ++ p) {
+		const TPairPass &pass = pp.passes[p];
+		Forward_Enqueue(s, cv, passes[p], 0, pass.b_dense); // (no pair of the pass reaches the top: nobody reads d_Zb)
+		hipLaunchKernelGGL(cov_gram_kernel, dim3(unsigned(pass.pair1 - pass.pair0)), dim3(64 * COV_GRAM_WAVES), 0, s.stream,
+			cv.d_pairs.p(), pass.pair0, cv.d_pair_rows.p(), cv.d_X.p(), cv.d_Zb.p(), s.n_dense_dim, passes[p].kp, p_out_dev);
 	}
 	s.Phase_End();
 	SLAMPP_HIP_CHECK(hipGetLastError());

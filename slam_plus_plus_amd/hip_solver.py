@@ -135,6 +135,8 @@ ABI = {
     "slampp_hip_marginals_pattern_device_async": (C.c_int, [_P, _P, _P]),
     "slampp_hip_marginal_columns": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "slampp_hip_marginal_columns_device_async": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "slampp_hip_marginal_blocks": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
+    "slampp_hip_marginal_blocks_device_async": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
     "slampp_hip_schur_marginals": (C.c_int, [_P, _P, _P, _P]),
     "slampp_hip_schur_marginals_device_async": (C.c_int, [_P, _P, _P, _P]),
     "slampp_hip_schur_marginals_pattern": (C.c_int, [_P, _P, _P]),
@@ -689,6 +691,55 @@ def _marginal_columns(self, lam, bcols, reuse_factor: bool = False) -> np.ndarra
 
 CLinearSolver_HIP.Marginals_Pattern = _pattern_marginals
 CLinearSolver_HIP.Marginal_Columns = _marginal_columns
+
+
+def _marginal_blocks(self, lam, pairs, reuse_factor: bool = False) -> list:
+    """Blocks of Lambda^-1 at arbitrary pairs ``(r, c)`` of block columns, inside Lambda's pattern or outside it: a list
+    of d_r x d_c arrays in the listed order (what g2o's computeMarginals(spinv, blockIndices) answers).  Forward
+    substitutions over the two columns' elimination-tree paths only (slampp_hip_marginal_blocks): no whole columns are
+    formed.  ``reuse_factor``: as for Marginal_Columns."""
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    rows, cols = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+    if reuse_factor:
+        if not self._analyzed or self._structure_key != self._key(lam):
+            raise ValueError("Marginal_Blocks: there is no factorization of this structure to reuse")
+        vals = None
+    else:
+        if not self._analyzed or self._structure_key != self._key(lam):
+            self.SymbolicDecomposition_Blocky(lam)
+        vals = np.ascontiguousarray(lam.values, dtype=np.float64)
+        if vals.shape != (self._n_values,):
+            raise ValueError("lam.values does not match the block structure")
+    dims = np.diff(np.asarray(lam.cumsum, dtype=np.int64))
+    in_range = pr.size and pr.min() >= 0 and pr.max() < len(dims)
+    sizes = dims[rows] * dims[cols] if in_range else np.zeros(0, dtype=np.int64)
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    flat = np.empty(max(int(off[-1]), 1), dtype=np.float64)
+    if not self._check(self._lib.slampp_hip_marginal_blocks(self._h, _ptr(vals) if vals is not None else None, int(rows.size),
+                                                            _ptr(rows), _ptr(cols), _ptr(flat))):
+        raise ArithmeticError("Marginal_Blocks: the system is not positive definite")
+    return [flat[off[k]:off[k + 1]].reshape(int(dims[cols[k]]), int(dims[rows[k]])).T.copy() for k in range(rows.size)]
+
+
+def _joint_marginal(self, lam, bcols, reuse_factor: bool = False) -> np.ndarray:
+    """The joint marginal covariance of the block columns ``bcols`` (distinct, at least one): the dense symmetric k x k
+    matrix of Lambda^-1 at every pair of them, k = the sum of their dimensions, in the listed order (GTSAM's
+    jointMarginalCovariance).  The upper pairs are computed (Marginal_Blocks) and mirrored."""
+    cols = [int(c) for c in np.atleast_1d(np.asarray(bcols, dtype=np.int64))]
+    if not cols or len(set(cols)) != len(cols):
+        raise ValueError("Joint_Marginal: an empty set of block columns, or one listed twice")
+    pairs = [(cols[a], cols[b]) for b in range(len(cols)) for a in range(b + 1)]
+    blocks = self.Marginal_Blocks(lam, pairs, reuse_factor)
+    dims = np.diff(np.asarray(lam.cumsum, dtype=np.int64))
+    off = np.concatenate([[0], np.cumsum(dims[cols])]).astype(np.int64)
+    joint = np.empty((int(off[-1]), int(off[-1])), dtype=np.float64)
+    for (a, b), blk in zip(((a, b) for b in range(len(cols)) for a in range(b + 1)), blocks):
+        joint[off[a]:off[a + 1], off[b]:off[b + 1]] = blk
+    return np.triu(joint) + np.triu(joint, 1).T   # (the lower triangle is never filled: symmetric bit for bit)
+
+
+CLinearSolver_HIP.Marginal_Blocks = _marginal_blocks
+CLinearSolver_HIP.Joint_Marginal = _joint_marginal
 
 
 class CLinearSolver_Schur_HIP(_SolverBase):

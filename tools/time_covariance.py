@@ -13,7 +13,19 @@ same number of doubles of Z read.  "share of HBM peak" = those bytes / time / 8.
 the hardware could do for that traffic, not a kernel's utilisation.  Per-kernel times: run this under
 rocprofv3 --kernel-trace --stats in a separate run.
 
-usage: python tools/time_covariance.py [--reps N] [--out FILE.json]
+With --pairs, instead: blocks at arbitrary pairs (slampp_hip_marginal_blocks) next to the only other route to them,
+whole block columns, on C3 with the values in HBM and the factor in place:
+
+  (a) marginal_blocks for 32 seeded random pairs;
+  (b) marginal_columns(values = NULL) on those pairs' distinct columns (the blocks are then rows picked out of n_scalars x k);
+  (c) the last pose against 64 candidates: marginal_blocks for the 64 pairs, next to marginal_columns([last]), whose single
+      column holds all of them.
+
+Each time is the median of --repeats windows of --reps calls between two device events; the host's list building lies
+inside the window (the device waits for it), and is also given alone (host clock around one call, enqueue only).  Device
+bytes each route allocates are computed from the shapes: the n_scalars x 48 workspace both share, and each route's output.
+
+usage: python tools/time_covariance.py [--reps N] [--out FILE.json] [--pairs [--repeats M]]
 """
 import argparse
 import json
@@ -110,11 +122,79 @@ def case(name, lam, reps):
     return res
 
 
+def pairs_case(name, lam, reps, repeats):
+    dev = torch.device("cuda:0")
+    s = CLinearSolver_HIP()
+    s.SymbolicDecomposition_Blocky(lam)
+    lib, h = s._lib, s._h
+    st, plan = s.stats(), s.plan()
+    n, nb, d = lam.n_scalars, lam.n_bcols, int(lam.cumsum[1])
+    vals = torch.from_numpy(lam.values).to(dev)
+    rng = np.random.default_rng(17)
+    rows32, cols32 = (np.ascontiguousarray(rng.integers(0, nb, 32), dtype=np.int64) for _ in range(2))
+    distinct = np.unique(np.concatenate([rows32, cols32])).astype(np.int64)
+    last = np.array([nb - 1], dtype=np.int64)
+    cand = np.ascontiguousarray(np.sort(rng.choice(nb - 1, size=64, replace=False)), dtype=np.int64)
+    last64 = np.full(64, nb - 1, dtype=np.int64)
+    blocks = torch.empty(64 * d * d, dtype=torch.float64, device=dev)
+    out = torch.empty(n * d * len(distinct), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+
+    def rc(x):
+        assert x == 0, s._error()
+
+    rc(lib.slampp_hip_marginal_blocks_device_async(h, vals.data_ptr(), 32, _ptr(rows32), _ptr(cols32), blocks.data_ptr()))
+    assert s.sync()                                                       # the factor is in place from here on
+    legs = {
+        "a_blocks_32_pairs": lambda: rc(lib.slampp_hip_marginal_blocks_device_async(h, None, 32, _ptr(rows32), _ptr(cols32), blocks.data_ptr())),
+        "b_columns_of_32_pairs": lambda: rc(lib.slampp_hip_marginal_columns_device_async(h, None, len(distinct), _ptr(distinct), out.data_ptr())),
+        "c_blocks_last_vs_64": lambda: rc(lib.slampp_hip_marginal_blocks_device_async(h, None, 64, _ptr(cand), _ptr(last64), blocks.data_ptr())),
+        "c_columns_last": lambda: rc(lib.slampp_hip_marginal_columns_device_async(h, None, 1, _ptr(last), out.data_ptr())),
+    }
+    times = {k: [] for k in legs}
+    for _ in range(repeats):                                              # the legs alternate: drift hits all of them alike
+        for k, fn in legs.items():
+            times[k].append(device_ms(s, fn, reps))
+    host = {}
+    for k, fn in legs.items():
+        t0 = time.perf_counter()
+        fn()
+        host[k] = (time.perf_counter() - t0) * 1e3
+        assert s.sync()
+    # the two routes give the same blocks
+    legs["b_columns_of_32_pairs"]()
+    assert s.sync()
+    X = out[:n * d * len(distinct)].view(d * len(distinct), n).cpu().numpy().T
+    legs["a_blocks_32_pairs"]()
+    assert s.sync()
+    B = blocks[:32 * d * d].cpu().numpy().reshape(32, d, d).transpose(0, 2, 1)
+    where = {int(c): i for i, c in enumerate(distinct)}
+    agree = max(float(np.abs(B[k] - X[d * r:d * r + d, d * where[int(c)]:d * where[int(c)] + d]).max() /
+                      np.abs(B[k]).max()) for k, (r, c) in enumerate(zip(rows32, cols32)))
+    ws = 8.0 * n * 48
+
+    def leg(k, out_bytes):
+        t = np.asarray(times[k])
+        return {"ms_median": round(float(np.median(t)), 4), "ms_min": round(float(t.min()), 4), "ms_max": round(float(t.max()), 4),
+                "host_enqueue_ms": round(host[k], 4), "device_bytes_workspace": ws, "device_bytes_output": out_bytes}
+    return {
+        "case": name + " pairs", "n_bcols": nb, "n_scalars": n, "dense_dim": plan["dense_dim"], "etree_height": st["etree_height"],
+        "reps": reps, "repeats": repeats, "distinct_columns_of_32_pairs": int(len(distinct)),
+        "a_blocks_32_pairs": leg("a_blocks_32_pairs", 8.0 * 32 * d * d),
+        "b_columns_of_32_pairs": leg("b_columns_of_32_pairs", 8.0 * n * d * len(distinct)),
+        "c_blocks_last_vs_64": leg("c_blocks_last_vs_64", 8.0 * 64 * d * d),
+        "c_columns_last": leg("c_columns_last", 8.0 * n * d),
+        "blocks_vs_columns_rel_inf": agree,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default=None, help="C3 or C2")
+    ap.add_argument("--pairs", action="store_true", help="blocks at arbitrary pairs next to whole columns (see above)")
+    ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("time_covariance: needs the GPU")
@@ -123,7 +203,7 @@ def main():
     for name, make in cases:
         if a.only and a.only != name:
             continue
-        r = case(name, make(), a.reps)
+        r = pairs_case(name, make(), a.reps, a.repeats) if a.pairs else case(name, make(), a.reps)
         print(json.dumps(r))
         results.append(r)
     if a.out:
