@@ -1,7 +1,7 @@
 // capi.hip -- C ABI of libslampp_hip.so (include/slampp_hip.h): argument checks, error mapping, orchestration
 // (one of the translation units solver.hip was split into in round 5: solver.hip the handle and its device memory,
 // staging.hip pinned staging and uploads, sparse_setup.hip the analysis of the sparse block path, sparse_enqueue.hip its launches,
-// capi.hip the C ABI of include/slampp_hip.h).  This file: the handle's life cycle, options, structure, analysis, solve, sync,
+// capi.hip the C ABI of include/slampp_hip.h; the records the analysis lays out are host-only code: sparse_records.cpp, host_pool.cpp).  This file: the handle's life cycle, options, structure, analysis, solve, sync,
 // batch, staging, statistics, plan views and assembly; capi_covariance.hip: the covariance entry points; capi_resolve.hip:
 // the factor handed out, re-solves, products and refinement; capi_util.h: what the three share
 #include <execinfo.h>
@@ -639,7 +639,7 @@ int slampp_hip_analyze(slampp_hip_solver *p_solver, int n_mode, int64_t n_matrix
 		}
 		s.Join_Bringup(); // (every path above has: the handle's state after analyze does not depend on which)
 		if(!s.t_discard.joinable())
-			host_pool_release(); // (no thread is freeing this analysis' arrays: what its work arrays left mapped goes back now -- solver.h)
+			host_pool_release(); // (no thread is freeing this analysis' arrays: what its work arrays left mapped goes back now -- host_pool.h)
 		s.b_analyzed = true;
 		return SLAMPP_HIP_OK;
 	}, false);
@@ -970,7 +970,7 @@ int slampp_hip_get_stats(const slampp_hip_solver *p_solver, slampp_hip_stats *p_
 		p_stats->n_tasks = int64_t(P.task_ptr.size()) - 1;
 		p_stats->etree_height = P.etree_height;
 		p_stats->n_update_pairs = int64_t(P.pa.size());
-		p_stats->n_bottom_stages = s.n_bottom_stages;
+		p_stats->n_bottom_stages = s.lists.n_bottom_stages;
 		p_stats->schur_dim = P.dense_dim; // sparse path: dimension of the dense top (0 = none)
 	} else if(s.b_analyzed && s.p_schur)
 		schur_fill_stats(s.p_schur, *p_stats);

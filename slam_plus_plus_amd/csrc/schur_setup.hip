@@ -250,7 +250,7 @@ CSchurState *schur_analyze(slampp_hip_solver &s)
 		std::vector<int64_t> sb_ptr;
 		std::vector<int32_t> sb_row, sb_col;
 		raw_vector<int32_t> ent_a;    // (the contribution lists -- 5 M entries at the uniform-visibility C4 -- and the counters they are
-		raw_vector<int64_t> ent_uoff; // placed with: mappings of the library's own on huge pages, solver.h)
+		raw_vector<int64_t> ent_uoff; // placed with: mappings of the library's own on huge pages, host_pool.h)
 		bool b_tiles_built = false;
 		{
 			int64_t n_entries = 0;

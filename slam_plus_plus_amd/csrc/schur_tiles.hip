@@ -949,7 +949,7 @@ void schur_tiles_build(CSchurTiles &T, int n_mode, int DC, int DP, int64_t nc, i
 			for(size_t t = 0; t < threads.size(); ++ t)
 				threads[t].join();
 		};
-		raw_vector<uint64_t> hash(np), hash2(np); // (hash2: a second, independent hash of the same list -- see "same lists" below; raw_vector: not zero-filled, solver.h)
+		raw_vector<uint64_t> hash(np), hash2(np); // (hash2: a second, independent hash of the same list -- see "same lists" below; raw_vector: not zero-filled, host_pool.h)
 		raw_vector<int32_t> k_of(np); // observations per landmark (8 MB that stay in the caches better than two reads of ptr[] per use)
 		For_Landmark_Ranges(0, [&](int64_t n_first, int64_t n_last) {
 			for(int64_t pt = n_first; pt < n_last; ++ pt) {

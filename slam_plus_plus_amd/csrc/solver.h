@@ -13,6 +13,8 @@
 
 #include "../../include/slampp_hip.h"
 #include "plan.h"
+#include "host_pool.h"
+#include "sparse_records.h"
 #include <utility>
 #include "sparse_kernels.h"
 #include "dense_chol.h"
@@ -25,12 +27,6 @@ struct CDeviceError : public std::runtime_error {
 
 #define SLAMPP_HIP_CHECK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { \
 	throw slampp::CDeviceError(std::string(#call) + ": " + hipGetErrorString(e_)); } } while(0)
-
-inline double wall_ms()
-{
-	using namespace std::chrono;
-	return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
 
 // owning device array
 // CDevArray::Free() keeps the memory while this is set (thread-local: a handle is used from one thread at a time, the members
@@ -87,52 +83,6 @@ public:
 	void Swap(CDevArray &r_other) { std::swap(m_p, r_other.m_p); std::swap(m_n, r_other.m_n); std::swap(m_cap, r_other.m_cap); }
 };
 
-// allocator for the big work arrays of the analysis that are written in full before they are read: std::vector<T>(n)
-// zero-fills -- 32 MB on one thread, a page fault every 4 KB: 5 ms, and C5's analysis made six of them --; with this
-// allocator the elements are left as they are and the pages are first touched by the (threaded) loops that fill them
-// ... and from one megabyte on their memory is mapped by the library itself, aligned to 2 MB and offered to the kernel as
-// transparent huge pages (round 6, solver.hip: host_pool_*).  First touches are what an analysis of a large system waits for
-// (tools/micro/page_touch.cpp on the box: 256 MB of fresh 4 KB pages take 38 ms to touch on one thread and 15 - 17 ms on
-// eight -- the threads queue for the process's memory map --, and 30 - 39 ms to unmap; as huge pages 9.7 / 1.7 - 2.2 ms and
-// 12 - 19 ms).  The C library's allocator hands out addresses 16 bytes behind a page boundary, which madvise() refuses: the
-// one attempt at huge pages of the round's first hours did nothing for that reason.  A dropped array's mapping is kept for the
-// next array of about its size and everything goes back to the system when the analysis is over (host_pool_release, called by
-// the thread that frees the analysis' arrays).
-void *host_pool_alloc(size_t n_bytes); // throws std::bad_alloc
-void host_pool_free(void *p) noexcept;
-void host_pool_release() noexcept;     // unmaps the blocks nobody holds
-enum { host_pool_min_bytes = 1 << 20 };
-
-template <class T>
-struct CNoInitAlloc : std::allocator<T> {
-	template <class U> struct rebind { typedef CNoInitAlloc<U> other; };
-	CNoInitAlloc() {}
-	template <class U> CNoInitAlloc(const CNoInitAlloc<U>&) {}
-	T *allocate(size_t n)
-	{
-		if(n > size_t(-1) / sizeof(T))
-			throw std::bad_alloc();
-		return (n * sizeof(T) >= size_t(host_pool_min_bytes))? static_cast<T*>(host_pool_alloc(n * sizeof(T))) : static_cast<T*>(::operator new(n * sizeof(T)));
-	}
-	void deallocate(T *p, size_t n) noexcept
-	{
-		if(n * sizeof(T) >= size_t(host_pool_min_bytes))
-			host_pool_free(p);
-		else
-			::operator delete(p);
-	}
-	template <class U> void construct(U *p) { ::new((void*)p) U; } // default-initialization: nothing for arithmetic types
-	template <class U, class... CArgs> void construct(U *p, CArgs&&... args) { ::new((void*)p) U(std::forward<CArgs>(args)...); }
-};
-template <class T> using raw_vector = std::vector<T, CNoInitAlloc<T> >;
-
-// work arrays of the analysis that nobody reads any more, kept until a thread that has nothing urgent left frees them:
-// giving 150 MB back to the system (C5: hashes, sort items, orders of two million landmarks) is 9 - 15 ms of page-table
-// work, and it used to happen on the analysis' own thread at the end of a scope
-struct TTrash { virtual ~TTrash() {} };
-template <class T> struct TTrashOf : TTrash { T t; explicit TTrashOf(T &r) { t.swap(r); } };
-typedef std::vector<std::unique_ptr<TTrash> > CTrashList;
-template <class T> inline void Discard_Later(CTrashList &r_trash, T &r_v) { r_trash.emplace_back(new TTrashOf<T>(r_v)); }
 
 // while one of these lives on a thread, the device arrays freed on that thread keep their memory (a re-analysis)
 struct CKeepDeviceMemory {
@@ -219,7 +169,7 @@ struct slampp_hip_solver {
 	int n_staging_ahead = 0; // option "staging_ahead": slampp_hip_analyze brings up the pinned host staging on a thread of its own
 	int n_schur_fallback_option = 1; // option "schur_fallback": 0 = report SLAMPP_HIP_ERR_UNSUPPORTED instead
 	slampp::Plan plan;
-	int n_bottom_stages; // leading stages launched with one wave per task
+	slampp::SparseLaunchLists lists; // what the launches of a step read on the host (sparse_records.h): filled by the analysis
 	slampp::TDevPlan dplan;
 	slampp::CDevArray<slampp::TColDesc> d_cols;
 	slampp::CDevArray<slampp::TBlkDesc> d_blks;
@@ -241,14 +191,10 @@ struct slampp_hip_solver {
 	slampp::CDevArray<longlong2> d_panel_pkg;
 	slampp::CDevArray<int64_t> d_panel_off, d_panel_out_off;
 	slampp::CDevArray<double> d_handup; // the blocks the panel tasks hand up to the next stage's (TPanelOut)
-	bool b_any_hand_up = false;
 	int n_panel_handup = 1; // option "panel_handup": 1 = a panel task computes what it owes the next stage's tasks out of its own image (round 4), 0 = they fetch the operands
 	slampp::CDevArray<int32_t> d_panel_rest;
 	slampp::CDevArray<slampp::TUpdSlot> d_panel_upd_slots; // the factor blocks of the panel tasks, stage by stage, and the
 	slampp::CDevArray<slampp::TUpdEnt> d_panel_upd_ents;   // updates they receive from earlier stages (panel_update_kernel)
-	std::vector<int32_t> panel_ptr, panel_rest_ptr, panel_upd_ptr; // [n_stages + 1] ranges of the lists (empty: no panels)
-	std::vector<slampp::TPanelLaunch> panel_cfg; // [n_stages] waves per task and LDS capacities of the stage's panel launch
-	std::vector<char> panel_ride; // [n_stages + 1] the stage's updates from further down are applied inside the launch of the stage below
 	slampp::CDevArray<int64_t> d_simt_tab;
 	// the same chunks for the backward substitution (backward_simt_kernel): per shape [n_cols, blocks below the diagonals, nb per column],
 	// per lane (offset of the column's first factor block, scalar offset in the workspace, in the caller's vector) per column and
@@ -256,10 +202,6 @@ struct slampp_hip_solver {
 	slampp::CDevArray<slampp::TSimtChunk> d_simt_bwd_chunks;
 	slampp::CDevArray<int32_t> d_simt_bwd_prog;
 	slampp::CDevArray<int64_t> d_simt_bwd_tab;
-	std::vector<int32_t> simt_bwd_lds_bytes;
-	std::vector<slampp::TSimtChunk> simt_host_bwd_chunks;
-	std::vector<int32_t> simt_host_bwd_prog;
-	slampp::raw_vector<int64_t> simt_host_bwd_tab; // (raw_vector: written in full by the table pass, never zero-filled; its own mapping on huge pages)
 	// inv(L_jj) of the columns the lane-per-task kernel factors is not on the solve's path any more (its backward kernel solves with
 	// L_jj^T): stored only once something has asked for it (another right-hand side, covariances) -- from then on always
 	bool b_leaf_linv_wanted = false, b_leaf_linv_valid = true;
@@ -274,18 +216,12 @@ struct slampp_hip_solver {
 	int n_batch_pending = 0;    // members of the batches enqueued since the last slampp_hip_sync_batch (the largest)
 	int n_simt_backward = -1; // option "simt_backward": 1 = the leaf subtrees' backward substitution a lane per task as well and no inv(L_jj) stored for them; 0 = a wave per task; -1 (default) = by the number of leaf subtrees (round 4, after the new ordering: slower below ~12 000 of them, 1.6 % faster at C3, 7 % at a million poses)
 	void Ensure_Leaf_Inverses();
-	std::vector<int32_t> simt_chunk_ptr, simt_rest_ptr; // [n_bottom_stages + 1] each; empty = not in use
-	std::vector<int32_t> simt_lds_bytes; // per stage: the largest chunk table (it is staged in LDS)
 	int n_simt = -1; // option "simt": 1 / -1 = use it where it applies (default), 0 = never
 	int n_wide_min_tasks = 8192; // option "wide_min_tasks": stages with more tasks than this run one wave per task, one tree level per stage (throughput); below, tasks are slices of the tree in LDS (C3: its 7 513-task stage 0.433 -> 0.404 ms as slices; a million poses: 2.31 ms with the 75 000-task stages wide, 2.36 as slices)
 	int n_simt_width = 32; // option "simt_width": tasks per wave (16, 32, 64)
 	int n_simt_stages = 1; // option "simt_stages": how many of the bottom stages it takes (the stages above the leaves hold
 	                       // single separator columns whose operands other waves wrote: no gain there, measured)
-	void Build_Simt(); // throws; host work only
-	void Upload_Simt(); // throws
-	std::vector<slampp::TSimtChunk> simt_host_chunks; // what Build_Simt() made, until Upload_Simt() has sent it
-	std::vector<int32_t> simt_host_prog, simt_host_rest;
-	slampp::raw_vector<int64_t> simt_host_tab;
+	void Upload_Simt(const slampp::SparseRecords &r_rec); // throws; what build_simt_tables() made (sparse_records.h)
 	// dense top of the sparse path (plan.h): assembled Schur complement + dense factor workspaces
 	slampp::CDevArray<slampp::TDenseBlk> d_dense_blks;
 	slampp::CDevArray<int64_t> d_dense_blk_loff; // where each of those blocks lives in the factor's block layout (slampp_hip_factorize)

@@ -2,7 +2,7 @@
 // sparse_kernels.hip / schur.hip / dense_chol.hip.
 // (one of the translation units solver.hip was split into in round 5: solver.hip the handle and its device memory,
 // staging.hip pinned staging and uploads, sparse_setup.hip the analysis of the sparse block path, sparse_enqueue.hip its launches,
-// capi.hip the C ABI of include/slampp_hip.h)
+// capi.hip the C ABI of include/slampp_hip.h; the records the analysis lays out are host-only code: sparse_records.cpp, host_pool.cpp)
 #include <execinfo.h>
 #include <signal.h>
 #include <unistd.h>
@@ -36,7 +36,7 @@ thread_local bool g_b_keep_device_memory = false;
 slampp_hip_solver::slampp_hip_solver()
 	:n_device(0), stream(0), n_dense_nb(64), b_shard_primary(1), n_shard_rank(-1), n_shard_world(0), n_marginals_dense(0), n_schur_sparse(-1), b_has_structure(false),
 	b_analyzed(false), b_factored(false), n_mode(SLAMPP_HIP_MODE_SPARSE), n_matrix_cut(0),
-	n_values(0), n_scalars(0), n_bottom_stages(1), n_dense_gaps(0), b_dense_tiles(false), b_dense_clean(false), n_dense_top_tiles(-1), n_dense_blks(0), n_dense_cols(0),
+	n_values(0), n_scalars(0), n_dense_gaps(0), b_dense_tiles(false), b_dense_clean(false), n_dense_top_tiles(-1), n_dense_blks(0), n_dense_cols(0),
 	n_dense_dim(0), n_dense_pad(0),
 	p_host_flag(0), p_schur(0), p_allreduce(0), p_allreduce_context(0),
 	b_profile(0), n_open_phase(-1)
@@ -44,98 +44,6 @@ slampp_hip_solver::slampp_hip_solver()
 	memset(&dplan, 0, sizeof(dplan));
 	memset(&times, 0, sizeof(times));
 }
-
-// ---- the mappings behind raw_vector (solver.h) ----
-namespace slampp {
-
-namespace {
-
-struct THostBlock { void *p_map; size_t n_map_bytes, n_bytes; }; // the mapping as mmap() gave it, and the aligned part handed out
-
-struct THostPool {
-	std::mutex t_mutex;
-	std::vector<std::pair<void*, THostBlock> > free_blocks; // (aligned address, block) of the mappings nobody holds
-	std::unordered_map<void*, THostBlock> held;            // aligned address -> block
-};
-
-THostPool &r_Host_Pool()
-{
-	static THostPool *p_pool = new THostPool(); // (never destroyed: containers of other static objects may be freed after it would be)
-	return *p_pool;
-}
-
-} // anonymous namespace
-
-void *host_pool_alloc(size_t n_bytes)
-{
-	const size_t n_huge = size_t(2) << 20;
-	const size_t n_need = (n_bytes + n_huge - 1) / n_huge * n_huge;
-	THostPool &r_pool = r_Host_Pool();
-	{
-		std::lock_guard<std::mutex> t_lock(r_pool.t_mutex);
-		size_t n_best = size_t(-1);
-		for(size_t i = 0; i < r_pool.free_blocks.size(); ++ i) { // the smallest block that holds it and is not more than twice as large
-			const size_t n_size = r_pool.free_blocks[i].second.n_bytes;
-			if(n_size >= n_need && n_size <= 2 * n_need && (n_best == size_t(-1) || n_size < r_pool.free_blocks[n_best].second.n_bytes))
-				n_best = i;
-		}
-		if(n_best != size_t(-1)) {
-			const std::pair<void*, THostBlock> t_block = r_pool.free_blocks[n_best];
-			r_pool.free_blocks[n_best] = r_pool.free_blocks.back();
-			r_pool.free_blocks.pop_back();
-			r_pool.held[t_block.first] = t_block.second;
-			return t_block.first;
-		}
-	}
-	THostBlock t_block;
-	t_block.n_map_bytes = n_need + n_huge;
-	t_block.n_bytes = n_need;
-	t_block.p_map = mmap(0, t_block.n_map_bytes, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-	if(t_block.p_map == MAP_FAILED)
-		throw std::bad_alloc();
-	void *p = (void*)((uintptr_t(t_block.p_map) + n_huge - 1) / n_huge * n_huge);
-	if(!dev_knob_set("SLAMPP_HIP_DEV_NO_HUGE_PAGES")) // (development aid, plan.h)
-		(void)madvise(p, n_need, MADV_HUGEPAGE); // (refused or ignored where the system has them off: 4 KB pages then, as before)
-	try {
-		std::lock_guard<std::mutex> t_lock(r_pool.t_mutex);
-		r_pool.held[p] = t_block;
-	} catch(std::bad_alloc&) {
-		(void)munmap(t_block.p_map, t_block.n_map_bytes);
-		throw;
-	}
-	return p;
-}
-
-void host_pool_free(void *p) noexcept
-{
-	if(!p)
-		return;
-	THostPool &r_pool = r_Host_Pool();
-	std::lock_guard<std::mutex> t_lock(r_pool.t_mutex);
-	std::unordered_map<void*, THostBlock>::iterator p_it = r_pool.held.find(p);
-	if(p_it == r_pool.held.end())
-		return; // (not ours: cannot happen -- CNoInitAlloc decides by the same size on both ways)
-	try {
-		r_pool.free_blocks.push_back(std::make_pair(p, p_it->second));
-	} catch(std::bad_alloc&) {
-		(void)munmap(p_it->second.p_map, p_it->second.n_map_bytes);
-	}
-	r_pool.held.erase(p_it);
-}
-
-void host_pool_release() noexcept
-{
-	std::vector<std::pair<void*, THostBlock> > blocks;
-	{
-		THostPool &r_pool = r_Host_Pool();
-		std::lock_guard<std::mutex> t_lock(r_pool.t_mutex);
-		blocks.swap(r_pool.free_blocks);
-	}
-	for(size_t i = 0; i < blocks.size(); ++ i)
-		(void)munmap(blocks[i].second.p_map, blocks[i].second.n_map_bytes);
-}
-
-} // ~slampp
 
 slampp_hip_solver::~slampp_hip_solver()
 {
@@ -169,7 +77,7 @@ void slampp_hip_solver::Free_Device(bool b_keep_multiply)
 	d_simt_bwd_chunks.Free(); d_simt_bwd_prog.Free(); d_simt_bwd_tab.Free();
 	b_leaf_linv_valid = true;
 	d_panel_pkg.Free(); d_panel_off.Free(); d_panel_out_off.Free(); d_handup.Free(); d_panel_rest.Free(); d_panel_upd_slots.Free(); d_panel_upd_ents.Free();
-	simt_chunk_ptr.clear(); simt_rest_ptr.clear();
+	lists = SparseLaunchLists();
 	d_dense_blks.Free(); d_dense_blk_loff.Free(); d_dense.Free(); d_dense_invdiag.Free(); d_dense_z.Free(); d_dense_x.Free();
 	n_dense_blks = n_dense_cols = n_dense_dim = n_dense_pad = 0;
 	dense_tiles.Free();

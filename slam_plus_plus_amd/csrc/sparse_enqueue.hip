@@ -1,7 +1,7 @@
 // sparse_enqueue.hip -- the launches of one numeric factorization + substitutions of the sparse block path (warm path)
 // (one of the translation units solver.hip was split into in round 5: solver.hip the handle and its device memory,
 // staging.hip pinned staging and uploads, sparse_setup.hip the analysis of the sparse block path, sparse_enqueue.hip its launches,
-// capi.hip the C ABI of include/slampp_hip.h)
+// capi.hip the C ABI of include/slampp_hip.h; the records the analysis lays out are host-only code: sparse_records.cpp, host_pool.cpp)
 #include <execinfo.h>
 #include <signal.h>
 #include <unistd.h>
@@ -37,7 +37,7 @@ void slampp_hip_solver::Enqueue_Sparse(const double *p_values_dev, double *p_rhs
 	// (option simt_backward, -1 = by size: with the leaf subtrees of 20 000 poses the lane-per-task backward kernel costs 14 us of
 	// 179, at 100 000 -- 15 928 subtrees -- the step is 0.318 -> 0.313 ms, at 300 000 0.853 -> 0.805, at a million 2.11 -> 1.96)
 	const bool b_simt_backward_wanted = (n_simt_backward < 0)? P.stage_ptr.size() > 1 && P.stage_ptr[1] - P.stage_ptr[0] >= 12288 : n_simt_backward != 0;
-	const bool b_simt_bwd = b_simt_backward_wanted && !simt_chunk_ptr.empty() && d_simt_bwd_chunks.p() &&
+	const bool b_simt_bwd = b_simt_backward_wanted && !lists.simt_chunk_ptr.empty() && d_simt_bwd_chunks.p() &&
 		(P.max_dim % 2 != 0 || ((reinterpret_cast<uintptr_t>(p_rhs_dev) & 15) == 0 && t_batch.b % 2 == 0));
 	if(b_factor)
 		b_leaf_linv_valid = true; // (every factor kernel but the lane-per-task one stores its inverses; that one answers below)
@@ -49,34 +49,34 @@ void slampp_hip_solver::Enqueue_Sparse(const double *p_values_dev, double *p_rhs
 		// A memset per solve erased an earlier solve's failure before slampp_hip_sync() could report it: the call answers for
 		// everything enqueued since the last one)
 		// the lane-per-task kernel reads blocks and vectors with 16-byte loads where the block dimension is even
-		const bool b_simt = !simt_chunk_ptr.empty() && (P.max_dim % 2 != 0 ||
+		const bool b_simt = !lists.simt_chunk_ptr.empty() && (P.max_dim % 2 != 0 ||
 			(((reinterpret_cast<uintptr_t>(p_values_dev) | reinterpret_cast<uintptr_t>(p_rhs_dev)) & 15) == 0 && (t_batch.a | t_batch.b) % 2 == 0));
 		// phases: the leaf subtrees (stage 0), the wide stages right above them, the separators further up
-		const int n_wide_end = std::min(n_bottom_stages, n_stages);
+		const int n_wide_end = std::min(lists.n_bottom_stages, n_stages);
 		// A stage of panel tasks: the updates its blocks receive from stages further down were applied inside the launch of the
 		// stage below if that was a panel launch too (nothing there depends on them: they ride as extra workgroups), by a
 		// launch of their own otherwise; what the stage right below contributed is brought in by the tasks themselves.
 		bool b_panel_fused = false;
-		for(size_t i = 0; i < panel_ride.size(); ++ i)
-			b_panel_fused = b_panel_fused || panel_ride[i] != 0;
-		b_panel_fused = b_panel_fused || b_any_hand_up; // (the handed-up blocks come in through the fresh entries' loop)
+		for(size_t i = 0; i < lists.panel_ride.size(); ++ i)
+			b_panel_fused = b_panel_fused || lists.panel_ride[i] != 0;
+		b_panel_fused = b_panel_fused || lists.b_any_hand_up; // (the handed-up blocks come in through the fresh entries' loop)
 		auto Launch_Panels = [&](int s, bool b_bottom) {
-			const int n_panels = panel_ptr[s + 1] - panel_ptr[s];
-			const bool b_rode = panel_ride[s] != 0;
+			const int n_panels = lists.panel_ptr[s + 1] - lists.panel_ptr[s];
+			const bool b_rode = lists.panel_ride[s] != 0;
 			if(!b_rode)
-				launch_panel_update(P.max_dim, d_panel_upd_slots.p() + panel_upd_ptr[s], panel_upd_ptr[s + 1] - panel_upd_ptr[s],
+				launch_panel_update(P.max_dim, d_panel_upd_slots.p() + lists.panel_upd_ptr[s], lists.panel_upd_ptr[s + 1] - lists.panel_upd_ptr[s],
 					d_panel_upd_ents.p(), p_values_dev, d_L.p(), p_rhs_dev, d_w.p(), stream, t_batch);
-			const int n_next = (s + 1 < n_stages && panel_ride[s + 1] == 1)? panel_upd_ptr[s + 2] - panel_upd_ptr[s + 1] : 0;
-			if(!launch_factor_panel(P.max_dim, b_panel_fused, (n_panel_rows < 0)? P.max_dim >= 6 : n_panel_rows != 0, panel_cfg[s], d_panel_pkg.p(), d_panel_off.p() + panel_ptr[s],
-				d_panel_out_off.p() + panel_ptr[s], n_panels,
-				d_panel_upd_slots.p() + ((n_next > 0)? panel_upd_ptr[s + 1] : 0), n_next, d_panel_upd_ents.p(), p_values_dev, p_rhs_dev,
+			const int n_next = (s + 1 < n_stages && lists.panel_ride[s + 1] == 1)? lists.panel_upd_ptr[s + 2] - lists.panel_upd_ptr[s + 1] : 0;
+			if(!launch_factor_panel(P.max_dim, b_panel_fused, (n_panel_rows < 0)? P.max_dim >= 6 : n_panel_rows != 0, lists.panel_cfg[s], d_panel_pkg.p(), d_panel_off.p() + lists.panel_ptr[s],
+				d_panel_out_off.p() + lists.panel_ptr[s], n_panels,
+				d_panel_upd_slots.p() + ((n_next > 0)? lists.panel_upd_ptr[s + 1] : 0), n_next, d_panel_upd_ents.p(), p_values_dev, p_rhs_dev,
 				d_L.p(), d_Linv.p(), d_w.p(), d_handup.p(), p_flag, stream, dplan.p_timing, t_batch))
 				throw CDeviceError("panel launch refused: block size or LDS request outside what the analysis planned for");
-			if(panel_rest_ptr[s + 1] > panel_rest_ptr[s]) {
+			if(lists.panel_rest_ptr[s + 1] > lists.panel_rest_ptr[s]) {
 				TDevPlan t_rest = dplan;
 				t_rest.task_map = d_panel_rest.p();
-				launch_factor_stage(t_rest, p_values_dev, d_L.p(), d_Linv.p(), p_rhs_dev, d_w.p(), panel_rest_ptr[s],
-					panel_rest_ptr[s + 1] - panel_rest_ptr[s], b_bottom, p_flag, stream, t_batch);
+				launch_factor_stage(t_rest, p_values_dev, d_L.p(), d_Linv.p(), p_rhs_dev, d_w.p(), lists.panel_rest_ptr[s],
+					lists.panel_rest_ptr[s + 1] - lists.panel_rest_ptr[s], b_bottom, p_flag, stream, t_batch);
 			}
 		};
 		for(int s = 0; s < n_stages; ++ s) {
@@ -88,28 +88,28 @@ void slampp_hip_solver::Enqueue_Sparse(const double *p_values_dev, double *p_rhs
 				Phase_Begin("factor_rest"); // the wide stages and the separators as one phase
 			else if(s == n_wide_end && b_profile >= 2)
 				Phase_Begin("factor_upper");
-			if(b_simt && s + 1 < int(simt_chunk_ptr.size())) {
-				const int n_chunks = simt_chunk_ptr[s + 1] - simt_chunk_ptr[s], n_rest = simt_rest_ptr[s + 1] - simt_rest_ptr[s];
+			if(b_simt && s + 1 < int(lists.simt_chunk_ptr.size())) {
+				const int n_chunks = lists.simt_chunk_ptr[s + 1] - lists.simt_chunk_ptr[s], n_rest = lists.simt_rest_ptr[s + 1] - lists.simt_rest_ptr[s];
 				const bool b_store_linv = b_leaf_linv_wanted || !b_simt_backward_wanted; // (the wave-per-task backward kernel reads the inverses)
-				launch_factor_simt(d_simt_chunks.p() + simt_chunk_ptr[s], n_chunks, n_simt_width, simt_lds_bytes[s], d_simt_prog.p(), d_simt_tab.p(), P.max_dim,
+				launch_factor_simt(d_simt_chunks.p() + lists.simt_chunk_ptr[s], n_chunks, n_simt_width, lists.simt_lds_bytes[s], d_simt_prog.p(), d_simt_tab.p(), P.max_dim,
 					p_values_dev, d_L.p(), b_store_linv? d_Linv.p() : 0, p_rhs_dev, d_w.p(), p_flag, stream, dplan.p_timing, t_batch);
 				b_leaf_linv_valid = b_leaf_linv_valid && b_store_linv;
 				if(n_rest > 0) {
 					TDevPlan t_rest = dplan;
 					t_rest.task_map = d_simt_rest.p();
-					launch_factor_stage(t_rest, p_values_dev, d_L.p(), d_Linv.p(), p_rhs_dev, d_w.p(), simt_rest_ptr[s], n_rest,
+					launch_factor_stage(t_rest, p_values_dev, d_L.p(), d_Linv.p(), p_rhs_dev, d_w.p(), lists.simt_rest_ptr[s], n_rest,
 						true, p_flag, stream, t_batch);
 				}
-			} else if(s == 0 && !panel_ptr.empty() && panel_ptr[1] > panel_ptr[0]) {
+			} else if(s == 0 && !lists.panel_ptr.empty() && lists.panel_ptr[1] > lists.panel_ptr[0]) {
 				Launch_Panels(s, true); // few leaf subtrees: as panels (they receive no updates: the update just copies Lambda's blocks over)
-			} else if(s > 0 && s < n_bottom_stages && dplan.task_pkg)
+			} else if(s > 0 && s < lists.n_bottom_stages && dplan.task_pkg)
 				launch_factor_wide(dplan, p_values_dev, d_L.p(), d_Linv.p(), p_rhs_dev, d_w.p(), P.stage_ptr[s],
 					P.stage_ptr[s + 1] - P.stage_ptr[s], p_flag, stream, t_batch);
-			else if(s >= n_bottom_stages && !panel_ptr.empty()) {
+			else if(s >= lists.n_bottom_stages && !lists.panel_ptr.empty()) {
 				Launch_Panels(s, false); // separators: as panels in LDS where they fit, column by column otherwise
 			} else
 			launch_factor_stage(dplan, p_values_dev, d_L.p(), d_Linv.p(), p_rhs_dev, d_w.p(), P.stage_ptr[s],
-				P.stage_ptr[s + 1] - P.stage_ptr[s], s < n_bottom_stages, p_flag, stream, t_batch);
+				P.stage_ptr[s + 1] - P.stage_ptr[s], s < lists.n_bottom_stages, p_flag, stream, t_batch);
 			if(s == 0 || (s == n_wide_end - 1 && b_profile >= 2) || s == n_stages - 1)
 				Phase_End();
 		}
@@ -170,20 +170,20 @@ void slampp_hip_solver::Enqueue_Sparse(const double *p_values_dev, double *p_rhs
 	}
 	Phase_Begin("backward");
 	for(int s = n_stages; s > 0; -- s) {
-		if(b_simt_bwd && s < int(simt_chunk_ptr.size())) {
+		if(b_simt_bwd && s < int(lists.simt_chunk_ptr.size())) {
 			// a lane-per-task stage: its chunks by backward_simt_kernel (no inverses read), the tasks of rare shapes by the
 			// wave-per-task kernel (their factor kernel stored the inverses)
-			const int n_chunks = simt_chunk_ptr[s] - simt_chunk_ptr[s - 1], n_rest = simt_rest_ptr[s] - simt_rest_ptr[s - 1];
-			launch_backward_simt(d_simt_bwd_chunks.p() + simt_chunk_ptr[s - 1], n_chunks, n_simt_width, simt_bwd_lds_bytes[s - 1],
+			const int n_chunks = lists.simt_chunk_ptr[s] - lists.simt_chunk_ptr[s - 1], n_rest = lists.simt_rest_ptr[s] - lists.simt_rest_ptr[s - 1];
+			launch_backward_simt(d_simt_bwd_chunks.p() + lists.simt_chunk_ptr[s - 1], n_chunks, n_simt_width, lists.simt_bwd_lds_bytes[s - 1],
 				d_simt_bwd_prog.p(), d_simt_bwd_tab.p(), P.max_dim, d_L.p(), d_w.p(), p_rhs_dev, stream, t_batch);
 			if(n_rest > 0) {
 				TDevPlan t_rest = dplan;
 				t_rest.task_map = d_simt_rest.p();
-				launch_backward_stage(t_rest, d_L.p(), d_Linv.p(), d_w.p(), p_rhs_dev, simt_rest_ptr[s - 1], n_rest, stream, t_batch);
+				launch_backward_stage(t_rest, d_L.p(), d_Linv.p(), d_w.p(), p_rhs_dev, lists.simt_rest_ptr[s - 1], n_rest, stream, t_batch);
 			}
 			continue;
 		}
-		if(s < int(simt_chunk_ptr.size()))
+		if(s < int(lists.simt_chunk_ptr.size()))
 			Ensure_Leaf_Inverses(); // (the wave-per-task kernel on a lane-per-task stage: unaligned caller vector)
 		launch_backward_stage(dplan, d_L.p(), d_Linv.p(), d_w.p(), p_rhs_dev, P.stage_ptr[s - 1],
 			P.stage_ptr[s] - P.stage_ptr[s - 1], stream, t_batch);

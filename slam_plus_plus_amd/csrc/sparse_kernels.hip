@@ -650,7 +650,7 @@ void launch_factor_stage(const TDevPlan &p, const double *A, double *L, double *
 {
 	if(n_tasks <= 0)
 		return;
-	if(b_bottom_stage) { // one wave per task (the host decides which stages: solver.hip, n_bottom_stages)
+	if(b_bottom_stage) { // one wave per task (the host decides which stages: count_bottom_stages(), sparse_records.cpp)
 		const bool b_first_version = dev_knob_set("SLAMPP_HIP_DEV_SUBTREE_V1"); // development aid: A/B timing (plan.h)
 		if(!b_first_version && launch_factor_subtree_image(p, A, L, Linv, b, w, task_begin, n_tasks, p_flag, stream, t_batch))
 			return;

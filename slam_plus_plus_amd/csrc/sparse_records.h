@@ -1,0 +1,134 @@
+// sparse_records.h -- host records of the sparse block path: what the analysis lays out for the kernels (sparse_kernels.h),
+// from the plan alone.  Host code only: no HIP call, nothing of the handle (solver.h); sparse_setup.hip runs these builders
+// on its threads and uploads what they made, tests/sparse_records_driver.cpp runs them on the CPU under sanitizers.
+#pragma once
+#include "plan.h"
+#include "sparse_kernels.h"
+#include "host_pool.h"
+
+#include <algorithm>
+#include <exception>
+#include <mutex>
+#include <thread>
+
+namespace slampp {
+
+// what the builders read of the handle's options (filled by sparse_setup.hip); the development knobs (plan.h) are read
+// by the builders themselves, where they apply
+struct SparseRecordOptions {
+	int n_panel;          // option "panel"
+	int n_panel_handup;   // option "panel_handup"
+	int n_simt;           // option "simt"
+	int n_simt_width;     // option "simt_width"
+	int n_simt_stages;    // option "simt_stages"
+	int n_wide_min_tasks; // option "wide_min_tasks"
+	bool b_small;         // a small system: all host work on the calling thread
+	bool b_timing;        // SLAMPP_HIP_PLAN_TIMING: the builders print what they decided
+};
+
+// what the launches of a step read on the host (sparse_enqueue.hip)
+struct SparseLaunchLists {
+	int n_bottom_stages = 1; // leading stages launched with one wave per task
+	// separator tasks that run as panels in LDS (panel_kernel.hip)
+	std::vector<int32_t> panel_ptr, panel_rest_ptr, panel_upd_ptr; // [n_stages + 1] ranges of the lists (empty: no panels)
+	std::vector<TPanelLaunch> panel_cfg; // [n_stages] waves per task and LDS capacities of the stage's panel launch
+	std::vector<char> panel_ride; // [n_stages + 1] the stage's updates from further down are applied inside the launch of the stage below (2: the tasks bring in everything themselves)
+	bool b_any_hand_up = false;
+	// lane-per-task kernels of the wide bottom stages (simt_kernel.hip)
+	std::vector<int32_t> simt_chunk_ptr, simt_rest_ptr; // [n_bottom_stages + 1] each; empty = not in use
+	std::vector<int32_t> simt_lds_bytes, simt_bwd_lds_bytes; // per stage: the largest chunk table (it is staged in LDS)
+};
+
+// the host arrays of one analysis, until they are on the device
+struct SparseRecords {
+	// packed device records (see sparse_kernels.h)
+	raw_vector<TColDesc> cols; // in schedule order (raw_vector: not zero-filled -- host_pool.h; every record is written in full)
+	raw_vector<TBlkDesc> blks;
+	raw_vector<longlong2> pairs;
+	raw_vector<TRowEnt> rents;
+	// column packages of the upper stages
+	raw_vector<longlong2> pkg;
+	std::vector<int64_t> task_pkg;
+	// panel packages of the separator stages, and the updates those tasks receive from earlier stages (panel_update_kernel)
+	raw_vector<longlong2> panel_pkg; // (raw_vector: the big arrays of the analysis live in mappings of the library's own, on huge pages)
+	std::vector<int64_t> panel_off, panel_out_off; // (panel_out_off: per package the offset of its hand-up list, or -1)
+	std::vector<int32_t> panel_units; // per package its size in 16-byte units: what the launch order of a stage goes by
+	std::vector<int32_t> panel_rest;  // the tasks of the panel stages left to the column kernel
+	raw_vector<TUpdSlot> upd_slots;
+	raw_vector<TUpdEnt> upd_ents;
+	int64_t n_handup_doubles = 0;
+	// dense top
+	std::vector<TDenseBlk> dense_blks;
+	std::vector<TDenseCol> dense_cols;
+	std::vector<int64_t> dense_blk_loff;
+	std::vector<int32_t> gaps;   // positions inside the dense top that no column maps to
+	std::vector<uint8_t> unit;   // per position of the padded dense top: 1 = padding or gap
+	std::vector<longlong2> dst;  // per position: where x goes (.x in the workspace, .y in the caller's vector; < 0: nowhere)
+	// lane-per-task tables, forward and backward
+	std::vector<TSimtChunk> simt_chunks, simt_bwd_chunks;
+	std::vector<int32_t> simt_prog, simt_rest, simt_bwd_prog;
+	raw_vector<int64_t> simt_tab, simt_bwd_tab; // (raw_vector: written in full by the table pass, never zero-filled)
+};
+
+// index ranges on a few threads (the record loops of the cold path: every entry written once, from the plan alone)
+template <class F>
+void Parallel_Ranges(int64_t n, int64_t n_min_per_thread, F f, int n_max_threads = 4)
+{
+	n_max_threads = std::min(n_max_threads, std::max(dev_knob("SLAMPP_HIP_DEV_SETUP_THREADS", n_max_threads), 1)); // (development knob, plan.h)
+	const int n_threads = int(std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_max_threads, std::max(1u, std::thread::hardware_concurrency())), n / std::max<int64_t>(n_min_per_thread, 1))));
+	if(n_threads <= 1) {
+		f(int64_t(0), n);
+		return;
+	}
+	std::vector<std::thread> threads;
+	std::exception_ptr p_error;
+	std::mutex t_mutex;
+	for(int t = 0; t < n_threads; ++ t) {
+		const int64_t b = n * t / n_threads, e = n * (t + 1) / n_threads;
+		auto job = [&, b, e]() {
+			try {
+				f(b, e);
+			} catch(...) {
+				std::lock_guard<std::mutex> t_lock(t_mutex);
+				p_error = std::current_exception();
+			}
+		};
+		if(t + 1 < n_threads)
+			threads.emplace_back(job);
+		else
+			job();
+	}
+	for(size_t t = 0; t < threads.size(); ++ t)
+		threads[t].join();
+	if(p_error)
+		std::rethrow_exception(p_error);
+}
+
+// The builders, one per job.  Each reads the plan, the options and what earlier builders left, and writes the parts named;
+// all throw (std::domain_error: a system the sparse path does not take).
+
+// the bottom stage and the wide stages right above it, which run one wave per task
+int count_bottom_stages(const Plan &P, const SparseRecordOptions &t_opt);
+// where the columns of the separator stages begin in the schedule (their records are written first: the panel packages are
+// built from them beside the rest); 0 where the leaf tasks may get panel packages too
+int64_t first_upper_column(const Plan &P, const SparseRecordOptions &t_opt, const SparseLaunchLists &r_lists);
+// sizes cols, blks, pairs, rents (not filled)
+void alloc_column_records(const Plan &P, SparseRecords &r_rec);
+// everything of the scheduled columns [i_begin, i_end): their records, their blocks, those blocks' update pairs, the row
+// entries of their diagonal blocks.  Ranges may be filled in any order and side by side.
+void fill_column_records(const Plan &P, SparseRecords &r_rec, int64_t i_begin, int64_t i_end);
+// the blocks, pairs and row entries of the dense top's columns (not scheduled; their records are read all the same)
+void fill_dense_top_column_records(const Plan &P, SparseRecords &r_rec);
+// address space for the panel lists up front (reads cols[n_upper_begin ..))
+void reserve_panel_packages(const Plan &P, const SparseLaunchLists &r_lists, int64_t n_upper_begin, SparseRecords &r_rec);
+// panel_pkg .. n_handup_doubles, and the panel_* members of the launch lists; reads cols, blks, rents of the columns from
+// n_upper_begin on (see first_upper_column) and n_bottom_stages
+void build_panel_packages(const Plan &P, const SparseRecordOptions &t_opt, SparseRecords &r_rec, SparseLaunchLists &r_lists);
+// pkg, task_pkg; reads cols, blks, pairs, rents and n_bottom_stages
+void build_column_packages(const Plan &P, const SparseLaunchLists &r_lists, SparseRecords &r_rec);
+// dense_blks .. dst; n_dense_pad: the padded dimension of the dense system
+void build_dense_top_records(const Plan &P, int n_dense_pad, SparseRecords &r_rec);
+// simt_* of both; reads n_bottom_stages
+void build_simt_tables(const Plan &P, const SparseRecordOptions &t_opt, SparseRecords &r_rec, SparseLaunchLists &r_lists);
+
+} // namespace slampp

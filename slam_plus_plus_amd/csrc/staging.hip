@@ -1,7 +1,7 @@
 // staging.hip -- pinned host staging owned by the library and the transfers through it (host arrays in, solution out)
 // (one of the translation units solver.hip was split into in round 5: solver.hip the handle and its device memory,
 // staging.hip pinned staging and uploads, sparse_setup.hip the analysis of the sparse block path, sparse_enqueue.hip its launches,
-// capi.hip the C ABI of include/slampp_hip.h)
+// capi.hip the C ABI of include/slampp_hip.h; the records the analysis lays out are host-only code: sparse_records.cpp, host_pool.cpp)
 #include <execinfo.h>
 #include <signal.h>
 #include <unistd.h>

@@ -3,6 +3,7 @@
 // a graph in several pieces, checked against a brute-force walk of parent[].  Built with AddressSanitizer + UBSan on the CPU.
 // Prints one line per graph ("<name>: pairs .. passes .. ok") and exits 0, or says what is wrong and exits 1.
 #include "pair_plan.h"
+#include "driver_graphs.h"
 #include <algorithm>
 #include <cstdio>
 #include <random>
@@ -97,32 +98,12 @@ static bool check(const char *name, const Plan &P, const std::vector<int64_t> &r
 	return true;
 }
 
-static bool run(const char *name, int n, const std::vector<std::pair<int, int> > &edges, const std::vector<int> &dims,
+static bool run(const char *name, int n, const CEdgeList &edges, const std::vector<int> &dims,
 	const PlanOptions &opt, std::mt19937 &rng)
 {
-	std::vector<std::set<int> > bcols(n);
-	for(int i = 0; i < n; ++ i)
-		bcols[i].insert(i);
-	for(size_t e = 0; e < edges.size(); ++ e) {
-		const int a = std::min(edges[e].first, edges[e].second), b = std::max(edges[e].first, edges[e].second);
-		if(a != b)
-			bcols[b].insert(a);
-	}
-	std::vector<int64_t> cumsum(n + 1, 0), ptr(n + 1, 0);
-	std::vector<int32_t> brow;
-	for(int i = 0; i < n; ++ i)
-		cumsum[i + 1] = cumsum[i] + dims[size_t(i) % dims.size()];
-	for(int c = 0; c < n; ++ c) {
-		for(std::set<int>::const_iterator p = bcols[c].begin(); p != bcols[c].end(); ++ p)
-			brow.push_back(*p);
-		ptr[c + 1] = int64_t(brow.size());
-	}
 	Plan P;
-	const std::string err = build_plan(n, cumsum.data(), ptr.data(), brow.data(), opt, P);
-	if(!err.empty()) {
-		printf("%s: build_plan: %s\n", name, err.c_str());
+	if(!plan_of_graph(name, n, edges, dims, opt, P))
 		return false;
-	}
 	// seeded pair lists: random pairs, one column against many, diagonal pairs, repeats, a single pair
 	const int sizes[] = {1, 7, 64, 300};
 	for(int t = 0; t < 4; ++ t) {
@@ -150,28 +131,16 @@ int main()
 	bool b_ok = true;
 	{ // chain with loop closures
 		int n = 6000;
-		std::vector<std::pair<int, int> > e;
-		for(int i = 1; i < n; ++ i)
-			e.push_back(std::make_pair(i - 1, i));
-		for(int i = 60; i < n; i += 50)
-			e.push_back(std::make_pair(i, i - 26 - int(rng() % 30)));
+		const CEdgeList e = chain_with_closures(n, rng);
 		b_ok = run("chain", n, e, std::vector<int>(1, 6), PlanOptions(), rng) && b_ok;
 		const int mixed[] = {2, 3, 6, 7, 8, 4, 5};
 		PlanOptions opt;
 		opt.dense_top_nb = 0;
-		b_ok = run("mixed", 900, std::vector<std::pair<int, int> >(e.begin(), e.begin() + 899), std::vector<int>(mixed, mixed + 7), opt, rng) && b_ok;
+		b_ok = run("mixed", 900, CEdgeList(e.begin(), e.begin() + 899), std::vector<int>(mixed, mixed + 7), opt, rng) && b_ok;
 	}
 	{ // grid: the default options, and a forced dense top
 		int w = 40, n = w * w;
-		std::vector<std::pair<int, int> > e;
-		for(int y = 0; y < w; ++ y) {
-			for(int x = 0; x < w; ++ x) {
-				if(x)
-					e.push_back(std::make_pair(y * w + x - 1, y * w + x));
-				if(y)
-					e.push_back(std::make_pair((y - 1) * w + x, y * w + x));
-			}
-		}
+		const CEdgeList e = grid_graph(w);
 		b_ok = run("grid", n, e, std::vector<int>(1, 3), PlanOptions(), rng) && b_ok;
 		PlanOptions opt;
 		opt.dense_top_nb = 4;
@@ -180,13 +149,8 @@ int main()
 		b_ok = run("grid+dense_top", n, e, std::vector<int>(1, 3), opt, rng) && b_ok;
 	}
 	{ // several pieces and isolated vertices: pairs whose paths never meet
-		int n = 1500;
-		std::vector<std::pair<int, int> > e;
-		for(int i = 0; i < 2500; ++ i)
-			e.push_back(std::make_pair(int(rng() % 800), int(rng() % 800)));
-		for(int i = 901; i < 1300; ++ i)
-			e.push_back(std::make_pair(i - 1, i));
-		b_ok = run("pieces", n, e, std::vector<int>(1, 6), PlanOptions(), rng) && b_ok;
+		const CEdgeList e = pieces_graph(rng);
+		b_ok = run("pieces", 1500, e, std::vector<int>(1, 6), PlanOptions(), rng) && b_ok;
 	}
 	return b_ok? 0 : 1;
 }

@@ -83,12 +83,12 @@ PANEL_CASES = {
     "w2_rows1": ({"panel_rows": 1}, {W2: 0}, [V.reach_panel_waves(2)]),
     "no_riders": ({}, {"SLAMPP_HIP_DEV_PANEL_RIDE_FRESH": 0}, [V.reach_panel_no_riders]),
     "handup_narrow": ({}, {"SLAMPP_HIP_DEV_HANDUP_MAX_TASKS": 4}, [V.reach_handup_narrow]),
-    # (the crowded branch itself, sparse_setup.hip:349, wants more than 1 024 panel tasks in the stage below: the knob is set and
+    # (the crowded branch itself, b_below_crowded in CPanelPass::Decide_Stage() of sparse_records.cpp, wants more than 1 024 panel tasks in the stage below: the knob is set and
     # the two-wave launch it is listed with is what is reached at this size)
     "self_above_crowded_w2": ({}, {"SLAMPP_HIP_DEV_PANEL_SELF_ABOVE_CROWDED": 1, W2: 0}, [V.reach_panel_waves(2)]),
     "max_cols_2": ({}, {"SLAMPP_HIP_DEV_TASK_MAX_COLS": 2}, [V.reach_task_caps]),
     "max_blocks_1": ({}, {"SLAMPP_HIP_DEV_TASK_MAX_BLOCKS": 1}, [V.reach_task_caps]),   # (1: the knob's floor, plan.cpp:1347)
-    # (simt = 0 alone leaves few leaf tasks to the panel kernel, sparse_setup.hip:292: panel = 0 takes them to launch_factor_stage)
+    # (simt = 0 alone leaves few leaf tasks to the panel kernel, b_leaf_panels in CPanelPass::Run() of sparse_records.cpp: panel = 0 takes them to launch_factor_stage)
     "subtree_v1": ({"simt": 0, "panel": 0}, {"SLAMPP_HIP_DEV_SUBTREE_V1": 1}, [V.reach_subtree_v1]),
 }
 

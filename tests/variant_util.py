@@ -13,7 +13,7 @@ from slam_plus_plus_amd import synth
 TOL = 1e-10                       # the project's bound on ||x - x_ref||_inf / ||x_ref||_inf
 L_TOL = 1e-11                     # ... and on max|L - L_ref| / max|L_ref| (test_factorize_returns_the_cholesky_factor)
 WIDE_CHUNK, WIDE_NR, WIDE_NP = 8, 32, 48        # sparse_kernels.h:174: what a packaged column of a wide stage may hold
-SIMT_MAX_PROG, SIMT_MAX_TABLE_BYTES = 4096, 40960   # sparse_setup.hip:1013
+SIMT_MAX_PROG, SIMT_MAX_TABLE_BYTES = 4096, 40960   # sparse_records.cpp: SIMT_MAX_PROG, SIMT_MAX_TABLE_BYTES
 PLAN_OPTIONS = {"subtree_size": 4, "leaf_size": 1, "dense_top_nb": 0}   # ~n/4 leaf tasks, six or more stages, no dense top
 ALPHAS = (0.0, 0.5, 1e-3)                       # the batch members: Lambda + alpha I
 ALPHAS_8 = (0.0, 0.5, 1e-3, 7.0, 1e-6, 0.25, 2.0, 0.03)
@@ -193,13 +193,13 @@ def stage_columns(plan, s):
 
 
 def column_counts(plan, j):
-    """(nb, nr, np) of scheduled column j as Fill_Scheduled packs them (sparse_setup.hip:217-227)."""
+    """(nb, nr, np) of scheduled column j as fill_column_records() packs them (sparse_records.cpp)."""
     lptr, rptr, pptr = plan["lptr"], plan["rptr"], plan["pptr"]
     return int(lptr[j + 1] - lptr[j]), int(rptr[j + 1] - rptr[j]), int(pptr[lptr[j + 1]] - pptr[lptr[j] + 1])
 
 
 def bottom_stages(plan, wide_min_tasks):
-    """n_bottom_stages as Analyze_Sparse counts them (sparse_setup.hip:151-154)."""
+    """n_bottom_stages as count_bottom_stages() counts them (sparse_records.cpp)."""
     n_stages, n = len(plan["stage_ptr"]) - 1, 1
     while n < n_stages and stage_tasks(plan, n) > wide_min_tasks:
         n += 1
@@ -207,7 +207,7 @@ def bottom_stages(plan, wide_min_tasks):
 
 
 def task_shapes(plan, s, width):
-    """The tasks of stage s grouped by shape as Build_Simt groups them (sparse_setup.hip:1041-1155): a shape is the task's
+    """The tasks of stage s grouped by shape as build_simt_tables() groups them (sparse_records.cpp: Simt_Task_Program(), Group_Simt_Shapes()): a shape is the task's
     program, its operands numbered in order of first use.  Returns [(number of tasks, fits the lane-per-task kernel)]."""
     lptr, lrow, pptr, pa, pb, rptr, rblk = (plan[k] for k in ("lptr", "lrow", "pptr", "pa", "pb", "rptr", "rblk"))
     blk_col = np.repeat(np.arange(len(lptr) - 1), np.diff(lptr))
@@ -267,7 +267,7 @@ class Reach:
         return self.sysrec.uniform and self.sysrec.d in (3, 6, 7)
 
     def simt_stage_count(self):
-        """Stages the lane-per-task kernels take (Build_Simt, sparse_setup.hip:1007-1029, 1267): option simt = 1, one of
+        """Stages the lane-per-task kernels take (build_simt_tables() in sparse_records.cpp: its early returns, the condition of its stage loop, and no chunk at all): option simt = 1, one of
         the fixed block sizes, s < n_bottom_stages and s < simt_stages, and tasks that fit the kernel's tables."""
         if self.opt("simt", -1) != 1 or not self.fixed_dim:
             return 0
@@ -276,10 +276,10 @@ class Reach:
         return n if any(f for s in range(n) for _, f in task_shapes(self.plan, s, width)) else 0
 
     def panels_on(self):
-        return self.opt("panel", 1) != 0 and self.fixed_dim       # sparse_setup.hip:286
+        return self.opt("panel", 1) != 0 and self.fixed_dim       # b_Panel_Pass(), sparse_records.cpp: t_opt.n_panel && b_Package_Dim(P)
 
     def panel_stages(self):
-        """Stages launched as panels (sparse_setup.hip:292, 319; sparse_enqueue.hip:103, 108): the separator stages, and the
+        """Stages launched as panels (b_leaf_panels and b_panel_stage in CPanelPass::Run(), sparse_records.cpp; sparse_enqueue.hip:103, 108): the separator stages, and the
         leaf stage where the lane-per-task kernel is not asked for and the leaf tasks are at most 512."""
         if not self.panels_on():
             return []
@@ -291,7 +291,7 @@ class Reach:
 
 def reach_wide(r):
     """Gate 1, sparse_enqueue.hip:105: s > 0 && s < n_bottom_stages && dplan.task_pkg (packages exist for one fixed block size,
-    sparse_setup.hip:760), for a stage the lane-per-task kernel has not taken (sparse_enqueue.hip:91)."""
+    build_column_packages(): b_Package_Dim(P)), for a stage the lane-per-task kernel has not taken (sparse_enqueue.hip:91)."""
     assert r.n_bottom >= 2 and r.n_bottom == bottom_stages(r.plan, r.opt("wide_min_tasks", 8192))
     assert r.fixed_dim
     assert max(r.simt_stage_count(), 1) < r.n_bottom
@@ -310,7 +310,7 @@ def reach_wide_packages(r):
 
 
 def reach_wide_mixed(r):
-    """Gate 2, sparse_enqueue.hip:105 is false without packages (!P.uniform_dim, sparse_setup.hip:760, 956) and the stage falls
+    """Gate 2, sparse_enqueue.hip:105 is false without packages (!P.uniform_dim: b_Package_Dim(P) in build_column_packages(), dplan.task_pkg in Analyze_Sparse()) and the stage falls
     through to launch_factor_stage(..., s < n_bottom_stages) at sparse_enqueue.hip:111 with s > 0."""
     assert r.n_bottom >= 2 and r.n_bottom == bottom_stages(r.plan, r.opt("wide_min_tasks", 8192))
     assert not r.sysrec.uniform and len(set(r.sysrec.dims.tolist())) > 1
@@ -336,7 +336,7 @@ def reach_simt_backward(r):
 
 
 def reach_simt_stages(r):
-    """Gate 4, sparse_setup.hip:1029: s < n_bottom_stages && s < n_simt_stages for a stage above the leaves."""
+    """Gate 4, the stage loop of build_simt_tables(): s < n_bottom_stages && s < n_simt_stages for a stage above the leaves."""
     assert r.n_bottom >= 2 and r.opt("simt_stages", 1) >= 2
     assert r.simt_stage_count() >= 2
     width = r.opt("simt_width", 32)
@@ -345,7 +345,7 @@ def reach_simt_stages(r):
 
 def reach_panel_waves(waves):
     def reach(r):
-        """Gate 7, sparse_setup.hip:328-331: a panel stage with more tasks than SLAMPP_HIP_DEV_PANEL_W2_MIN runs two waves a task,
+        """Gate 7, n_stage_waves in CPanelPass::Decide_Stage(): a panel stage with more tasks than SLAMPP_HIP_DEV_PANEL_W2_MIN runs two waves a task,
         one with more than _W4_MIN (and not more than _W2_MIN) four."""
         w4, w2 = r.knob("SLAMPP_HIP_DEV_PANEL_W4_MIN", 512), r.knob("SLAMPP_HIP_DEV_PANEL_W2_MIN", 1024)
         got = {2 if stage_tasks(r.plan, s) > w2 else 4 if stage_tasks(r.plan, s) > w4 else 8 for s in r.panel_stages()}
@@ -354,7 +354,7 @@ def reach_panel_waves(waves):
 
 
 def reach_panel_no_riders(r):
-    """Gate 7, sparse_setup.hip:317, 373: with SLAMPP_HIP_DEV_PANEL_RIDE_FRESH = 0 a stage's updates ride in the launch below only
+    """Gate 7, n_ride_max_fresh in CPanelPass::Decide_Stage() (panel_ride[s] = n_max_fresh <= n_ride_max_fresh): with SLAMPP_HIP_DEV_PANEL_RIDE_FRESH = 0 a stage's updates ride in the launch below only
     if the stage right below contributes nothing; there are panel stages on top of panel stages for that to matter."""
     assert r.knob("SLAMPP_HIP_DEV_PANEL_RIDE_FRESH", 96) == 0
     ps = r.panel_stages()
@@ -362,7 +362,7 @@ def reach_panel_no_riders(r):
 
 
 def reach_handup_narrow(r):
-    """Gate 7, sparse_setup.hip:305, 335: hand-ups only from stages of at most SLAMPP_HIP_DEV_HANDUP_MAX_TASKS tasks -- the plan has
+    """Gate 7, b_hand_up_stage in CPanelPass::Decide_Stage() (n_handup_max_tasks): hand-ups only from stages of at most SLAMPP_HIP_DEV_HANDUP_MAX_TASKS tasks -- the plan has
     panel stages on either side of the line."""
     n_max = r.knob("SLAMPP_HIP_DEV_HANDUP_MAX_TASKS", 1 << 30)
     ps = [s for s in r.panel_stages() if s > 0 and s - 1 in r.panel_stages()]
@@ -388,7 +388,7 @@ def reach_task_caps(r):
 def reach_subtree_v1(r):
     """Gate 7, sparse_kernels.hip:653-657 behind sparse_enqueue.hip:111: the leaf stage by launch_factor_stage(b_bottom_stage)
     with SLAMPP_HIP_DEV_SUBTREE_V1 set -- neither lane-per-task (simt = 0) nor panels (few leaf tasks would go to the panel
-    kernel, sparse_setup.hip:292)."""
+    kernel, b_leaf_panels in CPanelPass::Run())."""
     assert "SLAMPP_HIP_DEV_SUBTREE_V1" in r.knobs and r.opt("simt", -1) == 0
     assert 0 not in r.panel_stages() and r.fixed_dim
 
