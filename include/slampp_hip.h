@@ -175,7 +175,7 @@ const char *slampp_hip_last_error(const slampp_hip_solver *p_solver);
  *                        many as fit in LDS; 0 = no groups, one wave per block of Lambda)
  *   "profile"            (*) 0 / 1 / 2 / 3, see slampp_hip_get_profile
  *
- * Anything else set_option knows ("panel", "panel_rows", "panel_handup", "simt", "simt_width", "simt_stages",
+ * Anything else set_option knows ("panel", "panel_rows", "panel_handup", "panel_backward", "simt", "simt_width", "simt_stages",
  * "simt_backward", "wide_min_tasks", "nd_balance", "dense_nb", "dense_top_tiles", "schur_distributed", "group_fail_member", "multiply_long_row")
  * is a development option: an alternative the defaults were measured against, or a test hook.  They are refused with
  * SLAMPP_HIP_ERR_INVALID unless the process runs with SLAMPP_HIP_DEV=1, and are described where they are implemented

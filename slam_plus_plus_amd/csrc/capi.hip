@@ -295,7 +295,7 @@ static int set_option_checked(slampp_hip_solver *p_solver, const char *p_s_name,
 		// defaults were measured against, test hooks --: they keep kernels and plan branches reachable for A/B timing and
 		// for the parity tests of those branches, and are refused unless the process runs with SLAMPP_HIP_DEV=1 (plan.h).
 		static const char *p_dev_options[] = {"nd_balance", "dense_nb", "dense_top_tiles", "simt", "simt_width", "simt_stages",
-			"simt_backward", "wide_min_tasks", "panel", "panel_handup", "panel_rows", "group_fail_member", "schur_distributed",
+			"simt_backward", "wide_min_tasks", "panel", "panel_handup", "panel_rows", "panel_backward", "group_fail_member", "schur_distributed",
 			"multiply_long_row"};
 		for(const char *p_s_dev : p_dev_options) {
 			if(s == p_s_dev && !dev_knobs_on())
@@ -387,6 +387,10 @@ static int set_option_checked(slampp_hip_solver *p_solver, const char *p_s_name,
 		p_solver->n_panel_handup = int(n_value);
 	else if(s == "panel_rows" && n_value >= -1 && n_value <= 1) {
 		p_solver->n_panel_rows = int(n_value);
+		return SLAMPP_HIP_OK; // read at every launch
+	}
+	else if(s == "panel_backward" && n_value >= -1 && n_value <= 1) {
+		p_solver->n_panel_backward = int(n_value);
 		return SLAMPP_HIP_OK; // read at every launch
 	}
 	else if(s == "simt_stages" && n_value >= 0)

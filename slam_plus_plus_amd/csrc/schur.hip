@@ -794,6 +794,7 @@ static void schur_enqueue_t(slampp_hip_solver &s, CSchurState &S, const double *
 		s.Phase_Begin("reduced_sparse");
 		S.p_inner->p_flag_shared = s.d_flag.p();
 		S.p_inner->n_panel_rows = s.n_panel_rows; // (read at every launch)
+		S.p_inner->n_panel_backward = s.n_panel_backward;
 		S.p_inner->Enqueue_Sparse(p_S, p_r, true); // p_r: the reduced right-hand side on entry, dx on return
 		s.Phase_End();
 		p_dx = p_r;

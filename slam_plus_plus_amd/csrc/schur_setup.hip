@@ -641,6 +641,7 @@ static void schur_try_sparse_reduced(slampp_hip_solver &s, CSchurState &S)
 	p_inner->n_simt_stages = s.n_simt_stages;
 	p_inner->n_wide_min_tasks = s.n_wide_min_tasks;
 	p_inner->n_panel_rows = s.n_panel_rows;
+	p_inner->n_panel_backward = s.n_panel_backward;
 	p_inner->n_panel_handup = s.n_panel_handup;
 	p_inner->n_dense_top_tiles = s.n_dense_top_tiles;
 	// (a small system is all latency: round 1 cut its leaf subtrees to four columns for the wave-per-task kernel; as panels

@@ -530,29 +530,32 @@ backward_simt_kernel(const TSimtChunk *__restrict__ chunks, const int32_t *__res
 		w[0] = f_touched;
 }
 
-bool launch_backward_simt(const TSimtChunk *chunks, int n_chunks, int n_width, int n_lds_bytes, const int32_t *prog, const int64_t *tab,
+bool launch_backward_simt(const TSimtChunk *chunks, int n_chunks, int n_width, int n_lds_bytes, size_t n_lds_limit, const int32_t *prog, const int64_t *tab,
 	int n_dim, const double *L, double *w, double *x_out, hipStream_t stream, const TBatch &t_batch)
 {
 	if(n_chunks <= 0)
 		return true;
+	if(n_lds_bytes < 0 || size_t(n_lds_bytes) > n_lds_limit)
+		return false; // (the chunk tables are staged in LDS: a launch over the limit would fail without a word)
 	const long long *t = reinterpret_cast<const long long*>(tab);
 #define BWD_LAUNCH(D_, W_) hipLaunchKernelGGL((backward_simt_kernel<D_, W_>), dim3(n_chunks, t_batch.n), dim3(64), n_lds_bytes, stream, chunks, prog, t, L, w, x_out, t_batch)
 #define BWD_WIDTHS(D_) do { if(n_width == 16) BWD_LAUNCH(D_, 16); else if(n_width == 32) BWD_LAUNCH(D_, 32); else BWD_LAUNCH(D_, 64); } while(0)
 	switch(n_dim) {
 	case 3:
 		BWD_WIDTHS(3);
-		return true;
+		break;
 	case 6:
 		BWD_WIDTHS(6);
-		return true;
+		break;
 	case 7:
 		BWD_WIDTHS(7);
-		return true;
+		break;
 	default:
 		return false;
 	}
 #undef BWD_WIDTHS
 #undef BWD_LAUNCH
+	return hipGetLastError() == hipSuccess;
 }
 
 // inv(L_jj) from L_jj, a thread per column (forward substitution on the identity)

@@ -193,6 +193,13 @@ struct slampp_hip_solver {
 	slampp::CDevArray<double> d_handup; // the blocks the panel tasks hand up to the next stage's (TPanelOut)
 	int n_panel_handup = 1; // option "panel_handup": 1 = a panel task computes what it owes the next stage's tasks out of its own image (round 4), 0 = they fetch the operands
 	slampp::CDevArray<int32_t> d_panel_rest;
+	// the backward substitution of the packaged tasks (backward_slice_kernel): their backward records, and per package the offset of its record
+	int n_panel_backward = -1; // option "panel_backward": 1 = the tasks the panel kernel factored are solved backward by backward_slice_kernel (one trip to
+	                           // memory per task), 0 = by backward_stage_kernel (one per column), -1 = the former in stages of at most 1 024 tasks (sparse_enqueue.hip:
+	                           // the crowded stage loses); read at every launch: one kept factor can be solved both ways; the results are bit-identical
+	size_t n_lds_limit = 0; // plain_launch_lds_limit() of the handle's device, asked at analysis: what the backward launchers compare their LDS requests with
+	slampp::CDevArray<longlong2> d_bwd_rec;
+	slampp::CDevArray<int64_t> d_bwd_off;
 	slampp::CDevArray<slampp::TUpdSlot> d_panel_upd_slots; // the factor blocks of the panel tasks, stage by stage, and the
 	slampp::CDevArray<slampp::TUpdEnt> d_panel_upd_ents;   // updates they receive from earlier stages (panel_update_kernel)
 	slampp::CDevArray<int64_t> d_simt_tab;

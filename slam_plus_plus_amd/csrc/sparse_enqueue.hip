@@ -168,14 +168,23 @@ void slampp_hip_solver::Enqueue_Sparse(const double *p_values_dev, double *p_rhs
 			d_dense_dst.p(), d_w.p(), p_rhs_dev); // (x goes to w and to the caller's vector as each panel publishes it)
 		Phase_End();
 	}
+	// option panel_backward: the stages that were factored as panels take backward_slice_kernel for their packaged tasks; -1 =
+	// by size: only stages of at most 1 024 tasks.  Measured at C3, per launch (profiles/backward_slices_ab.txt, run A): stages of 1 / 4 / 32 / 262 tasks 4.6 / 7.0 / 7.9 /
+	// 7.9 us with the column kernel, 4.7 / 4.9 / 4.9 / 5.3 with this one; the 2 066-task stage 11.6 against 14.6 (run C) -- one wave per
+	// task keeps all of them resident at once, workgroups of two to eight waves come in two rounds (the crossover lies between 262
+	// and 2 066 tasks; the line is where the panel launches turn to two waves a task, CPanelPass::Decide_Stage())
+	const bool b_slice_bwd = n_panel_backward != 0 && !lists.panel_ptr.empty() && d_bwd_rec.p() && d_bwd_off.p() &&
+		(P.max_dim == 3 || P.max_dim == 6 || P.max_dim == 7) && P.uniform_dim;
+	const int n_slice_max_tasks = dev_knob("SLAMPP_HIP_DEV_BWD_SLICE_MAX_TASKS", 1024);
 	Phase_Begin("backward");
 	for(int s = n_stages; s > 0; -- s) {
 		if(b_simt_bwd && s < int(lists.simt_chunk_ptr.size())) {
 			// a lane-per-task stage: its chunks by backward_simt_kernel (no inverses read), the tasks of rare shapes by the
 			// wave-per-task kernel (their factor kernel stored the inverses)
 			const int n_chunks = lists.simt_chunk_ptr[s] - lists.simt_chunk_ptr[s - 1], n_rest = lists.simt_rest_ptr[s] - lists.simt_rest_ptr[s - 1];
-			launch_backward_simt(d_simt_bwd_chunks.p() + lists.simt_chunk_ptr[s - 1], n_chunks, n_simt_width, lists.simt_bwd_lds_bytes[s - 1],
-				d_simt_bwd_prog.p(), d_simt_bwd_tab.p(), P.max_dim, d_L.p(), d_w.p(), p_rhs_dev, stream, t_batch);
+			if(!launch_backward_simt(d_simt_bwd_chunks.p() + lists.simt_chunk_ptr[s - 1], n_chunks, n_simt_width, lists.simt_bwd_lds_bytes[s - 1], n_lds_limit,
+				d_simt_bwd_prog.p(), d_simt_bwd_tab.p(), P.max_dim, d_L.p(), d_w.p(), p_rhs_dev, stream, t_batch))
+				throw CDeviceError("lane-per-task backward launch refused: block size or LDS request outside what the analysis planned for");
 			if(n_rest > 0) {
 				TDevPlan t_rest = dplan;
 				t_rest.task_map = d_simt_rest.p();
@@ -185,6 +194,20 @@ void slampp_hip_solver::Enqueue_Sparse(const double *p_values_dev, double *p_rhs
 		}
 		if(s < int(lists.simt_chunk_ptr.size()))
 			Ensure_Leaf_Inverses(); // (the wave-per-task kernel on a lane-per-task stage: unaligned caller vector)
+		if(b_slice_bwd && lists.panel_ptr[s] > lists.panel_ptr[s - 1] && (n_panel_backward > 0 || P.stage_ptr[s] - P.stage_ptr[s - 1] <= n_slice_max_tasks)) {
+			// a stage the panel kernel factored: its packaged tasks with one trip to memory per task, the tasks beyond the
+			// package limits column by column (tasks of one stage do not depend on each other)
+			if(!launch_backward_slice(P.max_dim, lists.bwd_cfg[s - 1], n_lds_limit, d_bwd_rec.p(), d_bwd_off.p() + lists.panel_ptr[s - 1],
+			   lists.panel_ptr[s] - lists.panel_ptr[s - 1], d_L.p(), d_Linv.p(), d_w.p(), p_rhs_dev, stream, t_batch))
+				throw CDeviceError("backward slice launch refused: block size or LDS request outside what the analysis planned for");
+			if(lists.panel_rest_ptr[s] > lists.panel_rest_ptr[s - 1]) {
+				TDevPlan t_rest = dplan;
+				t_rest.task_map = d_panel_rest.p();
+				launch_backward_stage(t_rest, d_L.p(), d_Linv.p(), d_w.p(), p_rhs_dev, lists.panel_rest_ptr[s - 1],
+					lists.panel_rest_ptr[s] - lists.panel_rest_ptr[s - 1], stream, t_batch);
+			}
+			continue;
+		}
 		launch_backward_stage(dplan, d_L.p(), d_Linv.p(), d_w.p(), p_rhs_dev, P.stage_ptr[s - 1],
 			P.stage_ptr[s] - P.stage_ptr[s - 1], stream, t_batch);
 	}

@@ -169,6 +169,50 @@ bool launch_factor_panel(int n_dim, bool b_fused, bool b_rows, const TPanelLaunc
 void launch_panel_update(int n_dim, const TUpdSlot *slots, int n_slots, const TUpdEnt *ents, const double *A, double *L,
 	const double *b, double *w, hipStream_t stream, const TBatch &t_batch = t_No_Batch());
 
+// ---- backward records (backward_slice_kernel): the backward substitution of a panel task, in one buffer ----
+// 16-byte units: head (4) | columns (2 each), level by level as in the panel package | sub-diagonal blocks (1 each), column
+// by column.  Everything a column multiplies except the x of rows inside the task is known when the task starts, so the
+// task requests it all at once; x of its own columns travels between its levels through LDS.
+enum { BWD_OFF_BITS = 48 }; // a task's entry in the offset list: (offset of its record, in 16-byte units) | (units of the record) << 48 -- the size comes
+                            // with the offset, so one coalesced read brings the whole record and nothing is fetched on speculation
+struct TBwdHead { // 64 B
+	int32_t n_cols, n_levels, n_blks, n_units;
+	int32_t lvl_ptr[PANEL_COLS + 1]; // the columns of level l are lvl_ptr[l] .. lvl_ptr[l + 1]
+	int32_t pad[3];
+};
+struct TBwdCol { // 32 B
+	int64_t linv_off, cs_src;
+	int32_t cs_new;   // scalar offset in the permuted workspace (alloc_column_records: below 2^31)
+	int32_t blk0, nb; // its sub-diagonal blocks: blk0 .. blk0 + nb - 1 of the record's block list
+	int32_t level;
+};
+struct TBwdBlk { // 16 B
+	int64_t loff;
+	int32_t xsrc;     // x of the block's row: >= 0 scalar offset in the workspace (TBlkDesc::xcs), < 0: ~(number of the column in this task)
+	int32_t pad;
+};
+// How one stage's launch is shaped: every wave owns n_cols_per_wave columns of its task (column o: wave o % n_waves), whose
+// operands it keeps in registers; one where the stage is a launch on the critical path, more where it is crowded (as
+// TPanelLaunch::n_waves).  n_cap_units: the largest record of the stage (its LDS copy).
+struct TBwdLaunch {
+	int32_t n_waves, n_cols_per_wave, n_cap_units;
+};
+// dynamic LDS a launch may ask for without raising the kernel's own limit (hipFuncAttributeMaxDynamicSharedMemorySize):
+// what the device gives a block, 64 KB at the most; 0 if the device does not answer
+inline size_t plain_launch_lds_limit()
+{
+	int n_device = 0, n_bytes = 0;
+	if(hipGetDevice(&n_device) != hipSuccess || hipDeviceGetAttribute(&n_bytes, hipDeviceAttributeMaxSharedMemoryPerBlock, n_device) != hipSuccess)
+		return 0;
+	return size_t((n_bytes < 64 * 1024)? ((n_bytes > 0)? n_bytes : 0) : 64 * 1024);
+}
+inline size_t backward_slice_lds_bytes(const TBwdLaunch &c) { return size_t(c.n_cap_units) * 16 + PANEL_COLS * 8 * sizeof(double); }
+// one workgroup per record (rec_off: offset | units << BWD_OFF_BITS of each); n_lds_limit: plain_launch_lds_limit() of the
+// handle's device, asked once at analysis; false: no kernel for this block size or shape, the LDS request is over that
+// limit, or the launch failed
+bool launch_backward_slice(int n_dim, const TBwdLaunch &r_cfg, size_t n_lds_limit, const longlong2 *rec, const int64_t *rec_off, int n_tasks,
+	const double *L, const double *Linv, double *w, double *x_out, hipStream_t stream, const TBatch &t_batch = t_No_Batch());
+
 // capacities of the staged path of the separator kernel (blocks, row entries, update pairs of a column): near the root,
 // and in the wide stages right above the leaves
 enum { UP_CHUNK = 16, UP_NR = 128, UP_NP = 512, WIDE_CHUNK = 8, WIDE_NR = 32, WIDE_NP = 48 };
@@ -223,7 +267,7 @@ bool launch_factor_simt(const TSimtChunk *chunks, int n_chunks, int n_width /* t
 // backward substitution of the same tasks, a lane per task (chunk programs: n_cols, number of sub-diagonal blocks, nb per
 // column; tables: per column offset of its first factor block, scalar offsets in the workspace and in the caller's vector,
 // then the workspace offset of every sub-diagonal block's row): x_j from L_jj^T directly, no inverse
-bool launch_backward_simt(const TSimtChunk *chunks, int n_chunks, int n_width, int n_lds_bytes, const int32_t *prog, const int64_t *tab,
+bool launch_backward_simt(const TSimtChunk *chunks, int n_chunks, int n_width, int n_lds_bytes, size_t n_lds_limit /* plain_launch_lds_limit(), asked at analysis */, const int32_t *prog, const int64_t *tab,
 	int n_dim, const double *L, double *w, double *x_out, hipStream_t stream, const TBatch &t_batch = t_No_Batch());
 // inv(L_jj) of the columns cols[col_begin .. col_end) (schedule order) from their factor blocks: for callers that need the
 // inverses the lane-per-task factorization did not store (another right-hand side, covariances)

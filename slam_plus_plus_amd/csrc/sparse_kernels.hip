@@ -593,6 +593,117 @@ backward_stage_kernel(TDevPlan p, const double *L, const double *Linv, double *w
 	}
 }
 
+// ---- backward substitution of a slice task (a task the panel kernel factored): one trip to memory per task ----
+// backward_stage_kernel pays a trip per column: a column begins by loading the x the column before has just stored.  But
+// of what a column multiplies only the x of rows inside the task depends on the task's own work; the blocks, inv(L_jj),
+// y_j and the x of rows outside the task (earlier launches wrote it) are known when the task starts.  So the workgroup
+// reads the task's backward record (TBwdHead, sparse_kernels.h) with one coalesced read, every wave requests the operands
+// of the CPW columns it owns at once, into registers, and the levels of the task -- whose columns do not depend on each
+// other (Plan::col_sub) -- run side by side, last level first, with x of the task's own columns handed on through LDS and
+// one barrier per level.  Per column the arithmetic is backward_stage_kernel's, operation for operation and in its order
+// (lane (g, q), blocks 1 + g, 9 + g, ..., the three shuffle steps, y - acc, the product with inv(L_jj)): the results are
+// bit-identical.  No scratch: every register array is indexed by unrolled loops only.
+template <int D, int CPW>
+__global__ void __launch_bounds__(64 * PANEL_COLS / CPW)
+backward_slice_kernel(const longlong2 *__restrict__ rec, const int64_t *__restrict__ rec_off, const double *L, const double *Linv,
+	double *w, double *__restrict__ x_out, int n_cap_units, TBatch t_batch)
+{	{ const int64_t n_member = blockIdx.y; L += n_member * t_batch.l; Linv += n_member * t_batch.linv; w += n_member * t_batch.w; x_out += n_member * t_batch.b; } // (TBatch: sparse_kernels.h)
+
+	extern __shared__ __attribute__((aligned(16))) char s_mem[];
+	longlong2 *s_rec = reinterpret_cast<longlong2*>(s_mem);                                  // [n_cap_units] the record
+	double *s_x = reinterpret_cast<double*>(s_mem + size_t(n_cap_units) * sizeof(longlong2)); // [PANEL_COLS][8] x of the task's columns
+	const int tid = threadIdx.x, n_threads = blockDim.x, wave = tid >> 6, n_waves = n_threads >> 6, lane = tid & 63, g = lane >> 3, q = lane & 7;
+	const int qq = (q < D)? q : 0;
+	{
+		const int64_t n_entry = rec_off[blockIdx.x]; // offset | units << BWD_OFF_BITS
+		const longlong2 *p_rec = rec + (n_entry & ((int64_t(1) << BWD_OFF_BITS) - 1));
+		const int n_units = min(int(n_entry >> BWD_OFF_BITS), n_cap_units);
+		for(int u = tid; u < n_units; u += n_threads)
+			s_rec[u] = p_rec[u];
+		__syncthreads();
+	}
+	const TBwdHead *p_head = reinterpret_cast<const TBwdHead*>(s_rec);
+	const int n_cols = p_head->n_cols, n_levels = p_head->n_levels;
+	const TBwdCol *p_cols = reinterpret_cast<const TBwdCol*>(s_rec + 4);
+	const TBwdBlk *p_blks = reinterpret_cast<const TBwdBlk*>(s_rec + 4 + 2 * n_cols);
+	// the operands of this wave's columns (column o = wave + i n_waves), all requested here
+	int n_nb[CPW], n_level[CPW], n_cs[CPW], n_blk0[CPW], n_xsrc[CPW];
+	int64_t n_src[CPW];
+	double xv[CPW][D], lv[CPW][D], li[CPW][D], yv[CPW];
+	#pragma unroll
+	for(int i = 0; i < CPW; ++ i) {
+		const int o = wave + i * n_waves;
+		const TBwdCol &r_col = p_cols[min(o, n_cols - 1)];
+		n_nb[i] = r_col.nb;
+		n_level[i] = (o < n_cols)? r_col.level : -1;
+		n_cs[i] = r_col.cs_new;
+		n_src[i] = r_col.cs_src;
+		n_blk0[i] = r_col.blk0;
+		const int64_t n_linv = r_col.linv_off;
+		// the lane group's first block (a group without one repeats the column's last; a column without blocks reads valid addresses)
+		const bool b_blk = n_nb[i] > 0;
+		const TBwdBlk &r_blk = p_blks[b_blk? n_blk0[i] + min(g, n_nb[i] - 1) : 0];
+		const int64_t n_loff = b_blk? r_blk.loff : 0;
+		n_xsrc[i] = b_blk? r_blk.xsrc : 0;
+		const int n_xcs = max(n_xsrc[i], 0);
+		#pragma unroll
+		for(int t = 0; t < D; ++ t)
+			xv[i][t] = w[n_xcs + t];
+		#pragma unroll
+		for(int t = 0; t < D; ++ t) {
+			lv[i][t] = L[n_loff + qq * D + t];
+			li[i][t] = Linv[n_linv + t + qq * D];
+		}
+		yv[i] = w[n_cs[i] + qq];
+	}
+	for(int l = n_levels - 1; l >= 0; -- l) {
+		#pragma unroll
+		for(int i = 0; i < CPW; ++ i) {
+			if(n_level[i] != l) // (wave-uniform)
+				continue;
+			const int n_xcol = (n_xsrc[i] < 0)? ~n_xsrc[i] : 0; // x of a row inside the task: from LDS
+			double acc = 0;
+			#pragma unroll
+			for(int t = 0; t < D; ++ t) {
+				double xt = xv[i][t];
+				if(n_xsrc[i] < 0)
+					xt = s_x[n_xcol * 8 + t]; // (only then: a column of an earlier level, behind a barrier)
+				acc += lv[i][t] * xt;
+			}
+			acc = (g < n_nb[i])? acc : 0.0;
+			if(n_nb[i] > 8) { // (more than eight blocks below the diagonal: the rest as they come)
+				for(int kb = 8 + g; kb < n_nb[i]; kb += 8) {
+					const int64_t n_loff_k = p_blks[n_blk0[i] + kb].loff;
+					const int n_xsrc_k = p_blks[n_blk0[i] + kb].xsrc;
+					#pragma unroll
+					for(int t = 0; t < D; ++ t) {
+						const double xt = (n_xsrc_k < 0)? s_x[(~n_xsrc_k) * 8 + t] : w[n_xsrc_k + t];
+						acc += L[n_loff_k + qq * D + t] * xt;
+					}
+				}
+			}
+			acc += __shfl_xor(acc, 8);
+			acc += __shfl_xor(acc, 16);
+			acc += __shfl_xor(acc, 32);
+			const double val = (q < D)? yv[i] - acc : 0; // every slot g holds the same totals
+			double x = 0;
+			#pragma unroll
+			for(int t = 0; t < D; ++ t) {
+				const double vt = __shfl(val, t);
+				if(t >= qq)
+					x += li[i][t] * vt;
+			}
+			if(lane < D) {
+				s_x[(wave + i * n_waves) * 8 + lane] = x;
+				w[n_cs[i] + lane] = x;
+				x_out[n_src[i] + lane] = x;
+			}
+		}
+		if(l > 0)
+			__syncthreads(); // x of this level is where the levels below look for it
+	}
+}
+
 // ---- dense top: assemble the Schur complement onto the dense-top columns ----
 // one workgroup of 4 waves per block (i,j), j in the dense top: D(i,j) = Lambda(i,j) - sum of the updates
 // from block-eliminated columns (the updates among dense-top columns happen in dense_cholesky);
@@ -684,6 +795,31 @@ void launch_backward_stage(const TDevPlan &p, const double *L, const double *Lin
 	if(n_tasks > 0)
 		DISPATCH_DIM(p.uniform_dim, hipLaunchKernelGGL((backward_stage_kernel<D>), dim3(n_tasks, t_batch.n), dim3(64), 0, stream,
 			p, L, Linv, w, x_out, task_begin, t_batch));
+}
+
+bool launch_backward_slice(int n_dim, const TBwdLaunch &r_cfg, size_t n_lds_limit, const longlong2 *rec, const int64_t *rec_off, int n_tasks,
+	const double *L, const double *Linv, double *w, double *x_out, hipStream_t stream, const TBatch &t_batch)
+{
+	if(n_tasks <= 0)
+		return true;
+	const int W = r_cfg.n_waves, CPW = r_cfg.n_cols_per_wave;
+	if(!rec || !rec_off || W < 1 || W * CPW > int(PANEL_COLS) || r_cfg.n_cap_units < 4)
+		return false;
+	const size_t n_lds_bytes = backward_slice_lds_bytes(r_cfg);
+	if(n_lds_bytes > n_lds_limit)
+		return false;
+#define SLICE_LAUNCH(D_, CPW_) hipLaunchKernelGGL((backward_slice_kernel<D_, CPW_>), dim3(n_tasks, t_batch.n), dim3(64 * W), n_lds_bytes, stream, \
+	rec, rec_off, L, Linv, w, x_out, r_cfg.n_cap_units, t_batch)
+#define SLICE_SHAPES(D_) do { if(CPW == 1) SLICE_LAUNCH(D_, 1); else if(CPW == 2) SLICE_LAUNCH(D_, 2); else if(CPW == 4) SLICE_LAUNCH(D_, 4); else return false; } while(0)
+	switch(n_dim) {
+	case 3: SLICE_SHAPES(3); break;
+	case 6: SLICE_SHAPES(6); break;
+	case 7: SLICE_SHAPES(7); break;
+	default: return false;
+	}
+#undef SLICE_SHAPES
+#undef SLICE_LAUNCH
+	return hipGetLastError() == hipSuccess;
 }
 
 void launch_dense_assemble(const TDevPlan &p, const TDenseBlk *blks, int n_blks, const double *A, const double *L,

@@ -122,6 +122,8 @@ void reserve_panel_packages(const Plan &P, const SparseLaunchLists &r_lists, int
 	r_rec.upd_ents.reserve(n_upper_pairs + 16);
 	r_rec.panel_off.reserve(n_tasks_cap + 16);
 	r_rec.panel_out_off.reserve(n_tasks_cap + 16);
+	r_rec.bwd_rec.reserve(n_tasks_cap * (4 + 2 * PANEL_COLS) + n_upper_blocks + 16);
+	r_rec.bwd_off.reserve(n_tasks_cap + 16);
 }
 
 // ---- panel packages for the separator stages (panel_kernel.hip) ----
@@ -130,6 +132,7 @@ void reserve_panel_packages(const Plan &P, const SparseLaunchLists &r_lists, int
 
 namespace {
 
+static_assert(sizeof(TBwdHead) == 64 && sizeof(TBwdCol) == 32 && sizeof(TBwdBlk) == 16, "record sizes");
 static_assert(sizeof(TPanelOut) == 16 && sizeof(TPanelHead) == 64 && sizeof(TPanelCol) == 48 && sizeof(TPanelSlot) == 32 && sizeof(TPanelExt) == 32 && sizeof(TUpdSlot) == 64 &&
 	sizeof(TUpdEnt) == 16, "record sizes");
 
@@ -156,6 +159,7 @@ class CPanelPass {
 	bool b_panel_stage, b_hand_up_stage;
 	int n_stage_waves;
 	int64_t n_stage_max_slots, n_stage_max_units, n_stage_rest; // (for the development print)
+	int n_stage_bwd_units, n_stage_bwd_blocks, n_stage_bwd_levels; // (the same for the backward records: largest record, most blocks below a diagonal, most levels)
 	// the task being packed: what Size_Task() found
 	std::vector<int64_t> order; // the task's columns (indices into cols) level by level
 	bool b_tall;
@@ -191,10 +195,12 @@ public:
 		}
 		L.panel_ride.assign(n_stages + 1, 0);
 		L.panel_cfg.assign(size_t(n_stages) + 1, TPanelLaunch{int32_t(PANEL_W), int32_t(64 * PANEL_W), 1, 1, 1, 0});
+		L.bwd_cfg.assign(size_t(n_stages) + 1, TBwdLaunch{1, 1, 4});
 		for(s = 0; s < n_stages; ++ s) {
 			b_panel_stage = s >= L.n_bottom_stages || (s == 0 && b_leaf_panels);
 			Decide_Stage();
 			n_stage_max_slots = n_stage_max_units = n_stage_rest = 0;
+			n_stage_bwd_units = n_stage_bwd_blocks = n_stage_bwd_levels = 0;
 			for(int t = P.stage_ptr[s]; b_panel_stage && t < P.stage_ptr[s + 1]; ++ t) {
 				if(Size_Task(t))
 					Pack_Task(t);
@@ -206,6 +212,9 @@ public:
 			if(t_opt.b_timing && b_panel_stage)
 				fprintf(stderr, "[setup] stage %d panels: at most %lld blocks and %lld package units per task, %lld tasks left to the column kernel\n",
 					s, (long long)n_stage_max_slots, (long long)n_stage_max_units, (long long)n_stage_rest);
+			if(t_opt.b_timing && L.panel_ptr[s + 1] > L.panel_ptr[s])
+				fprintf(stderr, "[setup] stage %d backward records: %d tasks, at most %d units, %d blocks below a diagonal and %d levels per task; %d columns per wave\n",
+					s, int(L.panel_ptr[s + 1] - L.panel_ptr[s]), n_stage_bwd_units, n_stage_bwd_blocks, n_stage_bwd_levels, int(L.bwd_cfg[s].n_cols_per_wave));
 			L.panel_rest_ptr[s + 1] = int32_t(R.panel_rest.size());
 			L.panel_upd_ptr[s + 1] = int32_t(R.upd_slots.size());
 		}
@@ -246,6 +255,11 @@ private:
 		// above they compute instead of the next task's columns: C3's 2 420-task launch 70 -> 92 us; the stage above gains more)
 		b_hand_up_stage = b_hand_up && s > 0 && P.stage_ptr[s] - P.stage_ptr[s - 1] <= n_handup_max_tasks;
 		L.panel_cfg[s].n_waves = n_stage_waves;
+		// the backward launch of the stage (backward_slice_kernel): a wave owns one column of its task where the stage is a
+		// launch on the critical path, two or four where it is crowded; the waves per task follow from the stage's tasks
+		// (measured at C3's 2 066-task stage: four, two and one column per wave all take 14 - 15 us where the column kernel takes
+		// 11.6 -- the shape does not decide there; option panel_backward = -1 leaves such a stage to the column kernel)
+		L.bwd_cfg[s] = TBwdLaunch{1, int32_t(PANEL_W) / n_stage_waves, 4};
 		L.panel_cfg[s].n_cap_units = 64 * n_stage_waves; // (one speculative unit per thread)
 		// The first stage above a leaf stage that is not a panel launch: everything its tasks receive comes from that one
 		// stage, nothing from further down -- the tasks bring it in themselves and no update launch is needed (if it fits
@@ -494,6 +508,7 @@ private:
 		if(int64_t(fresh.size()) != n_fresh)
 			throw std::logic_error("panel package: fresh entries miscounted");
 		Append_Package(n_cols);
+		Append_Backward_Record();
 		for(size_t o = 0, n_level = 0; o < order.size(); ++ o) {
 			const TColDesc &c = R.cols[order[o]];
 			for(int64_t k = c.k0; k < c.k0 + c.nb; ++ k)
@@ -560,6 +575,63 @@ private:
 		hand_up.push_back(THandUp());
 	}
 
+	// the task's backward record (TBwdHead: sparse_kernels.h): its columns level by level as in the package, and per
+	// sub-diagonal block where the x of its row comes from -- a column of a later level of this task, or the workspace
+	void Append_Backward_Record()
+	{
+		TBwdHead hd;
+		memset(&hd, 0, sizeof(hd));
+		std::vector<TBwdCol> bcols;
+		std::vector<TBwdBlk> bblks;
+		for(size_t o = 0; o < order.size(); ++ o) {
+			const TColDesc &c = R.cols[order[o]];
+			if(o > 0 && pcols[o].sub != pcols[o - 1].sub)
+				++ hd.n_levels;
+			hd.lvl_ptr[hd.n_levels + 1] = int32_t(o) + 1;
+			TBwdCol bc;
+			bc.linv_off = c.linv_off;
+			bc.cs_src = c.cs_src;
+			bc.cs_new = int32_t(c.cs_new);
+			bc.blk0 = int32_t(bblks.size());
+			bc.nb = c.nb - 1;
+			bc.level = hd.n_levels;
+			bcols.push_back(bc);
+			for(int64_t k = c.k0 + 1; k < c.k0 + c.nb; ++ k) {
+				const int32_t n_row = P.lrow[k];
+				TBwdBlk bb;
+				bb.loff = R.blks[k].loff;
+				bb.xsrc = R.blks[k].xcs;
+				bb.pad = 0;
+				if(slot_of[P.lptr[n_row]] >= 0) { // (the row is a column of this task: col_local is this task's, set by Pack_Task)
+					const int32_t n_local = col_local[n_row];
+					if(n_local <= int32_t(o) || pcols[size_t(n_local)].sub == pcols[o].sub)
+						throw std::logic_error("backward record: a block's row is not in a later level of its task");
+					bb.xsrc = ~n_local;
+				}
+				bblks.push_back(bb);
+			}
+		}
+		++ hd.n_levels;
+		hd.n_cols = int32_t(order.size());
+		hd.n_blks = int32_t(bblks.size());
+		hd.n_units = int32_t(4 + 2 * bcols.size() + bblks.size());
+		n_stage_bwd_units = std::max(n_stage_bwd_units, int(hd.n_units));
+		n_stage_bwd_levels = std::max(n_stage_bwd_levels, int(hd.n_levels));
+		for(size_t o = 0; o < bcols.size(); ++ o)
+			n_stage_bwd_blocks = std::max(n_stage_bwd_blocks, int(bcols[o].nb));
+		TBwdLaunch &r_cfg = L.bwd_cfg[s];
+		r_cfg.n_cap_units = std::max(r_cfg.n_cap_units, hd.n_units);
+		r_cfg.n_waves = std::max(r_cfg.n_waves, (hd.n_cols + r_cfg.n_cols_per_wave - 1) / r_cfg.n_cols_per_wave);
+		const size_t n_at = R.bwd_rec.size();
+		R.bwd_rec.resize(n_at + size_t(hd.n_units), longlong2{0, 0});
+		char *p_dst = reinterpret_cast<char*>(&R.bwd_rec[n_at]);
+		memcpy(p_dst, &hd, sizeof(hd));
+		memcpy(p_dst + 64, bcols.data(), bcols.size() * sizeof(TBwdCol));
+		if(!bblks.empty())
+			memcpy(p_dst + 64 + bcols.size() * sizeof(TBwdCol), bblks.data(), bblks.size() * sizeof(TBwdBlk));
+		R.bwd_off.push_back(int64_t(n_at) | (int64_t(hd.n_units) << BWD_OFF_BITS));
+	}
+
 	// the hand-up lists of the stage below (its packages exist already: the lists go behind this stage's, the heads are told)
 	void Write_Hand_Up_Lists()
 	{
@@ -623,6 +695,9 @@ bool b_Panel_Pass(const Plan &P, const SparseRecordOptions &t_opt, SparseRecords
 	R.panel_off.clear();
 	R.panel_out_off.clear();
 	R.panel_units.clear();
+	R.bwd_rec.clear();
+	R.bwd_off.clear();
+	L.bwd_cfg.clear();
 	R.n_handup_doubles = 0;
 	R.panel_rest.clear();
 	R.upd_slots.clear();
@@ -653,7 +728,7 @@ bool b_Panel_Pass(const Plan &P, const SparseRecordOptions &t_opt, SparseRecords
 void Sort_Launch_Order(SparseRecords &R, const SparseLaunchLists &L)
 {
 	std::vector<int32_t> order;
-	std::vector<int64_t> off_sorted, out_off_sorted;
+	std::vector<int64_t> off_sorted, out_off_sorted, bwd_off_sorted;
 	for(size_t st = 0; st + 1 < L.panel_ptr.size(); ++ st) {
 		const int32_t n_first = L.panel_ptr[st], n_num = L.panel_ptr[st + 1] - n_first;
 		if(n_num < 2)
@@ -664,12 +739,15 @@ void Sort_Launch_Order(SparseRecords &R, const SparseLaunchLists &L)
 		std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return R.panel_units[size_t(a)] > R.panel_units[size_t(b)]; });
 		off_sorted.resize(size_t(n_num));
 		out_off_sorted.resize(size_t(n_num));
+		bwd_off_sorted.resize(size_t(n_num));
 		for(int32_t i = 0; i < n_num; ++ i) {
 			off_sorted[size_t(i)] = R.panel_off[size_t(order[size_t(i)])];
 			out_off_sorted[size_t(i)] = R.panel_out_off[size_t(order[size_t(i)])];
+			bwd_off_sorted[size_t(i)] = R.bwd_off[size_t(order[size_t(i)])];
 		}
 		std::copy(off_sorted.begin(), off_sorted.end(), R.panel_off.begin() + n_first);
 		std::copy(out_off_sorted.begin(), out_off_sorted.end(), R.panel_out_off.begin() + n_first);
+		std::copy(bwd_off_sorted.begin(), bwd_off_sorted.end(), R.bwd_off.begin() + n_first);
 	}
 }
 

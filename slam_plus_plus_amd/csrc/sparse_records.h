@@ -32,6 +32,7 @@ struct SparseLaunchLists {
 	// separator tasks that run as panels in LDS (panel_kernel.hip)
 	std::vector<int32_t> panel_ptr, panel_rest_ptr, panel_upd_ptr; // [n_stages + 1] ranges of the lists (empty: no panels)
 	std::vector<TPanelLaunch> panel_cfg; // [n_stages] waves per task and LDS capacities of the stage's panel launch
+	std::vector<TBwdLaunch> bwd_cfg;     // [n_stages] the shape of the stage's backward launch (backward_slice_kernel)
 	std::vector<char> panel_ride; // [n_stages + 1] the stage's updates from further down are applied inside the launch of the stage below (2: the tasks bring in everything themselves)
 	bool b_any_hand_up = false;
 	// lane-per-task kernels of the wide bottom stages (simt_kernel.hip)
@@ -54,6 +55,8 @@ struct SparseRecords {
 	std::vector<int64_t> panel_off, panel_out_off; // (panel_out_off: per package the offset of its hand-up list, or -1)
 	std::vector<int32_t> panel_units; // per package its size in 16-byte units: what the launch order of a stage goes by
 	std::vector<int32_t> panel_rest;  // the tasks of the panel stages left to the column kernel
+	raw_vector<longlong2> bwd_rec;    // backward records of the packaged tasks (TBwdHead ..)
+	std::vector<int64_t> bwd_off;     // per package (as panel_off) the offset of its backward record | its units << BWD_OFF_BITS
 	raw_vector<TUpdSlot> upd_slots;
 	raw_vector<TUpdEnt> upd_ents;
 	int64_t n_handup_doubles = 0;

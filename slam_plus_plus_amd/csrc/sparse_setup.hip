@@ -316,6 +316,9 @@ void slampp_hip_solver::Analyze_Sparse()
 	d_panel_out_off.Upload(rec.panel_out_off, stream);
 	d_handup.Alloc(size_t(std::max<int64_t>(rec.n_handup_doubles, int64_t(P.max_dim) * P.max_dim + 8))); // (every wave of a fused panel launch prefetches one block + 8 from offset 0, hand-ups or not)
 	d_panel_rest.Upload(rec.panel_rest, stream);
+	n_lds_limit = plain_launch_lds_limit();
+	d_bwd_rec.Upload(rec.bwd_rec, stream);
+	d_bwd_off.Upload(rec.bwd_off, stream);
 	if(t_upload_thread.t.joinable())
 		t_upload_thread.t.join();
 	if(p_upload_error)
