@@ -123,6 +123,42 @@ protected:
 		}
 	}
 
+	/** @brief the upper pairs (a <= b, column by column) of a set of distinct block columns, for Joint_Marginal() */
+	static void Joint_Marginal_Pairs(std::vector<std::pair<size_t, size_t> > &r_pairs, const std::vector<size_t> &r_block_columns,
+		const char *p_s_who) // throw(std::bad_alloc, std::runtime_error)
+	{
+		std::vector<size_t> sorted(r_block_columns);
+		std::sort(sorted.begin(), sorted.end());
+		if(sorted.empty() || std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+			throw std::runtime_error(std::string(p_s_who) + ": an empty set of block columns, or one listed twice");
+		r_pairs.clear();
+		for(size_t b = 0; b < r_block_columns.size(); ++ b) {
+			for(size_t a = 0; a <= b; ++ a)
+				r_pairs.push_back(std::make_pair(r_block_columns[a], r_block_columns[b]));
+		}
+	}
+
+	/** @brief the joint marginal from the blocks at those pairs: the upper blocks and their mirror images */
+	static void Joint_Marginal_Fill(Eigen::MatrixXd &r_joint, const CUberBlockMatrix &r_lambda,
+		const std::vector<size_t> &r_block_columns, const std::vector<Eigen::MatrixXd> &r_blocks) // throw(std::bad_alloc)
+	{
+		std::vector<size_t> off(r_block_columns.size() + 1, 0);
+		for(size_t a = 0; a < r_block_columns.size(); ++ a)
+			off[a + 1] = off[a] + r_lambda.n_BlockColumn_Column_Num(r_block_columns[a]);
+		r_joint.resize(off.back(), off.back());
+		for(size_t b = 0, k = 0; b < r_block_columns.size(); ++ b) {
+			for(size_t a = 0; a <= b; ++ a, ++ k) {
+				r_joint.block(off[a], off[b], off[a + 1] - off[a], off[b + 1] - off[b]) = r_blocks[k];
+				if(a != b)
+					r_joint.block(off[b], off[a], off[b + 1] - off[b], off[a + 1] - off[a]) = r_blocks[k].transpose();
+			}
+		}
+		for(size_t c = 0; c < size_t(r_joint.cols()); ++ c) { // (the diagonal blocks: the upper triangle mirrored, symmetric bit for bit)
+			for(size_t r = c + 1; r < size_t(r_joint.rows()); ++ r)
+				r_joint(r, c) = r_joint(c, r);
+		}
+	}
+
 	void Require_Handle() // throw(std::bad_alloc, std::runtime_error)
 	{
 		if(!m_p_solver) {
@@ -1020,33 +1056,12 @@ public:
 	bool Joint_Marginal(Eigen::MatrixXd &r_joint, const CUberBlockMatrix &r_lambda,
 		const std::vector<size_t> &r_block_columns) // throw(std::bad_alloc, std::runtime_error)
 	{
-		std::vector<size_t> sorted(r_block_columns);
-		std::sort(sorted.begin(), sorted.end());
-		if(sorted.empty() || std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
-			throw std::runtime_error("CLinearSolver_HIP::Joint_Marginal: an empty set of block columns, or one listed twice");
 		std::vector<std::pair<size_t, size_t> > pairs;
-		for(size_t b = 0; b < r_block_columns.size(); ++ b) {
-			for(size_t a = 0; a <= b; ++ a)
-				pairs.push_back(std::make_pair(r_block_columns[a], r_block_columns[b]));
-		}
+		Joint_Marginal_Pairs(pairs, r_block_columns, "CLinearSolver_HIP::Joint_Marginal");
 		std::vector<Eigen::MatrixXd> blocks;
 		if(!Marginal_Blocks(blocks, r_lambda, pairs))
 			return false;
-		std::vector<size_t> off(r_block_columns.size() + 1, 0);
-		for(size_t a = 0; a < r_block_columns.size(); ++ a)
-			off[a + 1] = off[a] + r_lambda.n_BlockColumn_Column_Num(r_block_columns[a]);
-		r_joint.resize(off.back(), off.back());
-		for(size_t b = 0, k = 0; b < r_block_columns.size(); ++ b) {
-			for(size_t a = 0; a <= b; ++ a, ++ k) {
-				r_joint.block(off[a], off[b], off[a + 1] - off[a], off[b + 1] - off[b]) = blocks[k];
-				if(a != b)
-					r_joint.block(off[b], off[a], off[b + 1] - off[b], off[a + 1] - off[a]) = blocks[k].transpose();
-			}
-		}
-		for(size_t c = 0; c < size_t(r_joint.cols()); ++ c) { // (the diagonal blocks: the upper triangle mirrored, symmetric bit for bit)
-			for(size_t r = c + 1; r < size_t(r_joint.rows()); ++ r)
-				r_joint(r, c) = r_joint(c, r);
-		}
+		Joint_Marginal_Fill(r_joint, r_lambda, r_block_columns, blocks);
 		return true;
 	}
 
@@ -1416,6 +1431,81 @@ public:
 		if(!Gather_For_Covariances(r_lambda))
 			return m_sparse_fallback.Marginal_Columns(r_columns, r_lambda, r_block_columns);
 		return Columns_Gathered(r_columns, r_lambda, std::vector<int64_t>(r_block_columns.begin(), r_block_columns.end()), false);
+	}
+
+	/**
+	 *	@brief calculates blocks of the covariance matrix (the inverse of lambda) of a BA system at arbitrary pairs of block
+	 *		columns, cameras and landmarks in any mix, inside lambda's pattern or outside it (slampp_hip_schur_marginal_blocks:
+	 *		no whole columns are formed)
+	 *
+	 *	@param[out] r_blocks is filled with one block per pair, in the listed order: block k has the rows of block column
+	 *		r_pairs[k].first and the columns of block column r_pairs[k].second of lambda
+	 *	@param[in] r_lambda is the system matrix (symmetric layout, upper triangle stored)
+	 *	@param[in] r_pairs lists the pairs (any order, first < second or not, repeats allowed)
+	 *
+	 *	@return Returns true on success, false if lambda is not positive definite.
+	 *	@note A lambda without a landmark part goes to the sparse solver, with the same result.
+	 *	@note This function throws std::bad_alloc and std::runtime_error.
+	 */
+	bool Marginal_Blocks(std::vector<Eigen::MatrixXd> &r_blocks, const CUberBlockMatrix &r_lambda,
+		const std::vector<std::pair<size_t, size_t> > &r_pairs) // throw(std::bad_alloc, std::runtime_error)
+	{
+		if(!Gather_For_Covariances(r_lambda))
+			return m_sparse_fallback.Marginal_Blocks(r_blocks, r_lambda, r_pairs);
+		const size_t n = r_lambda.n_BlockColumn_Num();
+		std::vector<size_t> inv_order(m_order.size());
+		for(size_t i = 0; i < m_order.size(); ++ i)
+			inv_order[m_order[i]] = i;
+		// the library's block (r', c') of a reordered lambda is lambda's own block (r, c), rows and columns as the caller
+		// names them: a pair the ordering turns around (r < c, r' > c') is one the library writes transposed itself
+		std::vector<int64_t> rows(r_pairs.size()), cols(r_pairs.size());
+		size_t n_out = 0;
+		for(size_t k = 0; k < r_pairs.size(); ++ k) {
+			const size_t r = r_pairs[k].first, c = r_pairs[k].second;
+			if(r >= n || c >= n)
+				throw std::runtime_error("CLinearSolver_Schur_HIP::Marginal_Blocks: block column index out of range");
+			rows[k] = int64_t(m_order.empty()? r : inv_order[r]);
+			cols[k] = int64_t(m_order.empty()? c : inv_order[c]);
+			n_out += r_lambda.n_BlockColumn_Column_Num(r) * r_lambda.n_BlockColumn_Column_Num(c);
+		}
+		std::vector<double> flat(std::max(n_out, size_t(1)));
+		const int n_result = slampp_hip_schur_marginal_blocks(m_p_solver, m_p_values, int64_t(r_pairs.size()),
+			rows.empty()? 0 : &rows[0], cols.empty()? 0 : &cols[0], &flat[0]);
+		if(n_result == SLAMPP_HIP_NOT_POSDEF)
+			return false;
+		Throw_On_Error(n_result);
+		r_blocks.resize(r_pairs.size());
+		const double *p_src = &flat[0];
+		for(size_t k = 0; k < r_pairs.size(); ++ k) {
+			const size_t dr = r_lambda.n_BlockColumn_Column_Num(r_pairs[k].first), dc = r_lambda.n_BlockColumn_Column_Num(r_pairs[k].second);
+			r_blocks[k] = Eigen::Map<const Eigen::MatrixXd>(p_src, dr, dc); // (column-major, as the library writes it)
+			p_src += dr * dc;
+		}
+		return true;
+	}
+
+	/**
+	 *	@brief calculates the joint marginal covariance of a set of block columns of a BA system, cameras and landmarks in
+	 *		any mix: the dense symmetric matrix of the blocks of the inverse of lambda at every pair of them (the upper pairs
+	 *		are computed and mirrored)
+	 *
+	 *	@param[out] r_joint is filled with k x k values, k = the sum of the listed columns' widths, in the listed order
+	 *	@param[in] r_lambda is the system matrix (symmetric layout, upper triangle stored)
+	 *	@param[in] r_block_columns lists distinct block column indices of lambda (at least one)
+	 *
+	 *	@return Returns true on success, false if lambda is not positive definite.
+	 *	@note This function throws std::bad_alloc and std::runtime_error.
+	 */
+	bool Joint_Marginal(Eigen::MatrixXd &r_joint, const CUberBlockMatrix &r_lambda,
+		const std::vector<size_t> &r_block_columns) // throw(std::bad_alloc, std::runtime_error)
+	{
+		std::vector<std::pair<size_t, size_t> > pairs;
+		Joint_Marginal_Pairs(pairs, r_block_columns, "CLinearSolver_Schur_HIP::Joint_Marginal");
+		std::vector<Eigen::MatrixXd> blocks;
+		if(!Marginal_Blocks(blocks, r_lambda, pairs))
+			return false;
+		Joint_Marginal_Fill(r_joint, r_lambda, r_block_columns, blocks);
+		return true;
 	}
 
 protected:

@@ -428,7 +428,8 @@ int slampp_hip_schur_marginals_device_async(slampp_hip_solver *p_solver, const d
  * -W_p^T Z(cams(p), c) on every landmark p; a landmark column is -Z W E_p on the cameras, then the same per landmark plus
  * C_p^-1 on its own block.  Passes of at most 48 scalar columns: the camera part is gathered from the dense inverse of S, or
  * solved by multi-right-hand-side substitutions with S's sparse factor; the landmark rows follow per landmark.
- * p_values = NULL (either call): the factor of S, C^-1 and W left by the previous call of these two on this handle are
+ * p_values = NULL (either call): the factor of S, C^-1 and W left by the previous call of these two (or of
+ * slampp_hip_schur_marginal_blocks) on this handle are
  * used; SLAMPP_HIP_ERR_INVALID if any other factorization ran since (a solve, schur_marginals, marginal poses, a batch) or if
  * that one was not positive definite.  Both calls recompute C^-1 and W from the values given: a later incremental solve
  * (slampp_hip_schur_set_changed_points) rebuilds the reduced system.  A handle whose Schur analysis went to the sparse
@@ -441,6 +442,43 @@ int slampp_hip_schur_marginal_columns(slampp_hip_solver *p_solver, const double 
 	double *p_out);
 int slampp_hip_schur_marginal_columns_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, int n_cols,
 	const int64_t *p_bcols, double *p_out_dev);
+
+/* Schur mode: blocks of Lambda^-1 of a BA system at arbitrary pairs of block columns, in the layout of
+ * slampp_hip_marginal_blocks: the indices are block columns of slampp_hip_set_structure (cameras < n_matrix_cut, landmarks
+ * after), pair k gives the d_r x d_c block, column-major, and the blocks follow each other in p_out in the listed order.  The
+ * joint covariance of two cameras that share no landmark, of two landmarks, of a camera and a landmark it does not observe
+ * yet: none of these is in Lambda's pattern, and slampp_hip_schur_marginal_columns would form n_scalars x k doubles to read
+ * a few small blocks out of them.  With Lambda^-1 = [Z, -Z W; -W^T Z, C^-1 + W^T Z W] (the notation above):
+ *   camera a, camera b        Z(a, b)
+ *   camera a, landmark q      -sum over b in cams(q) of Z(a, b) W_{b,q}
+ *   landmark p, camera b      the transpose of the above
+ *   landmark p, landmark q    delta_pq C_p^-1 + sum over a in cams(p), b in cams(q) of W_{a,p}^T Z(a, b) W_{b,q}
+ * Two routes, decided as slampp_hip_schur_marginals decides (options "schur_sparse", "marginals_dense").  S inverted densely:
+ * one workgroup per pair sums its block from the dense inverse, its lanes striding over the camera pairs (a, b), the partial
+ * sums meeting by lane shuffles and LDS in a fixed order.  S factored by the sparse block path, S = P^T L L^T P: with
+ * Y_c = L^-1 P E_c for a camera column and Y_q = L^-1 P (-W E_q) for a landmark column all four cases are
+ *   Lambda^-1(r, c) = Y_r^T Y_c   (+ C_p^-1 when r = c = landmark p),
+ * Y nonzero on the union of the elimination-tree paths of the cameras behind the column: passes of at most 48 scalar
+ * right-hand sides (both columns of a pair in one pass, pairs taken in the listed order until the next would not fit), each
+ * the pruned forward substitution and a Gram kernel over the rows two such unions share; no backward substitution, no
+ * inverse of S, no n_scalars x k result.  Neither route uses atomics: the same call gives the same bits.
+ * Nothing is refused about the pairs themselves: r < c, r > c and r == c, cameras and landmarks in any mix, inside Lambda's
+ * pattern or outside it, a column in any number of pairs, a pair listed twice (each listing is computed); a pair and its
+ * twin (c, r) are exact transposes of each other.
+ * p_values = NULL: the factor of S (or its dense inverse), C^-1 and W left by the previous call of the Schur covariance
+ * family on this handle (slampp_hip_schur_marginals_pattern, _schur_marginal_columns or this one) are used,
+ * SLAMPP_HIP_ERR_INVALID under the conditions of slampp_hip_schur_marginal_columns; otherwise the values are factored first.
+ * The call leaves all of that in place: the other two calls with p_values = NULL and slampp_hip_solve_again_device_async are
+ * valid afterwards by the rules they state.  n_pairs <= 0, a null pointer, an index out of range: SLAMPP_HIP_ERR_INVALID,
+ * decided before anything is enqueued.  Sparse mode (use slampp_hip_marginal_blocks), several devices, landmark shards:
+ * SLAMPP_HIP_ERR_UNSUPPORTED.  A handle whose Schur analysis went to the sparse path (option "schur_fallback") answers as
+ * slampp_hip_marginal_blocks (same layout).  Returns SLAMPP_HIP_NOT_POSDEF as the solve does, and leaves nothing to reuse
+ * then.  The device version only enqueues, once its lists are built on the host; the host version brings the blocks back
+ * in one copy. */
+int slampp_hip_schur_marginal_blocks(slampp_hip_solver *p_solver, const double *p_values, int64_t n_pairs, const int64_t *p_brows,
+	const int64_t *p_bcols, double *p_out);
+int slampp_hip_schur_marginal_blocks_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, int64_t n_pairs,
+	const int64_t *p_brows, const int64_t *p_bcols, double *p_out_dev);
 
 /* enqueue-only variants for benchmarking / stream capture: no host synchronisation, no status
  * read-back; slampp_hip_sync() waits and returns OK / NOT_POSDEF / error for everything enqueued since the

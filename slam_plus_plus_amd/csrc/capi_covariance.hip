@@ -1,6 +1,6 @@
 // capi_covariance.hip -- the covariance entry points of the C ABI (include/slampp_hip.h): block-diagonal marginals, Lambda^-1 on
-// Lambda's pattern, whole block columns of it and its blocks at arbitrary pairs, in the sparse mode and (but for the pairs)
-// in the Schur mode, and the landmark-only solve
+// Lambda's pattern, whole block columns of it and its blocks at arbitrary pairs, in the sparse mode and in the Schur mode, and
+// the landmark-only solve
 #include "capi_util.h"
 #include "sparse_inverse.h"
 #include "covariance.h"
@@ -209,17 +209,19 @@ int columns_checks(slampp_hip_solver *p_solver, int n_cols, const int64_t *p_bco
 }
 
 // n_pairs pairs of block columns in range; the doubles of their blocks in *p_n_out
-int pairs_checks(slampp_hip_solver *p_solver, int64_t n_pairs, const int64_t *p_brows, const int64_t *p_bcols, size_t *p_n_out)
+int pairs_checks(slampp_hip_solver *p_solver, const char *p_s_name, int64_t n_pairs, const int64_t *p_brows, const int64_t *p_bcols,
+	size_t *p_n_out)
 {
 	slampp_hip_solver &s = *p_solver;
+	const std::string s_name(p_s_name);
 	if(n_pairs <= 0 || !p_brows || !p_bcols)
-		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_blocks: no pairs");
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, (s_name + ": no pairs").c_str());
 	const int64_t n_bcols = int64_t(s.cumsum.size()) - 1;
 	*p_n_out = 0;
 	for(int64_t k = 0; k < n_pairs; ++ k) {
 		const int64_t r = p_brows[k], c = p_bcols[k];
 		if(r < 0 || r >= n_bcols || c < 0 || c >= n_bcols)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_blocks: block column index out of range");
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, (s_name + ": block column index out of range").c_str());
 		*p_n_out += size_t((s.cumsum[size_t(r + 1)] - s.cumsum[size_t(r)]) * (s.cumsum[size_t(c + 1)] - s.cumsum[size_t(c)]));
 	}
 	return SLAMPP_HIP_OK;
@@ -234,7 +236,7 @@ int marginal_blocks_checks(slampp_hip_solver *p_solver, bool b_values, int64_t n
 		return n_result;
 	if(!p_out)
 		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_blocks: null pointer");
-	if((n_result = pairs_checks(p_solver, n_pairs, p_brows, p_bcols, p_n_out)) != SLAMPP_HIP_OK)
+	if((n_result = pairs_checks(p_solver, "marginal_blocks", n_pairs, p_brows, p_bcols, p_n_out)) != SLAMPP_HIP_OK)
 		return n_result;
 	if(!b_values && !p_solver->b_factored)
 		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "marginal_blocks: no valid factorization to reuse (values = NULL)");
@@ -609,6 +611,70 @@ int slampp_hip_schur_marginal_columns(slampp_hip_solver *p_solver, const double 
 		return n_result;
 	// (values = NULL for the groups behind the first: the generation check lets them through)
 	return marginal_columns_in_groups(p_solver, p_values != 0, n_cols, p_bcols, p_out, slampp_hip_schur_marginal_columns_device_async);
+}
+
+namespace {
+
+// what the two schur_marginal_blocks entry points check (inside guarded())
+int schur_marginal_blocks_checks(slampp_hip_solver *p_solver, bool b_values, int64_t n_pairs, const int64_t *p_brows,
+	const int64_t *p_bcols, const double *p_out, size_t *p_n_out, bool *p_b_fallback)
+{
+	int n_result = schur_cov_checks(p_solver, "schur_marginal_blocks", !b_values, p_b_fallback);
+	if(n_result != SLAMPP_HIP_OK)
+		return n_result;
+	if(!p_out)
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "schur_marginal_blocks: null pointer");
+	if((n_result = pairs_checks(p_solver, "schur_marginal_blocks", n_pairs, p_brows, p_bcols, p_n_out)) != SLAMPP_HIP_OK)
+		return n_result;
+	if(*p_b_fallback) // what slampp_hip_marginal_blocks checks
+		return covariance_checks(p_solver, "schur_marginal_blocks");
+	return SLAMPP_HIP_OK;
+}
+
+} // anonymous namespace
+
+int slampp_hip_schur_marginal_blocks_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, int64_t n_pairs,
+	const int64_t *p_brows, const int64_t *p_bcols, double *p_out_dev)
+{
+	return guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		bool b_fallback = false;
+		size_t n_out = 0;
+		const int n_result = schur_marginal_blocks_checks(p_solver, p_values_dev != 0, n_pairs, p_brows, p_bcols, p_out_dev, &n_out,
+			&b_fallback);
+		if(n_result != SLAMPP_HIP_OK)
+			return n_result;
+		if(b_fallback) { // what slampp_hip_marginal_blocks does
+			substitution_factor_enqueue(s, p_values_dev);
+			covariance_pairs_enqueue(s, n_pairs, p_brows, p_bcols, p_out_dev);
+		} else
+			schur_cov_pairs_enqueue(s, p_values_dev, n_pairs, p_brows, p_bcols, p_out_dev);
+		schur_cov_done(s, p_values_dev != 0, b_fallback);
+		return SLAMPP_HIP_OK;
+	});
+}
+
+int slampp_hip_schur_marginal_blocks(slampp_hip_solver *p_solver, const double *p_values, int64_t n_pairs, const int64_t *p_brows,
+	const int64_t *p_bcols, double *p_out)
+{
+	size_t n_out = 0;
+	return host_round_trip(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		bool b_fallback = false;
+		const int n_check = schur_marginal_blocks_checks(p_solver, p_values != 0, n_pairs, p_brows, p_bcols, p_out, &n_out, &b_fallback);
+		if(n_check != SLAMPP_HIP_OK)
+			return n_check;
+		s.d_cov.Alloc(n_out);
+		if(p_values) {
+			s.d_A.Alloc(size_t(s.n_values));
+			Upload_Values_And_Join(s, p_values);
+		}
+		return SLAMPP_HIP_OK;
+	}, [&](slampp_hip_solver &s) {
+		return slampp_hip_schur_marginal_blocks_device_async(p_solver, p_values? s.d_A.p() : 0, n_pairs, p_brows, p_bcols, s.d_cov.p());
+	}, true, [&](slampp_hip_solver &s) {
+		SLAMPP_HIP_CHECK(hipMemcpyAsync(p_out, s.d_cov.p(), n_out * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+	});
 }
 
 } // extern "C"

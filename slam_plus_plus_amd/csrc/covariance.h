@@ -9,6 +9,7 @@ struct slampp_hip_solver;
 namespace slampp {
 
 struct CCovariance;
+struct PairPlan;
 
 // scalar columns of one pass of slampp_hip_marginal_columns: the workspace is n_scalars x COV_K_PASS doubles.  48 = eight
 // 6 x 6 block columns (or six 8 x 8 ones) in one pass; a lane of a wave per right-hand side, 48 of its 64 lanes busy
@@ -33,6 +34,18 @@ void covariance_columns_enqueue(slampp_hip_solver &s, int n_cols, const int64_t 
 // rows the two elimination-tree paths share (pair_plan.h) in a fixed order.  p_out_dev: the d_r x d_c blocks, column-major,
 // one after the other in the listed order.  Throws.
 void covariance_pairs_enqueue(slampp_hip_solver &s, int64_t n_pairs, const int64_t *p_brows, const int64_t *p_bcols, double *p_out_dev);
+
+// The same for pairs of columns whose right-hand sides are given whole, in two steps.  covariance_pair_sets_plan: pair k is
+// (p_set_r[k], p_set_c[k]) of n_sets column sets, set i nonzero on the rows of the block columns p_set_src[p_set_ptr[i] ..
+// p_set_ptr[i + 1]) (new order) only and p_set_width[i] scalar right-hand sides wide (plan_pair_sets, pair_plan.h); plans the
+// passes, lists their forward substitutions and uploads every list of the call, enqueues no kernel.  The plan it returns
+// (valid until the next covariance call on s) says which sets each pass holds and in which lanes.
+// covariance_pair_sets_pass: pass n_pass of that plan, its right-hand sides in p_rhs_dev (the factor's permuted row order,
+// interleaved: row * kp + lane): the pruned forward substitution and the Gram products into p_out_dev at the offsets the
+// plan gives.  Throw.
+const PairPlan &covariance_pair_sets_plan(slampp_hip_solver &s, int64_t n_pairs, const int32_t *p_set_r, const int32_t *p_set_c,
+	int32_t n_sets, const int64_t *p_set_ptr, const int32_t *p_set_src, const int32_t *p_set_width);
+void covariance_pair_sets_pass(slampp_hip_solver &s, size_t n_pass, const double *p_rhs_dev, double *p_out_dev);
 
 // one pass of kp <= COV_K_PASS right-hand sides given whole: p_rhs_dev is n_scalars x kp in the factor's permuted row order,
 // interleaved (row * kp + column), nonzero on the rows of the block columns p_src_bcols[0 .. n_src) only (the pruned forward

@@ -21,6 +21,8 @@
 // no backward substitution and no n_scalars x k output.  The pairs are grouped into passes (pair_plan.cpp); a pass runs the
 // forward half above for its distinct columns, then one Gram kernel sums, for every pair, the products of the two columns'
 // lanes over the rows both paths share (the path from their lowest common ancestor to the root) and over the dense top.
+// The same runs on right-hand sides given whole, each nonzero on a set of source block columns (covariance_pair_sets_plan,
+// covariance_pair_sets_pass): the columns of a BA system over its reduced camera system (schur_covariance.hip).
 //
 // Workspace X: n_scalars x k, interleaved -- the k values of a scalar row next to each other (X[row * k + c]): a lane per
 // right-hand side then reads and writes a block's rows as whole contiguous lines (d x k doubles), where a column stride of
@@ -52,6 +54,17 @@ struct TCovFwd { // 40 B: one listed column of the pruned forward substitution
 	int32_t dpos;     // dense top: position in the dense system (the column's reduced right-hand side goes there), else -1
 	int32_t s;        // schedule index (the stamp goes there)
 };
+
+namespace {
+struct TCovLaunch {
+	int n_stage;       // -1: the dense-top columns
+	int seg0, seg1;
+};
+struct TCovPass {
+	int col0, kp;
+	std::vector<TCovLaunch> launches;
+};
+} // anonymous namespace
 
 struct CCovariance {
 	// pattern gather
@@ -85,6 +98,7 @@ struct CCovariance {
 	std::vector<TPairRow> pair_rows;
 	CDevArray<TPairRec> d_pairs;
 	CDevArray<TPairRow> d_pair_rows;
+	std::vector<TCovPass> set_passes; // covariance_pair_sets_plan: the forward substitution of every pass of pair_plan
 	~CCovariance() { if(ev_lists) (void)hipEventDestroy(ev_lists); }
 };
 
@@ -459,17 +473,6 @@ static void Setup_Columns(slampp_hip_solver &s, CCovariance &cv)
 	cv.b_columns = true;
 }
 
-namespace {
-struct TCovLaunch {
-	int n_stage;       // -1: the dense-top columns
-	int seg0, seg1;
-};
-struct TCovPass {
-	int col0, kp;
-	std::vector<TCovLaunch> launches;
-};
-} // anonymous namespace
-
 // The lists of one call are built before anything is enqueued and go up in one set of uploads: Lists_Begin(), List_Pass()
 // per pass, Lists_Upload().
 static void Lists_Begin(CCovariance &cv)
@@ -754,6 +757,12 @@ cov_gram_kernel(const TPairRec *__restrict__ pairs, int64_t pair0, const TPairRo
 	}
 }
 
+static void Gram_Enqueue(slampp_hip_solver &s, CCovariance &cv, const TPairPass &pass, int kp, double *p_out_dev)
+{
+	hipLaunchKernelGGL(cov_gram_kernel, dim3(unsigned(pass.pair1 - pass.pair0)), dim3(64 * COV_GRAM_WAVES), 0, s.stream,
+		cv.d_pairs.p(), pass.pair0, cv.d_pair_rows.p(), cv.d_X.p(), cv.d_Zb.p(), s.n_dense_dim, kp, p_out_dev);
+}
+
 void covariance_pairs_enqueue(slampp_hip_solver &s, int64_t n_pairs, const int64_t *p_brows, const int64_t *p_bcols, double *p_out_dev)
 {
 	const Plan &P = s.plan;
@@ -776,10 +785,40 @@ void covariance_pairs_enqueue(slampp_hip_solver &s, int64_t n_pairs, const int64
 	for(size_t p = 0; p < passes.size(); ++ p) {
 		const TPairPass &pass = pp.passes[p];
 		Forward_Enqueue(s, cv, passes[p], 0, pass.b_dense); // (no pair of the pass reaches the top: nobody reads d_Zb)
-		hipLaunchKernelGGL(cov_gram_kernel, dim3(unsigned(pass.pair1 - pass.pair0)), dim3(64 * COV_GRAM_WAVES), 0, s.stream,
-			cv.d_pairs.p(), pass.pair0, cv.d_pair_rows.p(), cv.d_X.p(), cv.d_Zb.p(), s.n_dense_dim, passes[p].kp, p_out_dev);
+		Gram_Enqueue(s, cv, pass, passes[p].kp, p_out_dev);
 	}
 	s.Phase_End();
+	SLAMPP_HIP_CHECK(hipGetLastError());
+}
+
+const PairPlan &covariance_pair_sets_plan(slampp_hip_solver &s, int64_t n_pairs, const int32_t *p_set_r, const int32_t *p_set_c,
+	int32_t n_sets, const int64_t *p_set_ptr, const int32_t *p_set_src, const int32_t *p_set_width)
+{
+	const Plan &P = s.plan;
+	CCovariance &cv = Covariance_State(s);
+	if(!cv.b_columns)
+		Setup_Columns(s, cv);
+	Lists_Begin(cv); // (before the pair records are touched: the previous call's uploads read them)
+	plan_pair_sets(P, cv.sched_pos, n_pairs, p_set_r, p_set_c, n_sets, p_set_ptr, p_set_src, p_set_width, COV_K_PASS, cv.pair_plan);
+	const PairPlan &pp = cv.pair_plan;
+	cv.pairs = pp.pairs;
+	cv.pair_rows = pp.rows;
+	cv.set_passes.assign(pp.passes.size(), TCovPass());
+	for(size_t p = 0; p < pp.passes.size(); ++ p) {
+		cv.set_passes[p].col0 = 0;
+		cv.set_passes[p].kp = pp.passes[p].kp;
+		List_Pass(cv, P, int(pp.passes[p].srcs.size()), pp.passes[p].srcs.data(), 0, cv.set_passes[p]);
+	}
+	Lists_Upload(s, cv);
+	return pp;
+}
+
+void covariance_pair_sets_pass(slampp_hip_solver &s, size_t n_pass, const double *p_rhs_dev, double *p_out_dev)
+{
+	CCovariance &cv = Covariance_State(s);
+	const TPairPass &pass = cv.pair_plan.passes.at(n_pass);
+	Forward_Enqueue(s, cv, cv.set_passes.at(n_pass), p_rhs_dev, pass.b_dense);
+	Gram_Enqueue(s, cv, pass, pass.kp, p_out_dev);
 	SLAMPP_HIP_CHECK(hipGetLastError());
 }
 

@@ -14,10 +14,12 @@
 // Z is read either from the dense inverse (dense_inverse.hip: lower triangle and diagonal 64 x 64 tiles valid, element
 // (i, j) read as (max, min)) or from the sparse inverse subset on the reduced system's factor pattern (sparse_inverse.hip:
 // where a block sits and whether it is stored transposed comes from host-built tables, schur_setup.hip).
-// This file holds the kernels, their launches (functions of the state, one dispatch on the block sizes each) and the two
-// entry points that drive them behind the reduced system's factorization: schur_cov_pattern_enqueue, schur_cov_columns_enqueue.
+// This file holds the kernels, their launches (functions of the state, one dispatch on the block sizes each) and the three
+// entry points that drive them behind the reduced system's factorization: schur_cov_pattern_enqueue, schur_cov_columns_enqueue,
+// schur_cov_pairs_enqueue.
 #include "schur_state.h"
 #include "covariance.h"
+#include "pair_plan.h"
 
 #include <algorithm>
 
@@ -74,6 +76,31 @@ __device__ __forceinline__ void cov_zw_acc(double (&t)[DC * DP], const double *_
 				for(int q = 0; q < DC; ++ q)
 					sum += zr[q] * w[q + j * DC];
 				t[r + j * DC] += sum;
+			}
+		}
+	}
+}
+
+// t += Z(ca, cb) w with Z the dense inverse (leading dimension ld): the block below the diagonal as it is, the one above
+// it from its mirror image, transposed, the diagonal block (max, min) element by element
+template <int DC, int DP>
+__device__ __forceinline__ void cov_zw_dense_acc(double (&t)[DC * DP], const double *__restrict__ Z, int ld, int64_t ca, int64_t cb,
+	const double (&wb)[DC * DP])
+{
+	if(ca > cb)
+		cov_zw_acc<DC, DP>(t, Z + size_t(ca * DC) + size_t(cb * DC) * ld, ld, false, wb);
+	else if(ca < cb)
+		cov_zw_acc<DC, DP>(t, Z + size_t(cb * DC) + size_t(ca * DC) * ld, ld, true, wb);
+	else {
+		#pragma unroll
+		for(int q = 0; q < DC; ++ q) {
+			#pragma unroll
+			for(int r = 0; r < DC; ++ r) {
+				const int h = (r > q)? r : q, m = (r > q)? q : r;
+				const double z = Z[size_t(ca * DC + h) + size_t(ca * DC + m) * ld];
+				#pragma unroll
+				for(int j = 0; j < DP; ++ j)
+					t[r + j * DC] += z * wb[q + j * DC];
 			}
 		}
 	}
@@ -147,24 +174,7 @@ schur_cov_point_pattern_kernel(const int64_t *__restrict__ ptr, const int32_t *_
 				const bool b_tr = ((ent & 1) != 0) != (a < b);
 				cov_zw_acc<DC, DP>(t, Z + (ent >> 1), DC, b_tr, wb);
 			} else {
-				const int64_t cb = brow[k0 + b];
-				if(ca > cb)
-					cov_zw_acc<DC, DP>(t, Z + size_t(ca * DC) + size_t(cb * DC) * ld, ld, false, wb);
-				else if(ca < cb)
-					cov_zw_acc<DC, DP>(t, Z + size_t(cb * DC) + size_t(ca * DC) * ld, ld, true, wb);
-				else { // the diagonal block: (max, min) element by element
-					#pragma unroll
-					for(int q = 0; q < DC; ++ q) {
-						#pragma unroll
-						for(int r = 0; r < DC; ++ r) {
-							const int h = (r > q)? r : q, m = (r > q)? q : r;
-							const double z = Z[size_t(ca * DC + h) + size_t(ca * DC + m) * ld];
-							#pragma unroll
-							for(int j = 0; j < DP; ++ j)
-								t[r + j * DC] += z * wb[q + j * DC];
-						}
-					}
-				}
+				cov_zw_dense_acc<DC, DP>(t, Z, ld, ca, brow[k0 + b], wb);
 			}
 		}
 		double *p_obs = out + ubase + (o0 + a) * (DC * DP) + pt * (DP * DP); // observation block (c_a, p), DC x DP
@@ -321,6 +331,129 @@ schur_cov_point_rows_kernel(int64_t nc, int64_t np, const int64_t *__restrict__ 
 		p_out[r] = acc[r];
 }
 
+// ---- blocks at arbitrary pairs ----
+// Lambda^-1(r, c) for r <= c (TSchurPairRec; the caller's (c, r) is the same block written transposed: exact twins):
+//   camera a, camera b        Z(a, b)
+//   camera a, landmark q      -sum over b in cams(q) of Z(a, b) W_{b,q}
+//   landmark p, landmark q    delta_pq C_p^-1 + sum over a in cams(p), b in cams(q) of W_{a,p}^T Z(a, b) W_{b,q}
+
+enum { COV_PAIR_WAVES = 4 };
+
+// C_p^-1 read as its upper triangle mirrored: a diagonal block comes out symmetric bit for bit
+template <int DP>
+__device__ __forceinline__ double cov_cinv_sym(const double *__restrict__ Cinv, int64_t p, int i, int j)
+{
+	return Cinv[p * (DP * DP) + ((i < j)? i : j) + ((i < j)? j : i) * DP];
+}
+
+// dense Z: one workgroup of COV_PAIR_WAVES waves per pair.  The lanes stride over the k_r k_c camera pairs (a, b) behind the
+// two columns (k = 1 for a camera), each adding its terms into a block of its own; the blocks meet by a butterfly of lane
+// shuffles inside a wave and through LDS across the waves, summed in wave order: no atomics, every entry in one fixed order.
+template <int DC, int DP>
+__global__ void __launch_bounds__(64 * COV_PAIR_WAVES)
+schur_cov_pairs_dense_kernel(const TSchurPairRec *__restrict__ recs, int64_t nc, const int64_t *__restrict__ ptr,
+	const int32_t *__restrict__ brow, const double *__restrict__ W, const double *__restrict__ Cinv, const double *__restrict__ Z,
+	int ld, double *__restrict__ out)
+{
+	constexpr int NA = DC * DP; // (the largest block with a landmark in it; DP x DP uses the first DP * DP)
+	__shared__ double s_part[COV_PAIR_WAVES][NA];
+	const TSchurPairRec rec = recs[blockIdx.x];
+	const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+	if(rec.kind == 0) { // two cameras: a gather, element (i, j) read as (max, min) of the inverse
+		if(tid < DC * DC) {
+			const int i = tid % DC, j = tid / DC;
+			const int64_t gi = int64_t(rec.r) * DC + i, gj = int64_t(rec.c) * DC + j;
+			const double z = Z[size_t(gi > gj? gi : gj) + size_t(gi > gj? gj : gi) * ld];
+			out[rec.out + (rec.b_tr? j + i * DC : tid)] = z;
+		}
+		return;
+	}
+	const bool b_ll = rec.kind == 3;
+	// the cameras behind the row (one camera, or those of landmark r) and behind the column (those of landmark c)
+	const int64_t kr0 = b_ll? ptr[nc + rec.r] : 0, kr = b_ll? ptr[nc + rec.r + 1] - kr0 - 1 : 1, or0 = kr0 - ptr[nc] - rec.r;
+	const int64_t kc0 = ptr[nc + rec.c], kc = ptr[nc + rec.c + 1] - kc0 - 1, oc0 = kc0 - ptr[nc] - rec.c;
+	double acc[NA];
+	#pragma unroll
+	for(int i = 0; i < NA; ++ i)
+		acc[i] = 0;
+	for(int64_t e = tid; e < kr * kc; e += 64 * COV_PAIR_WAVES) {
+		const int64_t a = e / kc, b = e - a * kc;
+		const int64_t ca = b_ll? int64_t(brow[kr0 + a]) : int64_t(rec.r), cb = brow[kc0 + b];
+		double wb[NA];
+		cov_load<NA>(wb, W + (oc0 + b) * NA);
+		if(!b_ll)
+			cov_zw_dense_acc<DC, DP>(acc, Z, ld, ca, cb, wb); // (negated at the end)
+		else {
+			double t[NA], wa[NA];
+			#pragma unroll
+			for(int i = 0; i < NA; ++ i)
+				t[i] = 0;
+			cov_zw_dense_acc<DC, DP>(t, Z, ld, ca, cb, wb);
+			cov_load<NA>(wa, W + (or0 + a) * NA);
+			#pragma unroll
+			for(int j = 0; j < DP; ++ j) {
+				#pragma unroll
+				for(int i = 0; i < DP; ++ i) {
+					double sum = 0;
+					#pragma unroll
+					for(int r = 0; r < DC; ++ r)
+						sum += wa[r + i * DC] * t[r + j * DC];
+					acc[i + j * DP] += sum;
+				}
+			}
+		}
+	}
+	#pragma unroll
+	for(int i = 0; i < NA; ++ i) {
+		#pragma unroll
+		for(int m = 32; m > 0; m >>= 1)
+			acc[i] += __shfl_xor(acc[i], m, 64);
+	}
+	if(lane == 0) {
+		#pragma unroll
+		for(int i = 0; i < NA; ++ i)
+			s_part[w][i] = acc[i];
+	}
+	__syncthreads();
+	const int d1 = b_ll? DP : DC; // the block is d1 x DP
+	if(tid < d1 * DP) {
+		int i = tid % d1, j = tid / d1;
+		const bool b_diag = b_ll && rec.r == rec.c;
+		if(b_diag && i > j) { // a diagonal block: its upper triangle, mirrored
+			const int t = i;
+			i = j;
+			j = t;
+		}
+		double sum = s_part[0][i + j * d1];
+		#pragma unroll
+		for(int v = 1; v < COV_PAIR_WAVES; ++ v)
+			sum += s_part[v][i + j * d1];
+		if(!b_ll)
+			sum = -sum;
+		else if(b_diag)
+			sum += cov_cinv_sym<DP>(Cinv, rec.r, i, j);
+		i = tid % d1;
+		j = tid / d1;
+		out[rec.out + (rec.b_tr? j + i * DP : tid)] = sum;
+	}
+}
+
+// sparse factor: behind the Gram products of a pass, C_p^-1 onto the blocks of its pairs (p, p); a thread per entry
+template <int DP>
+__global__ void __launch_bounds__(256)
+schur_cov_pairs_diag_kernel(const TSchurPairRec *__restrict__ recs, int64_t n_recs, const double *__restrict__ Cinv, double *out)
+{
+	const int64_t gid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+	const int64_t k = gid / (DP * DP);
+	if(k >= n_recs)
+		return;
+	const TSchurPairRec rec = recs[k];
+	if(rec.kind != 3 || rec.r != rec.c)
+		return;
+	const int e = int(gid - k * (DP * DP));
+	out[rec.out + e] += cov_cinv_sym<DP>(Cinv, rec.r, e % DP, e / DP);
+}
+
 // ---- launches: Z is the sparse inverse subset in d_m_Zs (S.b_cov_sparse) or the dense inverse in d_m_Z ----
 
 static void schur_cov_pattern_gather(CSchurState &S, double *out, hipStream_t stream)
@@ -414,6 +547,30 @@ static void schur_cov_factor(slampp_hip_solver &s, CSchurState &S, const double 
 	}
 }
 
+// The host tables of one call (column tables, pair records) go up in one set of uploads out of the host vectors the call
+// before the previous one used: its uploads have long completed, so the host does not wait for the device.  Begin: which
+// of the two sets, emptied; upload: stream-ordered behind the previous call's kernels, which read the old tables.
+static int schur_cov_tables_begin(CSchurState &S)
+{
+	const int n_buf = (S.n_cov_call ++) & 1;
+	if(S.ev_cov_cols[n_buf])
+		SLAMPP_HIP_CHECK(hipEventSynchronize(S.ev_cov_cols[n_buf]));
+	S.h_cov_cols[n_buf].clear();
+	S.h_cov_pairs[n_buf].clear();
+	return n_buf;
+}
+
+static void schur_cov_tables_upload(CSchurState &S, int n_buf, hipStream_t st)
+{
+	if(!S.h_cov_cols[n_buf].empty())
+		S.d_cov_cols.Upload(S.h_cov_cols[n_buf], st);
+	if(!S.h_cov_pairs[n_buf].empty())
+		S.d_cov_pairs.Upload(S.h_cov_pairs[n_buf], st);
+	if(!S.ev_cov_cols[n_buf])
+		SLAMPP_HIP_CHECK(hipEventCreateWithFlags(&S.ev_cov_cols[n_buf], hipEventDisableTiming));
+	SLAMPP_HIP_CHECK(hipEventRecord(S.ev_cov_cols[n_buf], st));
+}
+
 void schur_cov_pattern_enqueue(slampp_hip_solver &s, const double *p_values_dev, double *p_cov_dev)
 {
 	CSchurState &S = *s.p_schur;
@@ -443,11 +600,8 @@ void schur_cov_columns_enqueue(slampp_hip_solver &s, const double *A, int n_cols
 	const int32_t *brow = s.brow.data();
 	// the column tables of every pass, one upload out of the host vector the call before the previous one used: its upload
 	// has long completed, so the host does not wait for the device here
-	const int n_buf = (S.n_cov_call ++) & 1;
+	const int n_buf = schur_cov_tables_begin(S);
 	std::vector<int64_t> &h_cols = S.h_cov_cols[n_buf];
-	if(S.ev_cov_cols[n_buf])
-		SLAMPP_HIP_CHECK(hipEventSynchronize(S.ev_cov_cols[n_buf]));
-	h_cols.clear();
 	std::vector<int> pass_first; // first listed column of every pass
 	int64_t n_pass_k = COV_K_PASS;
 	for(int i = 0; i < n_cols; ++ i) {
@@ -461,10 +615,7 @@ void schur_cov_columns_enqueue(slampp_hip_solver &s, const double *A, int n_cols
 			h_cols.push_back((c < nc)? c * DC + e : -1 - ((c - nc) * DP + e));
 	}
 	pass_first.push_back(n_cols);
-	S.d_cov_cols.Upload(h_cols, st); // (stream-ordered behind the previous call's kernels, which read the old tables)
-	if(!S.ev_cov_cols[n_buf])
-		SLAMPP_HIP_CHECK(hipEventCreateWithFlags(&S.ev_cov_cols[n_buf], hipEventDisableTiming));
-	SLAMPP_HIP_CHECK(hipEventRecord(S.ev_cov_cols[n_buf], st));
+	schur_cov_tables_upload(S, n_buf, st);
 	S.d_cov_X.Alloc(size_t(nc * DC) * COV_K_PASS);
 	if(S.b_cov_sparse) {
 		S.d_cov_B.Alloc(size_t(nc * DC) * COV_K_PASS);
@@ -499,6 +650,114 @@ void schur_cov_columns_enqueue(slampp_hip_solver &s, const double *A, int n_cols
 			schur_cov_cols_cam_launch(S, p_cols, kp, col0, out, n_ld, st);
 		schur_cov_cols_point_launch(S, p_cols, kp, col0, out, n_ld, st);
 		col0 += kp;
+	}
+	s.Phase_End();
+	SLAMPP_HIP_CHECK(hipGetLastError());
+}
+
+// Blocks at arbitrary pairs.  Dense reduced system: one launch over the pair records, each block summed from the dense
+// inverse (schur_cov_pairs_dense_kernel).  Sparse: Lambda^-1(r, c) = Y_r^T Y_c (+ C_p^-1 for r = c = landmark p) with
+// Y = L^-1 P E_c for a camera column and L^-1 P (-W E_q) for a landmark column -- passes of at most COV_K_PASS right-hand
+// sides (both columns of a pair in one pass), each the right-hand sides, the pruned forward substitution of the reduced
+// system's factor from the cameras behind the pass's columns and the Gram products over the rows two reaches share
+// (covariance.hip, pair_plan.h); no backward substitution, no inverse of the reduced system, no n_scalars x k result.
+void schur_cov_pairs_enqueue(slampp_hip_solver &s, const double *A, int64_t n_pairs, const int64_t *p_brows, const int64_t *p_bcols,
+	double *out)
+{
+	CSchurState &S = *s.p_schur;
+	if(A)
+		schur_invalidate_previous(&S);
+	hipStream_t st = s.stream;
+	schur_cov_factor(s, S, A, false);
+	const int DC = S.DC, DP = S.DP;
+	const int64_t nc = S.nc;
+	const int64_t *ptr = s.bcol_ptr.data();
+	const int32_t *brow = s.brow.data();
+	const int n_buf = schur_cov_tables_begin(S);
+	std::vector<TSchurPairRec> &h_pairs = S.h_cov_pairs[n_buf];
+	std::vector<int64_t> &h_cols = S.h_cov_cols[n_buf];
+	h_pairs.resize(size_t(n_pairs));
+	int64_t n_out = 0;
+	for(int64_t k = 0; k < n_pairs; ++ k) {
+		const int64_t r = std::min(p_brows[k], p_bcols[k]), c = std::max(p_brows[k], p_bcols[k]);
+		TSchurPairRec &rec = h_pairs[size_t(k)];
+		rec.out = n_out;
+		rec.r = int32_t((r < nc)? r : r - nc);
+		rec.c = int32_t((c < nc)? c : c - nc);
+		rec.kind = ((r < nc)? 0 : 1) | ((c < nc)? 0 : 2);
+		rec.b_tr = p_brows[k] > p_bcols[k];
+		n_out += int64_t((r < nc)? DC : DP) * ((c < nc)? DC : DP);
+	}
+	if(!S.b_cov_sparse) {
+		schur_cov_tables_upload(S, n_buf, st);
+		s.Phase_Begin("marginal_blocks");
+		schur_dispatch(DC, DP, [&](auto dc, auto dp) {
+			hipLaunchKernelGGL((schur_cov_pairs_dense_kernel<dc(), dp()>), dim3(unsigned(n_pairs)), dim3(64 * COV_PAIR_WAVES), 0, st,
+				S.d_cov_pairs.p(), nc, S.d_ptr.p(), S.d_brow.p(), S.d_W.p(), S.d_Cinv.p(), S.d_m_Z.p(), S.Npad, out);
+		});
+		s.Phase_End();
+		SLAMPP_HIP_CHECK(hipGetLastError());
+		return;
+	}
+	// the distinct columns of the call as sets of cameras of the reduced system: a camera itself, a landmark's observers
+	const Plan &P = S.p_inner->plan;
+	std::vector<int64_t> ids(size_t(n_pairs) * 2);
+	for(int64_t k = 0; k < n_pairs; ++ k) {
+		ids[size_t(2 * k)] = p_brows[k];
+		ids[size_t(2 * k + 1)] = p_bcols[k];
+	}
+	std::vector<int64_t> sets(ids);
+	std::sort(sets.begin(), sets.end());
+	sets.erase(std::unique(sets.begin(), sets.end()), sets.end());
+	const int32_t n_sets = int32_t(sets.size());
+	std::vector<int64_t> set_ptr(size_t(n_sets) + 1, 0);
+	std::vector<int32_t> set_src, set_width(size_t(n_sets), 0), set_r(size_t(n_pairs), 0), set_c(size_t(n_pairs), 0);
+	for(int32_t i = 0; i < n_sets; ++ i) {
+		const int64_t c = sets[size_t(i)];
+		set_width[size_t(i)] = (c < nc)? DC : DP;
+		if(c < nc)
+			set_src.push_back(P.pinv[size_t(c)]);
+		else {
+			for(int64_t k = ptr[c]; k < ptr[c + 1] - 1; ++ k)
+				set_src.push_back(P.pinv[size_t(brow[k])]);
+		}
+		set_ptr[size_t(i) + 1] = int64_t(set_src.size());
+	}
+	for(int64_t k = 0; k < n_pairs; ++ k) {
+		// (the row of the Gram product is the caller's row: Y_r^T Y_c and Y_c^T Y_r are exact transposes of each other)
+		set_r[size_t(k)] = int32_t(std::lower_bound(sets.begin(), sets.end(), ids[size_t(2 * k)]) - sets.begin());
+		set_c[size_t(k)] = int32_t(std::lower_bound(sets.begin(), sets.end(), ids[size_t(2 * k + 1)]) - sets.begin());
+	}
+	S.p_inner->Ensure_Leaf_Inverses(); // (the substitutions multiply by inv(L_jj) of every column)
+	const PairPlan &pp = covariance_pair_sets_plan(*S.p_inner, n_pairs, set_r.data(), set_c.data(), n_sets, set_ptr.data(),
+		set_src.data(), set_width.data());
+	std::vector<int64_t> pass_col0(pp.passes.size(), 0); // the column tables of every pass, one after the other
+	for(size_t p = 0; p < pp.passes.size(); ++ p) {
+		const TPairPass &pass = pp.passes[p];
+		pass_col0[p] = int64_t(h_cols.size());
+		for(size_t i = 0; i < pass.cols.size(); ++ i) { // (in lane order)
+			const int64_t c = sets[size_t(pass.cols[i])], d = (c < nc)? DC : DP;
+			for(int64_t e = 0; e < d; ++ e)
+				h_cols.push_back((c < nc)? c * DC + e : -1 - ((c - nc) * DP + e));
+		}
+	}
+	schur_cov_tables_upload(S, n_buf, st);
+	S.d_cov_B.Alloc(size_t(nc * DC) * COV_K_PASS);
+	s.Phase_Begin("marginal_blocks");
+	for(size_t p = 0; p < pp.passes.size(); ++ p) {
+		const TPairPass &pass = pp.passes[p];
+		const int kp = pass.kp;
+		SLAMPP_HIP_CHECK(hipMemsetAsync(S.d_cov_B.p(), 0, size_t(nc * DC) * kp * sizeof(double), st));
+		schur_dispatch(DC, DP, [&](auto dc, auto dp) {
+			hipLaunchKernelGGL((schur_cov_rhs_kernel<dc(), dp()>), dim3(unsigned(kp)), dim3(64), 0, st, nc, S.d_ptr.p(), S.d_brow.p(),
+				S.d_W.p(), S.d_cam_csn.p(), S.d_cov_cols.p() + pass_col0[p], kp, S.d_cov_B.p());
+		});
+		covariance_pair_sets_pass(*S.p_inner, p, S.d_cov_B.p(), out);
+		const int64_t n_recs = pass.pair1 - pass.pair0;
+		schur_dispatch(DC, DP, [&](auto, auto dp) {
+			hipLaunchKernelGGL(schur_cov_pairs_diag_kernel<dp()>, dim3(unsigned((n_recs * (dp() * dp()) + 255) / 256)), dim3(256), 0, st,
+				S.d_cov_pairs.p() + pass.pair0, n_recs, S.d_Cinv.p(), out);
+		});
 	}
 	s.Phase_End();
 	SLAMPP_HIP_CHECK(hipGetLastError());

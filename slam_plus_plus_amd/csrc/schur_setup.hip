@@ -48,7 +48,7 @@ size_t schur_device_bytes(const CSchurState *p)
 		p->d_pair_ptr.n_Bytes() + p->d_pair_tab.n_Bytes() + sparse_inverse_bytes(p->p_sinv) +
 		p->d_Cinv.n_Bytes() + p->d_t.n_Bytes() + p->d_invdiag.n_Bytes() + p->d_z.n_Bytes() + p->d_x.n_Bytes() +
 		p->d_A_prev.n_Bytes() + p->d_S_unf.n_Bytes() + p->d_changed.n_Bytes() + p->tiles.n_Bytes() + p->d_a_zent.n_Bytes() +
-		p->d_cam_csn.n_Bytes() + p->d_cov_cols.n_Bytes() + p->d_cov_B.n_Bytes() + p->d_cov_X.n_Bytes();
+		p->d_cam_csn.n_Bytes() + p->d_cov_cols.n_Bytes() + p->d_cov_B.n_Bytes() + p->d_cov_X.n_Bytes() + p->d_cov_pairs.n_Bytes();
 }
 
 void schur_invalidate_previous(CSchurState *p)

@@ -11,6 +11,13 @@
 
 namespace slampp {
 
+struct TSchurPairRec { // 24 B: one pair of slampp_hip_schur_marginal_blocks, r <= c in the caller's block columns
+	int64_t out;    // offset of its block in the output
+	int32_t r, c;   // camera index, or landmark index (0-based among the landmarks)
+	int32_t kind;   // bit 0: r is a landmark, bit 1: c is one (a camera and a landmark: the camera is r)
+	int32_t b_tr;   // the caller listed (c, r): the block is written transposed
+};
+
 struct CSchurState {
 	int DC, DP;
 	int64_t nc, np, n_obs, n_ablocks, n_sblocks, n_entries;
@@ -66,6 +73,8 @@ struct CSchurState {
 	std::vector<int64_t> h_cov_cols[2];        // the column tables of the last two calls (alternately)
 	hipEvent_t ev_cov_cols[2] = {0, 0};        // recorded behind the uploads out of them
 	int n_cov_call = 0;
+	std::vector<TSchurPairRec> h_cov_pairs[2]; // the pair records of the last two calls, beside the column tables
+	CDevArray<TSchurPairRec> d_cov_pairs;
 	CSchurState() :p_union_fn(0), p_union_context(0), b_union_dense(false), n_union(0), b_reduced_decided(false),
 		b_reduced_sparse(false), p_inner(0), n_in_blocks(0), p_sinv(0), b_sinv_tried(false) {}
 	~CSchurState();

@@ -370,6 +370,9 @@ void schur_enqueue_marginals(slampp_hip_solver &s, const double *p_values_dev, d
 // of these calls left in place (the caller checks that it is still valid).  Throw.
 void schur_cov_pattern_enqueue(slampp_hip_solver &s, const double *p_values_dev, double *p_cov_dev);
 void schur_cov_columns_enqueue(slampp_hip_solver &s, const double *p_values_dev, int n_cols, const int64_t *p_bcols, double *p_out_dev);
+// ... and its blocks at arbitrary pairs of block columns (in range: the caller checks), one after the other in the listed order
+void schur_cov_pairs_enqueue(slampp_hip_solver &s, const double *p_values_dev, int64_t n_pairs, const int64_t *p_brows,
+	const int64_t *p_bcols, double *p_out_dev);
 size_t schur_device_bytes(const CSchurState *p);
 void schur_invalidate_previous(CSchurState *p); // the kept reduced system no longer matches what the caller last solved
 void schur_set_changed_points(slampp_hip_solver &s, const int64_t *p_points, int64_t n_points); // throws

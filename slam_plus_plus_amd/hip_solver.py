@@ -143,6 +143,8 @@ ABI = {
     "slampp_hip_schur_marginals_pattern_device_async": (C.c_int, [_P, _P, _P]),
     "slampp_hip_schur_marginal_columns": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "slampp_hip_schur_marginal_columns_device_async": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "slampp_hip_schur_marginal_blocks": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
+    "slampp_hip_schur_marginal_blocks_device_async": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
     "slampp_hip_factor_solve_device_async": (C.c_int, [_P, _P, _P]),
     "slampp_hip_sync": (C.c_int, [_P]),
     "slampp_hip_factor_solve_batch_device_async": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64]),
@@ -695,9 +697,14 @@ CLinearSolver_HIP.Marginal_Columns = _marginal_columns
 
 def _marginal_blocks(self, lam, pairs, reuse_factor: bool = False) -> list:
     """Blocks of Lambda^-1 at arbitrary pairs ``(r, c)`` of block columns, inside Lambda's pattern or outside it: a list
-    of d_r x d_c arrays in the listed order (what g2o's computeMarginals(spinv, blockIndices) answers).  Forward
-    substitutions over the two columns' elimination-tree paths only (slampp_hip_marginal_blocks): no whole columns are
-    formed.  ``reuse_factor``: as for Marginal_Columns."""
+    of d_r x d_c arrays in the listed order (what g2o's computeMarginals(spinv, blockIndices) answers).  No whole columns
+    are formed.  ``reuse_factor``: as for the class's Marginal_Columns.
+    CLinearSolver_HIP (slampp_hip_marginal_blocks): forward substitutions over the two columns' elimination-tree paths.
+    CLinearSolver_Schur_HIP (slampp_hip_schur_marginal_blocks): cameras and landmarks in any mix -- two cameras that share
+    no landmark, two landmarks, a camera and a landmark it does not observe; each block is summed from the dense inverse of
+    the reduced camera system S, or from forward substitutions on S's sparse factor over the paths of the cameras behind
+    the two columns.  ``reuse_factor``: what the previous Marginals_Pattern / Marginal_Columns / Marginal_Blocks call left.
+    A handle whose analysis went to the sparse path answers through it."""
     pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
     rows, cols = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
     if reuse_factor:
@@ -715,8 +722,8 @@ def _marginal_blocks(self, lam, pairs, reuse_factor: bool = False) -> list:
     sizes = dims[rows] * dims[cols] if in_range else np.zeros(0, dtype=np.int64)
     off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
     flat = np.empty(max(int(off[-1]), 1), dtype=np.float64)
-    if not self._check(self._lib.slampp_hip_marginal_blocks(self._h, _ptr(vals) if vals is not None else None, int(rows.size),
-                                                            _ptr(rows), _ptr(cols), _ptr(flat))):
+    if not self._check(getattr(self._lib, self._marginal_blocks_entry)(self._h, _ptr(vals) if vals is not None else None,
+                                                                       int(rows.size), _ptr(rows), _ptr(cols), _ptr(flat))):
         raise ArithmeticError("Marginal_Blocks: the system is not positive definite")
     return [flat[off[k]:off[k + 1]].reshape(int(dims[cols[k]]), int(dims[rows[k]])).T.copy() for k in range(rows.size)]
 
@@ -724,7 +731,8 @@ def _marginal_blocks(self, lam, pairs, reuse_factor: bool = False) -> list:
 def _joint_marginal(self, lam, bcols, reuse_factor: bool = False) -> np.ndarray:
     """The joint marginal covariance of the block columns ``bcols`` (distinct, at least one): the dense symmetric k x k
     matrix of Lambda^-1 at every pair of them, k = the sum of their dimensions, in the listed order (GTSAM's
-    jointMarginalCovariance).  The upper pairs are computed (Marginal_Blocks) and mirrored."""
+    jointMarginalCovariance).  The upper pairs are computed (the class's Marginal_Blocks: in Schur mode the columns may be
+    cameras and landmarks in any mix) and mirrored."""
     cols = [int(c) for c in np.atleast_1d(np.asarray(bcols, dtype=np.int64))]
     if not cols or len(set(cols)) != len(cols):
         raise ValueError("Joint_Marginal: an empty set of block columns, or one listed twice")
@@ -738,6 +746,7 @@ def _joint_marginal(self, lam, bcols, reuse_factor: bool = False) -> np.ndarray:
     return np.triu(joint) + np.triu(joint, 1).T   # (the lower triangle is never filled: symmetric bit for bit)
 
 
+CLinearSolver_HIP._marginal_blocks_entry = "slampp_hip_marginal_blocks"
 CLinearSolver_HIP.Marginal_Blocks = _marginal_blocks
 CLinearSolver_HIP.Joint_Marginal = _joint_marginal
 
@@ -857,6 +866,11 @@ class CLinearSolver_Schur_HIP(_SolverBase):
                                                                       int(cols.size), _ptr(cols), _ptr(out))):
             raise ArithmeticError("Marginal_Columns: the system is not positive definite")
         return out[:k].T
+
+    # the sparse class's two methods over slampp_hip_schur_marginal_blocks (their docstrings describe both classes)
+    _marginal_blocks_entry = "slampp_hip_schur_marginal_blocks"
+    Marginal_Blocks = _marginal_blocks
+    Joint_Marginal = _joint_marginal
 
 
 class CLambdaAssembly_HIP:

@@ -25,7 +25,26 @@ Each time is the median of --repeats windows of --reps calls between two device 
 inside the window (the device waits for it), and is also given alone (host clock around one call, enqueue only).  Device
 bytes each route allocates are computed from the shapes: the n_scalars x 48 workspace both share, and each route's output.
 
-usage: python tools/time_covariance.py [--reps N] [--out FILE.json] [--pairs [--repeats M]]
+With --schur-pairs, the same for BA systems in Schur mode (slampp_hip_schur_marginal_blocks next to
+slampp_hip_schur_marginal_columns(values = NULL)), on the BA benchmark configuration (1000 cameras x 500 000 points,
+Venice-style visibility: the reduced system is inverted densely) and on the band configuration whose reduced system is
+factored by the sparse block path:
+
+  (a) schur_marginal_blocks for 32 seeded mixed pairs (cameras and landmarks in every combination);
+  (b) schur_marginal_columns on those pairs' distinct columns;
+  (c) one camera against 64 candidate landmarks, both ways: the 64 pairs, next to the camera's one block column.
+
+What its figures cover: "host_enqueue_ms" is the host clock around one whole enqueue-only call -- the checks, the list
+building (pair records, column sets, the planner, the passes' forward lists), the enqueue of the uploads and of every
+launch -- so it bounds the list building from above; the library does not time that part alone.
+"handle_device_bytes" is slampp_hip_get_stats' device_bytes of the handle after the analysis, after the first blocks call
+and after the columns calls: it counts everything the handle holds on the device, the Schur state's W, C^-1, tables and
+right-hand-side buffer, the reduced system's factor or dense inverse, and the inner solver's covariance workspace
+(n_scalars_S x 48 doubles) and pair lists included -- the differences are what each route allocates on top; the caller's
+own output buffers are "device_bytes_output".  Per-kernel times: a run of its own under rocprofv3 --kernel-trace --stats
+(--only picks the configuration).
+
+usage: python tools/time_covariance.py [--reps N] [--out FILE.json] [--pairs | --schur-pairs [--repeats M]]
 """
 import argparse
 import json
@@ -38,7 +57,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from slam_plus_plus_amd import synth  # noqa: E402
-from slam_plus_plus_amd.hip_solver import CLinearSolver_HIP, _ptr  # noqa: E402
+from slam_plus_plus_amd.hip_solver import CLinearSolver_HIP, CLinearSolver_Schur_HIP, _ptr  # noqa: E402
 
 HBM_PEAK = 8.0e12   # bytes/s, MI355X spec
 
@@ -188,22 +207,124 @@ def pairs_case(name, lam, reps, repeats):
     }
 
 
+def schur_pairs_case(name, lam, reps, repeats):
+    dev = torch.device("cuda:0")
+    s = CLinearSolver_Schur_HIP()
+    s.SymbolicDecomposition_Blocky(lam)
+    lib, h = s._lib, s._h
+    n, nb, nc = lam.n_scalars, lam.n_bcols, lam.n_matrix_cut
+    dims = np.diff(lam.cumsum).astype(np.int64)
+    dc, dp = int(dims[0]), int(dims[nc])
+    vals = torch.from_numpy(lam.values).to(dev)
+    rng = np.random.default_rng(17)
+    # 32 mixed pairs: 8 each of camera-camera, camera-landmark, landmark-camera, landmark-landmark
+    cam, pt = (lambda k: rng.integers(0, nc, k)), (lambda k: rng.integers(nc, nb, k))
+    rows32 = np.ascontiguousarray(np.concatenate([cam(8), cam(8), pt(8), pt(8)]), dtype=np.int64)
+    cols32 = np.ascontiguousarray(np.concatenate([cam(8), pt(8), cam(8), pt(8)]), dtype=np.int64)
+    shuffle = rng.permutation(32)
+    rows32, cols32 = np.ascontiguousarray(rows32[shuffle]), np.ascontiguousarray(cols32[shuffle])
+    distinct = np.unique(np.concatenate([rows32, cols32])).astype(np.int64)
+    k_distinct = int(dims[distinct].sum())
+    one_cam = np.array([nc // 2], dtype=np.int64)
+    cand = np.ascontiguousarray(np.sort(rng.choice(np.arange(nc, nb), size=64, replace=False)), dtype=np.int64)
+    cam64 = np.full(64, nc // 2, dtype=np.int64)
+    blocks = torch.empty(64 * dc * dc, dtype=torch.float64, device=dev)
+    out = torch.empty(n * k_distinct, dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+
+    def rc(x):
+        assert x == 0, s._error()
+
+    bytes_before = s.stats()["device_bytes"]
+    s.set_option("profile", 1)                                            # (this call only: which route answers)
+    rc(lib.slampp_hip_schur_marginal_blocks_device_async(h, vals.data_ptr(), 32, _ptr(rows32), _ptr(cols32), blocks.data_ptr()))
+    assert s.sync()                                                       # W, C^-1 and the factor of S are in place from here on
+    route = "dense inverse of S" if "marginals_inverse" in s.profile() else "forward substitutions on the sparse factor of S"
+    s.set_option("profile", 0)
+    bytes_blocks = s.stats()["device_bytes"]
+    blocks_fn, cols_fn = lib.slampp_hip_schur_marginal_blocks_device_async, lib.slampp_hip_schur_marginal_columns_device_async
+    legs = {
+        "a_blocks_32_pairs": lambda: rc(blocks_fn(h, None, 32, _ptr(rows32), _ptr(cols32), blocks.data_ptr())),
+        "b_columns_of_32_pairs": lambda: rc(cols_fn(h, None, len(distinct), _ptr(distinct), out.data_ptr())),
+        "c_blocks_camera_vs_64": lambda: rc(blocks_fn(h, None, 64, _ptr(cam64), _ptr(cand), blocks.data_ptr())),
+        "c_blocks_64_vs_camera": lambda: rc(blocks_fn(h, None, 64, _ptr(cand), _ptr(cam64), blocks.data_ptr())),
+        "c_columns_camera": lambda: rc(cols_fn(h, None, 1, _ptr(one_cam), out.data_ptr())),
+    }
+    times = {k: [] for k in legs}
+    for _ in range(repeats):                                              # the legs alternate: drift hits all of them alike
+        for k, fn in legs.items():
+            times[k].append(device_ms(s, fn, reps))
+    bytes_columns = s.stats()["device_bytes"]
+    host = {}
+    for k, fn in legs.items():
+        t0 = time.perf_counter()
+        fn()
+        host[k] = (time.perf_counter() - t0) * 1e3
+        assert s.sync()
+    # the two routes give the same blocks (against the scale that bounds a cross-covariance)
+    legs["b_columns_of_32_pairs"]()
+    assert s.sync()
+    X = out[:n * k_distinct].view(k_distinct, n).cpu().numpy().T
+    legs["a_blocks_32_pairs"]()
+    assert s.sync()
+    B = blocks.cpu().numpy()
+    cs = lam.cumsum
+    col_at = dict(zip((int(c) for c in distinct), np.concatenate([[0], np.cumsum(dims[distinct])])))
+
+    def x_block(r, c):
+        return X[cs[r]:cs[r + 1], col_at[int(c)]:col_at[int(c)] + int(dims[c])]
+    agree, at = 0.0, 0
+    for r, c in zip(rows32, cols32):
+        dr, dcc = int(dims[r]), int(dims[c])
+        blk = B[at:at + dr * dcc].reshape(dcc, dr).T
+        at += dr * dcc
+        bound = np.sqrt(np.abs(x_block(r, r)).max() * np.abs(x_block(c, c)).max())
+        agree = max(agree, float(np.abs(blk - x_block(r, c)).max() / bound))
+
+    def leg(k, out_bytes):
+        t = np.asarray(times[k])
+        return {"ms_median": round(float(np.median(t)), 4), "ms_min": round(float(t.min()), 4), "ms_max": round(float(t.max()), 4),
+                "host_enqueue_ms": round(host[k], 4), "device_bytes_output": out_bytes}
+    red = s.reduced_stats()
+    a, b = float(np.median(times["a_blocks_32_pairs"])), float(np.median(times["b_columns_of_32_pairs"]))
+    return {
+        "case": name + " schur pairs", "n_cams": nc, "n_points": nb - nc, "n_scalars": n, "reduced_system_sparse_in_solves": red["n_bcols"] > 0,
+        "covariance_route": route,
+        "reps": reps, "repeats": repeats, "distinct_columns_of_32_pairs": int(len(distinct)), "scalar_columns_of_32_pairs": k_distinct,
+        "a_blocks_32_pairs": leg("a_blocks_32_pairs", 8.0 * float((dims[rows32] * dims[cols32]).sum())),
+        "b_columns_of_32_pairs": leg("b_columns_of_32_pairs", 8.0 * n * k_distinct),
+        "c_blocks_camera_vs_64": leg("c_blocks_camera_vs_64", 8.0 * 64 * dc * dp),
+        "c_blocks_64_vs_camera": leg("c_blocks_64_vs_camera", 8.0 * 64 * dc * dp),
+        "c_columns_camera": leg("c_columns_camera", 8.0 * n * dc),
+        "columns_over_blocks": round(b / a, 2),
+        "handle_device_bytes": {"analyzed": bytes_before, "after_blocks": bytes_blocks, "after_columns": bytes_columns},
+        "blocks_vs_columns_over_scale": agree,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", default=None, help="C3 or C2")
+    ap.add_argument("--only", default=None, help="C3 or C2 (--schur-pairs: C4_venice or C4_band)")
     ap.add_argument("--pairs", action="store_true", help="blocks at arbitrary pairs next to whole columns (see above)")
+    ap.add_argument("--schur-pairs", action="store_true", help="the same for BA systems in Schur mode (see above)")
     ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("time_covariance: needs the GPU")
     results = []
     cases = [("C3", lambda: synth.pose_chain(n=100000)), ("C2", lambda: synth.sphere(50, 50))]
+    if a.schur_pairs:
+        cases = [("C4_venice", lambda: synth.ba(1000, 500_000, mode="venice", seed=777)),
+                 ("C4_band", lambda: synth.ba(1000, 500_000, k=4, mode="band", seed=777))]
     for name, make in cases:
         if a.only and a.only != name:
             continue
-        r = pairs_case(name, make(), a.reps, a.repeats) if a.pairs else case(name, make(), a.reps)
+        if a.schur_pairs:
+            r = schur_pairs_case(name, make(), a.reps, a.repeats)
+        else:
+            r = pairs_case(name, make(), a.reps, a.repeats) if a.pairs else case(name, make(), a.reps)
         print(json.dumps(r))
         results.append(r)
     if a.out:
