@@ -267,6 +267,34 @@ int slampp_hip_multiply_device_async(slampp_hip_solver *p_solver, const double *
 int slampp_hip_multiply(slampp_hip_solver *p_solver, const double *p_values, const double *p_x, double *p_y,
 	double f_alpha, double f_beta);
 
+/* out = alpha P(a, b) + beta out on Lambda's block pattern, where P(a, b) is the adjoint of the product above with respect to
+ * the packed values: <v, P(a, b)> = a^T M(v) b for the symmetric M(v) that slampp_hip_multiply defines from the values v.
+ * It is what the gradient of a solve needs (x = M(v)^-1 eta and an upstream gradient x_bar: g = M^-1 x_bar on the kept
+ * factor, eta_bar = g, v_bar = -P(g, x)), and what a Gauss-Newton caller that differentiates through Lambda would form:
+ *   out(r, c) = alpha (a_r b_c^T + b_r a_c^T) + beta out(r, c)   for every stored block with r < c,
+ *   out(r, r) = alpha  a_r b_r^T              + beta out(r, r)   for every diagonal block (the full d x d block);
+ * out has the length and the layout of p_values (same block order, blocks column-major).  Needs slampp_hip_set_structure only
+ * (no analysis, either mode, any block dimensions).  No atomics and no reductions: every value is at most two products and one
+ * add in one fixed form, so two calls give the same bits, batched or not.  beta = 0 does not read out (it may hold NaN).
+ * The kernel is a stream over the packed array: a thread owns pairs of consecutive values and writes each with one 16-byte
+ * store (a pair may lie in two blocks); a member whose out is not 16-byte aligned is written with 8-byte stores, to the same bits.
+ * SLAMPP_HIP_ERR_INVALID: a null pointer, no structure, n_batch outside 1 .. SLAMPP_HIP_MAX_BATCH, a stride below the length
+ * of one member (n_scalars for a and b, the number of values for out; the strides of a batch of one are not read), out
+ * overlapping a or b (a == b is fine).  A handle solving with landmark shards: SLAMPP_HIP_ERR_UNSUPPORTED.
+ * Enqueue-only on the solver's stream, but for the first call after a set_structure: that one builds lookup tables on the
+ * host (per block: its offset and the scalar rows it pairs; per 128 values: their first block) and, where tables of an earlier
+ * structure exist, waits for the stream before it frees them.  The tables live as the product's row lists do: until the
+ * next set_structure (slampp_hip_analyze leaves them; slampp_hip_free_memory frees them).
+ * _batch_: member m reads p_a_dev + m n_a_stride and p_b_dev + m n_b_stride and writes p_out_values_dev + m n_out_stride
+ * (strides in doubles), one launch for all members.  slampp_hip_pattern_outer: host arrays. */
+int slampp_hip_pattern_outer_device_async(slampp_hip_solver *p_solver, const double *p_a_dev, const double *p_b_dev,
+	double *p_out_values_dev, double f_alpha, double f_beta);
+int slampp_hip_pattern_outer(slampp_hip_solver *p_solver, const double *p_a, const double *p_b, double *p_out_values,
+	double f_alpha, double f_beta);
+int slampp_hip_pattern_outer_batch_device_async(slampp_hip_solver *p_solver, int n_batch, const double *p_a_dev,
+	int64_t n_a_stride, const double *p_b_dev, int64_t n_b_stride, double *p_out_values_dev, int64_t n_out_stride,
+	double f_alpha, double f_beta);
+
 /* *p_out_dev = sum a_i b_i over n device-resident entries, in two passes of a fixed shape (it depends on n alone): bit-
  * reproducible like the product.  With it the scalars of the LM / dog-leg step control (Eigen's dot products in
  * NonlinearSolver_Lambda_LM.h:207, NonlinearSolver_Lambda_DL.h:1270, 1510) stay on the device.  Enqueue-only; any handle. */

@@ -1,8 +1,10 @@
 // capi_resolve.hip -- the entry points of the C ABI (include/slampp_hip.h) that work with a factor or beside one: the factor
 // handed out (slampp_hip_factorize, slampp_hip_factor_structure), further right-hand sides with the kept factor
-// (slampp_hip_solve_again), y = alpha Lambda x + beta y, dot products and iterative refinement
+// (slampp_hip_solve_again), y = alpha Lambda x + beta y and its adjoint in the values (the outer product on Lambda's pattern),
+// dot products and iterative refinement
 #include "capi_util.h"
 #include "multiply.h"
+#include "pattern_outer.h"
 
 #include <algorithm>
 
@@ -328,6 +330,78 @@ int slampp_hip_multiply(slampp_hip_solver *p_solver, const double *p_values, con
 		return slampp_hip_multiply_device_async(p_solver, s.d_A.p(), s.d_mul_x.p(), s.d_mul_y.p(), f_alpha, f_beta);
 	}, false, [&](slampp_hip_solver &s) {
 		SLAMPP_HIP_CHECK(hipMemcpyAsync(p_y, s.d_mul_y.p(), size_t(s.n_scalars) * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+	});
+}
+
+// ---- out = alpha P(a, b) + beta out on Lambda's pattern (pattern_outer.hip) ----
+
+namespace {
+
+// do [p_a, p_a + n_a) and [p_b, p_b + n_b) share an element?
+bool ranges_overlap(const double *p_a, int64_t n_a, const double *p_b, int64_t n_b)
+{
+	const uintptr_t a0 = reinterpret_cast<uintptr_t>(p_a), b0 = reinterpret_cast<uintptr_t>(p_b);
+	return a0 < b0 + uintptr_t(n_b) * sizeof(double) && b0 < a0 + uintptr_t(n_a) * sizeof(double);
+}
+
+} // anonymous namespace
+
+int slampp_hip_pattern_outer_batch_device_async(slampp_hip_solver *p_solver, int n_batch, const double *p_a_dev, int64_t n_a_stride,
+	const double *p_b_dev, int64_t n_b_stride, double *p_out_values_dev, int64_t n_out_stride, double f_alpha, double f_beta)
+{
+	return guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		const int n_check = multiply_checks(p_solver, "pattern_outer");
+		if(n_check != SLAMPP_HIP_OK)
+			return n_check;
+		if(!p_a_dev || !p_b_dev || !p_out_values_dev || n_batch < 1 || n_batch > SLAMPP_HIP_MAX_BATCH)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "pattern_outer: null pointer, or a batch of fewer than 1 / more than SLAMPP_HIP_MAX_BATCH members");
+		if(n_batch == 1)
+			n_a_stride = n_b_stride = n_out_stride = 0; // (of no meaning)
+		else if(n_a_stride < s.n_scalars || n_b_stride < s.n_scalars || n_out_stride < s.n_values)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "pattern_outer: the members' vectors / values overlap (stride below their length)");
+		const int64_t n_out_span = int64_t(n_batch - 1) * n_out_stride + s.n_values;
+		if(ranges_overlap(p_a_dev, int64_t(n_batch - 1) * n_a_stride + s.n_scalars, p_out_values_dev, n_out_span) ||
+		   ranges_overlap(p_b_dev, int64_t(n_batch - 1) * n_b_stride + s.n_scalars, p_out_values_dev, n_out_span))
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "pattern_outer: out overlaps a or b");
+		s.Require_Pattern_Outer();
+		pattern_outer_enqueue(*s.p_outer, n_batch, p_a_dev, n_a_stride, p_b_dev, n_b_stride, p_out_values_dev, n_out_stride, f_alpha,
+			f_beta, s.stream);
+		return SLAMPP_HIP_OK;
+	});
+}
+
+int slampp_hip_pattern_outer_device_async(slampp_hip_solver *p_solver, const double *p_a_dev, const double *p_b_dev,
+	double *p_out_values_dev, double f_alpha, double f_beta)
+{
+	return slampp_hip_pattern_outer_batch_device_async(p_solver, 1, p_a_dev, 0, p_b_dev, 0, p_out_values_dev, 0, f_alpha, f_beta);
+}
+
+int slampp_hip_pattern_outer(slampp_hip_solver *p_solver, const double *p_a, const double *p_b, double *p_out_values, double f_alpha,
+	double f_beta)
+{
+	return host_round_trip(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		const int n_check = multiply_checks(p_solver, "pattern_outer");
+		if(n_check != SLAMPP_HIP_OK)
+			return n_check;
+		if(!p_a || !p_b || !p_out_values)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "pattern_outer: null pointer");
+		if(ranges_overlap(p_a, s.n_scalars, p_out_values, s.n_values) || ranges_overlap(p_b, s.n_scalars, p_out_values, s.n_values))
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "pattern_outer: out overlaps a or b");
+		const size_t n_bytes = size_t(s.n_scalars) * sizeof(double);
+		s.d_mul_x.Alloc(size_t(s.n_scalars));
+		s.d_mul_y.Alloc(size_t(s.n_scalars));
+		s.d_outer_out.Alloc(size_t(s.n_values));
+		SLAMPP_HIP_CHECK(hipMemcpyAsync(s.d_mul_x.p(), p_a, n_bytes, hipMemcpyHostToDevice, s.stream));
+		SLAMPP_HIP_CHECK(hipMemcpyAsync(s.d_mul_y.p(), p_b, n_bytes, hipMemcpyHostToDevice, s.stream));
+		if(f_beta != 0)
+			SLAMPP_HIP_CHECK(hipMemcpyAsync(s.d_outer_out.p(), p_out_values, size_t(s.n_values) * sizeof(double), hipMemcpyHostToDevice, s.stream));
+		return SLAMPP_HIP_OK;
+	}, [&](slampp_hip_solver &s) {
+		return slampp_hip_pattern_outer_device_async(p_solver, s.d_mul_x.p(), s.d_mul_y.p(), s.d_outer_out.p(), f_alpha, f_beta);
+	}, false, [&](slampp_hip_solver &s) {
+		SLAMPP_HIP_CHECK(hipMemcpyAsync(p_out_values, s.d_outer_out.p(), size_t(s.n_values) * sizeof(double), hipMemcpyDeviceToHost, s.stream));
 	});
 }
 

@@ -97,6 +97,7 @@ struct CSparseInverse; // sparse_inverse.hip
 struct CCovariance; // covariance.hip
 struct CAssemblyState; // assembly.hip
 struct CMultiplyState; // multiply.hip
+struct CPatternOuterState; // pattern_outer.hip
 
 } // namespace slampp
 
@@ -145,6 +146,12 @@ struct slampp_hip_solver {
 	int n_multiply_long_row = SLAMPP_HIP_MULTIPLY_LONG_ROW;
 	slampp::CDevArray<double> d_reduce, d_refine_r, d_mul_x, d_mul_y, d_refine_resid;
 	void Require_Multiply(); // throws
+	// out = alpha P(a, b) + beta out on Lambda's pattern (pattern_outer.hip): its lookup tables live as the row lists above do;
+	// the output array of the host entry point
+	slampp::CPatternOuterState *p_outer = 0;
+	bool b_outer_valid = false;
+	slampp::CDevArray<double> d_outer_out;
+	void Require_Pattern_Outer(); // throws
 	int n_mode;
 	int64_t n_matrix_cut;
 	std::vector<int64_t> cumsum, bcol_ptr;

@@ -120,6 +120,10 @@ ABI = {
     "slampp_hip_solve_again_device_async": (C.c_int, [_P, _P]),
     "slampp_hip_multiply_device_async": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double]),
     "slampp_hip_multiply": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double]),
+    "slampp_hip_pattern_outer_device_async": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double]),
+    "slampp_hip_pattern_outer": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double]),
+    "slampp_hip_pattern_outer_batch_device_async": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64,
+                                                              C.c_double, C.c_double]),
     "slampp_hip_dot_device_async": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
     "slampp_hip_refine_device_async": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
     "slampp_hip_refine": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
@@ -164,6 +168,30 @@ ABI = {
     "slampp_hip_plan_get": (C.c_int, [_P, C.POINTER(PlanView), C.POINTER(Stats)]),
     "slampp_hip_plan_destroy": (None, [_P]),
 }
+
+# the entry points that factor, drop the factor a handle keeps or change its structure: after any of them the factor an
+# earlier call left is not that call's any more (values = NULL reuses of the covariance calls are counted too: harmless)
+_FACTOR_CHANGING = frozenset(
+    ["slampp_hip_free_memory", "slampp_hip_set_structure", "slampp_hip_analyze", "slampp_hip_factor_solve",
+     "slampp_hip_factor_solve_device", "slampp_hip_factor_solve_device_async", "slampp_hip_factor_solve_batch_device_async",
+     "slampp_hip_factorize", "slampp_hip_solve_marginal_poses", "slampp_hip_solve_marginal_poses_device_async"] +
+    [n for n in ABI if "marginal" in n and "poses" not in n])
+
+
+class _FactorTrackingLib:
+    """The library as one solver object calls it: every fetch of an entry point of _FACTOR_CHANGING counts ``generation``
+    up, so that whoever remembers the generation of its own factorization (torch_solve) can tell whether the handle still
+    holds that factor.  One place instead of a line in every wrapper method."""
+
+    def __init__(self, lib):
+        self._lib = lib
+        self.generation = 0
+
+    def __getattr__(self, name):
+        if name in _FACTOR_CHANGING:
+            self.generation += 1
+        return getattr(self._lib, name)
+
 
 _lib = None
 
@@ -285,7 +313,8 @@ class _SolverBase:
         """``devices``: a list of HIP device ordinals -- one handle over several GPUs of this process
         (slampp_hip_create_multi): a BA system is cut into landmark shards, one per listed device, and the reduced camera
         system is summed inside the library (RCCL, or peer pointers); pose graphs run on ``devices[0]``."""
-        self._lib = load_library()
+        self._lib = _FactorTrackingLib(load_library())
+        self.n_backward_refactorizations = 0     # torch_solve: backward passes that had to factor again
         self._h = C.c_void_p()
         self._devices = None if devices is None else [int(d) for d in devices]
         if self._devices is not None:
@@ -305,6 +334,7 @@ class _SolverBase:
             raise RuntimeError(f"slampp_hip_create(device={device}) failed ({rc}): no usable HIP device")
         self._device = int(device)
         self._options = dict(options)
+        self._options_now = dict(options)        # ... and what set_option() has changed since (copies do not carry it)
         for k, v in options.items():
             self._check(self._lib.slampp_hip_set_option(self._h, k.encode(), int(v)))
         self._structure_key = None
@@ -468,6 +498,27 @@ class _SolverBase:
         self._check(self._lib.slampp_hip_multiply(self._h, _ptr(vals), _ptr(x), _ptr(y), float(alpha), float(beta)))
         return y
 
+    def Pattern_Outer(self, lam, a: np.ndarray, b: np.ndarray, out: np.ndarray = None, alpha: float = 1.0,
+                      beta: float = 0.0) -> np.ndarray:
+        """out = alpha P(a, b) + beta out on the block pattern of ``lam`` (slampp_hip_pattern_outer): alpha (a_r b_c^T +
+        b_r a_c^T) at every stored block r < c, alpha a_r b_r^T at every diagonal block -- the adjoint of Multiply with respect
+        to ``lam.values``.  Returns out, shaped like ``lam.values`` (a new array where none is given, which needs beta = 0).
+        No analysis is needed."""
+        if self._structure_key is None or self._structure_key != self._key(lam):
+            self._set_structure(lam)
+        n = int(lam.cumsum[-1])
+        if out is None:
+            if beta != 0:
+                raise ValueError("Pattern_Outer: beta != 0 needs an out")
+            out = np.empty(self._n_values, dtype=np.float64)
+        for v in (a, b):
+            if v.dtype != np.float64 or not v.flags.c_contiguous or v.shape != (n,):
+                raise ValueError("a and b must be contiguous float64 vectors of the system's dimension")
+        if out.dtype != np.float64 or not out.flags.c_contiguous or out.shape != (self._n_values,):
+            raise ValueError("out must be a contiguous float64 vector shaped like lam.values")
+        self._check(self._lib.slampp_hip_pattern_outer(self._h, _ptr(a), _ptr(b), _ptr(out), float(alpha), float(beta)))
+        return out
+
     def Refine(self, lam, eta: np.ndarray, x: np.ndarray, n_steps: int = 2) -> np.ndarray:
         """``n_steps`` of iterative refinement of ``x`` (in place) with the kept factor (slampp_hip_refine): r = eta - Lambda x,
         d = Solve_Again(r), x += d, where a step that does not at least halve max|eta - Lambda x| is taken back and ends the
@@ -534,6 +585,12 @@ class _SolverBase:
 
     def set_option(self, name: str, value: int) -> None:
         self._check(self._lib.slampp_hip_set_option(self._h, name.encode(), int(value)))
+        self._options_now[name] = int(value)
+
+    @property
+    def factor_generation(self) -> int:
+        """Counts up with every call through this object that factors, drops the kept factor or changes the structure."""
+        return self._lib.generation
 
     def profile(self, reset: bool = False) -> dict:
         """{phase: (count, total_ms)} measured with HIP events on the solver's stream (option profile=1)."""
@@ -585,6 +642,20 @@ class _SolverBase:
         """y = alpha Lambda x + beta y on device-resident arrays, enqueue-only (slampp_hip_multiply_device_async); the
         structure is the one last given to the handle."""
         self._check(self._lib.slampp_hip_multiply_device_async(self._h, values_ptr, x_ptr, y_ptr, float(alpha), float(beta)))
+
+    def pattern_outer_device(self, a_ptr: int, b_ptr: int, out_ptr: int, alpha: float = 1.0, beta: float = 0.0) -> None:
+        """out = alpha P(a, b) + beta out on device-resident arrays, enqueue-only (slampp_hip_pattern_outer_device_async);
+        the structure is the one last given to the handle, out has the length of its packed values."""
+        self._check(self._lib.slampp_hip_pattern_outer_device_async(self._h, a_ptr or None, b_ptr or None, out_ptr or None,
+                                                                    float(alpha), float(beta)))
+
+    def pattern_outer_batch_device(self, n_batch: int, a_ptr: int, a_stride: int, b_ptr: int, b_stride: int, out_ptr: int,
+                                   out_stride: int, alpha: float = 1.0, beta: float = 0.0) -> None:
+        """The same for n_batch members in one launch (slampp_hip_pattern_outer_batch_device_async): member m reads
+        a_ptr + 8 m a_stride and b_ptr + 8 m b_stride and writes out_ptr + 8 m out_stride (strides in doubles)."""
+        self._check(self._lib.slampp_hip_pattern_outer_batch_device_async(
+            self._h, int(n_batch), a_ptr or None, int(a_stride), b_ptr or None, int(b_stride), out_ptr or None, int(out_stride),
+            float(alpha), float(beta)))
 
     def dot_device(self, a_ptr: int, b_ptr: int, n: int, out_ptr: int) -> None:
         """*out = a . b over n device-resident doubles, in a fixed order (slampp_hip_dot_device_async)."""

@@ -1,0 +1,243 @@
+"""The block-sparse solve as a differentiable PyTorch operation, in both modes.
+
+``solve(solver, lam, values, eta)`` returns ``x = M(values)^-1 eta`` as a tensor that carries a ``backward``; ``M(v)`` is the
+symmetric matrix slampp_hip_multiply defines from the packed values ``v`` of the block structure of ``lam``: a stored upper
+block (r, c), r < c, stands at (r, c) and transposed at (c, r), diagonal blocks are the full d x d blocks.  With an upstream
+gradient ``x_bar``::
+
+    g        = M^-1 x_bar                       one more right-hand side on the KEPT factor
+    eta_bar  = g
+    v_bar(r, c) = -(g_r x_c^T + x_r g_c^T)      every stored block r < c
+    v_bar(r, r) = - g_r x_r^T                   every diagonal block
+
+so a backward pass costs two substitutions (slampp_hip_solve_again_device_async) and one streaming kernel
+(slampp_hip_pattern_outer_device_async, launched only when ``values`` needs a gradient); there is no second factorization.
+The function is once differentiable.
+
+Calling rules.  ``solver`` is a CLinearSolver_HIP or a CLinearSolver_Schur_HIP; ``lam`` supplies the block structure only:
+it is analyzed on first use and again when its structure key changes, as Solve_PosDef_Blocky decides.  ``values``
+(``lam.values.shape``) and ``eta`` (``(lam.n_scalars,)``) are contiguous float64 CUDA tensors on the solver's device;
+anything else raises TypeError / ValueError before the library is called.  The forward pass waits for the device once
+(slampp_hip_sync: that is how a matrix that is not positive definite is reported -- torch.linalg.LinAlgError, and nothing is
+saved for backward); the backward pass only enqueues.
+
+Who owns the factor.  A handle keeps ONE factor.  Every forward pass remembers the solver object's factor generation
+(``solver.factor_generation``), which counts up with every call through the Python wrapper that factors, drops the factor
+or changes the structure: another ``solve``, Solve_PosDef*, factor_solve_device*, a batch, the covariance calls,
+Free_Memory, a new structure (also through Multiply / Pattern_Outer on another system).  If the generation has moved by the
+time of the backward pass, the factor is someone else's and backward calls slampp_hip_factor_solve_device_async on the
+saved values and ``x_bar`` instead (after analyzing its own structure again, if the handle has been given another): the same
+``M^-1 x_bar``, at the price of a factorization.  A Schur-mode solver without the option ``schur_keep=1`` (or
+``schur_incremental``) keeps no factor a re-solve could use, and takes that route every time; it never raises for this
+reason.  ``solver.n_backward_refactorizations`` counts these events.  Calls that reach the handle around the Python
+wrapper (the C ABI directly) are not seen.
+
+Streams.  The library enqueues on its own stream, wrapped once per solver as ``torch.cuda.ExternalStream``.  Before a
+call enqueues, that stream waits for torch's current stream; afterwards torch's current stream waits for it.  So the
+inputs are ready when the library reads them, the outputs are ready for whatever torch enqueues next, and no tensor handed
+to the library is freed and reused ahead of the work that reads it.  There is no torch.cuda.synchronize().
+
+``solve_batch(solver, lam, values[K, n_values], eta[K, n_scalars])``: K <= 64 value sets of one structure, sparse mode
+only (slampp_hip_factor_solve_batch_device_async + slampp_hip_sync_batch; a member that is not positive definite raises and
+is named).  A batch keeps no factors, so its backward pass is the same batched call on ``(values, x_bar)`` -- K
+factorizations, the documented cost -- followed by the batched outer-product kernel.  The tensors are passed as they are
+(rows contiguous, any row stride of at least a row); odd strides are solved member by member inside the library, with the
+same results.
+
+``dense_from_packed`` and ``pattern_outer_reference`` restate M(v) and the outer product in plain torch / numpy: the
+yardsticks of the tests.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+from torch.autograd.function import once_differentiable
+
+from .hip_solver import CLinearSolver_HIP, CLinearSolver_Schur_HIP, MODE_SPARSE
+
+MAX_BATCH = 64     # SLAMPP_HIP_MAX_BATCH
+
+
+# ---- the yardsticks ----
+
+def _element_rows_cols(lam):
+    """(row, col, offdiag) of every packed value of ``lam``'s structure: its scalar row and column in the full matrix (blocks in
+    block-CSC order, each column-major) and whether its block lies off the diagonal."""
+    cs = np.asarray(lam.cumsum, dtype=np.int64)
+    dims = np.diff(cs)
+    brow = np.asarray(lam.brow_idx, dtype=np.int64)
+    bcol = np.repeat(np.arange(len(dims), dtype=np.int64), np.diff(lam.bcol_ptr))
+    sizes = dims[brow] * dims[bcol]
+    off = np.concatenate([[0], np.cumsum(sizes)])
+    blk = np.repeat(np.arange(len(brow), dtype=np.int64), sizes)
+    local = np.arange(int(off[-1]), dtype=np.int64) - off[blk]
+    d_r = dims[brow][blk]
+    return cs[brow][blk] + local % d_r, cs[bcol][blk] + local // d_r, (brow != bcol)[blk]
+
+
+def dense_from_packed(lam, values: torch.Tensor) -> torch.Tensor:
+    """The dense symmetric M(values) of ``lam``'s structure, as a differentiable function of ``values`` (a scatter)."""
+    row, col, offdiag = _element_rows_cols(lam)
+    n = int(lam.cumsum[-1])
+    src = np.arange(row.shape[0], dtype=np.int64)
+    idx = np.concatenate([row * n + col, (col * n + row)[offdiag]])
+    src = np.concatenate([src, src[offdiag]])
+    flat = values.new_zeros(n * n).index_put((torch.from_numpy(idx).to(values.device),),
+                                             values[torch.from_numpy(src).to(values.device)])
+    return flat.reshape(n, n)
+
+
+def pattern_outer_reference(lam, a: np.ndarray, b: np.ndarray, alpha: float = 1.0) -> np.ndarray:
+    """alpha P(a, b) on ``lam``'s pattern in numpy: alpha (a_r b_c^T + b_r a_c^T) at the stored blocks r < c, alpha a_r b_r^T
+    at the diagonal blocks; shaped like ``lam.values``."""
+    row, col, offdiag = _element_rows_cols(lam)
+    out = a[row] * b[col]
+    out[offdiag] += (b[row] * a[col])[offdiag]
+    return alpha * out
+
+
+# ---- the library's stream beside torch's ----
+
+def _solver_stream(solver) -> torch.cuda.Stream:
+    stream = getattr(solver, "_torch_stream", None)
+    if stream is None:
+        stream = solver._torch_stream = torch.cuda.ExternalStream(solver.stream(), device=torch.device("cuda", solver._device))
+    return stream
+
+
+def _enqueue(solver, fn) -> None:
+    """fn() enqueues on the solver's stream, behind what torch's current stream holds and ahead of what it gets next."""
+    ours, theirs = _solver_stream(solver), torch.cuda.current_stream(torch.device("cuda", solver._device))
+    ours.wait_stream(theirs)
+    fn()
+    theirs.wait_stream(ours)
+
+
+# ---- checks (before any call into the library) ----
+
+def _check_tensor(solver, t, name: str, shape) -> None:
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if t.dtype != torch.float64:
+        raise TypeError(f"{name} must be float64, not {t.dtype}")
+    if t.device.type != "cuda" or t.device.index != solver._device:
+        raise ValueError(f"{name} must live on the solver's device cuda:{solver._device}, not on {t.device}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have the shape {tuple(shape)}, not {tuple(t.shape)}")
+    if t.stride(-1) != 1 and t.shape[-1] > 1:
+        raise ValueError(f"{name} must be contiguous")
+
+
+def _check_solver(solver) -> None:
+    if not isinstance(solver, (CLinearSolver_HIP, CLinearSolver_Schur_HIP)):
+        raise TypeError("solver must be a CLinearSolver_HIP or a CLinearSolver_Schur_HIP")
+
+
+def _require_analysis(solver, lam) -> None:
+    if not solver._analyzed or solver._structure_key != solver._key(lam):
+        solver.SymbolicDecomposition_Blocky(lam)
+
+
+def _keeps_factor(solver) -> bool:
+    """Does a solve of this solver leave a factor slampp_hip_solve_again_device_async can work from?"""
+    if solver._mode == MODE_SPARSE:
+        return True
+    return bool(solver._options_now.get("schur_keep", 0) or solver._options_now.get("schur_incremental", 0))
+
+
+# ---- one system ----
+
+class _Solve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, values, eta, solver, lam):
+        x = eta.clone()
+        v = values.detach()
+        _enqueue(solver, lambda: solver.factor_solve_device_async(v.data_ptr(), x.data_ptr()))
+        if not solver.sync():
+            raise torch.linalg.LinAlgError("solve: the matrix is not positive definite")
+        ctx.solver, ctx.lam, ctx.generation = solver, lam, solver.factor_generation
+        ctx.save_for_backward(values, x)
+        return x
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, x_bar):
+        values, x = ctx.saved_tensors
+        solver, lam = ctx.solver, ctx.lam
+        g = x_bar.clone(memory_format=torch.contiguous_format)
+        v_bar = torch.empty_like(values) if ctx.needs_input_grad[0] else None
+        b_kept = ctx.generation == solver.factor_generation and _keeps_factor(solver)
+        if not b_kept:
+            _require_analysis(solver, lam)          # (the handle may have been given another structure since)
+
+        def work():
+            if b_kept:
+                solver.solve_again_device(g.data_ptr())
+            else:
+                solver.factor_solve_device_async(values.data_ptr(), g.data_ptr())
+            if v_bar is not None:
+                solver.pattern_outer_device(g.data_ptr(), x.data_ptr(), v_bar.data_ptr(), -1.0, 0.0)
+        _enqueue(solver, work)
+        if not b_kept:
+            solver.n_backward_refactorizations += 1
+            ctx.generation = solver.factor_generation     # the handle's factor is this node's again
+        return v_bar, (g if ctx.needs_input_grad[1] else None), None, None
+
+
+def solve(solver, lam, values: torch.Tensor, eta: torch.Tensor) -> torch.Tensor:
+    """x = M(values)^-1 eta on the block structure of ``lam``, differentiable in ``values`` and ``eta`` (module docstring)."""
+    _check_solver(solver)
+    _check_tensor(solver, values, "values", (int(lam.values.shape[0]),))
+    _check_tensor(solver, eta, "eta", (int(lam.cumsum[-1]),))
+    _require_analysis(solver, lam)
+    return _Solve.apply(values, eta, solver, lam)
+
+
+# ---- K value sets of one structure ----
+
+class _SolveBatch(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, values, eta, solver, lam):
+        n_batch = values.shape[0]
+        x = eta.clone()
+        v = values.detach()
+        _enqueue(solver, lambda: solver.factor_solve_batch_device_async(n_batch, v.data_ptr(), v.stride(0), x.data_ptr(), x.stride(0)))
+        bad = [k for k, ok in enumerate(solver.sync_batch(n_batch)) if not ok]
+        if bad:
+            raise torch.linalg.LinAlgError(f"solve_batch: the matrices of the members {bad} are not positive definite")
+        ctx.solver, ctx.lam = solver, lam
+        ctx.save_for_backward(values, x)
+        return x
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, x_bar):
+        values, x = ctx.saved_tensors
+        solver, n_batch = ctx.solver, values.shape[0]
+        g = x_bar.clone(memory_format=torch.contiguous_format)
+        v_bar = torch.empty((n_batch, values.shape[1]), dtype=values.dtype, device=values.device) if ctx.needs_input_grad[0] else None
+        _require_analysis(solver, ctx.lam)
+
+        def work():
+            solver.factor_solve_batch_device_async(n_batch, values.data_ptr(), values.stride(0), g.data_ptr(), g.stride(0))
+            if v_bar is not None:
+                solver.pattern_outer_batch_device(n_batch, g.data_ptr(), g.stride(0), x.data_ptr(), x.stride(0), v_bar.data_ptr(),
+                                                  v_bar.stride(0), -1.0, 0.0)
+        _enqueue(solver, work)
+        return v_bar, (g if ctx.needs_input_grad[1] else None), None, None
+
+
+def solve_batch(solver, lam, values: torch.Tensor, eta: torch.Tensor) -> torch.Tensor:
+    """x[k] = M(values[k])^-1 eta[k] for K <= 64 value sets of ``lam``'s structure (sparse mode), differentiable in both."""
+    _check_solver(solver)
+    if solver._mode != MODE_SPARSE:
+        raise TypeError("solve_batch: sparse mode only (a CLinearSolver_HIP)")
+    if not isinstance(values, torch.Tensor) or values.dim() != 2 or not 1 <= values.shape[0] <= MAX_BATCH:
+        raise ValueError(f"values must be a tensor of the shape (K, n_values), 1 <= K <= {MAX_BATCH}")
+    n_batch, n_values, n_scalars = values.shape[0], int(lam.values.shape[0]), int(lam.cumsum[-1])
+    _check_tensor(solver, values, "values", (n_batch, n_values))
+    _check_tensor(solver, eta, "eta", (n_batch, n_scalars))
+    if n_batch > 1 and (values.stride(0) < n_values or eta.stride(0) < n_scalars):
+        raise ValueError("the members of values / eta overlap (row stride below the row length)")
+    _require_analysis(solver, lam)
+    return _SolveBatch.apply(values, eta, solver, lam)
