@@ -123,42 +123,6 @@ protected:
 		}
 	}
 
-	/** @brief the upper pairs (a <= b, column by column) of a set of distinct block columns, for Joint_Marginal() */
-	static void Joint_Marginal_Pairs(std::vector<std::pair<size_t, size_t> > &r_pairs, const std::vector<size_t> &r_block_columns,
-		const char *p_s_who) // throw(std::bad_alloc, std::runtime_error)
-	{
-		std::vector<size_t> sorted(r_block_columns);
-		std::sort(sorted.begin(), sorted.end());
-		if(sorted.empty() || std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
-			throw std::runtime_error(std::string(p_s_who) + ": an empty set of block columns, or one listed twice");
-		r_pairs.clear();
-		for(size_t b = 0; b < r_block_columns.size(); ++ b) {
-			for(size_t a = 0; a <= b; ++ a)
-				r_pairs.push_back(std::make_pair(r_block_columns[a], r_block_columns[b]));
-		}
-	}
-
-	/** @brief the joint marginal from the blocks at those pairs: the upper blocks and their mirror images */
-	static void Joint_Marginal_Fill(Eigen::MatrixXd &r_joint, const CUberBlockMatrix &r_lambda,
-		const std::vector<size_t> &r_block_columns, const std::vector<Eigen::MatrixXd> &r_blocks) // throw(std::bad_alloc)
-	{
-		std::vector<size_t> off(r_block_columns.size() + 1, 0);
-		for(size_t a = 0; a < r_block_columns.size(); ++ a)
-			off[a + 1] = off[a] + r_lambda.n_BlockColumn_Column_Num(r_block_columns[a]);
-		r_joint.resize(off.back(), off.back());
-		for(size_t b = 0, k = 0; b < r_block_columns.size(); ++ b) {
-			for(size_t a = 0; a <= b; ++ a, ++ k) {
-				r_joint.block(off[a], off[b], off[a + 1] - off[a], off[b + 1] - off[b]) = r_blocks[k];
-				if(a != b)
-					r_joint.block(off[b], off[a], off[b + 1] - off[b], off[a + 1] - off[a]) = r_blocks[k].transpose();
-			}
-		}
-		for(size_t c = 0; c < size_t(r_joint.cols()); ++ c) { // (the diagonal blocks: the upper triangle mirrored, symmetric bit for bit)
-			for(size_t r = c + 1; r < size_t(r_joint.rows()); ++ r)
-				r_joint(r, c) = r_joint(c, r);
-		}
-	}
-
 	void Require_Handle() // throw(std::bad_alloc, std::runtime_error)
 	{
 		if(!m_p_solver) {
@@ -184,16 +148,11 @@ protected:
 		const bool b_timing = getenv("SLAMPP_HIP_PLAN_TIMING") != 0; // development aid: where the cold call's time goes
 		const double f_t0 = b_timing? f_Wall_Ms() : 0;
 		const size_t n = r_lambda.n_BlockColumn_Num();
-		std::vector<size_t> inv_order(n);
-		if(p_order) {
+		if(p_order)
 			m_order = *p_order;
-			for(size_t i = 0; i < n; ++ i)
-				inv_order[m_order[i]] = i;
-		} else {
+		else
 			m_order.clear();
-			for(size_t i = 0; i < n; ++ i)
-				inv_order[i] = i;
-		}
+		const std::vector<size_t> inv_order(Inverse_Order(n));
 		m_cumsum.resize(n + 1);
 		m_cumsum[0] = 0;
 		for(size_t i = 0; i < n; ++ i)
@@ -503,6 +462,221 @@ protected:
 			#pragma omp parallel for schedule(static) num_threads(n_thread_num) if(n_scalar_num > 65536)
 			for(long i = 0; i < n_scalar_num; ++ i)
 				p_x[i] = m_p_rhs[i];
+		}
+		return true;
+	}
+
+	/** @brief old block column -> new: the inverse of m_order (the identity if m_order is empty) */
+	std::vector<size_t> Inverse_Order(size_t n) const // throw(std::bad_alloc)
+	{
+		std::vector<size_t> inv_order(n);
+		for(size_t i = 0; i < n; ++ i)
+			inv_order[m_order.empty()? i : m_order[i]] = i;
+		return inv_order;
+	}
+
+	/**
+	 *	@brief the host entry points of the library that answer a class's covariance calls.  The members below do the rest
+	 *		for both classes: they work on the values a class has gathered, honour m_order (empty in the sparse class, which
+	 *		hands lambda over as it is), and take the entries they call and the class name for the exception texts -- each
+	 *		only its own, so that a program links no more of the library than the members it uses.
+	 */
+	typedef int (*TPatternEntry)(slampp_hip_solver*, const double*, double*);
+	typedef int (*TColumnsEntry)(slampp_hip_solver*, const double*, int, const int64_t*, double*); /**< @copydoc TPatternEntry */
+	typedef int (*TBlocksEntry)(slampp_hip_solver*, const double*, int64_t, const int64_t*, const int64_t*, double*); /**< @copydoc TPatternEntry */
+
+	/** @brief writes the di x dj column-major block (i, j) of lambda's order into r_m: at (j, i), transposed, if it is a lower one */
+	static void Put_Block(CUberBlockMatrix &r_m, size_t i, size_t j, size_t di, size_t dj, const double *p_src,
+		const char *p_s_class) // throw(std::bad_alloc, std::runtime_error)
+	{
+		const bool b_tr = i > j;
+		double *p_dest = (b_tr)? r_m.p_GetBlock_Log(j, i, dj, di, true, false) : r_m.p_GetBlock_Log(i, j, di, dj, true, false);
+		if(!p_dest)
+			throw std::runtime_error(std::string(p_s_class) + ": cannot write the marginals");
+		if(!b_tr)
+			std::copy(p_src, p_src + di * dj, p_dest);
+		else {
+			for(size_t c = 0; c < dj; ++ c)
+				for(size_t r = 0; r < di; ++ r)
+					p_dest[c + r * dj] = p_src[r + c * di];
+		}
+	}
+
+	/** @brief Marginals(): refuses mpart_Column other than as part of mpart_FullMatrix (before lambda is looked at) */
+	static void Check_Parts(EBlockMatrixPart n_part, const char *p_s_class) // throw(std::bad_alloc, std::runtime_error)
+	{
+		if((n_part & mpart_Column) && (n_part & mpart_FullMatrix) != mpart_FullMatrix)
+			throw std::runtime_error(std::string(p_s_class) + "::Marginals: mpart_Column does not say which column (use Marginal_Columns)");
+	}
+
+	/** @brief Marginals() with an EBlockMatrixPart, on the gathered values: lambda's pattern, then block columns in passes */
+	bool Marginals_Gathered(CUberBlockMatrix &r_marginals, const CUberBlockMatrix &r_lambda, EBlockMatrixPart n_part,
+		bool b_structure_of_lambda, TPatternEntry p_pattern, TColumnsEntry p_columns, const char *p_s_class) // throw(std::bad_alloc, std::runtime_error)
+	{
+		const size_t n = r_lambda.n_BlockColumn_Num();
+		const bool b_full = (n_part & mpart_FullMatrix) == mpart_FullMatrix;
+		const bool b_last_col = b_full || (n_part & mpart_LastColumn) != 0;
+		const bool b_last_block = b_last_col || (n_part & mpart_LastBlock) != 0;
+		const bool b_diag = b_full || (n_part & mpart_Diagonal) != 0;
+		r_lambda.CopyLayoutTo(r_marginals); // (blocks are then allocated anywhere in lambda's layout, in any order)
+		bool b_have_factor = false;
+		if(b_structure_of_lambda || (b_diag && !b_full)) { // lambda's pattern (the diagonal is among it)
+			std::vector<double> v(m_n_value_num);
+			const int n_result = (*p_pattern)(m_p_solver, m_p_values, v.empty()? 0 : &v[0]);
+			if(n_result == SLAMPP_HIP_NOT_POSDEF)
+				return false;
+			Throw_On_Error(n_result);
+			b_have_factor = true;
+			size_t n_at = 0;
+			for(size_t j = 0; j < n; ++ j) { // the library's block order
+				const size_t dj = size_t(m_cumsum[j + 1] - m_cumsum[j]), oj = m_order.empty()? j : m_order[j];
+				for(int64_t k = m_bcol_ptr[j]; k < m_bcol_ptr[j + 1]; ++ k) {
+					const size_t i = size_t(m_brow[size_t(k)]), di = size_t(m_cumsum[i + 1] - m_cumsum[i]);
+					if(b_structure_of_lambda || i == j)
+						Put_Block(r_marginals, m_order.empty()? i : m_order[i], oj, di, dj, &v[n_at], p_s_class);
+					n_at += di * dj;
+				}
+			}
+		}
+		std::vector<int64_t> cols;
+		if(b_full) {
+			for(size_t j = 0; j < n; ++ j)
+				cols.push_back(int64_t(j));
+		} else if(b_last_block)
+			cols.push_back(int64_t(n - 1));
+		std::vector<double> blk;
+		for(size_t c0 = 0; c0 < cols.size();) { // at most 48 scalar columns at a time (one pass of the library)
+			size_t c1 = c0, n_k = 0;
+			while(c1 < cols.size() && (c1 == c0 || n_k + r_lambda.n_BlockColumn_Column_Num(size_t(cols[c1])) <= 48))
+				n_k += r_lambda.n_BlockColumn_Column_Num(size_t(cols[c1 ++]));
+			Eigen::MatrixXd X;
+			if(!Columns_Gathered(X, r_lambda, std::vector<int64_t>(cols.begin() + c0, cols.begin() + c1), b_have_factor, p_columns, p_s_class))
+				return false;
+			b_have_factor = true;
+			size_t n_col = 0;
+			for(size_t q = c0; q < c1; ++ q) {
+				const size_t j = size_t(cols[q]), dj = r_lambda.n_BlockColumn_Column_Num(j);
+				for(size_t i = b_last_col? 0 : j; i <= j; ++ i) { // (mpart_LastBlock alone: the diagonal block only)
+					const size_t di = r_lambda.n_BlockColumn_Column_Num(i), b0 = r_lambda.n_BlockColumn_Base(i);
+					blk.resize(di * dj);
+					for(size_t c = 0; c < dj; ++ c)
+						for(size_t r = 0; r < di; ++ r)
+							blk[r + c * di] = X(b0 + r, n_col + c);
+					Put_Block(r_marginals, i, j, di, dj, &blk[0], p_s_class);
+				}
+				n_col += dj;
+			}
+			c0 = c1;
+		}
+		return true;
+	}
+
+	/**
+	 *	@brief block columns r_cols (lambda's indices) of the inverse, rows in lambda's scalar order, on the gathered values;
+	 *		b_reuse_factor: the factor the previous covariance call left in place is used (no values, no new factorization)
+	 */
+	bool Columns_Gathered(Eigen::MatrixXd &r_columns, const CUberBlockMatrix &r_lambda, const std::vector<int64_t> &r_cols,
+		bool b_reuse_factor, TColumnsEntry p_columns, const char *p_s_class) // throw(std::bad_alloc, std::runtime_error)
+	{
+		const size_t n = r_lambda.n_BlockColumn_Num();
+		const std::vector<size_t> inv_order(Inverse_Order(n));
+		std::vector<int64_t> lib_cols(r_cols.size());
+		size_t n_k = 0;
+		for(size_t i = 0; i < r_cols.size(); ++ i) {
+			if(r_cols[i] < 0 || size_t(r_cols[i]) >= n)
+				throw std::runtime_error(std::string(p_s_class) + "::Marginal_Columns: block column index out of range");
+			lib_cols[i] = int64_t(inv_order[size_t(r_cols[i])]);
+			n_k += r_lambda.n_BlockColumn_Column_Num(size_t(r_cols[i]));
+		}
+		Eigen::MatrixXd X(r_lambda.n_Column_Num(), n_k); // (column-major, as the library writes it; rows in its order)
+		const int n_result = (*p_columns)(m_p_solver, b_reuse_factor? 0 : m_p_values, int(lib_cols.size()),
+			lib_cols.empty()? 0 : &lib_cols[0], X.data());
+		if(n_result == SLAMPP_HIP_NOT_POSDEF)
+			return false;
+		Throw_On_Error(n_result);
+		if(m_order.empty())
+			r_columns.swap(X);
+		else { // rows back to lambda's scalar order
+			r_columns.resize(X.rows(), X.cols());
+			for(size_t i = 0; i < n; ++ i) {
+				const size_t n_dst = r_lambda.n_BlockColumn_Base(m_order[i]);
+				for(int64_t d = 0, w = m_cumsum[i + 1] - m_cumsum[i]; d < w; ++ d)
+					r_columns.row(int(n_dst + size_t(d))) = X.row(int(m_cumsum[i] + d));
+			}
+		}
+		return true;
+	}
+
+	/** @brief Marginal_Blocks() on the gathered values */
+	bool Marginal_Blocks_Gathered(std::vector<Eigen::MatrixXd> &r_blocks, const CUberBlockMatrix &r_lambda,
+		const std::vector<std::pair<size_t, size_t> > &r_pairs, TBlocksEntry p_blocks, const char *p_s_class) // throw(std::bad_alloc, std::runtime_error)
+	{
+		const size_t n = r_lambda.n_BlockColumn_Num();
+		const std::vector<size_t> inv_order(Inverse_Order(n));
+		// the library's block (r', c') of a reordered lambda is lambda's own block (r, c), rows and columns as the caller
+		// names them: a pair the ordering turns around (r < c, r' > c') is one the library writes transposed itself
+		std::vector<int64_t> rows(r_pairs.size()), cols(r_pairs.size());
+		size_t n_out = 0;
+		for(size_t k = 0; k < r_pairs.size(); ++ k) {
+			const size_t r = r_pairs[k].first, c = r_pairs[k].second;
+			if(r >= n || c >= n)
+				throw std::runtime_error(std::string(p_s_class) + "::Marginal_Blocks: block column index out of range");
+			rows[k] = int64_t(inv_order[r]);
+			cols[k] = int64_t(inv_order[c]);
+			n_out += r_lambda.n_BlockColumn_Column_Num(r) * r_lambda.n_BlockColumn_Column_Num(c);
+		}
+		std::vector<double> flat(std::max(n_out, size_t(1)));
+		const int n_result = (*p_blocks)(m_p_solver, m_p_values, int64_t(r_pairs.size()),
+			rows.empty()? 0 : &rows[0], cols.empty()? 0 : &cols[0], &flat[0]);
+		if(n_result == SLAMPP_HIP_NOT_POSDEF)
+			return false;
+		Throw_On_Error(n_result);
+		r_blocks.resize(r_pairs.size());
+		const double *p_src = &flat[0];
+		for(size_t k = 0; k < r_pairs.size(); ++ k) {
+			const size_t dr = r_lambda.n_BlockColumn_Column_Num(r_pairs[k].first), dc = r_lambda.n_BlockColumn_Column_Num(r_pairs[k].second);
+			r_blocks[k] = Eigen::Map<const Eigen::MatrixXd>(p_src, dr, dc); // (column-major, as the library writes it)
+			p_src += dr * dc;
+		}
+		return true;
+	}
+
+	/** @brief Joint_Marginal(): refuses an empty set of block columns and one with a repeat (before lambda is looked at) */
+	static void Check_Joint_Columns(const std::vector<size_t> &r_block_columns, const char *p_s_class) // throw(std::bad_alloc, std::runtime_error)
+	{
+		std::vector<size_t> sorted(r_block_columns);
+		std::sort(sorted.begin(), sorted.end());
+		if(sorted.empty() || std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+			throw std::runtime_error(std::string(p_s_class) + "::Joint_Marginal: an empty set of block columns, or one listed twice");
+	}
+
+	/** @brief Joint_Marginal() on the gathered values: the blocks at the upper pairs (a <= b, column by column) and their mirror images */
+	bool Joint_Marginal_Gathered(Eigen::MatrixXd &r_joint, const CUberBlockMatrix &r_lambda,
+		const std::vector<size_t> &r_block_columns, TBlocksEntry p_blocks, const char *p_s_class) // throw(std::bad_alloc, std::runtime_error)
+	{
+		const size_t n_cols = r_block_columns.size();
+		std::vector<std::pair<size_t, size_t> > pairs;
+		for(size_t b = 0; b < n_cols; ++ b) {
+			for(size_t a = 0; a <= b; ++ a)
+				pairs.push_back(std::make_pair(r_block_columns[a], r_block_columns[b]));
+		}
+		std::vector<Eigen::MatrixXd> blocks;
+		if(!Marginal_Blocks_Gathered(blocks, r_lambda, pairs, p_blocks, p_s_class))
+			return false;
+		std::vector<size_t> off(n_cols + 1, 0);
+		for(size_t a = 0; a < n_cols; ++ a)
+			off[a + 1] = off[a] + r_lambda.n_BlockColumn_Column_Num(r_block_columns[a]);
+		r_joint.resize(off.back(), off.back());
+		for(size_t b = 0, k = 0; b < n_cols; ++ b) {
+			for(size_t a = 0; a <= b; ++ a, ++ k) {
+				r_joint.block(off[a], off[b], off[a + 1] - off[a], off[b + 1] - off[b]) = blocks[k];
+				if(a != b)
+					r_joint.block(off[b], off[a], off[b + 1] - off[b], off[a + 1] - off[a]) = blocks[k].transpose();
+			}
+		}
+		for(size_t c = 0; c < size_t(r_joint.cols()); ++ c) { // (the diagonal blocks: the upper triangle mirrored, symmetric bit for bit)
+			for(size_t r = c + 1; r < size_t(r_joint.rows()); ++ r)
+				r_joint(r, c) = r_joint(c, r);
 		}
 		return true;
 	}
@@ -872,10 +1046,7 @@ public:
 		size_t n_at = 0;
 		for(size_t i = 0; i < n; ++ i) {
 			const size_t d = r_lambda.n_BlockColumn_Column_Num(i);
-			double *p_dest = r_marginals.p_GetBlock_Log(i, i, d, d, true, false);
-			if(!p_dest)
-				throw std::runtime_error("CLinearSolver_HIP: cannot write the marginals");
-			std::copy(&cov[n_at], &cov[n_at + d * d], p_dest);
+			Put_Block(r_marginals, i, i, d, d, &cov[n_at], "CLinearSolver_HIP");
 			n_at += d * d;
 		}
 		return true;
@@ -911,75 +1082,14 @@ public:
 	bool Marginals(CUberBlockMatrix &r_marginals, const CUberBlockMatrix &r_lambda, EBlockMatrixPart n_part,
 		bool b_structure_of_lambda = false) // throw(std::bad_alloc, std::runtime_error)
 	{
-		const size_t n = r_lambda.n_BlockColumn_Num();
-		const bool b_full = (n_part & mpart_FullMatrix) == mpart_FullMatrix;
-		const bool b_last_col = b_full || (n_part & mpart_LastColumn) != 0;
-		const bool b_last_block = b_last_col || (n_part & mpart_LastBlock) != 0;
-		const bool b_diag = b_full || (n_part & mpart_Diagonal) != 0;
-		if((n_part & mpart_Column) && !b_full)
-			throw std::runtime_error("CLinearSolver_HIP::Marginals: mpart_Column does not say which column (use Marginal_Columns)");
-		r_lambda.CopyLayoutTo(r_marginals); // (blocks are then allocated anywhere in lambda's layout, in any order)
-		if(!n)
-			return true;
-		std::vector<double> v;
-		// blocks of lambda's pattern (the diagonal is among them), then the block columns asked for
-		bool b_have_factor = false;
-		if(b_structure_of_lambda || (b_diag && !b_full)) {
-			Gather_Or_Reanalyze(r_lambda, [&]() { SymbolicDecomposition_Blocky(r_lambda); });
-			if(!m_order.empty())
-				throw std::runtime_error("CLinearSolver_HIP::Marginals: a reordered structure");
-			size_t n_values = 0;
-			for(size_t j = 0; j < n; ++ j) {
-				for(size_t k = 0, m = r_lambda.n_BlockColumn_Block_Num(j); k < m; ++ k)
-					n_values += r_lambda.n_BlockColumn_Column_Num(r_lambda.n_Block_Row(j, k)) * r_lambda.n_BlockColumn_Column_Num(j);
-			}
-			v.resize(n_values);
-			const int n_result = slampp_hip_marginals_pattern(m_p_solver, m_p_values, v.empty()? 0 : &v[0]);
-			if(n_result == SLAMPP_HIP_NOT_POSDEF)
-				return false;
-			Throw_On_Error(n_result);
-			b_have_factor = true;
-			size_t n_at = 0;
-			for(size_t j = 0; j < n; ++ j) {
-				const size_t dj = r_lambda.n_BlockColumn_Column_Num(j);
-				for(size_t k = 0, m = r_lambda.n_BlockColumn_Block_Num(j); k < m; ++ k) {
-					const size_t i = r_lambda.n_Block_Row(j, k), di = r_lambda.n_BlockColumn_Column_Num(i);
-					if(b_structure_of_lambda || i == j)
-						Put_Block(r_marginals, i, j, di, dj, &v[n_at]);
-					n_at += di * dj;
-				}
-			}
+		Check_Parts(n_part, p_s_Class());
+		if(!r_lambda.n_BlockColumn_Num()) {
+			r_lambda.CopyLayoutTo(r_marginals);
+			return true; // (nothing to analyze)
 		}
-		std::vector<int64_t> cols;
-		if(b_full) {
-			for(size_t j = 0; j < n; ++ j)
-				cols.push_back(int64_t(j));
-		} else if(b_last_block)
-			cols.push_back(int64_t(n - 1));
-		for(size_t c0 = 0; c0 < cols.size();) { // at most 48 scalar columns at a time (one pass of the library)
-			size_t c1 = c0, n_k = 0;
-			while(c1 < cols.size() && (c1 == c0 || n_k + r_lambda.n_BlockColumn_Column_Num(size_t(cols[c1])) <= 48))
-				n_k += r_lambda.n_BlockColumn_Column_Num(size_t(cols[c1 ++]));
-			Eigen::MatrixXd X;
-			if(!Columns(X, r_lambda, std::vector<int64_t>(cols.begin() + c0, cols.begin() + c1), b_have_factor))
-				return false;
-			b_have_factor = true;
-			size_t n_col = 0;
-			for(size_t q = c0; q < c1; ++ q) {
-				const size_t j = size_t(cols[q]), dj = r_lambda.n_BlockColumn_Column_Num(j);
-				for(size_t i = b_last_col? 0 : j; i <= j; ++ i) { // (mpart_LastBlock alone: the diagonal block only)
-					const size_t di = r_lambda.n_BlockColumn_Column_Num(i), b0 = r_lambda.n_BlockColumn_Base(i);
-					std::vector<double> blk(di * dj);
-					for(size_t c = 0; c < dj; ++ c)
-						for(size_t r = 0; r < di; ++ r)
-							blk[r + c * di] = X(b0 + r, n_col + c);
-					Put_Block(r_marginals, i, j, di, dj, &blk[0]);
-				}
-				n_col += dj;
-			}
-			c0 = c1;
-		}
-		return true;
+		Gather_Or_Reanalyze(r_lambda, [&]() { SymbolicDecomposition_Blocky(r_lambda); });
+		return Marginals_Gathered(r_marginals, r_lambda, n_part, b_structure_of_lambda, &slampp_hip_marginals_pattern,
+			&slampp_hip_marginal_columns, p_s_Class());
 	}
 
 	/**
@@ -996,7 +1106,9 @@ public:
 	bool Marginal_Columns(Eigen::MatrixXd &r_columns, const CUberBlockMatrix &r_lambda,
 		const std::vector<size_t> &r_block_columns) // throw(std::bad_alloc, std::runtime_error)
 	{
-		return Columns(r_columns, r_lambda, std::vector<int64_t>(r_block_columns.begin(), r_block_columns.end()), false);
+		Gather_Or_Reanalyze(r_lambda, [&]() { SymbolicDecomposition_Blocky(r_lambda); });
+		return Columns_Gathered(r_columns, r_lambda, std::vector<int64_t>(r_block_columns.begin(), r_block_columns.end()), false,
+			&slampp_hip_marginal_columns, p_s_Class());
 	}
 
 	/**
@@ -1015,31 +1127,7 @@ public:
 		const std::vector<std::pair<size_t, size_t> > &r_pairs) // throw(std::bad_alloc, std::runtime_error)
 	{
 		Gather_Or_Reanalyze(r_lambda, [&]() { SymbolicDecomposition_Blocky(r_lambda); });
-		if(!m_order.empty())
-			throw std::runtime_error("CLinearSolver_HIP::Marginal_Blocks: a reordered structure");
-		std::vector<int64_t> rows(r_pairs.size()), cols(r_pairs.size());
-		size_t n_out = 0;
-		for(size_t k = 0; k < r_pairs.size(); ++ k) {
-			if(r_pairs[k].first >= r_lambda.n_BlockColumn_Num() || r_pairs[k].second >= r_lambda.n_BlockColumn_Num())
-				throw std::runtime_error("CLinearSolver_HIP::Marginal_Blocks: block column index out of range");
-			rows[k] = int64_t(r_pairs[k].first);
-			cols[k] = int64_t(r_pairs[k].second);
-			n_out += r_lambda.n_BlockColumn_Column_Num(r_pairs[k].first) * r_lambda.n_BlockColumn_Column_Num(r_pairs[k].second);
-		}
-		std::vector<double> flat(std::max(n_out, size_t(1)));
-		const int n_result = slampp_hip_marginal_blocks(m_p_solver, m_p_values, int64_t(r_pairs.size()),
-			rows.empty()? 0 : &rows[0], cols.empty()? 0 : &cols[0], &flat[0]);
-		if(n_result == SLAMPP_HIP_NOT_POSDEF)
-			return false;
-		Throw_On_Error(n_result);
-		r_blocks.resize(r_pairs.size());
-		const double *p_src = &flat[0];
-		for(size_t k = 0; k < r_pairs.size(); ++ k) {
-			const size_t dr = r_lambda.n_BlockColumn_Column_Num(r_pairs[k].first), dc = r_lambda.n_BlockColumn_Column_Num(r_pairs[k].second);
-			r_blocks[k] = Eigen::Map<const Eigen::MatrixXd>(p_src, dr, dc); // (column-major, as the library writes it)
-			p_src += dr * dc;
-		}
-		return true;
+		return Marginal_Blocks_Gathered(r_blocks, r_lambda, r_pairs, &slampp_hip_marginal_blocks, p_s_Class());
 	}
 
 	/**
@@ -1056,50 +1144,17 @@ public:
 	bool Joint_Marginal(Eigen::MatrixXd &r_joint, const CUberBlockMatrix &r_lambda,
 		const std::vector<size_t> &r_block_columns) // throw(std::bad_alloc, std::runtime_error)
 	{
-		std::vector<std::pair<size_t, size_t> > pairs;
-		Joint_Marginal_Pairs(pairs, r_block_columns, "CLinearSolver_HIP::Joint_Marginal");
-		std::vector<Eigen::MatrixXd> blocks;
-		if(!Marginal_Blocks(blocks, r_lambda, pairs))
-			return false;
-		Joint_Marginal_Fill(r_joint, r_lambda, r_block_columns, blocks);
-		return true;
+		Check_Joint_Columns(r_block_columns, p_s_Class());
+		Gather_Or_Reanalyze(r_lambda, [&]() { SymbolicDecomposition_Blocky(r_lambda); });
+		return Joint_Marginal_Gathered(r_joint, r_lambda, r_block_columns, &slampp_hip_marginal_blocks, p_s_Class());
 	}
 
 protected:
-	/** @brief block columns of the inverse; b_reuse_factor: the factor the last call left in place (no new factorization) */
-	bool Columns(Eigen::MatrixXd &r_columns, const CUberBlockMatrix &r_lambda, const std::vector<int64_t> &r_cols,
-		bool b_reuse_factor) // throw(std::bad_alloc, std::runtime_error)
+	/** @brief the class name in the texts of the covariance members' exceptions */
+	static const char *p_s_Class()
 	{
-		if(!b_reuse_factor) {
-			Gather_Or_Reanalyze(r_lambda, [&]() { SymbolicDecomposition_Blocky(r_lambda); });
-			if(!m_order.empty())
-				throw std::runtime_error("CLinearSolver_HIP::Marginal_Columns: a reordered structure");
-		}
-		size_t n_k = 0;
-		for(size_t i = 0; i < r_cols.size(); ++ i) {
-			if(r_cols[i] < 0 || size_t(r_cols[i]) >= r_lambda.n_BlockColumn_Num())
-				throw std::runtime_error("CLinearSolver_HIP::Marginal_Columns: block column index out of range");
-			n_k += r_lambda.n_BlockColumn_Column_Num(size_t(r_cols[i]));
-		}
-		r_columns.resize(r_lambda.n_Column_Num(), n_k); // (column-major, as the library writes it)
-		const int n_result = slampp_hip_marginal_columns(m_p_solver, b_reuse_factor? 0 : m_p_values, int(r_cols.size()),
-			r_cols.empty()? 0 : &r_cols[0], r_columns.data());
-		if(n_result == SLAMPP_HIP_NOT_POSDEF)
-			return false;
-		Throw_On_Error(n_result);
-		return true;
+		return "CLinearSolver_HIP";
 	}
-
-	/** @brief writes a di x dj column-major block at (i, j) of r_m */
-	static void Put_Block(CUberBlockMatrix &r_m, size_t i, size_t j, size_t di, size_t dj, const double *p_src)
-	{
-		double *p_dest = r_m.p_GetBlock_Log(i, j, di, dj, true, false);
-		if(!p_dest)
-			throw std::runtime_error("CLinearSolver_HIP: cannot write the marginals");
-		std::copy(p_src, p_src + di * dj, p_dest);
-	}
-
-public:
 };
 
 /**
@@ -1350,66 +1405,11 @@ public:
 	bool Marginals(CUberBlockMatrix &r_marginals, const CUberBlockMatrix &r_lambda, EBlockMatrixPart n_part,
 		bool b_structure_of_lambda = false) // throw(std::bad_alloc, std::runtime_error)
 	{
-		const size_t n = r_lambda.n_BlockColumn_Num();
-		const bool b_full = (n_part & mpart_FullMatrix) == mpart_FullMatrix;
-		const bool b_last_col = b_full || (n_part & mpart_LastColumn) != 0;
-		const bool b_last_block = b_last_col || (n_part & mpart_LastBlock) != 0;
-		const bool b_diag = b_full || (n_part & mpart_Diagonal) != 0;
-		if((n_part & mpart_Column) && !b_full)
-			throw std::runtime_error("CLinearSolver_Schur_HIP::Marginals: mpart_Column does not say which column (use Marginal_Columns)");
+		Check_Parts(n_part, p_s_Class());
 		if(!Gather_For_Covariances(r_lambda))
 			return m_sparse_fallback.Marginals(r_marginals, r_lambda, n_part, b_structure_of_lambda);
-		r_lambda.CopyLayoutTo(r_marginals);
-		bool b_have_factor = false;
-		if(b_structure_of_lambda || (b_diag && !b_full)) { // lambda's pattern (the diagonal is among it)
-			std::vector<double> v(m_n_value_num);
-			const int n_result = slampp_hip_schur_marginals_pattern(m_p_solver, m_p_values, v.empty()? 0 : &v[0]);
-			if(n_result == SLAMPP_HIP_NOT_POSDEF)
-				return false;
-			Throw_On_Error(n_result);
-			b_have_factor = true;
-			size_t n_at = 0;
-			for(size_t j = 0; j < n; ++ j) { // the library's block order
-				const size_t dj = size_t(m_cumsum[j + 1] - m_cumsum[j]);
-				for(int64_t k = m_bcol_ptr[j]; k < m_bcol_ptr[j + 1]; ++ k) {
-					const size_t i = size_t(m_brow[size_t(k)]), di = size_t(m_cumsum[i + 1] - m_cumsum[i]);
-					if(b_structure_of_lambda || i == j)
-						Put_Library_Block(r_marginals, i, j, di, dj, &v[n_at]);
-					n_at += di * dj;
-				}
-			}
-		}
-		std::vector<int64_t> cols;
-		if(b_full) {
-			for(size_t j = 0; j < n; ++ j)
-				cols.push_back(int64_t(j));
-		} else if(b_last_block)
-			cols.push_back(int64_t(n - 1));
-		for(size_t c0 = 0; c0 < cols.size();) { // at most 48 scalar columns at a time (one pass of the library)
-			size_t c1 = c0, n_k = 0;
-			while(c1 < cols.size() && (c1 == c0 || n_k + r_lambda.n_BlockColumn_Column_Num(size_t(cols[c1])) <= 48))
-				n_k += r_lambda.n_BlockColumn_Column_Num(size_t(cols[c1 ++]));
-			Eigen::MatrixXd X;
-			if(!Columns_Gathered(X, r_lambda, std::vector<int64_t>(cols.begin() + c0, cols.begin() + c1), b_have_factor))
-				return false;
-			b_have_factor = true;
-			size_t n_col = 0;
-			for(size_t q = c0; q < c1; ++ q) {
-				const size_t j = size_t(cols[q]), dj = r_lambda.n_BlockColumn_Column_Num(j);
-				for(size_t i = b_last_col? 0 : j; i <= j; ++ i) { // (mpart_LastBlock alone: the diagonal block only)
-					const size_t di = r_lambda.n_BlockColumn_Column_Num(i), b0 = r_lambda.n_BlockColumn_Base(i);
-					double *p_dest = r_marginals.p_GetBlock_Log(i, j, di, dj, true, false);
-					if(!p_dest)
-						throw std::runtime_error("CLinearSolver_Schur_HIP: cannot write the marginals");
-					for(size_t c = 0; c < dj; ++ c)
-						for(size_t r = 0; r < di; ++ r)
-							p_dest[r + c * di] = X(b0 + r, n_col + c);
-				}
-				n_col += dj;
-			}
-			c0 = c1;
-		}
-		return true;
+		return Marginals_Gathered(r_marginals, r_lambda, n_part, b_structure_of_lambda, &slampp_hip_schur_marginals_pattern,
+			&slampp_hip_schur_marginal_columns, p_s_Class());
 	}
 
 	/**
@@ -1430,7 +1430,8 @@ public:
 	{
 		if(!Gather_For_Covariances(r_lambda))
 			return m_sparse_fallback.Marginal_Columns(r_columns, r_lambda, r_block_columns);
-		return Columns_Gathered(r_columns, r_lambda, std::vector<int64_t>(r_block_columns.begin(), r_block_columns.end()), false);
+		return Columns_Gathered(r_columns, r_lambda, std::vector<int64_t>(r_block_columns.begin(), r_block_columns.end()), false,
+			&slampp_hip_schur_marginal_columns, p_s_Class());
 	}
 
 	/**
@@ -1452,36 +1453,7 @@ public:
 	{
 		if(!Gather_For_Covariances(r_lambda))
 			return m_sparse_fallback.Marginal_Blocks(r_blocks, r_lambda, r_pairs);
-		const size_t n = r_lambda.n_BlockColumn_Num();
-		std::vector<size_t> inv_order(m_order.size());
-		for(size_t i = 0; i < m_order.size(); ++ i)
-			inv_order[m_order[i]] = i;
-		// the library's block (r', c') of a reordered lambda is lambda's own block (r, c), rows and columns as the caller
-		// names them: a pair the ordering turns around (r < c, r' > c') is one the library writes transposed itself
-		std::vector<int64_t> rows(r_pairs.size()), cols(r_pairs.size());
-		size_t n_out = 0;
-		for(size_t k = 0; k < r_pairs.size(); ++ k) {
-			const size_t r = r_pairs[k].first, c = r_pairs[k].second;
-			if(r >= n || c >= n)
-				throw std::runtime_error("CLinearSolver_Schur_HIP::Marginal_Blocks: block column index out of range");
-			rows[k] = int64_t(m_order.empty()? r : inv_order[r]);
-			cols[k] = int64_t(m_order.empty()? c : inv_order[c]);
-			n_out += r_lambda.n_BlockColumn_Column_Num(r) * r_lambda.n_BlockColumn_Column_Num(c);
-		}
-		std::vector<double> flat(std::max(n_out, size_t(1)));
-		const int n_result = slampp_hip_schur_marginal_blocks(m_p_solver, m_p_values, int64_t(r_pairs.size()),
-			rows.empty()? 0 : &rows[0], cols.empty()? 0 : &cols[0], &flat[0]);
-		if(n_result == SLAMPP_HIP_NOT_POSDEF)
-			return false;
-		Throw_On_Error(n_result);
-		r_blocks.resize(r_pairs.size());
-		const double *p_src = &flat[0];
-		for(size_t k = 0; k < r_pairs.size(); ++ k) {
-			const size_t dr = r_lambda.n_BlockColumn_Column_Num(r_pairs[k].first), dc = r_lambda.n_BlockColumn_Column_Num(r_pairs[k].second);
-			r_blocks[k] = Eigen::Map<const Eigen::MatrixXd>(p_src, dr, dc); // (column-major, as the library writes it)
-			p_src += dr * dc;
-		}
-		return true;
+		return Marginal_Blocks_Gathered(r_blocks, r_lambda, r_pairs, &slampp_hip_schur_marginal_blocks, p_s_Class());
 	}
 
 	/**
@@ -1499,13 +1471,10 @@ public:
 	bool Joint_Marginal(Eigen::MatrixXd &r_joint, const CUberBlockMatrix &r_lambda,
 		const std::vector<size_t> &r_block_columns) // throw(std::bad_alloc, std::runtime_error)
 	{
-		std::vector<std::pair<size_t, size_t> > pairs;
-		Joint_Marginal_Pairs(pairs, r_block_columns, "CLinearSolver_Schur_HIP::Joint_Marginal");
-		std::vector<Eigen::MatrixXd> blocks;
-		if(!Marginal_Blocks(blocks, r_lambda, pairs))
-			return false;
-		Joint_Marginal_Fill(r_joint, r_lambda, r_block_columns, blocks);
-		return true;
+		Check_Joint_Columns(r_block_columns, p_s_Class());
+		if(!Gather_For_Covariances(r_lambda))
+			return m_sparse_fallback.Joint_Marginal(r_joint, r_lambda, r_block_columns);
+		return Joint_Marginal_Gathered(r_joint, r_lambda, r_block_columns, &slampp_hip_schur_marginal_blocks, p_s_Class());
 	}
 
 protected:
@@ -1519,60 +1488,11 @@ protected:
 		return Gather_Or_Reanalyze(r_lambda, [&]() { SymbolicDecomposition_Blocky(r_lambda, true); });
 	}
 
-	/**
-	 *	@brief block columns r_cols (lambda's indices) of the inverse, with the values Gather_For_Covariances() staged;
-	 *		b_reuse_factor: the reduced system's factor the previous covariance call left (no new factorization)
-	 */
-	bool Columns_Gathered(Eigen::MatrixXd &r_columns, const CUberBlockMatrix &r_lambda, const std::vector<int64_t> &r_cols,
-		bool b_reuse_factor) // throw(std::bad_alloc, std::runtime_error)
+	/** @brief the class name in the texts of the covariance members' exceptions */
+	static const char *p_s_Class()
 	{
-		const size_t n = r_lambda.n_BlockColumn_Num();
-		std::vector<size_t> inv_order(m_order.size());
-		for(size_t i = 0; i < m_order.size(); ++ i)
-			inv_order[m_order[i]] = i;
-		std::vector<int64_t> lib_cols(r_cols.size());
-		size_t n_k = 0;
-		for(size_t i = 0; i < r_cols.size(); ++ i) {
-			if(r_cols[i] < 0 || size_t(r_cols[i]) >= n)
-				throw std::runtime_error("CLinearSolver_Schur_HIP::Marginal_Columns: block column index out of range");
-			lib_cols[i] = m_order.empty()? r_cols[i] : int64_t(inv_order[size_t(r_cols[i])]);
-			n_k += r_lambda.n_BlockColumn_Column_Num(size_t(r_cols[i]));
-		}
-		Eigen::MatrixXd X(r_lambda.n_Column_Num(), n_k); // (column-major, as the library writes it; rows in its order)
-		const int n_result = slampp_hip_schur_marginal_columns(m_p_solver, b_reuse_factor? 0 : m_p_values, int(lib_cols.size()),
-			lib_cols.empty()? 0 : &lib_cols[0], X.data());
-		if(n_result == SLAMPP_HIP_NOT_POSDEF)
-			return false;
-		Throw_On_Error(n_result);
-		if(m_order.empty())
-			r_columns.swap(X);
-		else { // rows back to lambda's scalar order
-			r_columns.resize(X.rows(), X.cols());
-			for(size_t i = 0; i < n; ++ i) {
-				const size_t n_dst = r_lambda.n_BlockColumn_Base(m_order[i]);
-				for(int64_t d = 0, w = m_cumsum[i + 1] - m_cumsum[i]; d < w; ++ d)
-					r_columns.row(int(n_dst + size_t(d))) = X.row(int(m_cumsum[i] + d));
-			}
-		}
-		return true;
+		return "CLinearSolver_Schur_HIP";
 	}
-
-	/** @brief writes the di x dj column-major block (i, j) of the library's order into r_m at lambda's block position,
-	 *	transposed where the ordering turns the pair into a lower block */
-	void Put_Library_Block(CUberBlockMatrix &r_m, size_t i, size_t j, size_t di, size_t dj, const double *p_src) const
-	{
-		const size_t oi = m_order.empty()? i : m_order[i], oj = m_order.empty()? j : m_order[j];
-		const bool b_tr = oi > oj;
-		double *p_dest = (b_tr)? r_m.p_GetBlock_Log(oj, oi, dj, di, true, false) : r_m.p_GetBlock_Log(oi, oj, di, dj, true, false);
-		if(!p_dest)
-			throw std::runtime_error("CLinearSolver_Schur_HIP: cannot write the marginals");
-		for(size_t c = 0; c < dj; ++ c) {
-			for(size_t r = 0; r < di; ++ r)
-				p_dest[(b_tr)? c + r * dj : r + c * di] = p_src[r + c * di];
-		}
-	}
-
-public:
 };
 
 /**

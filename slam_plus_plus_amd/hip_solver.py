@@ -690,11 +690,105 @@ class _SolverBase:
         self._check(self._lib.slampp_hip_set_allreduce(self._h, self._keepalive, None))
 
 
+    # ---- covariances: one implementation for both classes; ``_covariance_entries`` names the class's C entry points
+    # (pattern, columns, blocks) ----
+
+    def _covariance_values(self, lam, reuse_factor: bool, who: str):
+        """What a covariance call passes as values: ``None`` to reuse the factor in place (ValueError if this structure
+        has none), else the contiguous ``lam.values``, after the analysis of a new structure."""
+        if reuse_factor:
+            if not self._analyzed or self._structure_key != self._key(lam):
+                raise ValueError(f"{who}: there is no factorization of this structure to reuse")
+            return None
+        if not self._analyzed or self._structure_key != self._key(lam):
+            self.SymbolicDecomposition_Blocky(lam)
+        vals = np.ascontiguousarray(lam.values, dtype=np.float64)
+        if vals.shape != (self._n_values,):
+            raise ValueError("lam.values does not match the block structure")
+        return vals
+
+    def _marginals_pattern(self, lam, reuse_factor: bool = False) -> np.ndarray:
+        """Lambda^-1 at every stored block of Lambda: an array shaped like ``lam.values`` (same block order, each block
+        column-major), as CMarginals::Calculate_DenseMarginals_Recurrent_FBS gives it on a factor's pattern
+        (Marginals.h:1696) -- on Lambda's pattern here, which is the same under every ordering.
+        CLinearSolver_Schur_HIP: camera blocks, camera-landmark observation blocks, landmark diagonal blocks; it also takes
+        ``reuse_factor``: the reduced system's factor, C^-1 and W the previous Marginals_Pattern / Marginal_Columns call
+        left are used (ValueError if anything else factored since)."""
+        vals = self._covariance_values(lam, reuse_factor, "Marginals_Pattern")
+        out = np.empty(self._n_values, dtype=np.float64)
+        if not self._check(getattr(self._lib, self._covariance_entries[0])(self._h, _ptr(vals) if vals is not None else None,
+                                                                          _ptr(out))):
+            raise ArithmeticError("Marginals_Pattern: the system is not positive definite")
+        return out
+
+    def Marginal_Columns(self, lam, bcols, reuse_factor: bool = False) -> np.ndarray:
+        """Whole block columns ``bcols`` of Lambda^-1 (Schur mode: cameras and landmarks in any mix), shape (n_scalars, k),
+        k = the sum of their dimensions, in the listed order (the reference's mpart_Column / mpart_LastColumn,
+        IncrementalPolicy.h:366-372).  ``reuse_factor``: the factor the last solve or covariance call left in place is
+        used (Schur mode: what the previous Marginals_Pattern / Marginal_Columns call left), ``lam.values`` are not
+        factored again."""
+        cols = np.ascontiguousarray(np.atleast_1d(np.asarray(bcols, dtype=np.int64)))
+        vals = self._covariance_values(lam, reuse_factor, "Marginal_Columns")
+        dims = np.diff(np.asarray(lam.cumsum, dtype=np.int64))
+        k = int(dims[cols].sum()) if cols.size and cols.min() >= 0 and cols.max() < len(dims) else 0
+        out = np.empty((max(k, 1), int(lam.cumsum[-1])), dtype=np.float64)   # column-major (n_scalars, k) = row-major (k, n_scalars)
+        if not self._check(getattr(self._lib, self._covariance_entries[1])(self._h, _ptr(vals) if vals is not None else None,
+                                                                          int(cols.size), _ptr(cols), _ptr(out))):
+            raise ArithmeticError("Marginal_Columns: the system is not positive definite")
+        return out[:k].T
+
+    def Marginal_Blocks(self, lam, pairs, reuse_factor: bool = False) -> list:
+        """Blocks of Lambda^-1 at arbitrary pairs ``(r, c)`` of block columns, inside Lambda's pattern or outside it: a list
+        of d_r x d_c arrays in the listed order (what g2o's computeMarginals(spinv, blockIndices) answers).  No whole columns
+        are formed.  ``reuse_factor``: as for the class's Marginal_Columns.
+        CLinearSolver_HIP (slampp_hip_marginal_blocks): forward substitutions over the two columns' elimination-tree paths.
+        CLinearSolver_Schur_HIP (slampp_hip_schur_marginal_blocks): cameras and landmarks in any mix -- two cameras that share
+        no landmark, two landmarks, a camera and a landmark it does not observe; each block is summed from the dense inverse of
+        the reduced camera system S, or from forward substitutions on S's sparse factor over the paths of the cameras behind
+        the two columns.  ``reuse_factor``: what the previous Marginals_Pattern / Marginal_Columns / Marginal_Blocks call left.
+        A handle whose analysis went to the sparse path answers through it."""
+        pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        rows, cols = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        vals = self._covariance_values(lam, reuse_factor, "Marginal_Blocks")
+        dims = np.diff(np.asarray(lam.cumsum, dtype=np.int64))
+        in_range = pr.size and pr.min() >= 0 and pr.max() < len(dims)
+        sizes = dims[rows] * dims[cols] if in_range else np.zeros(0, dtype=np.int64)
+        off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        flat = np.empty(max(int(off[-1]), 1), dtype=np.float64)
+        if not self._check(getattr(self._lib, self._covariance_entries[2])(self._h, _ptr(vals) if vals is not None else None,
+                                                                          int(rows.size), _ptr(rows), _ptr(cols), _ptr(flat))):
+            raise ArithmeticError("Marginal_Blocks: the system is not positive definite")
+        return [flat[off[k]:off[k + 1]].reshape(int(dims[cols[k]]), int(dims[rows[k]])).T.copy() for k in range(rows.size)]
+
+    def Joint_Marginal(self, lam, bcols, reuse_factor: bool = False) -> np.ndarray:
+        """The joint marginal covariance of the block columns ``bcols`` (distinct, at least one): the dense symmetric k x k
+        matrix of Lambda^-1 at every pair of them, k = the sum of their dimensions, in the listed order (GTSAM's
+        jointMarginalCovariance).  The upper pairs are computed (Marginal_Blocks: in Schur mode the columns may be
+        cameras and landmarks in any mix) and mirrored."""
+        cols = [int(c) for c in np.atleast_1d(np.asarray(bcols, dtype=np.int64))]
+        if not cols or len(set(cols)) != len(cols):
+            raise ValueError("Joint_Marginal: an empty set of block columns, or one listed twice")
+        pairs = [(cols[a], cols[b]) for b in range(len(cols)) for a in range(b + 1)]
+        blocks = self.Marginal_Blocks(lam, pairs, reuse_factor)
+        dims = np.diff(np.asarray(lam.cumsum, dtype=np.int64))
+        off = np.concatenate([[0], np.cumsum(dims[cols])]).astype(np.int64)
+        joint = np.empty((int(off[-1]), int(off[-1])), dtype=np.float64)
+        for (a, b), blk in zip(((a, b) for b in range(len(cols)) for a in range(b + 1)), blocks):
+            joint[off[a]:off[a + 1], off[b]:off[b + 1]] = blk
+        return np.triu(joint) + np.triu(joint, 1).T   # (the lower triangle is never filled: symmetric bit for bit)
+
+
 class CLinearSolver_HIP(_SolverBase):
     """Sparse block Cholesky on the GPU; stands where CLinearSolver_CholMod / _CSparse / _UberBlock do."""
 
     _Tag = "CBlockwiseLinearSolverTag"   # LinearSolverTags.h:54
     _mode = MODE_SPARSE
+    _covariance_entries = ("slampp_hip_marginals_pattern", "slampp_hip_marginal_columns", "slampp_hip_marginal_blocks")
+
+    def Marginals_Pattern(self, lam) -> np.ndarray:
+        """Lambda^-1 at every stored block of Lambda (see _SolverBase._marginals_pattern; no ``reuse_factor`` here: the
+        sparse C entry refuses ``values = NULL``)."""
+        return self._marginals_pattern(lam)
 
 
 def _block_diagonal_marginals(self, lam):
@@ -721,105 +815,6 @@ def _block_diagonal_marginals(self, lam):
 
 
 CLinearSolver_HIP.Marginals = _block_diagonal_marginals
-
-
-def _pattern_marginals(self, lam) -> np.ndarray:
-    """Lambda^-1 at every stored block of Lambda: an array shaped like ``lam.values`` (same block order, each block
-    column-major), as CMarginals::Calculate_DenseMarginals_Recurrent_FBS gives it on a factor's pattern
-    (Marginals.h:1696) -- on Lambda's pattern here, which is the same under every ordering."""
-    if not self._analyzed or self._structure_key != self._key(lam):
-        self.SymbolicDecomposition_Blocky(lam)
-    vals = np.ascontiguousarray(lam.values, dtype=np.float64)
-    if vals.shape != (self._n_values,):
-        raise ValueError("lam.values does not match the block structure")
-    out = np.empty_like(vals)
-    if not self._check(self._lib.slampp_hip_marginals_pattern(self._h, _ptr(vals), _ptr(out))):
-        raise ArithmeticError("Marginals_Pattern: the system is not positive definite")
-    return out
-
-
-def _marginal_columns(self, lam, bcols, reuse_factor: bool = False) -> np.ndarray:
-    """Whole block columns ``bcols`` of Lambda^-1, shape (n_scalars, k), k = the sum of their dimensions, in the listed
-    order (the reference's mpart_Column / mpart_LastColumn, IncrementalPolicy.h:366-372).  ``reuse_factor``: the factor
-    the last solve or covariance call left in place is used, ``lam.values`` are not factored again."""
-    cols = np.ascontiguousarray(np.atleast_1d(np.asarray(bcols, dtype=np.int64)))
-    if reuse_factor:
-        if not self._analyzed or self._structure_key != self._key(lam):
-            raise ValueError("Marginal_Columns: there is no factorization of this structure to reuse")
-        vals = None
-    else:
-        if not self._analyzed or self._structure_key != self._key(lam):
-            self.SymbolicDecomposition_Blocky(lam)
-        vals = np.ascontiguousarray(lam.values, dtype=np.float64)
-        if vals.shape != (self._n_values,):
-            raise ValueError("lam.values does not match the block structure")
-    dims = np.diff(np.asarray(lam.cumsum, dtype=np.int64))
-    k = int(dims[cols].sum()) if cols.size and cols.min() >= 0 and cols.max() < len(dims) else 0
-    out = np.empty((max(k, 1), int(lam.cumsum[-1])), dtype=np.float64)   # column-major (n_scalars, k) = row-major (k, n_scalars)
-    if not self._check(self._lib.slampp_hip_marginal_columns(self._h, _ptr(vals) if vals is not None else None, int(cols.size),
-                                                             _ptr(cols), _ptr(out))):
-        raise ArithmeticError("Marginal_Columns: the system is not positive definite")
-    return out[:k].T
-
-
-CLinearSolver_HIP.Marginals_Pattern = _pattern_marginals
-CLinearSolver_HIP.Marginal_Columns = _marginal_columns
-
-
-def _marginal_blocks(self, lam, pairs, reuse_factor: bool = False) -> list:
-    """Blocks of Lambda^-1 at arbitrary pairs ``(r, c)`` of block columns, inside Lambda's pattern or outside it: a list
-    of d_r x d_c arrays in the listed order (what g2o's computeMarginals(spinv, blockIndices) answers).  No whole columns
-    are formed.  ``reuse_factor``: as for the class's Marginal_Columns.
-    CLinearSolver_HIP (slampp_hip_marginal_blocks): forward substitutions over the two columns' elimination-tree paths.
-    CLinearSolver_Schur_HIP (slampp_hip_schur_marginal_blocks): cameras and landmarks in any mix -- two cameras that share
-    no landmark, two landmarks, a camera and a landmark it does not observe; each block is summed from the dense inverse of
-    the reduced camera system S, or from forward substitutions on S's sparse factor over the paths of the cameras behind
-    the two columns.  ``reuse_factor``: what the previous Marginals_Pattern / Marginal_Columns / Marginal_Blocks call left.
-    A handle whose analysis went to the sparse path answers through it."""
-    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
-    rows, cols = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
-    if reuse_factor:
-        if not self._analyzed or self._structure_key != self._key(lam):
-            raise ValueError("Marginal_Blocks: there is no factorization of this structure to reuse")
-        vals = None
-    else:
-        if not self._analyzed or self._structure_key != self._key(lam):
-            self.SymbolicDecomposition_Blocky(lam)
-        vals = np.ascontiguousarray(lam.values, dtype=np.float64)
-        if vals.shape != (self._n_values,):
-            raise ValueError("lam.values does not match the block structure")
-    dims = np.diff(np.asarray(lam.cumsum, dtype=np.int64))
-    in_range = pr.size and pr.min() >= 0 and pr.max() < len(dims)
-    sizes = dims[rows] * dims[cols] if in_range else np.zeros(0, dtype=np.int64)
-    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    flat = np.empty(max(int(off[-1]), 1), dtype=np.float64)
-    if not self._check(getattr(self._lib, self._marginal_blocks_entry)(self._h, _ptr(vals) if vals is not None else None,
-                                                                       int(rows.size), _ptr(rows), _ptr(cols), _ptr(flat))):
-        raise ArithmeticError("Marginal_Blocks: the system is not positive definite")
-    return [flat[off[k]:off[k + 1]].reshape(int(dims[cols[k]]), int(dims[rows[k]])).T.copy() for k in range(rows.size)]
-
-
-def _joint_marginal(self, lam, bcols, reuse_factor: bool = False) -> np.ndarray:
-    """The joint marginal covariance of the block columns ``bcols`` (distinct, at least one): the dense symmetric k x k
-    matrix of Lambda^-1 at every pair of them, k = the sum of their dimensions, in the listed order (GTSAM's
-    jointMarginalCovariance).  The upper pairs are computed (the class's Marginal_Blocks: in Schur mode the columns may be
-    cameras and landmarks in any mix) and mirrored."""
-    cols = [int(c) for c in np.atleast_1d(np.asarray(bcols, dtype=np.int64))]
-    if not cols or len(set(cols)) != len(cols):
-        raise ValueError("Joint_Marginal: an empty set of block columns, or one listed twice")
-    pairs = [(cols[a], cols[b]) for b in range(len(cols)) for a in range(b + 1)]
-    blocks = self.Marginal_Blocks(lam, pairs, reuse_factor)
-    dims = np.diff(np.asarray(lam.cumsum, dtype=np.int64))
-    off = np.concatenate([[0], np.cumsum(dims[cols])]).astype(np.int64)
-    joint = np.empty((int(off[-1]), int(off[-1])), dtype=np.float64)
-    for (a, b), blk in zip(((a, b) for b in range(len(cols)) for a in range(b + 1)), blocks):
-        joint[off[a]:off[a + 1], off[b]:off[b + 1]] = blk
-    return np.triu(joint) + np.triu(joint, 1).T   # (the lower triangle is never filled: symmetric bit for bit)
-
-
-CLinearSolver_HIP._marginal_blocks_entry = "slampp_hip_marginal_blocks"
-CLinearSolver_HIP.Marginal_Blocks = _marginal_blocks
-CLinearSolver_HIP.Joint_Marginal = _joint_marginal
 
 
 class CLinearSolver_Schur_HIP(_SolverBase):
@@ -895,53 +890,9 @@ class CLinearSolver_Schur_HIP(_SolverBase):
         self._check(self._lib.slampp_hip_schur_marginals_device_async(self._h, values_ptr, cam_cov_ptr or None,
                                                                       point_cov_ptr or None))
 
-    def Marginals_Pattern(self, lam, reuse_factor: bool = False) -> np.ndarray:
-        """Lambda^-1 at every stored block of Lambda (camera blocks, camera-landmark observation blocks, landmark
-        diagonal blocks): an array shaped like ``lam.values``, each block column-major.  ``reuse_factor``: the reduced
-        system's factor, C^-1 and W the previous Marginals_Pattern / Marginal_Columns call left are used (ValueError
-        if anything else factored since)."""
-        if reuse_factor:
-            if not self._analyzed or self._structure_key != self._key(lam):
-                raise ValueError("Marginals_Pattern: there is no factorization of this structure to reuse")
-            vals = None
-        else:
-            if not self._analyzed or self._structure_key != self._key(lam):
-                self.SymbolicDecomposition_Blocky(lam, True)
-            vals = np.ascontiguousarray(lam.values, dtype=np.float64)
-            if vals.shape != (self._n_values,):
-                raise ValueError("lam.values does not match the block structure")
-        out = np.empty(self._n_values, dtype=np.float64)
-        if not self._check(self._lib.slampp_hip_schur_marginals_pattern(self._h, _ptr(vals) if vals is not None else None,
-                                                                        _ptr(out))):
-            raise ArithmeticError("Marginals_Pattern: the system is not positive definite")
-        return out
-
-    def Marginal_Columns(self, lam, bcols, reuse_factor: bool = False) -> np.ndarray:
-        """Whole block columns ``bcols`` (cameras and landmarks in any mix) of Lambda^-1, shape (n_scalars, k), in the
-        listed order.  ``reuse_factor``: what the previous Marginals_Pattern / Marginal_Columns call left is used."""
-        cols = np.ascontiguousarray(np.atleast_1d(np.asarray(bcols, dtype=np.int64)))
-        if reuse_factor:
-            if not self._analyzed or self._structure_key != self._key(lam):
-                raise ValueError("Marginal_Columns: there is no factorization of this structure to reuse")
-            vals = None
-        else:
-            if not self._analyzed or self._structure_key != self._key(lam):
-                self.SymbolicDecomposition_Blocky(lam, True)
-            vals = np.ascontiguousarray(lam.values, dtype=np.float64)
-            if vals.shape != (self._n_values,):
-                raise ValueError("lam.values does not match the block structure")
-        dims = np.diff(np.asarray(lam.cumsum, dtype=np.int64))
-        k = int(dims[cols].sum()) if cols.size and cols.min() >= 0 and cols.max() < len(dims) else 0
-        out = np.empty((max(k, 1), int(lam.cumsum[-1])), dtype=np.float64)   # column-major (n_scalars, k)
-        if not self._check(self._lib.slampp_hip_schur_marginal_columns(self._h, _ptr(vals) if vals is not None else None,
-                                                                      int(cols.size), _ptr(cols), _ptr(out))):
-            raise ArithmeticError("Marginal_Columns: the system is not positive definite")
-        return out[:k].T
-
-    # the sparse class's two methods over slampp_hip_schur_marginal_blocks (their docstrings describe both classes)
-    _marginal_blocks_entry = "slampp_hip_schur_marginal_blocks"
-    Marginal_Blocks = _marginal_blocks
-    Joint_Marginal = _joint_marginal
+    _covariance_entries = ("slampp_hip_schur_marginals_pattern", "slampp_hip_schur_marginal_columns",
+                           "slampp_hip_schur_marginal_blocks")
+    Marginals_Pattern = _SolverBase._marginals_pattern
 
 
 class CLambdaAssembly_HIP:

@@ -1,144 +1,55 @@
-// covariance_header_driver.cpp -- runs the covariance parts of include/slam/LinearSolver_HIP.h (Marginals with an
-// EBlockMatrixPart, Marginal_Columns) on the CPU against stand-ins for the C ABI: the stand-ins answer every covariance
-// request with a known symmetric matrix S(r, c), so the driver checks which blocks the header writes where, and with what.
-// Built and run by tests/test_covariance_header.py against the reference's block matrix.  Prints "ok" and exits 0.
-#include "slam/LinearSolver_HIP.h"
-#include <cmath>
-#include <map>
-#include <set>
+// covariance_header_driver.cpp -- runs the covariance members of both solver classes of include/slam/LinearSolver_HIP.h on
+// the CPU against the stand-ins for the C ABI of tests/capi_standins.h: "parts" runs Marginals with an EBlockMatrixPart and
+// Marginal_Columns, "pairs" runs Marginal_Blocks and Joint_Marginal; "sparse" takes CLinearSolver_HIP, "schur"
+// CLinearSolver_Schur_HIP on a BA lambda with the cameras first, one whose cameras and landmarks are interleaved (the class
+// reorders it: some pairs reach the library turned around) and one without a landmark part (the class's sparse solver
+// answers).  Built and run by tests/test_*covariance*_header.py against the reference's block matrix: the two words are its
+// arguments (none: everything).  Prints "ok" and exits 0.
+#include "capi_standins.h"
 
-// ---- stand-ins for the C ABI (what the header calls) ----
-
-struct slampp_hip_solver {
-	std::vector<int64_t> cumsum, bcol_ptr;
-	std::vector<int32_t> brow;
-	std::vector<double> values, rhs;
+struct TSystem {
+	std::vector<size_t> dims;
+	TBlockSet blocks; // of lambda (upper)
+	bool b_schur, b_flips; // with the Schur class: its Schur entries answer; the ordering turns some pairs around
+	const char *p_s_name;
 };
 
-static double S(int64_t r, int64_t c) // the "covariance": symmetric, every entry distinct
+static TSystem t_System(const char *p_s_name, const char *p_s_dims, const size_t (*p_blocks)[2], size_t n_block_num, bool b_schur, bool b_flips)
 {
-	const int64_t a = std::min(r, c), b = std::max(r, c);
-	return double(a) * 1009 + double(b) + 0.25;
+	TSystem t;
+	for(; *p_s_dims; ++ p_s_dims)
+		t.dims.push_back(size_t(*p_s_dims - '0'));
+	for(size_t c = 0; c < t.dims.size(); ++ c)
+		t.blocks.insert(std::make_pair(c, c));
+	for(size_t k = 0; k < n_block_num; ++ k)
+		t.blocks.insert(std::make_pair(p_blocks[k][0], p_blocks[k][1]));
+	t.b_schur = b_schur;
+	t.b_flips = b_flips;
+	t.p_s_name = p_s_name;
+	return t;
 }
 
-extern "C" {
-int slampp_hip_create(slampp_hip_solver **pp, int) { *pp = new slampp_hip_solver(); return SLAMPP_HIP_OK; }
-int slampp_hip_create_multi(slampp_hip_solver **pp, const int *, int) { *pp = new slampp_hip_solver(); return SLAMPP_HIP_OK; }
-int slampp_hip_group_info(const slampp_hip_solver *, int *p_n, int64_t *, int, const char **) { if(p_n) *p_n = 0; return SLAMPP_HIP_OK; }
-void slampp_hip_destroy(slampp_hip_solver *p) { delete p; }
-const char *slampp_hip_last_error(const slampp_hip_solver *) { return "stand-in"; }
-int slampp_hip_set_option(slampp_hip_solver *, const char *, int64_t) { return SLAMPP_HIP_OK; }
-int slampp_hip_set_structure(slampp_hip_solver *p, int64_t n, const int64_t *cs, const int64_t *ptr, const int32_t *brow)
-{
-	p->cumsum.assign(cs, cs + n + 1);
-	p->bcol_ptr.assign(ptr, ptr + n + 1);
-	p->brow.assign(brow, brow + ptr[n]);
-	int64_t n_values = 0;
-	for(int64_t c = 0; c < n; ++ c) {
-		for(int64_t b = ptr[c]; b < ptr[c + 1]; ++ b)
-			n_values += (cs[brow[b] + 1] - cs[brow[b]]) * (cs[c + 1] - cs[c]);
-	}
-	p->values.assign(size_t(n_values), 0.0);
-	p->rhs.assign(size_t(cs[n]), 0.0);
-	return SLAMPP_HIP_OK;
-}
-int slampp_hip_analyze(slampp_hip_solver *, int, int64_t) { return SLAMPP_HIP_OK; }
-int slampp_hip_host_staging(slampp_hip_solver *p, double **pv, double **pr) { *pv = &p->values[0]; *pr = &p->rhs[0]; return SLAMPP_HIP_OK; }
-int slampp_hip_upload_values_async(slampp_hip_solver *, int64_t, int64_t) { return SLAMPP_HIP_OK; }
-int slampp_hip_factor_solve(slampp_hip_solver *, const double *, double *, slampp_hip_times *) { return SLAMPP_HIP_ERR_UNSUPPORTED; }
-int slampp_hip_solve_marginal_poses(slampp_hip_solver *, const double *, double *) { return SLAMPP_HIP_ERR_UNSUPPORTED; }
-int slampp_hip_factorize(slampp_hip_solver *, const double *, double *) { return SLAMPP_HIP_ERR_UNSUPPORTED; }
-int slampp_hip_factor_structure(const slampp_hip_solver *, int64_t *, int64_t *, int64_t *, int32_t *, int32_t *, int64_t *, int32_t *,
-	int64_t *) { return SLAMPP_HIP_ERR_UNSUPPORTED; }
-int slampp_hip_schur_set_changed_points(slampp_hip_solver *, const int64_t *, int64_t) { return SLAMPP_HIP_ERR_UNSUPPORTED; }
-int slampp_hip_schur_marginals(slampp_hip_solver *, const double *, double *, double *) { return SLAMPP_HIP_ERR_UNSUPPORTED; }
-int slampp_hip_marginals(slampp_hip_solver *p, const double *, double *out)
-{
-	for(size_t c = 0; c + 1 < p->cumsum.size(); ++ c) {
-		const int64_t d = p->cumsum[c + 1] - p->cumsum[c];
-		for(int64_t q = 0; q < d; ++ q)
-			for(int64_t r = 0; r < d; ++ r)
-				*out ++ = S(p->cumsum[c] + r, p->cumsum[c] + q);
-	}
-	return SLAMPP_HIP_OK;
-}
-int slampp_hip_marginals_pattern(slampp_hip_solver *p, const double *, double *out)
-{
-	for(size_t c = 0; c + 1 < p->cumsum.size(); ++ c) {
-		for(int64_t b = p->bcol_ptr[c]; b < p->bcol_ptr[c + 1]; ++ b) {
-			const int64_t R = p->brow[size_t(b)], dr = p->cumsum[R + 1] - p->cumsum[R], dc = p->cumsum[c + 1] - p->cumsum[c];
-			for(int64_t q = 0; q < dc; ++ q)
-				for(int64_t r = 0; r < dr; ++ r)
-					*out ++ = S(p->cumsum[R] + r, p->cumsum[c] + q);
-		}
-	}
-	return SLAMPP_HIP_OK;
-}
-int slampp_hip_marginal_columns(slampp_hip_solver *p, const double *, int n_cols, const int64_t *bcols, double *out)
-{
-	const int64_t n = p->cumsum.back();
-	for(int i = 0; i < n_cols; ++ i) {
-		for(int64_t s = p->cumsum[size_t(bcols[i])]; s < p->cumsum[size_t(bcols[i]) + 1]; ++ s)
-			for(int64_t r = 0; r < n; ++ r)
-				*out ++ = S(r, s);
-	}
-	return SLAMPP_HIP_OK;
-}
-} // extern "C"
+// BA, cameras first: 3 cameras (6) with an odometry chain, 4 landmarks (3)
+static const size_t cameras_first[][2] = {{0, 1}, {1, 2}, {0, 3}, {1, 3}, {1, 4}, {2, 4}, {0, 5}, {2, 5}, {2, 6}};
+// BA, cameras (6) and landmarks (3) interleaved: the class reorders, the library sees the cameras first.  Landmark 1: cameras
+// 0, 2; landmark 3: cameras 2, 5; landmark 4: cameras 0, 5; landmark 6: camera 5; the camera chain
+static const size_t interleaved[][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 5}, {0, 4}, {4, 5}, {5, 6}, {0, 2}, {2, 5}};
+// no landmark part (every block column as wide): a chain with one closure; the Schur class's sparse solver answers, the same way
+static const size_t chain[][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {0, 3}};
+// mixed block sizes: a chain plus the chords (0, 3) and (2, 5)
+static const size_t mixed[][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {4, 5}, {0, 3}, {2, 5}};
 
-// ---- the checks ----
-
-static int n_failures = 0;
-#define CHECK(c) do { if(!(c)) { fprintf(stderr, "failed at line %d: %s\n", __LINE__, #c); ++ n_failures; } } while(0)
-
-// the blocks of r_m must be exactly r_expected (i, j) (upper triangle), each equal to S on its rows and columns
-static void Check_Blocks(const CUberBlockMatrix &r_m, const CUberBlockMatrix &r_lambda, const std::set<std::pair<size_t, size_t> > &r_expected,
-	const char *p_s_what)
+// every part combination and Marginal_Columns on one lambda
+template <class CSolver>
+static void Check_Parts(const TSystem &r_t)
 {
-	std::set<std::pair<size_t, size_t> > found;
-	CHECK(r_m.n_BlockColumn_Num() == r_lambda.n_BlockColumn_Num() && r_m.n_Column_Num() == r_lambda.n_Column_Num());
-	for(size_t j = 0; j < r_m.n_BlockColumn_Num(); ++ j) {
-		for(size_t k = 0; k < r_m.n_BlockColumn_Block_Num(j); ++ k) {
-			const size_t i = r_m.n_Block_Row(j, k);
-			found.insert(std::make_pair(i, j));
-			CUberBlockMatrix::_TyConstMatrixXdRef t_blk = r_m.t_Block_AtColumn(j, k);
-			const size_t r0 = r_lambda.n_BlockColumn_Base(i), c0 = r_lambda.n_BlockColumn_Base(j);
-			CHECK(size_t(t_blk.rows()) == r_lambda.n_BlockColumn_Column_Num(i) && size_t(t_blk.cols()) == r_lambda.n_BlockColumn_Column_Num(j));
-			for(int c = 0; c < t_blk.cols(); ++ c)
-				for(int r = 0; r < t_blk.rows(); ++ r)
-					CHECK(t_blk(r, c) == S(int64_t(r0 + r), int64_t(c0 + c)));
-		}
-	}
-	if(found != r_expected) {
-		fprintf(stderr, "%s: %d blocks, %d expected\n", p_s_what, int(found.size()), int(r_expected.size()));
-		++ n_failures;
-	}
-}
-
-int main()
-{
-	// lambda: 6 block columns of sizes 3, 2, 3, 3, 2, 3; a chain plus the chords (0, 3) and (2, 5)
-	const size_t dims[] = {3, 2, 3, 3, 2, 3}, n = 6;
-	std::set<std::pair<size_t, size_t> > lam_blocks;
-	for(size_t c = 0; c < n; ++ c) {
-		lam_blocks.insert(std::make_pair(c, c));
-		if(c)
-			lam_blocks.insert(std::make_pair(c - 1, c));
-	}
-	lam_blocks.insert(std::make_pair(size_t(0), size_t(3)));
-	lam_blocks.insert(std::make_pair(size_t(2), size_t(5)));
+	const bool b_schur = r_t.b_schur;
+	const std::vector<size_t> &r_dims = r_t.dims;
+	const size_t n = r_dims.size();
 	CUberBlockMatrix lambda;
-	for(size_t c = 0; c < n; ++ c) {
-		for(size_t r = 0; r <= c; ++ r) {
-			if(!lam_blocks.count(std::make_pair(r, c)))
-				continue;
-			double *p = lambda.p_GetBlock_Log(r, c, dims[r], dims[c], true, false);
-			CHECK(p != 0);
-			for(size_t e = 0; p && e < dims[r] * dims[c]; ++ e)
-				p[e] = (r == c && e % (dims[c] + 1) == 0)? 10.0 : 0.1;
-		}
-	}
-	std::set<std::pair<size_t, size_t> > diag, last_block, last_col, full;
+	Make_Lambda(lambda, r_dims, r_t.blocks);
+	Set_Library_Order(lambda, r_dims, b_schur);
+	TBlockSet diag, last_block, last_col, full;
 	for(size_t j = 0; j < n; ++ j) {
 		diag.insert(std::make_pair(j, j));
 		last_col.insert(std::make_pair(j, n - 1));
@@ -146,32 +57,38 @@ int main()
 			full.insert(std::make_pair(i, j));
 	}
 	last_block.insert(std::make_pair(n - 1, n - 1));
-	struct { int n_part; bool b_lambda; const std::set<std::pair<size_t, size_t> > *p_a, *p_b; const char *p_s_name; } cases[] = {
+	struct { int n_part; bool b_lambda; const TBlockSet *p_a, *p_b; const char *p_s_name; } cases[] = {
 		{mpart_LastBlock, false, &last_block, 0, "mpart_LastBlock"},
 		{mpart_LastColumn, false, &last_col, 0, "mpart_LastColumn"},
 		{mpart_Diagonal, false, &diag, 0, "mpart_Diagonal"},
 		{mpart_LastColumn | mpart_Diagonal, false, &last_col, &diag, "mpart_LastColumn | mpart_Diagonal"},
 		{mpart_LastBlock | mpart_Diagonal, false, &last_block, &diag, "mpart_LastBlock | mpart_Diagonal"},
 		{mpart_FullMatrix, false, &full, 0, "mpart_FullMatrix"},
-		{mpart_LastBlock, true, &last_block, &lam_blocks, "mpart_LastBlock + lambda's structure"},
-		{mpart_LastColumn, true, &last_col, &lam_blocks, "mpart_LastColumn + lambda's structure"},
-		{mpart_Nothing, true, &lam_blocks, 0, "lambda's structure"}
+		{mpart_FullMatrix, true, &full, 0, "mpart_FullMatrix + lambda's structure"},
+		{mpart_Diagonal, true, &diag, &r_t.blocks, "mpart_Diagonal + lambda's structure"},
+		{mpart_LastBlock, true, &last_block, &r_t.blocks, "mpart_LastBlock + lambda's structure"},
+		{mpart_LastColumn, true, &last_col, &r_t.blocks, "mpart_LastColumn + lambda's structure"},
+		{mpart_Nothing, true, &r_t.blocks, 0, "lambda's structure"}
 	};
-	CLinearSolver_HIP solver;
+	CSolver solver;
 	for(size_t t = 0; t < sizeof(cases) / sizeof(cases[0]); ++ t) {
-		std::set<std::pair<size_t, size_t> > expected(*cases[t].p_a);
+		TBlockSet expected(*cases[t].p_a);
 		if(cases[t].p_b)
 			expected.insert(cases[t].p_b->begin(), cases[t].p_b->end());
 		CUberBlockMatrix marginals;
 		bool b_ok = false;
+		const int n_calls_before = g_n_schur_calls;
 		try {
 			b_ok = solver.Marginals(marginals, lambda, EBlockMatrixPart(cases[t].n_part), cases[t].b_lambda);
 		} catch(std::exception &r_exc) {
-			fprintf(stderr, "%s: %s\n", cases[t].p_s_name, r_exc.what());
+			fprintf(stderr, "%s, %s: %s\n", r_t.p_s_name, cases[t].p_s_name, r_exc.what());
 		}
 		CHECK(b_ok);
-		if(b_ok)
-			Check_Blocks(marginals, lambda, expected, cases[t].p_s_name);
+		CHECK((g_n_schur_calls > n_calls_before) == b_schur);
+		if(b_ok) {
+			std::string s_name = std::string(r_t.p_s_name) + ", " + cases[t].p_s_name;
+			Check_Blocks(marginals, lambda, expected, s_name.c_str());
+		}
 	}
 	// mpart_Column does not say which column: refused, alone and in a union
 	const int column_parts[] = {mpart_Column, mpart_Column | mpart_Diagonal, mpart_Column | mpart_LastColumn};
@@ -185,17 +102,132 @@ int main()
 		}
 		CHECK(b_thrown);
 	}
-	// Marginal_Columns: n_scalars x k, the listed columns in order
-	Eigen::MatrixXd X;
+	// Marginal_Columns: n_scalars x k, the listed columns in order, rows in lambda's scalar order
 	std::vector<size_t> cols;
-	cols.push_back(4);
+	cols.push_back(n - 2);
 	cols.push_back(0);
+	cols.push_back(1);
+	Eigen::MatrixXd X;
 	CHECK(solver.Marginal_Columns(X, lambda, cols));
-	CHECK(size_t(X.rows()) == lambda.n_Column_Num() && X.cols() == 5);
-	for(int c = 0; c < X.cols(); ++ c) {
-		const int64_t s = (c < 2)? int64_t(lambda.n_BlockColumn_Base(4)) + c : c - 2;
-		for(int r = 0; r < X.rows(); ++ r)
-			CHECK(X(r, c) == S(r, s));
+	size_t n_k = 0;
+	for(size_t q = 0; q < cols.size(); ++ q)
+		n_k += r_dims[cols[q]];
+	CHECK(size_t(X.rows()) == lambda.n_Column_Num() && size_t(X.cols()) == n_k);
+	for(size_t q = 0, c = 0; q < cols.size() && size_t(X.cols()) == n_k; ++ q) {
+		for(size_t d = 0; d < r_dims[cols[q]]; ++ d, ++ c) {
+			const int64_t s = int64_t(lambda.n_BlockColumn_Base(cols[q]) + d);
+			for(int r = 0; r < X.rows(); ++ r)
+				CHECK(X(r, int(c)) == S(r, s));
+		}
+	}
+	bool b_thrown = false;
+	try {
+		std::vector<size_t> bad(1, n);
+		solver.Marginal_Columns(X, lambda, bad);
+	} catch(std::runtime_error&) {
+		b_thrown = true;
+	}
+	CHECK(b_thrown);
+}
+
+// Marginal_Blocks at every ordered pair of block columns (r > c and pairs outside lambda's pattern among them) and one
+// listed twice, and Joint_Marginal of a mixed set, on one lambda
+template <class CSolver>
+static void Check_Pairs(const TSystem &r_t)
+{
+	const bool b_schur = r_t.b_schur, b_flips = r_t.b_flips;
+	const std::vector<size_t> &r_dims = r_t.dims;
+	const size_t n = r_dims.size();
+	CUberBlockMatrix lambda;
+	Make_Lambda(lambda, r_dims, r_t.blocks);
+	Set_Library_Order(lambda, r_dims, b_schur);
+	CSolver solver;
+	std::vector<std::pair<size_t, size_t> > pairs;
+	for(size_t r = 0; r < n; ++ r)
+		for(size_t c = 0; c < n; ++ c)
+			pairs.push_back(std::make_pair(r, c));
+	pairs.push_back(std::make_pair(size_t(1), n - 1)); // listed twice
+	std::vector<Eigen::MatrixXd> blocks;
+	const int n_calls_before = g_n_schur_calls, n_flipped_before = g_n_flipped;
+	bool b_ok = false;
+	try {
+		b_ok = solver.Marginal_Blocks(blocks, lambda, pairs);
+	} catch(std::exception &r_exc) {
+		fprintf(stderr, "%s: Marginal_Blocks: %s\n", r_t.p_s_name, r_exc.what());
+	}
+	CHECK(b_ok && blocks.size() == pairs.size());
+	CHECK((g_n_schur_calls > n_calls_before) == b_schur);
+	CHECK((g_n_flipped > n_flipped_before) == b_flips);
+	for(size_t k = 0; b_ok && k < blocks.size(); ++ k) { // block (r, c) of lambda's own order, whatever the library's order is
+		const size_t r0 = lambda.n_BlockColumn_Base(pairs[k].first), c0 = lambda.n_BlockColumn_Base(pairs[k].second);
+		CHECK(size_t(blocks[k].rows()) == r_dims[pairs[k].first] && size_t(blocks[k].cols()) == r_dims[pairs[k].second]);
+		for(int c = 0; c < blocks[k].cols(); ++ c)
+			for(int r = 0; r < blocks[k].rows(); ++ r)
+				CHECK(blocks[k](r, c) == S(int64_t(r0 + r), int64_t(c0 + c)));
+	}
+	// Joint_Marginal: the listed columns in the listed order
+	std::vector<size_t> cols;
+	cols.push_back(n - 1); cols.push_back(0); cols.push_back(n - 2); cols.push_back(1);
+	std::vector<int64_t> scalars;
+	for(size_t q = 0; q < cols.size(); ++ q)
+		for(size_t d = 0; d < r_dims[cols[q]]; ++ d)
+			scalars.push_back(int64_t(lambda.n_BlockColumn_Base(cols[q]) + d));
+	Eigen::MatrixXd joint;
+	CHECK(solver.Joint_Marginal(joint, lambda, cols));
+	CHECK(size_t(joint.rows()) == scalars.size() && size_t(joint.cols()) == scalars.size());
+	for(size_t c = 0; c < scalars.size() && size_t(joint.cols()) == scalars.size(); ++ c)
+		for(size_t r = 0; r < scalars.size(); ++ r)
+			CHECK(joint(int(r), int(c)) == S(scalars[r], scalars[c]));
+	// refusals: an index out of range, a column listed twice, an empty set
+	const size_t bad_cols[][2] = {{0, n}, {1, 1}};
+	for(size_t t = 0; t < 3; ++ t) {
+		bool b_thrown = false;
+		try {
+			std::vector<size_t> bad;
+			if(t < 2)
+				bad.assign(bad_cols[t], bad_cols[t] + 2);
+			solver.Joint_Marginal(joint, lambda, bad);
+		} catch(std::runtime_error&) {
+			b_thrown = true;
+		}
+		CHECK(b_thrown);
+	}
+	bool b_thrown = false;
+	try {
+		std::vector<std::pair<size_t, size_t> > bad(1, std::make_pair(n, size_t(0)));
+		solver.Marginal_Blocks(blocks, lambda, bad);
+	} catch(std::runtime_error&) {
+		b_thrown = true;
+	}
+	CHECK(b_thrown);
+}
+
+int main(int n_arg_num, const char **p_arg_list)
+{
+	const std::string s_class = (n_arg_num == 3)? p_arg_list[1] : "both", s_what = (n_arg_num == 3)? p_arg_list[2] : "all";
+	if((n_arg_num != 1 && n_arg_num != 3) || (s_class != "sparse" && s_class != "schur" && s_class != "both") ||
+	   (s_what != "parts" && s_what != "pairs" && s_what != "all")) {
+		fprintf(stderr, "use: covariance_header_driver [sparse|schur parts|pairs]\n");
+		return 2;
+	}
+	const bool b_parts = s_what != "pairs", b_pairs = s_what != "parts";
+	std::vector<TSystem> systems;
+	systems.push_back(t_System("cameras first", "6663333", cameras_first, 9, true, false));
+	systems.push_back(t_System("interleaved", "6363363", interleaved, 9, true, true));
+	systems.push_back(t_System("no landmark part", "66666", chain, 5, false, false));
+	for(size_t i = 0; s_class != "sparse" && i < systems.size(); ++ i) {
+		if(b_parts)
+			Check_Parts<CLinearSolver_Schur_HIP<> >(systems[i]);
+		if(b_pairs)
+			Check_Pairs<CLinearSolver_Schur_HIP<> >(systems[i]);
+	}
+	if(s_class != "schur") { // (the sparse class takes lambda as it is: no Schur entry answers, nothing is turned around)
+		if(b_parts) {
+			Check_Parts<CLinearSolver_HIP>(t_System("mixed block sizes", "323323", mixed, 7, false, false));
+			Check_Parts<CLinearSolver_HIP>(systems[2]);
+		}
+		if(b_pairs)
+			Check_Pairs<CLinearSolver_HIP>(systems[2]);
 	}
 	if(n_failures) {
 		fprintf(stderr, "%d failures\n", n_failures);

@@ -1,16 +1,9 @@
 """The covariance parts of the header binding (include/slam/LinearSolver_HIP.h: Marginals with an EBlockMatrixPart,
 Marginal_Columns) compile against the reference's headers, with the include paths and defines oracle/Makefile.ref
 builds the drop-in driver with, and -- linked with the reference's block matrix that build() compiles into oracle/_ref
-and with stand-ins for the C ABI (tests/covariance_header_driver.cpp) -- write every requested part into the result.
+and with stand-ins for the C ABI (tests/capi_standins.h) -- write every requested part into the result.
 Skip where the reference's sources (or the archives built from them) are not present."""
-import os
-import re
-import shutil
-import subprocess
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from header_util import run_covariance_driver, syntax_check
 
 TU = r"""
 #include "slam/LinearSolver_HIP.h"
@@ -25,52 +18,13 @@ bool covariance_parts(CLinearSolver_HIP &r_solver, CUberBlockMatrix &r_marginals
 """
 
 
-def _makefile_vars():
-    text = open(os.path.join(ROOT, "oracle", "Makefile.ref")).read()
-    out = {}
-    for name in ("REF", "OUT", "OPT", "CDEFS", "INC", "CHOLMOD_DEFS"):
-        m = re.search(r"^%s\s*[?:]?=\s*(.*)$" % name, text, re.M)
-        assert m, name
-        out[name] = m.group(1).strip()
-    m = re.search(r"^REFLIBS\s*:=\s*((?:.*\\\n)*.*)$", text, re.M)
-    assert m, "REFLIBS"
-    out["REFLIBS"] = m.group(1).replace("\\\n", " ")
-    for name in ("OPT", "CDEFS", "INC", "CHOLMOD_DEFS", "REFLIBS"):
-        out[name] = out[name].replace("$(REF)", out["REF"]).replace("$(OUT)", os.path.join(ROOT, out["OUT"]))
-    return out
-
-
 def test_covariance_overloads_compile(tmp_path):
-    v = _makefile_vars()
-    if not os.path.isdir(os.path.join(v["REF"], "include", "slam")):
-        pytest.skip("the reference's headers are not present")
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    src = tmp_path / "covariance_tu.cpp"
-    src.write_text(TU)
-    cmd = ["g++", "-fsyntax-only", "-w"] + v["OPT"].split() + v["CDEFS"].split() + v["CHOLMOD_DEFS"].split() + \
-        ["-I" + os.path.join(ROOT, "include")] + v["INC"].split() + [str(src)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
+    syntax_check(tmp_path, "covariance_tu.cpp", TU)
 
 
-def test_covariance_parts_are_written(tmp_path):
+def test_covariance_parts_are_written(tmp_path_factory):
     """Every part of the Marginals overload -- mpart_LastBlock and mpart_LastColumn alone among them, whose first block
     lies outside an empty block layout -- and Marginal_Columns, run on the CPU against stand-ins for the C ABI that
-    answer with a known symmetric matrix: the driver checks the set of blocks written and their values."""
-    v = _makefile_vars()
-    if not os.path.isdir(os.path.join(v["REF"], "include", "slam")):
-        pytest.skip("the reference's headers are not present")
-    libs = v["REFLIBS"].split()
-    if not all(os.path.isfile(a) for a in libs):
-        pytest.skip("the reference's archives have not been built")
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = tmp_path / "covariance_header_driver"
-    cmd = ["g++", "-w"] + v["OPT"].split() + v["CDEFS"].split() + v["CHOLMOD_DEFS"].split() + \
-        ["-I" + os.path.join(ROOT, "include")] + v["INC"].split() + \
-        [os.path.join(ROOT, "tests", "covariance_header_driver.cpp"), "-o", str(exe)] + libs + ["-lrt", "-lm"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout[-2000:] + r.stderr[-4000:]
+    answer with a known symmetric matrix, for a lambda of mixed block sizes and a chain with a closure: the driver checks
+    the set of blocks written and their values."""
+    run_covariance_driver(tmp_path_factory, "sparse", "parts")

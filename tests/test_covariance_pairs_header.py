@@ -1,14 +1,12 @@
 """The pair parts of the header binding (include/slam/LinearSolver_HIP.h: Marginal_Blocks, Joint_Marginal) compile
-against the reference's headers, with the include paths and defines oracle/Makefile.ref builds the drop-in driver with.
-Skipped where the reference's headers are not present."""
+against the reference's headers, with the include paths and defines oracle/Makefile.ref builds the drop-in driver with,
+and -- linked with the reference's block matrix that build() compiles into oracle/_ref and with stand-ins for the C ABI
+(tests/capi_standins.h) -- return block (r, c) of lambda for every pair.
+Skip where the reference's sources (or the archives built from them) are not present."""
 import os
 import re
-import shutil
-import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from header_util import ROOT, run_covariance_driver, syntax_check
 
 TU = r"""
 #include "slam/LinearSolver_HIP.h"
@@ -29,18 +27,6 @@ bool covariance_pairs(CLinearSolver_HIP &r_solver, const CUberBlockMatrix &r_lam
 """
 
 
-def _makefile_vars():
-    text = open(os.path.join(ROOT, "oracle", "Makefile.ref")).read()
-    out = {}
-    for name in ("REF", "OUT", "OPT", "CDEFS", "INC", "CHOLMOD_DEFS"):
-        m = re.search(r"^%s\s*[?:]?=\s*(.*)$" % name, text, re.M)
-        assert m, name
-        out[name] = m.group(1).strip()
-    for name in ("OPT", "CDEFS", "INC", "CHOLMOD_DEFS"):
-        out[name] = out[name].replace("$(REF)", out["REF"]).replace("$(OUT)", os.path.join(ROOT, out["OUT"]))
-    return out
-
-
 def test_header_declares_the_pair_members():
     """(runs everywhere: the members and the C entry they call are there)"""
     text = open(os.path.join(ROOT, "include", "slam", "LinearSolver_HIP.h")).read()
@@ -51,14 +37,12 @@ def test_header_declares_the_pair_members():
 
 
 def test_pair_members_compile(tmp_path):
-    v = _makefile_vars()
-    if not os.path.isdir(os.path.join(v["REF"], "include", "slam")):
-        pytest.skip("the reference's headers are not present")
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    src = tmp_path / "covariance_pairs_tu.cpp"
-    src.write_text(TU)
-    cmd = ["g++", "-fsyntax-only", "-w"] + v["OPT"].split() + v["CDEFS"].split() + v["CHOLMOD_DEFS"].split() + \
-        ["-I" + os.path.join(ROOT, "include")] + v["INC"].split() + [str(src)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
+    syntax_check(tmp_path, "covariance_pairs_tu.cpp", TU)
+
+
+def test_covariance_pairs_are_the_blocks_of_lambda(tmp_path_factory):
+    """Marginal_Blocks at every ordered pair -- first > second, outside lambda's pattern and one listed twice among them --
+    and Joint_Marginal of a set of columns, run on the CPU against stand-ins for the C ABI that answer with a known
+    symmetric matrix, for a chain of 5 block columns of width 6 with one closure; the refusals of an index out of range,
+    a column listed twice and an empty set."""
+    run_covariance_driver(tmp_path_factory, "sparse", "pairs")
