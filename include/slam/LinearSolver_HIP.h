@@ -607,6 +607,16 @@ protected:
 		return true;
 	}
 
+	/** @brief Log_Determinant() on the gathered values: slampp_hip_logdet with b_reuse_factor = 0 */
+	bool Log_Determinant_Gathered(double &r_f_logdet) // throw(std::bad_alloc, std::runtime_error)
+	{
+		const int n_result = slampp_hip_logdet(m_p_solver, m_p_values, 0, &r_f_logdet);
+		if(n_result == SLAMPP_HIP_NOT_POSDEF)
+			return false;
+		Throw_On_Error(n_result);
+		return true;
+	}
+
 	/** @brief Marginal_Blocks() on the gathered values */
 	bool Marginal_Blocks_Gathered(std::vector<Eigen::MatrixXd> &r_blocks, const CUberBlockMatrix &r_lambda,
 		const std::vector<std::pair<size_t, size_t> > &r_pairs, TBlocksEntry p_blocks, const char *p_s_class) // throw(std::bad_alloc, std::runtime_error)
@@ -1060,6 +1070,23 @@ public:
 	}
 
 	/**
+	 *	@brief calculates log det lambda = 2 sum log L_ii from the Cholesky factor on the device (slampp_hip_logdet); lambda is
+	 *		gathered, analyzed where its structure is new and factored as by Solve_PosDef_Blocky(), and the factor stays for
+	 *		further right-hand sides
+	 *
+	 *	@param[out] r_f_logdet is the natural logarithm of the determinant (NaN if lambda is not positive definite)
+	 *	@param[in] r_lambda is the system matrix (symmetric layout, upper triangle stored)
+	 *
+	 *	@return Returns true on success, false if lambda is not positive definite.
+	 *	@note This function throws std::bad_alloc and std::runtime_error.
+	 */
+	bool Log_Determinant(double &r_f_logdet, const CUberBlockMatrix &r_lambda) // throw(std::bad_alloc, std::runtime_error)
+	{
+		Gather_Or_Reanalyze(r_lambda, [&]() { SymbolicDecomposition_Blocky(r_lambda); });
+		return Log_Determinant_Gathered(r_f_logdet);
+	}
+
+	/**
 	 *	@brief calculates the requested parts of the covariance matrix (the inverse of lambda): the parts of the reference's
 	 *		CMarginals::Calculate_DenseMarginals_Recurrent_FBS(margs, R, ordering, n_part), which CNonlinearSolver_Lambda calls
 	 *		after ordering and factoring lambda once more (NonlinearSolver_Lambda.h:690-752), with the matrix parts of
@@ -1280,6 +1307,29 @@ public:
 		if(!Gather_Or_Reanalyze(r_lambda, [&]() { SymbolicDecomposition_Blocky(r_lambda); })) // nonconforming ordering: a new one
 			return m_sparse_fallback.Solve_PosDef_Blocky(r_lambda, r_eta); // lambda lost its landmark part between two calls
 		return Solve_Gathered(r_lambda, r_eta);
+	}
+
+	/**
+	 *	@brief calculates log det lambda = log det S + sum of log det C_p over the landmarks (slampp_hip_logdet in Schur mode:
+	 *		the pivots of the reduced camera system's factor, and every landmark's block factored on its own); lambda is
+	 *		gathered, analyzed where its structure is new and factored as by Solve_PosDef_Blocky()
+	 *
+	 *	@param[out] r_f_logdet is the natural logarithm of the determinant (NaN if lambda is not positive definite)
+	 *	@param[in] r_lambda is the system matrix (symmetric layout, upper triangle stored)
+	 *
+	 *	@return Returns true on success, false if lambda is not positive definite.
+	 *	@note A lambda without a landmark part goes to the sparse solver, with the same result.
+	 *	@note This function throws std::bad_alloc and std::runtime_error.
+	 */
+	bool Log_Determinant(double &r_f_logdet, const CUberBlockMatrix &r_lambda) // throw(std::bad_alloc, std::runtime_error)
+	{
+		if(m_n_matrix_cut == size_t(-1))
+			SymbolicDecomposition_Blocky(r_lambda); // no ordering yet: calculate one
+		if(m_n_matrix_cut == 0 || m_n_matrix_cut == r_lambda.n_BlockColumn_Num())
+			return m_sparse_fallback.Log_Determinant(r_f_logdet, r_lambda); // (checks its own cached structure)
+		if(!Gather_Or_Reanalyze(r_lambda, [&]() { SymbolicDecomposition_Blocky(r_lambda); }))
+			return m_sparse_fallback.Log_Determinant(r_f_logdet, r_lambda); // lambda lost its landmark part between two calls
+		return Log_Determinant_Gathered(r_f_logdet);
 	}
 
 	/**

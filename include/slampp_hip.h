@@ -318,6 +318,33 @@ int slampp_hip_refine_device_async(slampp_hip_solver *p_solver, const double *p_
 int slampp_hip_refine(slampp_hip_solver *p_solver, const double *p_values, const double *p_eta, double *p_x_inout, int n_steps,
 	double *p_resid_inf);
 
+/* log det M(v) = 2 sum log L_ii from the Cholesky factor on the device, one double (M(v): the symmetric matrix
+ * slampp_hip_multiply defines) -- what CHOLMOD users sum from the factor's diagonal: the Gaussian log-likelihood and Laplace
+ * evidence of a graph, D-optimality, information gain.  In Schur mode log det Lambda = log det S + sum_p log det C_p: the
+ * pivots of the reduced camera system's factor, and every landmark's block C_p read from the values and factored in
+ * registers (not taken from the stored C_p^-1, whose determinant loses accuracy with cond(C_p)^2).
+ * b_reuse_factor = 0: the values (required) are factored first -- numeric factorization only in sparse mode without a dense
+ * top; with a dense top, and in Schur mode, a solve on a zero right-hand side of the library's own -- and the handle is left
+ * exactly as slampp_hip_factor_solve_device_async of these values leaves it (slampp_hip_solve_again*, the covariance calls
+ * with values = NULL, "schur_keep" / "schur_incremental" by the rules they state).
+ * b_reuse_factor = 1: nothing is factored, the factor in place is read.  Sparse mode: valid exactly when
+ * slampp_hip_solve_again_device_async is; the values are not read and may be NULL.  Schur mode: valid exactly while a solve
+ * that kept its factor (option "schur_keep" or "schur_incremental") is the handle's latest factorization; the values are
+ * required (the landmark term is computed from them) and trusted to be the ones the factor was made of, as slampp_hip_refine
+ * trusts its values.  What a Schur covariance call left does not serve: its dense route holds inv(L), not L.  No valid
+ * factor: SLAMPP_HIP_ERR_INVALID, with the reason in slampp_hip_last_error, before anything is enqueued.
+ * Two launches whose shape depends on the number of pivots alone, no atomics: the same call gives the same bits.  If the
+ * handle's not-positive-definite flag is raised when the second launch runs, NaN is written (decided on the device), and
+ * slampp_hip_sync reports SLAMPP_HIP_NOT_POSDEF as for any factorization.  Enqueue-only on the handle's stream; the table
+ * of the pivots' places is built on the host at the first call after an analysis.  slampp_hip_logdet: host arrays; it waits,
+ * returns SLAMPP_HIP_NOT_POSDEF and leaves NaN in *p_logdet where the matrix is not positive definite.
+ * SLAMPP_HIP_ERR_UNSUPPORTED for a handle that solves with landmark shards (an all-reduce callback, a device group);
+ * SLAMPP_HIP_ERR_INVALID for a null output, or null values where they are required.  A Schur-mode handle whose analysis
+ * went to the sparse path answers as the sparse path does. */
+int slampp_hip_logdet_device_async(slampp_hip_solver *p_solver, const double *p_values_dev, int b_reuse_factor,
+	double *p_logdet_dev);
+int slampp_hip_logdet(slampp_hip_solver *p_solver, const double *p_values, int b_reuse_factor, double *p_logdet);
+
 /* Numeric factorization only, the factor handed back to the host -- for CLinearSolverTag-style callers that keep
  * the factor themselves (the reference's Factorize_PosDef_Blocky, LinearSolver_CholMod.cpp:362-544, used by its
  * L / FastL solvers on a matrix they have ordered: set the option "natural_order" to 1 for that).  p_factor_out

@@ -152,6 +152,13 @@ struct slampp_hip_solver {
 	bool b_outer_valid = false;
 	slampp::CDevArray<double> d_outer_out;
 	void Require_Pattern_Outer(); // throws
+	// log det Lambda from the factor's pivots (logdet.hip): where every scalar pivot of this handle's plan lives
+	// (logdet_tables.h), built at the first slampp_hip_logdet after an analysis; the host copy stays while the upload may
+	// still be reading it
+	slampp::CDevArray<int64_t> d_logdet_tab;
+	std::vector<int64_t> logdet_tab_host;
+	bool b_logdet_valid = false;
+	void Require_Logdet_Table(); // throws
 	int n_mode;
 	int64_t n_matrix_cut;
 	std::vector<int64_t> cumsum, bcol_ptr;

@@ -127,6 +127,8 @@ ABI = {
     "slampp_hip_dot_device_async": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
     "slampp_hip_refine_device_async": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
     "slampp_hip_refine": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
+    "slampp_hip_logdet_device_async": (C.c_int, [_P, _P, C.c_int, _P]),
+    "slampp_hip_logdet": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_double)]),
     "slampp_hip_factorize": (C.c_int, [_P, _P, _P]),
     "slampp_hip_factor_structure": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P, _P, _P, _P, _P]),
     "slampp_hip_schur_set_changed_points": (C.c_int, [_P, _P, C.c_int64]),
@@ -174,7 +176,8 @@ ABI = {
 _FACTOR_CHANGING = frozenset(
     ["slampp_hip_free_memory", "slampp_hip_set_structure", "slampp_hip_analyze", "slampp_hip_factor_solve",
      "slampp_hip_factor_solve_device", "slampp_hip_factor_solve_device_async", "slampp_hip_factor_solve_batch_device_async",
-     "slampp_hip_factorize", "slampp_hip_solve_marginal_poses", "slampp_hip_solve_marginal_poses_device_async"] +
+     "slampp_hip_factorize", "slampp_hip_solve_marginal_poses", "slampp_hip_solve_marginal_poses_device_async",
+     "slampp_hip_logdet", "slampp_hip_logdet_device_async"] +
     [n for n in ABI if "marginal" in n and "poses" not in n])
 
 
@@ -469,6 +472,27 @@ class _SolverBase:
             raise ValueError("eta must be a contiguous float64 vector of the system's dimension")
         return self._check(self._lib.slampp_hip_solve_again(self._h, _ptr(eta)))
 
+    def Log_Determinant(self, lam, reuse_factor: bool = False) -> float:
+        """log det Lambda = 2 sum log L_ii from the Cholesky factor on the device (slampp_hip_logdet).  ``reuse_factor=False``:
+        analyzes a new structure, factors ``lam.values`` and leaves the handle as Solve_PosDef_Blocky leaves it (Solve_Again
+        is valid afterwards).  ``reuse_factor=True``: nothing is factored, the factor the last solve left is read
+        (ValueError if there is none; Schur mode: option ``schur_keep=1``, and ``lam.values`` must be the values that solve
+        factored).  A matrix that is not positive definite has no log-determinant: as Solve_PosDef_Blocky answers False
+        there without raising, this returns NaN without raising."""
+        if reuse_factor:
+            if not self._analyzed or self._structure_key != self._key(lam):
+                raise ValueError("Log_Determinant: there is no factorization of this structure to reuse")
+        elif not self._analyzed or self._structure_key != self._key(lam):
+            self._check(self._lib.slampp_hip_set_option(self._h, b"staging_ahead", 1))   # host arrays: the staging beside the analysis
+            self.SymbolicDecomposition_Blocky(lam)
+        vals = np.ascontiguousarray(lam.values, dtype=np.float64)
+        if vals.shape != (self._n_values,):
+            raise ValueError("lam.values does not match the block structure")
+        out = C.c_double(float("nan"))
+        if not self._check(self._lib.slampp_hip_logdet(self._h, _ptr(vals), int(bool(reuse_factor)), C.byref(out))):
+            return float("nan")
+        return float(out.value)
+
     def _set_structure(self, lam) -> None:
         """The block structure alone (slampp_hip_set_structure): what the product needs; a solve analyzes it later."""
         cs = np.ascontiguousarray(lam.cumsum, dtype=np.int64)
@@ -665,6 +689,21 @@ class _SolverBase:
         """Iterative refinement on device-resident arrays, enqueue-only (slampp_hip_refine_device_async); ``resid_ptr``:
         n_steps + 1 doubles, or 0."""
         self._check(self._lib.slampp_hip_refine_device_async(self._h, values_ptr, eta_ptr, x_ptr, int(n_steps), resid_ptr or None))
+
+    def logdet_device(self, values_ptr: int, out_ptr: int, reuse_factor: bool = False) -> None:
+        """*out = log det Lambda from the Cholesky factor, device-resident and enqueue-only (slampp_hip_logdet_device_async).
+        ``reuse_factor=False``: the values are factored first and the handle is left as factor_solve_device_async leaves
+        it; ``True``: the factor in place is read (sparse mode: wherever solve_again_device is valid, ``values_ptr`` may be
+        0; Schur mode: after a solve with ``schur_keep=1``, and the values are still needed for the landmark blocks).  NaN is
+        written where the matrix is not positive definite, which ``sync()`` then reports."""
+        self._check(self._lib.slampp_hip_logdet_device_async(self._h, values_ptr or None, int(bool(reuse_factor)), out_ptr or None))
+
+    def marginals_pattern_device(self, values_ptr: int, out_ptr: int) -> None:
+        """Lambda^-1 at every stored block of Lambda on device-resident arrays, enqueue-only: the class's pattern entry point
+        (slampp_hip_marginals_pattern_device_async / slampp_hip_schur_marginals_pattern_device_async); ``out_ptr``: as many
+        doubles as the packed values.  Factors the values (Schur mode: ``values_ptr`` = 0 reuses what the previous Schur
+        covariance call left)."""
+        self._check(getattr(self._lib, self._covariance_entries[0] + "_device_async")(self._h, values_ptr or None, out_ptr or None))
 
     def apply_damping_device_async(self, values_ptr: int, f_alpha: float, n_first_vertex: int, n_last_vertex: int) -> None:
         """ApplyDamping of the reference's LM solver (NonlinearSolver_Lambda_LM.h:228-239) on device-resident values."""

@@ -44,6 +44,18 @@ factorizations, the documented cost -- followed by the batched outer-product ker
 (rows contiguous, any row stride of at least a row); odd strides are solved member by member inside the library, with the
 same results.
 
+``logdet(solver, lam, values)`` returns ``log det M(values)`` as a 0-dim float64 tensor on the solver's device, once
+differentiable in ``values`` (both modes).  Forward: slampp_hip_logdet_device_async with ``b_reuse_factor = 0`` -- the values are
+factored and twice the sum of log of the factor's pivots is taken on the device, Schur mode adding every landmark's
+``log det C_p`` --, then one wait (a matrix that is not positive definite raises torch.linalg.LinAlgError).  Backward:
+``v_bar = y_bar * w * Sigma`` with ``Sigma = M^-1`` on the structure's pattern from the pattern-covariance device call of the
+solver's mode on the saved values, and ``w`` = 2 on off-diagonal blocks (a stored block (r, c), r < c, stands at (r, c) and
+transposed at (c, r)), 1 on diagonal blocks (whose gradient is Sigma(r, r)^T = Sigma(r, r)); ``w`` is cached on the solver
+as a device tensor per structure key.  The covariance call factors the saved values AGAIN: a backward pass costs one
+factorization plus the covariance recursion, and it leaves the handle's factor as that call leaves it.  Where the covariance
+call is unsupported (sparse mode: block columns wider than 8), backward raises a RuntimeError naming the limit; the forward
+pass works regardless.
+
 ``dense_from_packed`` and ``pattern_outer_reference`` restate M(v) and the outer product in plain torch / numpy: the
 yardsticks of the tests.
 """
@@ -241,3 +253,53 @@ def solve_batch(solver, lam, values: torch.Tensor, eta: torch.Tensor) -> torch.T
         raise ValueError("the members of values / eta overlap (row stride below the row length)")
     _require_analysis(solver, lam)
     return _SolveBatch.apply(values, eta, solver, lam)
+
+
+# ---- log det M(values) ----
+
+def _logdet_weights(solver, lam, like: torch.Tensor) -> torch.Tensor:
+    """w of the module docstring for ``lam``'s structure: 2 at the values of off-diagonal blocks, 1 at those of diagonal
+    blocks; one device tensor per structure key, kept on the solver."""
+    key = solver._key(lam)
+    cached = getattr(solver, "_logdet_w", None)
+    if cached is None or cached[0] != key:
+        offdiag = _element_rows_cols(lam)[2]
+        w = torch.from_numpy(np.where(offdiag, 2.0, 1.0)).to(like.device)
+        cached = solver._logdet_w = (key, w)
+    return cached[1]
+
+
+class _Logdet(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, values, solver, lam):
+        out = torch.empty((), dtype=torch.float64, device=values.device)
+        v = values.detach()
+        _enqueue(solver, lambda: solver.logdet_device(v.data_ptr(), out.data_ptr(), False))
+        if not solver.sync():
+            raise torch.linalg.LinAlgError("logdet: the matrix is not positive definite")
+        ctx.solver, ctx.lam = solver, lam
+        ctx.save_for_backward(values)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, y_bar):
+        values, = ctx.saved_tensors
+        solver, lam = ctx.solver, ctx.lam
+        _require_analysis(solver, lam)              # (the handle may have been given another structure since)
+        sigma = torch.empty_like(values)
+        try:
+            _enqueue(solver, lambda: solver.marginals_pattern_device(values.data_ptr(), sigma.data_ptr()))
+        except NotImplementedError as e:
+            raise RuntimeError("logdet: the gradient needs Lambda^-1 on Lambda's pattern, which the covariance call of this "
+                               f"solver does not give for this structure (sparse mode: block columns of at most 8): {e}") from e
+        return y_bar * (_logdet_weights(solver, lam, values) * sigma), None, None
+
+
+def logdet(solver, lam, values: torch.Tensor) -> torch.Tensor:
+    """log det M(values) on the block structure of ``lam``: a 0-dim float64 tensor, differentiable in ``values`` (module
+    docstring; the backward pass factors again inside the covariance call)."""
+    _check_solver(solver)
+    _check_tensor(solver, values, "values", (int(lam.values.shape[0]),))
+    _require_analysis(solver, lam)
+    return _Logdet.apply(values, solver, lam)
