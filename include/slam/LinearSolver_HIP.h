@@ -617,6 +617,51 @@ protected:
 		return true;
 	}
 
+	/**
+	 *	@brief Solve_Again_Columns() on the handle's kept factor: slampp_hip_solve_columns on the caller's matrix itself (it is
+	 *		column-major: leading dimension rows(), one host call for up to SLAMPP_HIP_SOLVE_MAX_COLUMNS columns), or -- where the
+	 *		analysis reordered lambda's block columns -- on a copy with the rows permuted by blocks, as Solve_Gathered() does
+	 */
+	bool Solve_Again_Columns_Kept(Eigen::MatrixXd &r_eta_columns) // throw(std::bad_alloc, std::runtime_error)
+	{
+		if(!m_p_solver || !m_b_structure_valid)
+			throw std::runtime_error("CLinearSolver_HIP: Solve_Again_Columns() needs a solve before it");
+		if(size_t(r_eta_columns.rows()) != size_t(m_cumsum.back()))
+			throw std::runtime_error("CLinearSolver_HIP: the right-hand sides do not match lambda");
+		const long n = long(m_cumsum.size()) - 1, n_scalar_num = long(r_eta_columns.rows()), n_column_num = long(r_eta_columns.cols());
+		if(!n_column_num || !n_scalar_num)
+			return true;
+		std::vector<size_t> base; // where the library's block column i begins in the caller's rows
+		Eigen::MatrixXd permuted;
+		if(!m_order.empty()) {
+			std::vector<size_t> orig_cumsum(size_t(n) + 1, 0);
+			for(long i = 0; i < n; ++ i)
+				orig_cumsum[m_order[i] + 1] = size_t(m_cumsum[i + 1] - m_cumsum[i]);
+			for(long i = 0; i < n; ++ i)
+				orig_cumsum[i + 1] += orig_cumsum[i];
+			base.resize(size_t(n));
+			for(long i = 0; i < n; ++ i)
+				base[i] = orig_cumsum[m_order[i]];
+			permuted.resize(n_scalar_num, n_column_num);
+			for(long i = 0; i < n; ++ i) {
+				for(int64_t d = 0, w = m_cumsum[i + 1] - m_cumsum[i]; d < w; ++ d)
+					permuted.row(int(m_cumsum[i] + d)) = r_eta_columns.row(int(base[i] + size_t(d)));
+			}
+		}
+		Eigen::MatrixXd &r_work = m_order.empty()? r_eta_columns : permuted;
+		for(long n_first = 0; n_first < n_column_num; n_first += SLAMPP_HIP_SOLVE_MAX_COLUMNS) {
+			const long n_group = std::min(n_column_num - n_first, long(SLAMPP_HIP_SOLVE_MAX_COLUMNS));
+			Throw_On_Error(slampp_hip_solve_columns(m_p_solver, &r_work(0, n_first), int64_t(n_scalar_num), int(n_group)));
+		}
+		if(!m_order.empty()) {
+			for(long i = 0; i < n; ++ i) {
+				for(int64_t d = 0, w = m_cumsum[i + 1] - m_cumsum[i]; d < w; ++ d)
+					r_eta_columns.row(int(base[i] + size_t(d))) = permuted.row(int(m_cumsum[i] + d));
+			}
+		}
+		return true;
+	}
+
 	/** @brief Marginal_Blocks() on the gathered values */
 	bool Marginal_Blocks_Gathered(std::vector<Eigen::MatrixXd> &r_blocks, const CUberBlockMatrix &r_lambda,
 		const std::vector<std::pair<size_t, size_t> > &r_pairs, TBlocksEntry p_blocks, const char *p_s_class) // throw(std::bad_alloc, std::runtime_error)
@@ -1087,6 +1132,20 @@ public:
 	}
 
 	/**
+	 *	@brief solves for several right-hand sides with the factor the last Solve_PosDef_Blocky() left, in one call
+	 *		(slampp_hip_solve_columns; cholmod_solve with a dense B of several columns, LinearSolver_CholMod.cpp:322-347)
+	 *
+	 *	@param[in,out] r_eta_columns holds a right-hand side per column (rows as lambda's) on entry, the solutions on return
+	 *
+	 *	@return Returns true on success.
+	 *	@note This function throws std::bad_alloc and std::runtime_error (no kept factor, mismatched dimensions).
+	 */
+	bool Solve_Again_Columns(Eigen::MatrixXd &r_eta_columns) // throw(std::bad_alloc, std::runtime_error)
+	{
+		return Solve_Again_Columns_Kept(r_eta_columns);
+	}
+
+	/**
 	 *	@brief calculates the requested parts of the covariance matrix (the inverse of lambda): the parts of the reference's
 	 *		CMarginals::Calculate_DenseMarginals_Recurrent_FBS(margs, R, ordering, n_part), which CNonlinearSolver_Lambda calls
 	 *		after ordering and factoring lambda once more (NonlinearSolver_Lambda.h:690-752), with the matrix parts of
@@ -1330,6 +1389,23 @@ public:
 		if(!Gather_Or_Reanalyze(r_lambda, [&]() { SymbolicDecomposition_Blocky(r_lambda); }))
 			return m_sparse_fallback.Log_Determinant(r_f_logdet, r_lambda); // lambda lost its landmark part between two calls
 		return Log_Determinant_Gathered(r_f_logdet);
+	}
+
+	/**
+	 *	@brief solves for several right-hand sides with what the last Solve_PosDef_Blocky() kept, in one call
+	 *		(slampp_hip_solve_columns in Schur mode: needs Set_Option("schur_keep", 1) before that solve)
+	 *
+	 *	@param[in,out] r_eta_columns holds a right-hand side per column (rows as lambda's) on entry, the solutions on return
+	 *
+	 *	@return Returns true on success.
+	 *	@note Where the last lambda had no landmark part, the sparse solver that answered for it answers here.
+	 *	@note This function throws std::bad_alloc and std::runtime_error (no kept factor, mismatched dimensions).
+	 */
+	bool Solve_Again_Columns(Eigen::MatrixXd &r_eta_columns) // throw(std::bad_alloc, std::runtime_error)
+	{
+		if(!this->m_b_structure_valid) // (SymbolicDecomposition_Blocky: a lambda without a landmark part went to the sparse solver)
+			return m_sparse_fallback.Solve_Again_Columns(r_eta_columns);
+		return this->Solve_Again_Columns_Kept(r_eta_columns);
 	}
 
 	/**

@@ -246,6 +246,36 @@ int slampp_hip_solve_again(slampp_hip_solver *p_solver, double *p_rhs_inout);
  * before (SLAMPP_HIP_ERR_UNSUPPORTED after a plain Schur solve). */
 int slampp_hip_solve_again_device_async(slampp_hip_solver *p_solver, double *p_rhs_inout_dev);
 
+/* n_columns right-hand sides with the kept factor in one call -- cholmod_solve with a dense B of several columns, which the
+ * reference's linear solvers sit on (LinearSolver_CholMod.cpp:322-347): J Sigma J^T, Lambda^-1 B, several adjoints of one
+ * backward pass, block Krylov and sampling code, LM steps at several damped right-hand sides.  Column c is the n_scalars doubles at
+ * p_rhs_inout_dev + c * n_ld, in the caller's scalar order: eta on entry, Lambda^-1 eta on return; the n_ld - n_scalars
+ * doubles behind a column are not touched.  Valid exactly when slampp_hip_solve_again_device_async is, in both modes, with
+ * its error codes and its slampp_hip_last_error texts under the name solve_columns (landmark shards:
+ * SLAMPP_HIP_ERR_UNSUPPORTED).  SLAMPP_HIP_ERR_INVALID: a null pointer, n_columns outside 1 .. SLAMPP_HIP_SOLVE_MAX_COLUMNS,
+ * n_ld < n_scalars with more than one column.
+ * Sparse mode, block columns of at most 8: both substitutions run on all the columns at once, over the static plan of the
+ * single-vector substitutions, one launch per stage and pass of at most 48 columns; a lane owns one (row of a block,
+ * right-hand side) pair, so a wave carries 64 / d right-hand sides (10 at 6 x 6 blocks) and every block of L is read once
+ * for them; the permutation to and from the caller's order is fused into the kernels.  With a dense top its columns'
+ * reduced right-hand sides go through k-column tile solves on the top's factor.  The factor is read once per pass and
+ * group of right-hand sides, where n_columns calls of slampp_hip_solve_again_device_async read it n_columns times.  Measured
+ * on 100 000 SE(3) poses: 8 columns in the time of 1.8 single re-solves, 48 in the time of 6.5; 2
+ * columns win 10 % only, and one column is better served by slampp_hip_solve_again_device_async (the call's launches are
+ * latency-bound up to the right-hand sides of one wave).  The results agree with slampp_hip_solve_again_device_async to
+ * rounding, not to the bit (another summation order).
+ * Schur mode, and sparse mode with block columns wider than 8 (factored in pieces): no k-column kernels here (W and the
+ * factor are read once per column) -- the call runs the single-vector route of slampp_hip_solve_again_device_async column
+ * by column, from either kept state, and gives its bits.
+ * No atomics.  Column c's result depends on column c alone: not on n_columns, not on its place, and a NaN in one column
+ * reaches no other.  The same call twice gives the same bits.  Enqueue-only on the handle's stream, but for the first call
+ * after an analysis, which builds the row lists of the dense-top columns on the host and waits for their upload.
+ * Installs no factor.  slampp_hip_solve_columns: host array (column-major, leading dimension n_ld), through device memory
+ * in groups of 48 columns; it waits. */
+#define SLAMPP_HIP_SOLVE_MAX_COLUMNS 256
+int slampp_hip_solve_columns_device_async(slampp_hip_solver *p_solver, double *p_rhs_inout_dev, int64_t n_ld, int n_columns);
+int slampp_hip_solve_columns(slampp_hip_solver *p_solver, double *p_rhs_inout, int64_t n_ld, int n_columns);
+
 /* y = alpha Lambda x + beta y with Lambda's packed values as slampp_hip_factor_solve_device reads them -- what the
  * reference's LM and dog-leg solvers compute on the host after every linear solve: the gain ratio's dx^T (alpha dx + eta)
  * and the Cauchy step's g^T Lambda g (include/slam/NonlinearSolver_Lambda_LM.h:207, NonlinearSolver_Lambda_DL.h:1175-1177 and 1270:
@@ -294,6 +324,18 @@ int slampp_hip_pattern_outer(slampp_hip_solver *p_solver, const double *p_a, con
 int slampp_hip_pattern_outer_batch_device_async(slampp_hip_solver *p_solver, int n_batch, const double *p_a_dev,
 	int64_t n_a_stride, const double *p_b_dev, int64_t n_b_stride, double *p_out_values_dev, int64_t n_out_stride,
 	double f_alpha, double f_beta);
+
+/* out = alpha sum over k < n_terms of P(a_k, b_k) + beta out, a_k = p_a_dev + k n_a_stride, b_k = p_b_dev + k n_b_stride
+ * (strides in doubles), P as above: the adjoint of a k-column solve with respect to the values (x_k = M^-1 eta_k and upstream
+ * gradients: g = slampp_hip_solve_columns of them, v_bar = -sum P(g_k, x_k)).  The same streaming kernel: a thread keeps its
+ * pair of values in registers over the terms, adds them in ascending k in one fixed form and writes out once; beta = 0 does
+ * not read out.  One term gives the bits of slampp_hip_pattern_outer_device_async; two calls give the same bits, whatever
+ * the alignment of out (16-byte stores where it is 16-byte aligned, 8-byte stores otherwise).  The checks of the batched call:
+ * SLAMPP_HIP_ERR_INVALID for a null pointer, no structure, n_terms outside 1 .. SLAMPP_HIP_SOLVE_MAX_COLUMNS, a stride below
+ * n_scalars (not read for one term), out overlapping any a_k or b_k; landmark shards: SLAMPP_HIP_ERR_UNSUPPORTED.
+ * Enqueue-only as the calls above. */
+int slampp_hip_pattern_outer_sum_device_async(slampp_hip_solver *p_solver, int n_terms, const double *p_a_dev, int64_t n_a_stride,
+	const double *p_b_dev, int64_t n_b_stride, double *p_out_values_dev, double f_alpha, double f_beta);
 
 /* *p_out_dev = sum a_i b_i over n device-resident entries, in two passes of a fixed shape (it depends on n alone): bit-
  * reproducible like the product.  With it the scalars of the LM / dog-leg step control (Eigen's dot products in

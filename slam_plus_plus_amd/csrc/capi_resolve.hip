@@ -1,8 +1,9 @@
 // capi_resolve.hip -- the entry points of the C ABI (include/slampp_hip.h) that work with a factor or beside one: the factor
 // handed out (slampp_hip_factorize, slampp_hip_factor_structure), further right-hand sides with the kept factor
-// (slampp_hip_solve_again), y = alpha Lambda x + beta y and its adjoint in the values (the outer product on Lambda's pattern),
+// (slampp_hip_solve_again; several at once: slampp_hip_solve_columns), y = alpha Lambda x + beta y and its adjoint in the values (the outer product on Lambda's pattern),
 // dot products and iterative refinement
 #include "capi_util.h"
+#include "covariance.h"
 #include "multiply.h"
 #include "pattern_outer.h"
 
@@ -270,6 +271,75 @@ int slampp_hip_solve_again(slampp_hip_solver *p_solver, double *p_rhs_inout)
 	});
 }
 
+// ---- several right-hand sides with the kept factor in one call (covariance.hip: solve_columns_enqueue) ----
+
+namespace {
+
+// the checks of both solve_columns entry points (inside guarded())
+int solve_columns_checks(slampp_hip_solver *p_solver, const double *p_rhs, int64_t n_ld, int n_columns, int *p_n_schur_source)
+{
+	const int n_check = resolve_checks(p_solver, "solve_columns", p_n_schur_source);
+	if(n_check != SLAMPP_HIP_OK)
+		return n_check;
+	if(!p_rhs)
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_columns: null pointer");
+	if(n_columns < 1 || n_columns > SLAMPP_HIP_SOLVE_MAX_COLUMNS)
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_columns: between 1 and SLAMPP_HIP_SOLVE_MAX_COLUMNS columns");
+	if(n_columns > 1 && n_ld < p_solver->n_scalars)
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_columns: the columns overlap (leading dimension below n_scalars)");
+	return SLAMPP_HIP_OK;
+}
+
+} // anonymous namespace
+
+int slampp_hip_solve_columns_device_async(slampp_hip_solver *p_solver, double *p_rhs_inout_dev, int64_t n_ld, int n_columns)
+{
+	return guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		int n_source = 0;
+		const int n_check = solve_columns_checks(p_solver, p_rhs_inout_dev, n_ld, n_columns, &n_source);
+		if(n_check != SLAMPP_HIP_OK)
+			return n_check;
+		if(s.n_mode == SLAMPP_HIP_MODE_SPARSE && solve_columns_applies(s))
+			solve_columns_enqueue(s, p_rhs_inout_dev, n_ld, n_columns);
+		else { // Schur mode, block columns wider than 8: the single-vector route, column by column (slampp_hip_solve_again's bits)
+			for(int c = 0; c < n_columns; ++ c)
+				resolve_enqueue(s, p_rhs_inout_dev + int64_t(c) * n_ld, n_source);
+		}
+		return SLAMPP_HIP_OK;
+	});
+}
+
+int slampp_hip_solve_columns(slampp_hip_solver *p_solver, double *p_rhs_inout, int64_t n_ld, int n_columns)
+{
+	// groups of at most COV_K_PASS columns, each through the device array of the covariance columns (packed there) and back
+	// behind its pass: the device holds n_scalars x COV_K_PASS of them at a time, whatever n_columns is
+	int n_group0 = 0, n_group = n_columns;
+	do {
+		const int n_result = host_round_trip(p_solver, [&]() -> int {
+			slampp_hip_solver &s = *p_solver;
+			int n_source = 0;
+			const int n_check = solve_columns_checks(p_solver, p_rhs_inout, n_ld, n_columns, &n_source);
+			if(n_check != SLAMPP_HIP_OK)
+				return n_check;
+			n_group = std::min(n_columns - n_group0, int(COV_K_PASS));
+			s.d_cov.Alloc(size_t(s.n_scalars) * n_group);
+			SLAMPP_HIP_CHECK(hipMemcpy2DAsync(s.d_cov.p(), size_t(s.n_scalars) * sizeof(double), p_rhs_inout + int64_t(n_group0) * n_ld,
+				size_t(std::max(n_ld, s.n_scalars)) * sizeof(double) /* (one column: n_ld is of no meaning) */, size_t(s.n_scalars) * sizeof(double), size_t(n_group), hipMemcpyHostToDevice, s.stream));
+			return SLAMPP_HIP_OK;
+		}, [&](slampp_hip_solver &s) {
+			return slampp_hip_solve_columns_device_async(p_solver, s.d_cov.p(), s.n_scalars, n_group);
+		}, false, [&](slampp_hip_solver &s) {
+			SLAMPP_HIP_CHECK(hipMemcpy2DAsync(p_rhs_inout + int64_t(n_group0) * n_ld, size_t(std::max(n_ld, s.n_scalars)) * sizeof(double), s.d_cov.p(),
+				size_t(s.n_scalars) * sizeof(double), size_t(s.n_scalars) * sizeof(double), size_t(n_group), hipMemcpyDeviceToHost, s.stream));
+		});
+		if(n_result != SLAMPP_HIP_OK)
+			return n_result;
+		n_group0 += n_group;
+	} while(n_group0 < n_columns);
+	return SLAMPP_HIP_OK;
+}
+
 // ---- y = alpha Lambda x + beta y, dot products, iterative refinement (multiply.hip) ----
 
 namespace {
@@ -367,6 +437,29 @@ int slampp_hip_pattern_outer_batch_device_async(slampp_hip_solver *p_solver, int
 		s.Require_Pattern_Outer();
 		pattern_outer_enqueue(*s.p_outer, n_batch, p_a_dev, n_a_stride, p_b_dev, n_b_stride, p_out_values_dev, n_out_stride, f_alpha,
 			f_beta, s.stream);
+		return SLAMPP_HIP_OK;
+	});
+}
+
+int slampp_hip_pattern_outer_sum_device_async(slampp_hip_solver *p_solver, int n_terms, const double *p_a_dev, int64_t n_a_stride,
+	const double *p_b_dev, int64_t n_b_stride, double *p_out_values_dev, double f_alpha, double f_beta)
+{
+	return guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		const int n_check = multiply_checks(p_solver, "pattern_outer_sum");
+		if(n_check != SLAMPP_HIP_OK)
+			return n_check;
+		if(!p_a_dev || !p_b_dev || !p_out_values_dev || n_terms < 1 || n_terms > SLAMPP_HIP_SOLVE_MAX_COLUMNS)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "pattern_outer_sum: null pointer, or fewer than 1 / more than SLAMPP_HIP_SOLVE_MAX_COLUMNS terms");
+		if(n_terms == 1)
+			n_a_stride = n_b_stride = 0; // (of no meaning)
+		else if(n_a_stride < s.n_scalars || n_b_stride < s.n_scalars)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "pattern_outer_sum: the terms' vectors overlap (stride below their length)");
+		if(ranges_overlap(p_a_dev, int64_t(n_terms - 1) * n_a_stride + s.n_scalars, p_out_values_dev, s.n_values) ||
+		   ranges_overlap(p_b_dev, int64_t(n_terms - 1) * n_b_stride + s.n_scalars, p_out_values_dev, s.n_values))
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "pattern_outer_sum: out overlaps a or b");
+		s.Require_Pattern_Outer();
+		pattern_outer_sum_enqueue(*s.p_outer, n_terms, p_a_dev, n_a_stride, p_b_dev, n_b_stride, p_out_values_dev, f_alpha, f_beta, s.stream);
 		return SLAMPP_HIP_OK;
 	});
 }

@@ -54,4 +54,13 @@ void covariance_pair_sets_pass(slampp_hip_solver &s, size_t n_pass, const double
 void covariance_columns_rhs_enqueue(slampp_hip_solver &s, int n_src, const int64_t *p_src_bcols, int kp, const double *p_rhs_dev,
 	double *p_out_dev, int64_t n_ld_out, int64_t n_col0);
 
+// n_columns right-hand sides given whole, solved in place from the factor in place (slampp_hip_solve_columns): column c is
+// the n_scalars doubles at p_rhs_dev + c * n_ld, rows in the caller's scalar order.  Unpruned k-column substitutions over
+// the static device plan, in passes of COV_K_PASS columns through the interleaved workspace; the dense top by the k-column
+// tile solves above.  solve_columns_applies: the plan has kernels for it (no block column wider than 8, which the analysis
+// would have cut into pieces); the caller solves column by column otherwise.  Enqueue-only but for the first call after an
+// analysis, which builds the dense-top columns' row lists on the host.  Throws.
+bool solve_columns_applies(const slampp_hip_solver &s);
+void solve_columns_enqueue(slampp_hip_solver &s, double *p_rhs_dev, int64_t n_ld, int n_columns);
+
 } // namespace slampp

@@ -24,6 +24,9 @@
 // The same runs on right-hand sides given whole, each nonzero on a set of source block columns (covariance_pair_sets_plan,
 // covariance_pair_sets_pass): the columns of a BA system over its reduced camera system (schur_covariance.hip).
 //
+// Right-hand sides given whole (slampp_hip_solve_columns: solve_columns_enqueue below) share the workspace and the dense top's
+// tile solves, with unpruned substitutions of their own over the static device plan: a lane per (block row, right-hand side).
+//
 // Workspace X: n_scalars x k, interleaved -- the k values of a scalar row next to each other (X[row * k + c]): a lane per
 // right-hand side then reads and writes a block's rows as whole contiguous lines (d x k doubles), where a column stride of
 // n_scalars would make every lane of a wave touch a line of its own.  Rows of the permuted order (Plan::cs_new).  Which
@@ -53,6 +56,14 @@ struct TCovFwd { // 40 B: one listed column of the pruned forward substitution
 	int32_t bcol;     // right-hand side c of this pass has its 1 in row c - bcol of this column (if 0 <= c - bcol < dj)
 	int32_t dpos;     // dense top: position in the dense system (the column's reduced right-hand side goes there), else -1
 	int32_t s;        // schedule index (the stamp goes there)
+};
+
+struct TSolveTopCol { // 32 B: one dense-top column of solve_columns_enqueue
+	int64_t cs_src;   // scalar offset in the caller's vectors
+	int64_t e0;       // first of its row entries L(j,c) with c below the dense top
+	int32_t ne, dj;
+	int32_t dpos;     // position in the dense system
+	int32_t pad;
 };
 
 namespace {
@@ -99,6 +110,12 @@ struct CCovariance {
 	CDevArray<TPairRec> d_pairs;
 	CDevArray<TPairRow> d_pair_rows;
 	std::vector<TCovPass> set_passes; // covariance_pair_sets_plan: the forward substitution of every pass of pair_plan
+	// right-hand sides given whole (slampp_hip_solve_columns): the dense-top columns and their row entries L(j,c), c below the
+	// top -- a static list, built at the first such call after an analysis
+	bool b_solve_top = false;
+	int n_top_cols = 0;
+	CDevArray<TSolveTopCol> d_top_cols;
+	CDevArray<TRowEnt> d_top_ents;
 	~CCovariance() { if(ev_lists) (void)hipEventDestroy(ev_lists); }
 };
 
@@ -107,7 +124,8 @@ void covariance_destroy(CCovariance *p) { delete p; }
 size_t covariance_bytes(const CCovariance *p)
 {
 	return p? p->d_gather.n_Bytes() + p->d_X.n_Bytes() + p->d_Bd.n_Bytes() + p->d_Zb.n_Bytes() + p->d_mark.n_Bytes() +
-		p->d_fwd.n_Bytes() + p->d_ents.n_Bytes() + p->d_seg.n_Bytes() + p->d_pairs.n_Bytes() + p->d_pair_rows.n_Bytes() : 0;
+		p->d_fwd.n_Bytes() + p->d_ents.n_Bytes() + p->d_seg.n_Bytes() + p->d_pairs.n_Bytes() + p->d_pair_rows.n_Bytes() +
+		p->d_top_cols.n_Bytes() + p->d_top_ents.n_Bytes() : 0;
 }
 
 // ---- pattern gather ----
@@ -709,6 +727,281 @@ static void columns_enqueue(slampp_hip_solver &s, int n_cols, const int64_t *p_b
 	for(size_t p = 0; p < passes.size(); ++ p) {
 		Forward_Enqueue(s, cv, passes[p], p_rhs, true);
 		Backward_Enqueue(s, cv, passes[p], p_out_dev, n_ld_out, n_col0);
+	}
+	s.Phase_End();
+	SLAMPP_HIP_CHECK(hipGetLastError());
+}
+
+// ---- right-hand sides given whole (slampp_hip_solve_columns): both substitutions over the static plan ----
+//
+// Nothing is pruned and nothing is listed per call: the kernels walk TDevPlan::cols / rents / blks / task_ptr, the records of
+// the single-vector substitutions, one launch per stage.  A lane owns one (row r of the block, right-hand side c) pair: with
+// blocks of dimension D a wave carries 64 / D right-hand sides (21 at D = 3, 10 at D = 6, 9 at D = 7; 8 with mixed
+// dimensions, each right-hand side eight lanes apart), further right-hand sides of the same task go to further workgroups
+// (blockIdx.y).  A lane sums its row of every block product in the order of the records, so what column c gets depends on
+// column c alone -- not on k, not on where c sits in a wave -- and never meets another column's numbers (a NaN stays in its
+// column).  The product with inv(L_jj) needs the other rows of the same c: they come from the neighbouring lanes by
+// __shfl.  The forward kernel reads column c of the caller's array at TColDesc::cs_src (the permutation is fused in) and
+// writes the interleaved workspace X[row * kp + c]; the backward kernel writes X and the caller's array.
+
+template <int D>
+struct TSolveLanes {
+	enum { DM = D? D : 8, PER_WAVE = 64 / DM };
+	int r, c, base; // row of the block, right-hand side of the pass, lane of row 0 of that right-hand side
+	bool b_rhs;     // the lane has a right-hand side at all
+	__device__ __forceinline__ TSolveLanes(int kp)
+	{
+		const int lane = threadIdx.x, cl = lane / DM;
+		r = lane - cl * DM;
+		base = cl * DM;
+		c = int(blockIdx.y) * PER_WAVE + cl;
+		b_rhs = cl < PER_WAVE && c < kp;
+		if(!b_rhs)
+			c = 0; // (addresses stay valid; nothing of such a lane is stored)
+	}
+};
+
+// records a lane has in flight at a time: the loads of a batch -- the records, then every block element and vector entry they
+// name -- are issued together, so a batch costs two trips to memory where record by record every record costs two.  The sum
+// itself goes on in the order of the records (a record past the end adds products of zeros, which change nothing)
+template <int D>
+struct TSolveBatch {
+	enum { N = D? 4 : 2 };
+};
+
+// acc - sum over the row entries e0 .. e0 + ne of row r of L(j,c') y_c'
+template <int D>
+__device__ __forceinline__ double solve_cols_row_sum(double acc, const TRowEnt *__restrict__ ents, int64_t e0, int ne, int dj,
+	const double *__restrict__ L, const double *X, int kp, int r, int c, bool b_act)
+{
+	constexpr int DM = D? D : 8, NB = TSolveBatch<D>::N;
+	const int64_t e_end = e0 + ne;
+	for(int64_t e = e0; e < e_end; e += NB) {
+		double lv[NB][DM], xv[NB][DM];
+		#pragma unroll
+		for(int u = 0; u < NB; ++ u) {
+			const bool b_on = b_act && e + u < e_end;
+			const TRowEnt t_e = ents[(e + u < e_end)? e + u : e]; // (a record of this column either way)
+			const int dc = D? D : t_e.dc;
+			const double *Lb = L + t_e.off + r; // L(j,c'): dj x dc
+			const double *Xc = X + int64_t(t_e.ycs) * kp + c;
+			#pragma unroll
+			for(int t = 0; t < DM; ++ t) {
+				lv[u][t] = (b_on && t < dc)? Lb[t * dj] : 0.0;
+				xv[u][t] = (b_on && t < dc)? Xc[int64_t(t) * kp] : 0.0;
+			}
+		}
+		#pragma unroll
+		for(int u = 0; u < NB; ++ u) {
+			#pragma unroll
+			for(int t = 0; t < DM; ++ t)
+				acc -= lv[u][t] * xv[u][t];
+		}
+	}
+	return acc;
+}
+
+// forward substitution of one stage: a workgroup (one wave) per task and group of right-hand sides, the task's columns in order
+template <int D>
+__global__ void __launch_bounds__(64)
+solve_cols_forward_kernel(const TColDesc *__restrict__ cols, const TRowEnt *__restrict__ rents, const int64_t *__restrict__ task_ptr,
+	int task_begin, const double *__restrict__ L, const double *__restrict__ Linv, const double *rhs, int64_t n_ld, double *X, int kp)
+{
+	constexpr int DM = D? D : 8;
+	const TSolveLanes<D> m(kp);
+	const int task = task_begin + blockIdx.x;
+	const int64_t sc_end = task_ptr[task + 1];
+	for(int64_t sc = task_ptr[task]; sc < sc_end; ++ sc) {
+		const TColDesc cd = cols[sc];
+		const int dj = D? D : cd.dj;
+		const bool b_act = m.b_rhs && m.r < dj;
+		const int r = b_act? m.r : 0;
+		double acc = b_act? rhs[cd.cs_src + r + int64_t(m.c) * n_ld] : 0.0;
+		acc = solve_cols_row_sum<D>(acc, rents, cd.r0, cd.nr, dj, L, X, kp, r, m.c, b_act);
+		const double *iL = Linv + cd.linv_off;
+		double y = 0;
+		#pragma unroll
+		for(int t = 0; t < DM; ++ t) {
+			if(t < dj) {
+				const double vt = __shfl(acc, m.base + t); // (every lane of the wave takes part)
+				if(t <= r)
+					y += iL[r + t * dj] * vt;
+			}
+		}
+		if(b_act)
+			X[(cd.cs_new + r) * kp + m.c] = y;
+		__syncthreads(); // single-wave workgroup: y_j is where the following columns' other rows look for it
+	}
+}
+
+// the reduced right-hand sides of the dense-top columns, for the dense tiles' substitutions: a workgroup per column and group
+template <int D>
+__global__ void __launch_bounds__(64)
+solve_cols_top_kernel(const TSolveTopCol *__restrict__ top, const TRowEnt *__restrict__ ents, const double *__restrict__ L,
+	const double *rhs, int64_t n_ld, const double *X, int kp, double *Bd)
+{
+	const TSolveLanes<D> m(kp);
+	const TSolveTopCol rec = top[blockIdx.x];
+	const int dj = D? D : rec.dj;
+	const bool b_act = m.b_rhs && m.r < dj;
+	const int r = b_act? m.r : 0;
+	double acc = b_act? rhs[rec.cs_src + r + int64_t(m.c) * n_ld] : 0.0;
+	acc = solve_cols_row_sum<D>(acc, ents, rec.e0, rec.ne, dj, L, X, kp, r, m.c, b_act);
+	if(b_act)
+		Bd[int64_t(rec.dpos + r) * kp + m.c] = acc;
+}
+
+// backward substitution of one stage, the task's columns last to first: x_j = inv(L_jj)^T (y_j - sum L(i,j)^T x_i); lane
+// (r, c) sums column r of every block L(i,j) against x_i of right-hand side c
+template <int D>
+__global__ void __launch_bounds__(64)
+solve_cols_backward_kernel(const TColDesc *__restrict__ cols, const TBlkDesc *__restrict__ blks, const int64_t *__restrict__ task_ptr,
+	int task_begin, const double *__restrict__ L, const double *__restrict__ Linv, double *X, int kp, double *out, int64_t n_ld)
+{
+	constexpr int DM = D? D : 8, NB = TSolveBatch<D>::N;
+	const TSolveLanes<D> m(kp);
+	const int task = task_begin + blockIdx.x;
+	const int64_t sc_begin = task_ptr[task];
+	for(int64_t sc = task_ptr[task + 1] - 1; sc >= sc_begin; -- sc) {
+		const TColDesc cd = cols[sc];
+		const int dj = D? D : cd.dj;
+		const bool b_act = m.b_rhs && m.r < dj;
+		const int r = b_act? m.r : 0;
+		double acc = b_act? X[(cd.cs_new + r) * kp + m.c] : 0.0;
+		const int64_t b_end = cd.k0 + cd.nb;
+		for(int64_t b = cd.k0 + 1; b < b_end; b += NB) { // (in batches, as solve_cols_row_sum)
+			double lv[NB][DM], xv[NB][DM];
+			#pragma unroll
+			for(int u = 0; u < NB; ++ u) {
+				const bool b_on = b_act && b + u < b_end;
+				const TBlkDesc &bd = blks[(b + u < b_end)? b + u : b];
+				const int di = D? D : int(bd.np_di >> 24);
+				const double *Lb = L + bd.loff + r * di; // L(i,j): di x dj, its column r
+				const double *Xi = X + int64_t(bd.xcs) * kp + m.c;
+				#pragma unroll
+				for(int t = 0; t < DM; ++ t) {
+					lv[u][t] = (b_on && t < di)? Lb[t] : 0.0;
+					xv[u][t] = (b_on && t < di)? Xi[int64_t(t) * kp] : 0.0;
+				}
+			}
+			#pragma unroll
+			for(int u = 0; u < NB; ++ u) {
+				#pragma unroll
+				for(int t = 0; t < DM; ++ t)
+					acc -= lv[u][t] * xv[u][t];
+			}
+		}
+		const double *iL = Linv + cd.linv_off;
+		double x = 0;
+		#pragma unroll
+		for(int t = 0; t < DM; ++ t) {
+			if(t < dj) {
+				const double vt = __shfl(acc, m.base + t);
+				if(t >= r)
+					x += iL[t + r * dj] * vt;
+			}
+		}
+		if(b_act) {
+			X[(cd.cs_new + r) * kp + m.c] = x; // (y_j was read by this very lane)
+			out[cd.cs_src + r + int64_t(m.c) * n_ld] = x;
+		}
+		__syncthreads(); // x_j is where the columns before it look for it
+	}
+}
+
+// the dense-top columns and their row entries below the top (once per analysis)
+static void Setup_Solve_Top(slampp_hip_solver &s, CCovariance &cv)
+{
+	const Plan &P = s.plan;
+	std::vector<TSolveTopCol> top;
+	std::vector<TRowEnt> ents;
+	for(int32_t j = 0; s.n_dense_dim && j < P.n; ++ j) {
+		if(cv.sched_pos[size_t(j)] >= 0)
+			continue; // (a block-eliminated column)
+		TSolveTopCol rec;
+		rec.cs_src = P.cs_src[size_t(j)];
+		rec.e0 = int64_t(ents.size());
+		rec.dj = P.dim[size_t(j)];
+		rec.dpos = P.dense_pos[size_t(j)];
+		rec.pad = 0;
+		for(int64_t r = P.rptr[size_t(j)]; r < P.rptr[size_t(j) + 1]; ++ r) {
+			const int32_t b = P.rblk[size_t(r)], c = P.blk_col[size_t(b)];
+			if(cv.sched_pos[size_t(c)] < 0)
+				continue; // (c is in the dense top: its part is the dense solve's)
+			TRowEnt t_e;
+			t_e.off = P.loff[size_t(b)];
+			t_e.ycs = int32_t(P.cs_new[size_t(c)]);
+			t_e.dc = P.dim[size_t(c)];
+			ents.push_back(t_e);
+		}
+		rec.ne = int32_t(int64_t(ents.size()) - rec.e0);
+		top.push_back(rec);
+	}
+	cv.n_top_cols = int(top.size());
+	cv.d_top_cols.Upload(top, s.stream);
+	cv.d_top_ents.Upload(ents, s.stream);
+	SLAMPP_HIP_CHECK(hipStreamSynchronize(s.stream)); // the host vectors live in this scope
+	cv.b_solve_top = true;
+}
+
+bool solve_columns_applies(const slampp_hip_solver &s)
+{
+	return !s.b_refined && s.plan.max_dim <= 8;
+}
+
+void solve_columns_enqueue(slampp_hip_solver &s, double *p_rhs_dev, int64_t n_ld, int n_columns)
+{
+	const Plan &P = s.plan;
+	CCovariance &cv = Covariance_State(s);
+	if(!cv.b_columns)
+		Setup_Columns(s, cv);
+	if(!cv.b_solve_top)
+		Setup_Solve_Top(s, cv);
+	s.Ensure_Leaf_Inverses(); // (the substitutions multiply by inv(L_jj) of every column)
+	const int D = Unrolled_Dim(P);
+	const int n_per_wave = 64 / (D? D : 8);
+	const int n_stages = int(P.stage_ptr.size()) - 1;
+	const int ld = s.n_dense_pad, n_dense = s.n_dense_dim, n_tiles = ld / COV_NB;
+	s.Phase_Begin("solve_columns");
+	for(int col0 = 0; col0 < n_columns; col0 += COV_K_PASS) {
+		const int kp = std::min(int(COV_K_PASS), n_columns - col0);
+		const unsigned n_groups = unsigned((kp + n_per_wave - 1) / n_per_wave);
+		double *p_pass = p_rhs_dev + int64_t(col0) * n_ld;
+#define SOLVE_COLS_DISPATCH(LAUNCH) switch(D) { case 3: LAUNCH(3); break; case 6: LAUNCH(6); break; case 7: LAUNCH(7); break; default: LAUNCH(0); break; }
+		for(int st = 0; st < n_stages; ++ st) {
+			const int n_tasks = P.stage_ptr[size_t(st + 1)] - P.stage_ptr[size_t(st)];
+			if(n_tasks <= 0)
+				continue;
+#define SOLVE_COLS_FWD(DD) hipLaunchKernelGGL(solve_cols_forward_kernel<DD>, dim3(unsigned(n_tasks), n_groups), dim3(64), 0, s.stream, s.dplan.cols, \
+				s.dplan.rents, s.dplan.task_ptr, P.stage_ptr[size_t(st)], s.d_L.p(), s.d_Linv.p(), p_pass, n_ld, cv.d_X.p(), kp)
+			SOLVE_COLS_DISPATCH(SOLVE_COLS_FWD)
+#undef SOLVE_COLS_FWD
+		}
+		if(n_dense) {
+			SLAMPP_HIP_CHECK(hipMemsetAsync(cv.d_Bd.p(), 0, size_t(ld) * kp * sizeof(double), s.stream)); // (gaps between the columns' positions)
+			if(cv.n_top_cols) {
+#define SOLVE_COLS_TOP(DD) hipLaunchKernelGGL(solve_cols_top_kernel<DD>, dim3(unsigned(cv.n_top_cols), n_groups), dim3(64), 0, s.stream, cv.d_top_cols.p(), \
+				cv.d_top_ents.p(), s.d_L.p(), p_pass, n_ld, cv.d_X.p(), kp, cv.d_Bd.p())
+				SOLVE_COLS_DISPATCH(SOLVE_COLS_TOP)
+#undef SOLVE_COLS_TOP
+			}
+			for(int t = 0; t < n_tiles; ++ t)
+				hipLaunchKernelGGL(cov_dense_forward_kernel, dim3(n_tiles - t), dim3(256), 0, s.stream, s.d_dense.p(), ld, n_dense, t,
+					s.d_dense_invdiag.p(), cv.d_Bd.p(), cv.d_Zb.p(), kp);
+			for(int t = n_tiles - 1; t >= 0; -- t)
+				hipLaunchKernelGGL(cov_dense_backward_kernel, dim3(t + 1), dim3(256), 0, s.stream, s.d_dense.p(), ld, n_dense, t,
+					s.d_dense_invdiag.p(), cv.d_Zb.p(), kp, s.d_dense_dst.p(), cv.d_X.p(), p_pass, n_ld, 0);
+		}
+		for(int st = n_stages - 1; st >= 0; -- st) {
+			const int n_tasks = P.stage_ptr[size_t(st + 1)] - P.stage_ptr[size_t(st)];
+			if(n_tasks <= 0)
+				continue;
+#define SOLVE_COLS_BWD(DD) hipLaunchKernelGGL(solve_cols_backward_kernel<DD>, dim3(unsigned(n_tasks), n_groups), dim3(64), 0, s.stream, s.dplan.cols, \
+				s.dplan.blks, s.dplan.task_ptr, P.stage_ptr[size_t(st)], s.d_L.p(), s.d_Linv.p(), cv.d_X.p(), kp, p_pass, n_ld)
+			SOLVE_COLS_DISPATCH(SOLVE_COLS_BWD)
+#undef SOLVE_COLS_BWD
+		}
+#undef SOLVE_COLS_DISPATCH
 	}
 	s.Phase_End();
 	SLAMPP_HIP_CHECK(hipGetLastError());

@@ -18,5 +18,9 @@ size_t pattern_outer_device_bytes(const CPatternOuterState *p);
 // beta = 0: out is not read
 void pattern_outer_enqueue(const CPatternOuterState &r_state, int n_batch, const double *p_a, int64_t n_a_stride, const double *p_b,
 	int64_t n_b_stride, double *p_out, int64_t n_out_stride, double f_alpha, double f_beta, hipStream_t stream);
+// out = alpha sum over k < n_terms of P(a_k, b_k) + beta out (a_k = p_a + k n_a_stride, b_k = p_b + k n_b_stride), one launch
+// that writes out once; the terms are added in ascending k, one term gives the bits of pattern_outer_enqueue
+void pattern_outer_sum_enqueue(const CPatternOuterState &r_state, int n_terms, const double *p_a, int64_t n_a_stride, const double *p_b,
+	int64_t n_b_stride, double *p_out, double f_alpha, double f_beta, hipStream_t stream);
 
 } // namespace slampp

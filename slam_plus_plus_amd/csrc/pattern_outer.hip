@@ -11,6 +11,7 @@
 // (3 x 3 and 7 x 7 blocks have odd sizes: the pairs straddle blocks).  A member whose out is not 16-byte aligned is written with
 // 8-byte stores, with the same values.  No atomics, no reductions: every value is at most two products and one add, in one
 // fixed form (explicit fused multiply-adds), so two calls -- batched or not, aligned or not -- give the same bits.
+// The sum over several vector pairs (slampp_hip_pattern_outer_sum) is the same kernel with a loop over the terms.
 #include "pattern_outer.h"
 #include "pattern_outer_tables.h"
 #include "solver.h"
@@ -49,13 +50,17 @@ __device__ __forceinline__ double outer_value(const double *__restrict__ a, cons
 // loads of a phase are issued together.
 enum { outer_PAIRS = 4 };
 
+// B_SUM (slampp_hip_pattern_outer_sum): one member, out = alpha sum over the n_terms vector pairs p_a + k n_a_stride,
+// p_b + k n_b_stride + beta out: the thread keeps its values in registers over the terms, added in ascending k, and writes
+// out once; the first term is computed as the plain kernel computes it, so one term gives that kernel's bits
+template <bool B_SUM>
 __global__ void __launch_bounds__(256)
 pattern_outer_kernel(TOuterTables t, const double *__restrict__ p_a, int64_t n_a_stride, const double *__restrict__ p_b,
-	int64_t n_b_stride, double *p_out, int64_t n_out_stride, double f_alpha, double f_beta)
+	int64_t n_b_stride, double *p_out, int64_t n_out_stride, double f_alpha, double f_beta, int n_terms)
 {
-	const double *__restrict__ a = p_a + int64_t(blockIdx.y) * n_a_stride;
-	const double *__restrict__ b = p_b + int64_t(blockIdx.y) * n_b_stride;
-	double *out = p_out + int64_t(blockIdx.y) * n_out_stride;
+	const double *__restrict__ a = p_a + (B_SUM? 0 : int64_t(blockIdx.y) * n_a_stride);
+	const double *__restrict__ b = p_b + (B_SUM? 0 : int64_t(blockIdx.y) * n_b_stride);
+	double *out = p_out + (B_SUM? 0 : int64_t(blockIdx.y) * n_out_stride);
 	const int64_t n_first = int64_t(blockIdx.x) * (512 * outer_PAIRS) + 2 * threadIdx.x;
 	int64_t e[outer_PAIRS];
 	int32_t k[outer_PAIRS], k_hi[outer_PAIRS];
@@ -104,8 +109,28 @@ pattern_outer_kernel(TOuterTables t, const double *__restrict__ p_a, int64_t n_a
 	double f0[outer_PAIRS], f1[outer_PAIRS];
 	#pragma unroll
 	for(int u = 0; u < outer_PAIRS; ++ u) {
-		f0[u] = outer_value(a, b, n_r0[u], n_c0[u], b_diag0[u], f_alpha);
-		f1[u] = outer_value(a, b, n_r1[u], n_c1[u], b_diag1[u], f_alpha);
+		if(!B_SUM) {
+			f0[u] = outer_value(a, b, n_r0[u], n_c0[u], b_diag0[u], f_alpha);
+			f1[u] = outer_value(a, b, n_r1[u], n_c1[u], b_diag1[u], f_alpha);
+		} else {
+			f0[u] = outer_value(a, b, n_r0[u], n_c0[u], b_diag0[u], 1.0);
+			f1[u] = outer_value(a, b, n_r1[u], n_c1[u], b_diag1[u], 1.0);
+		}
+	}
+	if(B_SUM) {
+		for(int k = 1; k < n_terms; ++ k) {
+			const double *__restrict__ a_k = a + int64_t(k) * n_a_stride, *__restrict__ b_k = b + int64_t(k) * n_b_stride;
+			#pragma unroll
+			for(int u = 0; u < outer_PAIRS; ++ u) {
+				f0[u] += outer_value(a_k, b_k, n_r0[u], n_c0[u], b_diag0[u], 1.0);
+				f1[u] += outer_value(a_k, b_k, n_r1[u], n_c1[u], b_diag1[u], 1.0);
+			}
+		}
+		#pragma unroll
+		for(int u = 0; u < outer_PAIRS; ++ u) {
+			f0[u] *= f_alpha;
+			f1[u] *= f_alpha;
+		}
 	}
 	const bool b_aligned = (reinterpret_cast<uintptr_t>(out) & 15) == 0; // (the same for the whole member: no divergence)
 	#pragma unroll
@@ -165,8 +190,18 @@ void pattern_outer_enqueue(const CPatternOuterState &S, int n_batch, const doubl
 {
 	if(!S.t.n_values)
 		return;
-	hipLaunchKernelGGL(pattern_outer_kernel, dim3(unsigned((S.t.n_values + 512 * outer_PAIRS - 1) / (512 * outer_PAIRS)), unsigned(n_batch)), dim3(256), 0, st, S.t,
-		p_a, n_a_stride, p_b, n_b_stride, p_out, n_out_stride, f_alpha, f_beta);
+	hipLaunchKernelGGL(pattern_outer_kernel<false>, dim3(unsigned((S.t.n_values + 512 * outer_PAIRS - 1) / (512 * outer_PAIRS)), unsigned(n_batch)), dim3(256), 0, st, S.t,
+		p_a, n_a_stride, p_b, n_b_stride, p_out, n_out_stride, f_alpha, f_beta, 1);
+	SLAMPP_HIP_CHECK(hipGetLastError());
+}
+
+void pattern_outer_sum_enqueue(const CPatternOuterState &S, int n_terms, const double *p_a, int64_t n_a_stride, const double *p_b,
+	int64_t n_b_stride, double *p_out, double f_alpha, double f_beta, hipStream_t st)
+{
+	if(!S.t.n_values)
+		return;
+	hipLaunchKernelGGL(pattern_outer_kernel<true>, dim3(unsigned((S.t.n_values + 512 * outer_PAIRS - 1) / (512 * outer_PAIRS))), dim3(256), 0, st, S.t,
+		p_a, n_a_stride, p_b, n_b_stride, p_out, 0, f_alpha, f_beta, n_terms);
 	SLAMPP_HIP_CHECK(hipGetLastError());
 }
 

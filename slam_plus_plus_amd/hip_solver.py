@@ -33,6 +33,7 @@ LIB_PATH = os.path.join(_HERE, "libslampp_hip.so")
 OK, NOT_POSDEF = 0, 1
 ERR_INVALID, ERR_ALLOC, ERR_DEVICE, ERR_UNSUPPORTED = -1, -2, -3, -4
 MODE_SPARSE, MODE_SCHUR = 0, 1
+SOLVE_MAX_COLUMNS = 256    # SLAMPP_HIP_SOLVE_MAX_COLUMNS
 # slampp_hip_multiply: block rows with more blocks than MULTIPLY_LONG_ROW are cut into chunks of MULTIPLY_CHUNK
 # (SLAMPP_HIP_MULTIPLY_* in include/slampp_hip.h; the development option "multiply_long_row" lowers the threshold)
 MULTIPLY_LONG_ROW, MULTIPLY_CHUNK = 256, 256
@@ -118,6 +119,10 @@ ABI = {
     "slampp_hip_upload_values_async": (C.c_int, [_P, C.c_int64, C.c_int64]),
     "slampp_hip_solve_again": (C.c_int, [_P, _P]),
     "slampp_hip_solve_again_device_async": (C.c_int, [_P, _P]),
+    "slampp_hip_solve_columns_device_async": (C.c_int, [_P, _P, C.c_int64, C.c_int]),
+    "slampp_hip_solve_columns": (C.c_int, [_P, _P, C.c_int64, C.c_int]),
+    "slampp_hip_pattern_outer_sum_device_async": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64, _P, C.c_double,
+                                                            C.c_double]),
     "slampp_hip_multiply_device_async": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double]),
     "slampp_hip_multiply": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double]),
     "slampp_hip_pattern_outer_device_async": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double]),
@@ -472,6 +477,18 @@ class _SolverBase:
             raise ValueError("eta must be a contiguous float64 vector of the system's dimension")
         return self._check(self._lib.slampp_hip_solve_again(self._h, _ptr(eta)))
 
+    def Solve_Columns(self, B: np.ndarray) -> bool:
+        """k right-hand sides with the factor the last solve left behind, in one call (slampp_hip_solve_columns: cholmod_solve
+        with a dense B of several columns).  ``B``: a C-contiguous float64 ``(k, n_scalars)`` array, 1 <= k <= 256, row c =
+        right-hand side c on entry and its solution on return.  Valid where Solve_Again is."""
+        if self._structure_key is None or not self._analyzed:
+            raise ValueError("Solve_Columns: there is no factorization")
+        n_scalars = self._structure_key[2]
+        if (not isinstance(B, np.ndarray) or B.dtype != np.float64 or not B.flags.c_contiguous or B.ndim != 2
+                or B.shape[1] != n_scalars or not 1 <= B.shape[0] <= SOLVE_MAX_COLUMNS):
+            raise ValueError(f"B must be a C-contiguous float64 array of the shape (k, n_scalars), 1 <= k <= {SOLVE_MAX_COLUMNS}")
+        return self._check(self._lib.slampp_hip_solve_columns(self._h, _ptr(B), n_scalars, int(B.shape[0])))
+
     def Log_Determinant(self, lam, reuse_factor: bool = False) -> float:
         """log det Lambda = 2 sum log L_ii from the Cholesky factor on the device (slampp_hip_logdet).  ``reuse_factor=False``:
         analyzes a new structure, factors ``lam.values`` and leaves the handle as Solve_PosDef_Blocky leaves it (Solve_Again
@@ -662,6 +679,12 @@ class _SolverBase:
         (slampp_hip_solve_again_device_async; Schur mode: option ``schur_keep=1``)."""
         self._check(self._lib.slampp_hip_solve_again_device_async(self._h, rhs_ptr))
 
+    def solve_columns_device(self, rhs_ptr: int, ld: int, k: int) -> None:
+        """k right-hand sides with the kept factor in one call, device-resident and enqueue-only, in both modes
+        (slampp_hip_solve_columns_device_async): column c is the n_scalars doubles at rhs_ptr + 8 c ld; valid where
+        solve_again_device is."""
+        self._check(self._lib.slampp_hip_solve_columns_device_async(self._h, rhs_ptr or None, int(ld), int(k)))
+
     def multiply_device(self, values_ptr: int, x_ptr: int, y_ptr: int, alpha: float = 1.0, beta: float = 0.0) -> None:
         """y = alpha Lambda x + beta y on device-resident arrays, enqueue-only (slampp_hip_multiply_device_async); the
         structure is the one last given to the handle."""
@@ -679,6 +702,14 @@ class _SolverBase:
         a_ptr + 8 m a_stride and b_ptr + 8 m b_stride and writes out_ptr + 8 m out_stride (strides in doubles)."""
         self._check(self._lib.slampp_hip_pattern_outer_batch_device_async(
             self._h, int(n_batch), a_ptr or None, int(a_stride), b_ptr or None, int(b_stride), out_ptr or None, int(out_stride),
+            float(alpha), float(beta)))
+
+    def pattern_outer_sum_device(self, n_terms: int, a_ptr: int, a_stride: int, b_ptr: int, b_stride: int, out_ptr: int,
+                                 alpha: float = 1.0, beta: float = 0.0) -> None:
+        """out = alpha sum_k P(a_k, b_k) + beta out in one launch (slampp_hip_pattern_outer_sum_device_async): term k reads
+        a_ptr + 8 k a_stride and b_ptr + 8 k b_stride (strides in doubles), out is written once."""
+        self._check(self._lib.slampp_hip_pattern_outer_sum_device_async(
+            self._h, int(n_terms), a_ptr or None, int(a_stride), b_ptr or None, int(b_stride), out_ptr or None,
             float(alpha), float(beta)))
 
     def dot_device(self, a_ptr: int, b_ptr: int, n: int, out_ptr: int) -> None:

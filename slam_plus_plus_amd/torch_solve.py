@@ -44,6 +44,16 @@ factorizations, the documented cost -- followed by the batched outer-product ker
 (rows contiguous, any row stride of at least a row); odd strides are solved member by member inside the library, with the
 same results.
 
+``solve_multi(solver, lam, values, eta[K, n_scalars])``: K <= 256 right-hand sides on ONE set of values, in both modes (rows
+contiguous, any row stride of at least a row).  Forward: slampp_hip_factor_solve_device_async on row 0, then the rows after it
+in one slampp_hip_solve_columns_device_async on the factor that left, and one wait.  Backward: ``g = M^-1 x_bar`` for all rows in
+one slampp_hip_solve_columns_device_async on the kept factor -- under the generation rule above --, ``eta_bar = g`` and
+``v_bar = -sum_k P(g_k, x_k)`` in one launch (slampp_hip_pattern_outer_sum_device_async).  If the factor is someone else's by
+then, row 0 of ``g`` factors the saved values again and the other rows follow on that factor: one factorization.  A
+Schur-mode solver without ``schur_keep=1`` (or ``schur_incremental``) keeps no factor: it solves row by row with
+slampp_hip_factor_solve_device_async, forward and backward (K factorizations each), and never raises for it.
+``solver.n_backward_refactorizations`` counts the factorizations backward passes had to make: 1, or K for such a solver.
+
 ``logdet(solver, lam, values)`` returns ``log det M(values)`` as a 0-dim float64 tensor on the solver's device, once
 differentiable in ``values`` (both modes).  Forward: slampp_hip_logdet_device_async with ``b_reuse_factor = 0`` -- the values are
 factored and twice the sum of log of the factor's pivots is taken on the device, Schur mode adding every landmark's
@@ -68,6 +78,7 @@ from torch.autograd.function import once_differentiable
 from .hip_solver import CLinearSolver_HIP, CLinearSolver_Schur_HIP, MODE_SPARSE
 
 MAX_BATCH = 64     # SLAMPP_HIP_MAX_BATCH
+MAX_COLUMNS = 256  # SLAMPP_HIP_SOLVE_MAX_COLUMNS
 
 
 # ---- the yardsticks ----
@@ -203,6 +214,78 @@ def solve(solver, lam, values: torch.Tensor, eta: torch.Tensor) -> torch.Tensor:
     _check_tensor(solver, eta, "eta", (int(lam.cumsum[-1]),))
     _require_analysis(solver, lam)
     return _Solve.apply(values, eta, solver, lam)
+
+
+# ---- K right-hand sides on one set of values ----
+
+def _solve_rows(solver, values, rows, b_factor_first: bool) -> int:
+    """Enqueues M(values)^-1 on every row of ``rows`` (K, n_scalars; contiguous) in place and returns the number of
+    factorizations that took.  ``b_factor_first``: row 0 by slampp_hip_factor_solve_device_async, which installs the factor
+    the other rows are solved from (slampp_hip_solve_columns_device_async); a Schur solver that keeps no factor solves every
+    row with a factorization of its own.  Otherwise all rows from the factor in place."""
+    n_rows, n_ld = rows.shape[0], rows.stride(0)
+    if not b_factor_first:
+        solver.solve_columns_device(rows.data_ptr(), n_ld, n_rows)
+        return 0
+    solver.factor_solve_device_async(values.data_ptr(), rows.data_ptr())
+    if n_rows == 1:
+        return 1
+    if _keeps_factor(solver):
+        solver.solve_columns_device(rows.data_ptr() + 8 * n_ld, n_ld, n_rows - 1)
+        return 1
+    for k in range(1, n_rows):
+        solver.factor_solve_device_async(values.data_ptr(), rows.data_ptr() + 8 * k * n_ld)
+    return n_rows
+
+
+class _SolveMulti(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, values, eta, solver, lam):
+        x = eta.clone(memory_format=torch.contiguous_format)
+        v = values.detach()
+        _enqueue(solver, lambda: _solve_rows(solver, v, x, True))
+        if not solver.sync():
+            raise torch.linalg.LinAlgError("solve_multi: the matrix is not positive definite")
+        ctx.solver, ctx.lam, ctx.generation = solver, lam, solver.factor_generation
+        ctx.save_for_backward(values, x)
+        return x
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, x_bar):
+        values, x = ctx.saved_tensors
+        solver, lam = ctx.solver, ctx.lam
+        g = x_bar.clone(memory_format=torch.contiguous_format)
+        v_bar = torch.empty_like(values) if ctx.needs_input_grad[0] else None
+        b_kept = ctx.generation == solver.factor_generation and _keeps_factor(solver)
+        if not b_kept:
+            _require_analysis(solver, lam)          # (the handle may have been given another structure since)
+        n_factorizations = []
+
+        def work():
+            n_factorizations.append(_solve_rows(solver, values, g, not b_kept))
+            if v_bar is not None:
+                solver.pattern_outer_sum_device(g.shape[0], g.data_ptr(), g.stride(0), x.data_ptr(), x.stride(0),
+                                                v_bar.data_ptr(), -1.0, 0.0)
+        _enqueue(solver, work)
+        if not b_kept:
+            solver.n_backward_refactorizations += n_factorizations[0]
+            ctx.generation = solver.factor_generation     # the handle's factor is this node's again
+        return v_bar, (g if ctx.needs_input_grad[1] else None), None, None
+
+
+def solve_multi(solver, lam, values: torch.Tensor, eta: torch.Tensor) -> torch.Tensor:
+    """x[k] = M(values)^-1 eta[k] for K <= 256 right-hand sides on ONE set of values, differentiable in both (module docstring)."""
+    _check_solver(solver)
+    _check_tensor(solver, values, "values", (int(lam.values.shape[0]),))
+    n_scalars = int(lam.cumsum[-1])
+    if isinstance(eta, torch.Tensor) and (eta.dim() != 2 or not 1 <= eta.shape[0] <= MAX_COLUMNS):
+        raise ValueError(f"eta must be a tensor of the shape (K, n_scalars), 1 <= K <= {MAX_COLUMNS}")
+    _check_tensor(solver, eta, "eta", (eta.shape[0] if isinstance(eta, torch.Tensor) else 1, n_scalars))
+    if eta.shape[0] > 1 and eta.stride(0) < n_scalars:
+        raise ValueError("the rows of eta overlap (row stride below the row length)")
+    _require_analysis(solver, lam)
+    return _SolveMulti.apply(values, eta, solver, lam)
 
 
 # ---- K value sets of one structure ----
