@@ -20,6 +20,7 @@
 // Tasks whose columns are not consecutive, or that exceed the capacities, stay with factor_stage_kernel.
 // Own translation unit (see dense_tiles.hip for why).
 #include <hip/hip_runtime.h>
+#include <cstdio>
 #include "sparse_kernels.h"
 
 namespace slampp {
@@ -202,11 +203,103 @@ __device__ __forceinline__ void panel_hand_up(const longlong2 *s_out, int n_out,
 	}
 }
 
+// The products whose operands a wave fetches itself (the entries [e0, e1) of s_ext, kinds 0 / 1), even block sizes: the
+// operand blocks as 16-byte loads, a block in D * D / 2 lanes, PANEL_FETCH_BLOCKS blocks per instruction -- block 2 k of a
+// group is a_off of its entry k, block 2 k + 1 its b_off, each lane reads its offset from the entry in LDS --, the y of the
+// group's row entries in one more load (D / 2 lanes per vector), and the whole group of G products requested before the
+// first is used.  The registers then go through the staging area in passes of PASS products: the loads of a pass are
+// stored as they came (lane l of the pass's load i at 16 (54 i + l) bytes: the blocks lie one behind the other as the
+// block-per-load fetch lays them), and the products are that fetch's, lane = element, each sum over t = 0 .. D - 1 in
+// that order, subtracted from the image in entry order: the same bits.  Lanes beyond the last block of an instruction and blocks beyond the last entry repeat
+// a valid one (a load behind a branch would wait for the others); their registers are not stored / their products skipped.
+// L and w are 16-byte aligned (launch_factor_panel checks), block offsets are multiples of D * D and ycs of D.
+template <int D, int W>
+__device__ __forceinline__ void panel_fetch_packed(const TPanelExt *s_ext, int e0, const int e1, const double *L, const double *w, int lane,
+	const TLaneMap mm, bool b_y, int yq, double *s_ops, double *s_yv, double *s_L, double *s_w)
+{
+	enum { DD = D * D, BL = DD / 2 /* lanes per block */, BPI = PANEL_FETCH_BLOCKS, YL = D / 2 /* lanes per y */, PASS = panel_fetch_pass(W), G = panel_fetch_group(W),
+		N_LOADS = 2 * G / BPI, PASS_LOADS = 2 * PASS / BPI, N_PASSES = G / PASS, AHEAD = (W == 2)? 3 : 1 /* sums taken together: three where the fetch is the default; the other shapes keep the registers they had (panel_fetch_group) */ };
+	static_assert(D % 2 == 0 && BPI * BL <= 64 && G * YL <= 64, "a load instruction holds whole blocks");
+	static_assert(2 * G % BPI == 0 && 2 * PASS % BPI == 0 && G % PASS == 0 && PASS % AHEAD == 0 && 2 * PASS <= 2 * panel_fresh_batch(W) && PASS * D <= panel_fresh_batch(W) * 8,
+		"a pass is whole load instructions and fits the staging area");
+	const int lb = min(lane, BPI * BL - 1); // (the lanes past the last block repeat its last lane)
+	const int n_blk = lb / BL, n_piece = lb % BL;
+	const int n_yk = min(lane / YL, G - 1), n_ypiece = lane % YL;
+	typedef double TPair __attribute__((ext_vector_type(2))); // 16 bytes, one load / store instruction
+	TPair *s_ops2 = reinterpret_cast<TPair*>(s_ops), *s_yv2 = reinterpret_cast<TPair*>(s_yv);
+	for(; e0 < e1; e0 += G) {
+		TPair v[N_LOADS], vy;
+		{ // (y first: the first pass needs it)
+			const TPanelExt *p_en = s_ext + min(e0 + n_yk, e1 - 1);
+			vy = *reinterpret_cast<const TPair*>(w + (p_en->kind? p_en->ycs + 2 * n_ypiece : 0));
+		}
+		#pragma unroll
+		for(int i = 0; i < N_LOADS; ++ i) {
+			const int n_b = BPI * i + n_blk; // the lane's block of the group
+			const int64_t n_off = reinterpret_cast<const int64_t*>(s_ext + min(e0 + n_b / 2, e1 - 1))[n_b & 1]; // a_off, b_off
+			v[i] = *reinterpret_cast<const TPair*>(L + n_off + 2 * n_piece);
+		}
+		#pragma unroll
+		for(int p = 0; p < N_PASSES; ++ p) {
+			if(e0 + p * PASS < e1) { // wave-uniform
+				#pragma unroll
+				for(int i = 0; i < PASS_LOADS; ++ i) {
+					if(lane < BPI * BL)
+						s_ops2[i * BPI * BL + lane] = v[p * PASS_LOADS + i];
+				}
+				if(lane >= p * PASS * YL && lane < (p + 1) * PASS * YL)
+					s_yv2[lane - p * PASS * YL] = vy; // y of the pass's product u at s_yv + u * D
+				// the pass's products: AHEAD sums first (three at two waves a task) -- they do not depend on each other, they read
+				// the staging area only, and one after the other each is a chain of four trips to LDS (entry, operands, target,
+				// back) with two or three waves a SIMD to hide it --, then their subtractions in entry order (entries of one slot
+				// follow each other).  Products beyond the last entry are those of the repeated blocks; they are not subtracted.
+				uint16_t n_kind[PASS], n_slot[PASS];
+				int32_t n_col[PASS];
+				#pragma unroll
+				for(int u = 0; u < PASS; ++ u) {
+					const TPanelExt *p_en = s_ext + min(e0 + p * PASS + u, e1 - 1);
+					n_kind[u] = p_en->kind;
+					n_slot[u] = p_en->slot;
+					n_col[u] = p_en->col;
+				}
+				wave_sync();
+				#pragma unroll
+				for(int u0 = 0; u0 < PASS; u0 += AHEAD) { // (AHEAD sums at a time: their operands are what the registers hold)
+					double sum[AHEAD];
+					#pragma unroll
+					for(int k = 0; k < AHEAD; ++ k) {
+						const int u = u0 + k;
+						const bool b_vec = n_kind[u] && b_y; // the right-hand side rides along the diagonal block's row entries
+						const double *pa = b_vec? s_yv + u * D : s_ops + (2 * u) * DD + mm.r;
+						const double *pb = s_ops + (2 * u + 1) * DD + (n_kind[u]? yq : mm.q);
+						const int as = b_vec? 1 : D;
+						sum[k] = 0;
+						#pragma unroll
+						for(int t = 0; t < D; ++ t)
+							sum[k] += pa[t * as] * pb[t * D];
+					}
+					#pragma unroll
+					for(int k = 0; k < AHEAD; ++ k) {
+						const int u = u0 + k;
+						if(e0 + p * PASS + u < e1) { // wave-uniform
+							if(n_kind[u] && b_y)
+								s_w[n_col[u] * D + yq] -= sum[k];
+							else if(mm.b_act)
+								s_L[int(n_slot[u]) * DD + lane] -= sum[k];
+						}
+					}
+				}
+				wave_sync();
+			}
+		}
+	}
+}
+
 template <int D, int W, bool b_fused, bool b_rows>
 __global__ void __launch_bounds__(64 * W)
 factor_panel_kernel(const longlong2 *__restrict__ pkg, const int64_t *__restrict__ pkg_off, const int64_t *__restrict__ out_off, int n_panels,
 	TPanelLaunch t_cfg, const TUpdSlot *__restrict__ upd_slots, int n_upd_slots, const TUpdEnt *__restrict__ upd_ents, const double *__restrict__ A,
-	const double *__restrict__ b, double *L, double *Linv, double *w, double *H, int *p_flag, long long *p_timing, TBatch t_batch)
+	const double *__restrict__ b, double *L, double *Linv, double *w, double *H, int *p_flag, long long *p_timing, TBatch t_batch, int b_packed_fetch)
 {	{ const int64_t n_member = blockIdx.y; A += n_member * t_batch.a; b += n_member * t_batch.b; L += n_member * t_batch.l; Linv += n_member * t_batch.linv; w += n_member * t_batch.w; H += n_member * t_batch.h; p_flag += n_member; } // (TBatch: sparse_kernels.h)
 
 	enum { DD = D * D, BATCH = panel_fresh_batch(W), UPD_BATCH = PANEL_UPD_BATCH, UPD_W = (W < int(PANEL_UPD_W))? W : int(PANEL_UPD_W), // (two waves per task: two per update block)
@@ -353,7 +446,14 @@ factor_panel_kernel(const longlong2 *__restrict__ pkg, const int64_t *__restrict
 		}
 		n_ext0 += n_up;
 	}
-	// (b) products whose operands this task fetches itself
+	// (b) products whose operands this task fetches itself: an even block size takes them three blocks to a load instruction
+	// (panel_fetch_packed; b_packed_fetch is the launch's choice, wave-uniform), what follows is a block per instruction
+	if constexpr(b_fused && D % 2 == 0) {
+		if(b_packed_fetch) {
+			panel_fetch_packed<D, W>(s_ext, n_ext0, n_ext1, L, w, lane, mm, b_y, yq, s_ops, s_yv, s_L, s_w);
+			n_ext0 = n_ext1;
+		}
+	}
 	for(int e0 = n_ext0, e1 = n_ext1; e0 < e1; e0 += BATCH) {
 		double va[BATCH], vb[BATCH], vy[BATCH];
 		#pragma unroll
@@ -535,6 +635,18 @@ bool launch_factor_panel(int n_dim, bool b_fused, bool b_rows, const TPanelLaunc
 	const int n_grid = n_tasks + (n_upd_slots + n_groups - 1) / n_groups;
 	if(n_grid <= 0)
 		return true;
+	// the fetch of the products a task brings in itself: packed (panel_fetch_packed) for an even block size at two waves a
+	// task, the shape where it measured faster (C3's crowded launch 73.5 -> 67.6 us); at eight it gains nothing (14.7 -> 14.8 us:
+	// those tasks fetch a handful of products) and four was not measured, so both stay with a block per load.  The factor and
+	// the workspace are the handle's own allocations, 16-byte aligned, and a batch's member strides are even; a base that is
+	// not takes the block-per-load fetch, which computes the same bits.  Development aid (plan.h): 0 = a block per load
+	// everywhere, 1 = packed wherever the block size is even, at every number of waves.
+	const int n_fetch_env = dev_knob("SLAMPP_HIP_DEV_PANEL_FETCH", -1);
+	const bool b_aligned = (reinterpret_cast<uintptr_t>(L) | reinterpret_cast<uintptr_t>(w)) % 16 == 0 && (t_batch.n <= 1 || (t_batch.l % 2 == 0 && t_batch.w % 2 == 0));
+	const bool b_packed = b_fused && n_dim % 2 == 0 && b_aligned && ((n_fetch_env >= 0)? n_fetch_env != 0 : W == 2);
+	if(p_timing) // (development aid SLAMPP_HIP_STAGE_TIMING: which fetch the launch takes, for the tests)
+		fprintf(stderr, "stage_timing panel launch: %d tasks, %d waves a task, block size %d, fused %d, fetch %s\n", n_tasks, W, n_dim, int(b_fused),
+			b_packed? "packed" : "block per load");
 	const size_t n_lds_bytes = size_t(panel_lds(n_dim, b_fused, r_cfg).TOTAL) * sizeof(double);
 	if(n_lds_bytes > PANEL_LDS_BUDGET)
 		return false; // (the analysis keeps every stage inside the budget: solver.hip, the hand-up lists; a launch past it would fail with a device error on a valid system)
@@ -546,7 +658,7 @@ bool launch_factor_panel(int n_dim, bool b_fused, bool b_rows, const TPanelLaunc
 			b_attribute_set = true; \
 		} \
 		hipLaunchKernelGGL((factor_panel_kernel<D, WW, F, RW>), dim3(n_grid, t_batch.n), dim3(64 * WW), n_lds_bytes, stream, pkg, pkg_off, out_off, n_tasks, r_cfg, \
-			upd_slots, n_upd_slots, upd_ents, A, b, L, Linv, w, H, p_flag, p_timing, t_batch); } while(0)
+			upd_slots, n_upd_slots, upd_ents, A, b, L, Linv, w, H, p_flag, p_timing, t_batch, int(b_packed)); } while(0)
 #define LAUNCH_PANEL_F(D, WW, F) do { if(b_rows) LAUNCH_PANEL_INSTANCE(D, WW, F, true); else LAUNCH_PANEL_INSTANCE(D, WW, F, false); } while(0)
 #define LAUNCH_PANEL(D) do { \
 		if(W == 2) { if(b_fused) LAUNCH_PANEL_F(D, 2, true); else LAUNCH_PANEL_F(D, 2, false); } \

@@ -133,8 +133,22 @@ struct TPanelLaunch {
 enum { PANEL_UPD_BATCH = 8 };
 // fresh products a wave has in flight: four at eight waves per task, eight at four (the same operand staging per workgroup;
 // at two waves per task four again: the launch is crowded, and 4.6 KB less LDS per workgroup is a workgroup more per CU -- C3 141 -> 139 us;
-// the first slice stage above the leaves brings in ~100 products per task, each batch a trip to L2)
+// the first slice stage above the leaves brings in ~100 products per task, each batch a trip to L2 -- with an odd block
+// size; an even one has the packed fetch below, and the batch is then only what sizes the staging area)
 inline __host__ __device__ constexpr int panel_fresh_batch(int n_waves) { return (n_waves == 4)? 8 : 4; }
+// The packed fetch (even block sizes; panel_kernel.hip: panel_fetch_packed): a block is D * D / 2 lanes of a 16-byte load, so
+// one load instruction brings PANEL_FETCH_BLOCKS of them where the fetch above brings one, and for about the same registers
+// a wave has a group of nine products in flight instead of four: a third of the trips to L2.  The staging area stays the
+// size it is: a group goes through it in passes of whole load instructions -- three products (six blocks, two instructions)
+// into the eight blocks' room of two and eight waves a task, six at four.
+// By default only launches of two waves a task take it (launch_factor_panel: the crowded stages, whose tasks fetch ~100
+// products each; measured faster there).  Four and eight waves a task take it with SLAMPP_HIP_DEV_PANEL_FETCH=1 only, and
+// their groups (twelve and six products, two passes) are sized so that those kernels keep the registers they had: nine at
+// eight waves made it 130, three waves a SIMD, and a CU then holds one workgroup of eight waves where it held two -- C3's
+// narrow launches 14.7 -> 16.7 us, on either fetch, since registers belong to the kernel and not to the path taken.
+enum { PANEL_FETCH_BLOCKS = 3 };
+inline __host__ __device__ constexpr int panel_fetch_pass(int n_waves) { return 2 * panel_fresh_batch(n_waves) / (2 * PANEL_FETCH_BLOCKS) * PANEL_FETCH_BLOCKS; } // products per pass: 3 (6)
+inline __host__ __device__ constexpr int panel_fetch_group(int n_waves) { return (n_waves == 2)? 3 * panel_fetch_pass(n_waves) : 2 * panel_fetch_pass(n_waves); } // products in flight: 9 (12, 6)
 // LDS of a panel launch, in doubles: offsets of the panel role's regions (package, image, vectors, inverses of the
 // level's diagonal blocks, one tile per wave, operand staging of the fresh updates) and the total, which also covers
 // the update role's staging (riders: the next stage's updates from further down, PANEL_UPD_W waves per factor block)

@@ -2,6 +2,7 @@
 // panel packages with their hand-up lists, dense-top records, lane-per-task tables.  Host code only.
 #include "sparse_records.h"
 
+#include <climits>
 #include <atomic>
 #include <cstdio>
 #include <cstring>
@@ -160,6 +161,9 @@ class CPanelPass {
 	int n_stage_waves;
 	int64_t n_stage_max_slots, n_stage_max_units, n_stage_rest; // (for the development print)
 	int n_stage_bwd_units, n_stage_bwd_blocks, n_stage_bwd_levels; // (the same for the backward records: largest record, most blocks below a diagonal, most levels)
+	enum { FETCH_MAX_PASS = 8 };
+	int64_t n_stage_fetch_mod[FETCH_MAX_PASS], n_stage_fetch_few[FETCH_MAX_PASS]; // (the same for the fresh entries a wave fetches itself, kinds 0 / 1: waves by their count modulo the packed fetch's pass -- panel_fetch_pass() of the stage's waves --, waves with fewer than a pass by their count)
+	int n_stage_fetch_min, n_stage_fetch_max;
 	// the task being packed: what Size_Task() found
 	std::vector<int64_t> order; // the task's columns (indices into cols) level by level
 	bool b_tall;
@@ -201,6 +205,10 @@ public:
 			Decide_Stage();
 			n_stage_max_slots = n_stage_max_units = n_stage_rest = 0;
 			n_stage_bwd_units = n_stage_bwd_blocks = n_stage_bwd_levels = 0;
+			for(int i = 0; i < FETCH_MAX_PASS; ++ i)
+				n_stage_fetch_mod[i] = n_stage_fetch_few[i] = 0;
+			n_stage_fetch_min = INT_MAX;
+			n_stage_fetch_max = 0;
 			for(int t = P.stage_ptr[s]; b_panel_stage && t < P.stage_ptr[s + 1]; ++ t) {
 				if(Size_Task(t))
 					Pack_Task(t);
@@ -212,6 +220,17 @@ public:
 			if(t_opt.b_timing && b_panel_stage)
 				fprintf(stderr, "[setup] stage %d panels: at most %lld blocks and %lld package units per task, %lld tasks left to the column kernel\n",
 					s, (long long)n_stage_max_slots, (long long)n_stage_max_units, (long long)n_stage_rest);
+			if(t_opt.b_timing && L.panel_ptr[s + 1] > L.panel_ptr[s]) {
+				const int n_pass = std::min(panel_fetch_pass(n_stage_waves), int(FETCH_MAX_PASS));
+				fprintf(stderr, "[setup] stage %d fresh fetch: %d waves a task, pass of %d, %d to %d self-fetched entries per wave; waves by entries modulo the pass:",
+					s, n_stage_waves, n_pass, n_stage_fetch_min, n_stage_fetch_max);
+				for(int i = 0; i < n_pass; ++ i)
+					fprintf(stderr, " %lld", (long long)n_stage_fetch_mod[i]);
+				fprintf(stderr, "; waves with fewer than a pass, by entries:");
+				for(int i = 0; i < n_pass; ++ i)
+					fprintf(stderr, " %lld", (long long)n_stage_fetch_few[i]);
+				fprintf(stderr, "\n");
+			}
 			if(t_opt.b_timing && L.panel_ptr[s + 1] > L.panel_ptr[s])
 				fprintf(stderr, "[setup] stage %d backward records: %d tasks, at most %d units, %d blocks below a diagonal and %d levels per task; %d columns per wave\n",
 					s, int(L.panel_ptr[s + 1] - L.panel_ptr[s]), n_stage_bwd_units, n_stage_bwd_blocks, n_stage_bwd_levels, int(L.bwd_cfg[s].n_cols_per_wave));
@@ -540,6 +559,17 @@ private:
 			++ hd.ext_ptr[fresh[e].slot % n_waves + 1];
 		for(int v = 0; v < n_waves; ++ v)
 			hd.ext_ptr[v + 1] += hd.ext_ptr[v];
+		for(int v = 0; t_opt.b_timing && v < n_waves; ++ v) { // (development print: what the fetch loop of each wave gets)
+			int n_self = 0;
+			for(int e = hd.ext_ptr[v]; e < hd.ext_ptr[v + 1]; ++ e)
+				n_self += fresh[size_t(e)].kind < 2;
+			const int n_pass = std::min(panel_fetch_pass(n_waves), int(FETCH_MAX_PASS));
+			++ n_stage_fetch_mod[n_self % n_pass];
+			if(n_self < n_pass)
+				++ n_stage_fetch_few[n_self];
+			n_stage_fetch_min = std::min(n_stage_fetch_min, n_self);
+			n_stage_fetch_max = std::max(n_stage_fetch_max, n_self);
+		}
 		{ // what the stage's launch must hold
 			TPanelLaunch &r_cfg = L.panel_cfg[s];
 			r_cfg.n_cap_units = std::max(r_cfg.n_cap_units, int32_t(n_units));

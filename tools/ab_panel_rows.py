@@ -1,6 +1,8 @@
 """Dev helper (round 4): an option of the panel tasks on (1) and off (0) -- AB_OPTION=panel_rows (the level walk as rows; the
 default) or panel_handup (tasks hand their contributions up; takes effect at analysis: a solver per setting) -- on C3, C2,
-C1 and the reduced camera systems of the BA legs, same process, alternating."""
+C1 and the reduced camera systems of the BA legs, same process, alternating.  With AB_KNOB set (e.g.
+AB_KNOB=SLAMPP_HIP_DEV_PANEL_FETCH AB_VALUES=0,1,0,1,0,1) an environment knob the launch helpers read at every launch is
+alternated instead, on one solver."""
 import os as _os; _os.environ.setdefault("SLAMPP_HIP_DEV", "1")  # development options and knobs are refused without it (csrc/plan.h)
 import sys, time, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -11,6 +13,7 @@ dev = torch.device("cuda:0")
 
 
 OPTION = os.environ.get("AB_OPTION", "panel_rows")
+KNOB = os.environ.get("AB_KNOB", "")  # a development knob read at every launch (csrc/plan.h): alternated instead of the option
 VALUES = [int(v) for v in os.environ.get("AB_VALUES", "0,1,0,1").split(",")]  # e.g. AB_OPTION=task_height AB_VALUES=4,5,6,4,5,6
 
 
@@ -19,10 +22,13 @@ def run(name, lam, cls, reps=20):
     out = {}
     solvers = {}
     for rows in VALUES:
-        if rows not in solvers:
-            solvers[rows] = cls(**{OPTION: rows})
-            solvers[rows].SymbolicDecomposition_Blocky(lam)
-        s = solvers[rows]
+        key = 0 if KNOB else rows
+        if key not in solvers:
+            solvers[key] = cls() if KNOB else cls(**{OPTION: rows})
+            solvers[key].SymbolicDecomposition_Blocky(lam)
+        s = solvers[key]
+        if KNOB:
+            os.environ[KNOB] = str(rows)
         s.set_option("profile", 0)
         bufs = [torch.from_numpy(lam.rhs).to(dev) for _ in range(2 * reps + 1)]
         torch.cuda.synchronize()
@@ -39,7 +45,7 @@ def run(name, lam, cls, reps=20):
         s.sync()
         x = bufs[-1].cpu().numpy()
         res = np.abs(lam.to_scipy() @ x - lam.rhs).max() / np.abs(lam.rhs).max()
-        print(f"{name:14s} {OPTION}={rows}  {dt*1e3:.3f} ms  resid {res:.1e}  " +
+        print(f"{name:14s} {KNOB or OPTION}={rows}  {dt*1e3:.3f} ms  resid {res:.1e}  " +
               "  ".join(f"{k}={ms/max(c,1)*1e3:.0f}" for k, (c, ms) in s.profile().items()), flush=True)
 
 
