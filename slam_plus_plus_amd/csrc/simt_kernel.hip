@@ -22,6 +22,9 @@
 #include <hip/hip_runtime.h>
 #include "sparse_kernels.h"
 
+#include <algorithm>
+#include <cstdio>
+
 namespace slampp {
 
 __device__ __forceinline__ double simt_rsqrt(double x)
@@ -67,6 +70,28 @@ __device__ __forceinline__ void load_block(const double *__restrict__ p, double 
 		#pragma unroll
 		for(int i = 0; i < D * D; ++ i)
 			v[i / D][i % D] = p[i];
+	}
+}
+
+// the lower triangle of a block: v[q][r] = p[r + q D] for r >= q (even D: 16-byte loads; the element above the diagonal that
+// shares one with the diagonal element of an odd column comes along)
+template <int D>
+__device__ __forceinline__ void load_lower(const double *__restrict__ p, double (&v)[D][D])
+{
+	#pragma unroll
+	for(int q = 0; q < D; ++ q) {
+		if(D % 2 == 0) {
+			#pragma unroll
+			for(int r = q & ~1; r < D; r += 2) {
+				const double2 t = *reinterpret_cast<const double2*>(p + r + q * D);
+				v[q][r] = t.x;
+				v[q][r + 1] = t.y;
+			}
+		} else {
+			#pragma unroll
+			for(int r = q; r < D; ++ r)
+				v[q][r] = p[r + q * D];
+		}
 	}
 }
 
@@ -530,15 +555,294 @@ backward_simt_kernel(const TSimtChunk *__restrict__ chunks, const int32_t *__res
 		w[0] = f_touched;
 }
 
-bool launch_backward_simt(const TSimtChunk *chunks, int n_chunks, int n_width, int n_lds_bytes, size_t n_lds_limit, const int32_t *prog, const int64_t *tab,
-	int n_dim, const double *L, double *w, double *x_out, hipStream_t stream, const TBatch &t_batch)
+// The same substitution for launches that cannot fill the chip (C3's leaf stage: 592 waves on 1 024 SIMDs), where nothing but
+// the wave itself hides its waits.  backward_simt_kernel pays four to six dependent trips to memory a column: its touches are
+// loads whose sum is taken inside a loop of run-time length, so each of them is waited for, and the blocks below the diagonal
+// come one per wait.  Nothing a column reads from memory depends on what the kernel computes (L is read-only, y_j and x of the
+// rows outside the task are earlier launches' stores, x of the task's own columns travels through LDS), so here everything
+// column ci - 1 needs is requested into a second register set before column ci is solved out of the first, and the wait of a
+// column is for loads a whole column old, with the newer ones still in flight.  A set: y_j, L_jj, the first SIMT_BWD_AHEAD
+// blocks below it and x of one row outside the task -- the first such row among those blocks; at C3 nearly every column has two
+// blocks below its diagonal, one row inside the task and one outside.  A second outside row among them (the last column of a
+// task) has its x fetched in the column, and waited for.  The column loop is unrolled by two, so the two sets stay in fixed
+// registers (108 doubles each at D = 6 with two blocks: 512 registers in all, one wave a SIMD, no scratch; an x per block, 114
+// doubles a set, spilled -- DESIGN.md section 10).  Columns with more blocks fetch the rest themselves, SIMT_BWD_AHEAD at a time
+// into the set they are solving from, all before the first product: one more trip, and this one is waited for.  The arithmetic,
+// its order and every store are backward_simt_kernel's: the results are the same bits.  No touches.
+template <int D, int AHEAD>
+struct TBwdAheadSet {
+	double y[D], a[D][D], c[AHEAD][D][D], xs[D]; // xs: x of the first of those blocks' rows that lies outside the task; a[q][r] = L_jj(r, q), c[k][q][r] = L(i_k,j)(r, q)
+	int nb, n_blk0; // (the column's offsets are read from the LDS table again where they are needed: registers) blocks of the column; position of its first sub-diagonal block among the task's
+	int n_xk; // the block xs belongs to, or -1
+	int n_local[AHEAD]; // which of the task's columns the row of block k + 1 is, or -1 (wave-uniform, as nb)
+};
+
+// Every fetch issues the same number of loads, whatever the column holds: a wait is written as "at most N loads outstanding",
+// loads return in the order they went out, and N is what the compiler can prove of every path to the wait -- with a load count
+// that followed nb and the rows' places it proved little (vmcnt(0) to (17) with 57 newer loads in flight: the newer column's
+// trip exposed after all).  So a block the column does not have is the diagonal block once more (lines just requested), and a
+// column with no row outside the task among its blocks reads its own y_j a second time for xs.
+template <int D, int W, int AHEAD>
+__device__ __forceinline__ void bwd_ahead_fetch(TBwdAheadSet<D, AHEAD> &s, int ci, int n_blk_end, int n_cols, const int32_t *P, const int32_t *p_local,
+	const long long *T, const double *__restrict__ L, const double *w)
+{
+	enum { DD = D * D };
+	s.nb = P[2 + ci];
+	const long long l_base = T[W * (3 * ci)];
+	s.n_blk0 = n_blk_end - (s.nb - 1);
+	load_column<D>(w + T[W * (3 * ci + 1)], s.y); // y_j
+	load_lower<D>(L + l_base, s.a);
+	s.n_xk = -1;
+	int n_x_field = 3 * ci + 1;
+	#pragma unroll
+	for(int k = 0; k < AHEAD; ++ k) {
+		const bool b_have = k + 1 < s.nb; // (wave-uniform)
+		s.n_local[k] = b_have? p_local[s.n_blk0 + k] : 0;
+		if(b_have && s.n_local[k] < 0 && s.n_xk < 0) {
+			s.n_xk = k;
+			n_x_field = 3 * n_cols + s.n_blk0 + k;
+		}
+		int n_blk_off = b_have? (k + 1) * DD : 0;
+		asm volatile("" : "+s"(n_blk_off)); // (or the stand-ins are recognized as the loads above, dropped, and their values copied: waits again)
+		load_block<D>(L + l_base + n_blk_off, s.c[k]);
+	}
+	asm volatile("" : "+s"(n_x_field));
+	load_column<D>(w + T[W * n_x_field], s.xs);
+	asm volatile("" ::: "memory"); // (the requests go out here, not where the scheduler would like them: next to their use)
+}
+
+// requests of one fetch (even D: 16-byte loads, of L_jj those that hold an element of its lower triangle: load_lower), stores
+// of one solve, and s_waitcnt's operand for "at most n vector memory operations
+// outstanding" (gfx9 layout: vmcnt in bits 3:0 and 15:14; expcnt and lgkmcnt left at their maxima: not waited for)
+template <int D, int AHEAD>
+constexpr int bwd_ahead_fetch_loads()
+{
+	if(D % 2 != 0)
+		return D + D * (D + 1) / 2 + AHEAD * (D * D) + D;
+	int n = D / 2;
+	for(int q = 0; q < D; ++ q)
+		n += (D - (q & ~1)) / 2;
+	return n + AHEAD * (D * D / 2) + D / 2;
+}
+template <int D> constexpr int bwd_ahead_solve_stores() { return (D % 2 == 0)? D : 2 * D; }
+constexpr int bwd_ahead_wait_imm(int n) { return ((n > 63)? 63 : n) % 16 | 7 << 4 | 15 << 8 | ((n > 63)? 63 : n) / 16 << 14; }
+
+template <int D, int W, int AHEAD, int N_NEWER /* vector memory operations issued since the set's fetch, at the least */>
+__device__ __forceinline__ void bwd_ahead_solve(TBwdAheadSet<D, AHEAD> &s, int ci, int n_cols, const int32_t *p_local, const long long *T, double *s_x,
+	const double *__restrict__ L, double *w, double *x_out)
+{
+	enum { DD = D * D };
+	// The one wait of the column, written out: everything older than the N_NEWER newest requests -- this set -- has arrived.  The
+	// compiler's own waits stay (it adds what correctness needs), but where paths of different load counts meet, behind the loop
+	// of the remaining blocks, it no longer finds this set pending and asks for nothing: it asked for vmcnt(1) there.
+	__builtin_amdgcn_s_waitcnt(bwd_ahead_wait_imm(N_NEWER));
+	#pragma unroll
+	for(int q = 0; q < D; ++ q) { // the reciprocals take the diagonal's place (registers)
+		const double d = s.a[q][q];
+		double r = __builtin_amdgcn_rcp(d);
+		r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
+		r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
+		s.a[q][q] = r;
+	}
+	double acc[D];
+	#pragma unroll
+	for(int q = 0; q < D; ++ q)
+		acc[q] = s.y[q];
+	#pragma unroll
+	for(int k = 0; k < AHEAD; ++ k) {
+		if(k + 1 < s.nb) {
+			double xi[D];
+			if(s.n_local[k] >= 0) { // a row inside the task: x from LDS
+				#pragma unroll
+				for(int r = 0; r < D; ++ r)
+					xi[r] = s_x[(s.n_local[k] * D + r) * W];
+			} else if(s.n_xk == k) {
+				#pragma unroll
+				for(int r = 0; r < D; ++ r)
+					xi[r] = s.xs[r];
+			} else { // a second row outside the task: fetched here, and waited for
+				load_column<D>(w + T[W * (3 * n_cols + s.n_blk0 + k)], xi);
+				__builtin_amdgcn_s_waitcnt(bwd_ahead_wait_imm(0));
+			}
+			#pragma unroll
+			for(int q = 0; q < D; ++ q) {
+				#pragma unroll
+				for(int r = 0; r < D; ++ r)
+					acc[q] -= s.c[k][q][r] * xi[r];
+			}
+		}
+	}
+	const long long l_base = (s.nb > AHEAD + 1)? T[W * (3 * ci)] : 0;
+	for(int kb = AHEAD + 1; kb < s.nb; kb += AHEAD) {
+		double xr[AHEAD][D]; // the blocks the set did not hold: AHEAD of them a trip, into the set's own registers (their first tenants are used up)
+		#pragma unroll
+		for(int i = 0; i < AHEAD; ++ i) {
+			if(kb + i < s.nb) {
+				load_block<D>(L + l_base + (kb + i) * DD, s.c[i]);
+				const int n_local = p_local[s.n_blk0 + kb + i - 1];
+				if(n_local >= 0) {
+					#pragma unroll
+					for(int r = 0; r < D; ++ r)
+						xr[i][r] = s_x[(n_local * D + r) * W];
+				} else
+					load_column<D>(w + T[W * (3 * n_cols + s.n_blk0 + kb + i - 1)], xr[i]);
+			}
+		}
+		asm volatile("" ::: "memory"); // (all of them requested before the first product)
+		__builtin_amdgcn_s_waitcnt(bwd_ahead_wait_imm(0)); // (written out for the same reason: no path leaves this loop with a request of its own pending)
+		#pragma unroll
+		for(int i = 0; i < AHEAD; ++ i) {
+			if(kb + i < s.nb) {
+				#pragma unroll
+				for(int q = 0; q < D; ++ q) {
+					#pragma unroll
+					for(int r = 0; r < D; ++ r)
+						acc[q] -= s.c[i][q][r] * xr[i][r];
+				}
+			}
+		}
+	}
+	double x[D];
+	#pragma unroll
+	for(int q = D - 1; q >= 0; -- q) {
+		double sum = acc[q];
+		#pragma unroll
+		for(int r = q + 1; r < D; ++ r)
+			sum -= s.a[q][r] * x[r];
+		x[q] = sum * s.a[q][q];
+	}
+	#pragma unroll
+	for(int q = 0; q < D; ++ q)
+		s_x[(ci * D + q) * W] = x[q];
+	const long long cs_new = T[W * (3 * ci + 1)], cs_src = T[W * (3 * ci + 2)];
+	if(D % 2 == 0) {
+		#pragma unroll
+		for(int q = 0; q < D; q += 2) {
+			*reinterpret_cast<double2*>(w + cs_new + q) = double2{x[q], x[q + 1]};
+			*reinterpret_cast<double2*>(x_out + cs_src + q) = double2{x[q], x[q + 1]};
+		}
+	} else {
+		#pragma unroll
+		for(int q = 0; q < D; ++ q) {
+			w[cs_new + q] = x[q];
+			x_out[cs_src + q] = x[q];
+		}
+	}
+}
+
+template <int D, int W, int AHEAD>
+__global__ void __launch_bounds__(64)
+backward_simt_ahead_kernel(const TSimtChunk *__restrict__ chunks, const int32_t *__restrict__ prog, const long long *__restrict__ tab,
+	const double *__restrict__ L, double *w, double *x_out, TBatch t_batch)
+{	{ const int64_t n_member = blockIdx.y; L += n_member * t_batch.l; w += n_member * t_batch.w; x_out += n_member * t_batch.b; } // (TBatch: sparse_kernels.h)
+
+	extern __shared__ long long s_tab[];
+	const TSimtChunk ch = chunks[blockIdx.x];
+	const int32_t *P = prog + ch.prog_off; // wave-uniform: scalar loads
+	const int n_cols = P[0], n_below = P[1];
+	{
+		const int n_entries = (3 * n_cols + n_below) * W;
+		for(int i = threadIdx.x; i < n_entries; i += 64)
+			s_tab[i] = tab[ch.tab_off + i];
+		__syncthreads();
+	}
+	if(int(threadIdx.x) >= W)
+		return; // (no barrier below)
+	const long long *T = s_tab + threadIdx.x;
+	double *s_x = reinterpret_cast<double*>(s_tab + (3 * n_cols + n_below) * W) + threadIdx.x; // x of the task's own columns (backward_simt_kernel)
+	const int32_t *p_local = P + 2 + n_cols;
+	TBwdAheadSet<D, AHEAD> t_even, t_odd; // (two named sets and a loop unrolled by two: an index into an array of sets would be scratch)
+	enum { N_FETCH = bwd_ahead_fetch_loads<D, AHEAD>(), N_STORES = bwd_ahead_solve_stores<D>() };
+	int ci = n_cols - 1;
+	bwd_ahead_fetch<D, W, AHEAD>(t_even, ci, n_below, n_cols, P, p_local, T, L, w); // prologue: the last column
+	for(; ci >= 2; ci -= 2) { // steady state: every solve with one fetch in front of it
+		bwd_ahead_fetch<D, W, AHEAD>(t_odd, ci - 1, t_even.n_blk0, n_cols, P, p_local, T, L, w);
+		bwd_ahead_solve<D, W, AHEAD, N_FETCH>(t_even, ci, n_cols, p_local, T, s_x, L, w, x_out); // (in the first round no store lies between the two fetches)
+		bwd_ahead_fetch<D, W, AHEAD>(t_even, ci - 2, t_odd.n_blk0, n_cols, P, p_local, T, L, w);
+		bwd_ahead_solve<D, W, AHEAD, N_STORES + N_FETCH>(t_odd, ci - 1, n_cols, p_local, T, s_x, L, w, x_out);
+	}
+	if(ci == 1) { // epilogue: the columns left (t_even holds column ci), the last of them with nothing to fetch
+		bwd_ahead_fetch<D, W, AHEAD>(t_odd, 0, t_even.n_blk0, n_cols, P, p_local, T, L, w);
+		bwd_ahead_solve<D, W, AHEAD, N_FETCH>(t_even, 1, n_cols, p_local, T, s_x, L, w, x_out);
+		bwd_ahead_solve<D, W, AHEAD, N_STORES>(t_odd, 0, n_cols, p_local, T, s_x, L, w, x_out);
+	} else
+		bwd_ahead_solve<D, W, AHEAD, 0>(t_even, 0, n_cols, p_local, T, s_x, L, w, x_out);
+}
+
+// the fetch-ahead form exists for the block sizes listed here (which compile without scratch)
+template <int D> struct TBwdAheadDim { enum { b_have = (D == 6) }; };
+
+template <int D, int W>
+static const void *p_Backward_Ahead_Kernel()
+{
+	if constexpr(TBwdAheadDim<D>::b_have)
+		return reinterpret_cast<const void*>(&backward_simt_ahead_kernel<D, W, SIMT_BWD_AHEAD>);
+	else
+		return 0;
+}
+
+static const void *p_Backward_Ahead_Kernel(int n_dim, int n_width)
+{
+#define BWD_AHEAD_WIDTHS(D_) return (n_width == 16)? p_Backward_Ahead_Kernel<D_, 16>() : (n_width == 32)? p_Backward_Ahead_Kernel<D_, 32>() : p_Backward_Ahead_Kernel<D_, 64>()
+	switch(n_dim) {
+	case 3:
+		BWD_AHEAD_WIDTHS(3);
+	case 6:
+		BWD_AHEAD_WIDTHS(6);
+	case 7:
+		BWD_AHEAD_WIDTHS(7);
+	default:
+		return 0;
+	}
+#undef BWD_AHEAD_WIDTHS
+}
+
+template <int D, int W>
+static void Launch_Backward_Simt(bool b_ahead, const TSimtChunk *chunks, int n_chunks, int n_lds_bytes, const int32_t *prog, const long long *t,
+	const double *L, double *w, double *x_out, hipStream_t stream, const TBatch &t_batch)
+{
+	if constexpr(TBwdAheadDim<D>::b_have) {
+		if(b_ahead) {
+			hipLaunchKernelGGL((backward_simt_ahead_kernel<D, W, SIMT_BWD_AHEAD>), dim3(n_chunks, t_batch.n), dim3(64), n_lds_bytes, stream,
+				chunks, prog, t, L, w, x_out, t_batch);
+			return;
+		}
+	}
+	hipLaunchKernelGGL((backward_simt_kernel<D, W>), dim3(n_chunks, t_batch.n), dim3(64), n_lds_bytes, stream, chunks, prog, t, L, w, x_out, t_batch);
+}
+
+int backward_simt_ahead_waves(int n_dim, int n_width, int n_lds_bytes)
+{
+	const void *p_kernel = p_Backward_Ahead_Kernel(n_dim, n_width);
+	int n_device = 0, n_cus = 0, n_blocks = 0;
+	if(!p_kernel || n_lds_bytes < 0 || hipGetDevice(&n_device) != hipSuccess ||
+	   hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, n_device) != hipSuccess ||
+	   hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_blocks, p_kernel, 64, size_t(n_lds_bytes)) != hipSuccess) {
+		(void)hipGetLastError();
+		return 0;
+	}
+	return (n_cus > 0 && n_blocks > 0)? n_cus * n_blocks : 0; // (a workgroup is one wave)
+}
+
+bool launch_backward_simt(const TSimtChunk *chunks, int n_chunks, int n_width, int n_lds_bytes, size_t n_lds_limit, int n_ahead_waves, const int32_t *prog, const int64_t *tab,
+	int n_dim, const double *L, double *w, double *x_out, hipStream_t stream, const TBatch &t_batch, bool b_report)
 {
 	if(n_chunks <= 0)
 		return true;
 	if(n_lds_bytes < 0 || size_t(n_lds_bytes) > n_lds_limit)
 		return false; // (the chunk tables are staged in LDS: a launch over the limit would fail without a word)
 	const long long *t = reinterpret_cast<const long long*>(tab);
-#define BWD_LAUNCH(D_, W_) hipLaunchKernelGGL((backward_simt_kernel<D_, W_>), dim3(n_chunks, t_batch.n), dim3(64), n_lds_bytes, stream, chunks, prog, t, L, w, x_out, t_batch)
+	// The fetch-ahead form runs at one wave a SIMD: it is for launches that fit the chip in one round at that occupancy and so
+	// could not hide a wave's waits behind other waves anyway (C3's leaves: 592 waves, 41.7 -> 30.3 us).  Larger
+	// launches -- a batch of eight (4 736 waves), a million poses -- keep the kernel above, where many waves a SIMD already hide
+	// the waits.  Development aid (plan.h): 0 = never, 1 = wherever the block size has the form; the results are the same bits.
+	const int n_ahead_env = dev_knob("SLAMPP_HIP_DEV_SIMT_BWD_AHEAD", -1);
+	const void *p_ahead = p_Backward_Ahead_Kernel(n_dim, n_width);
+	const bool b_ahead = p_ahead && ((n_ahead_env >= 0)? n_ahead_env != 0 : int64_t(n_chunks) * std::max<int64_t>(t_batch.n, 1) <= n_ahead_waves);
+	if(b_report) // (development aid SLAMPP_HIP_STAGE_TIMING: which form the launch takes, for the tests)
+		fprintf(stderr, "stage_timing lane-per-task backward launch: %d chunks, width %d, block size %d, %d members, %s\n", n_chunks, n_width, n_dim,
+			int(t_batch.n), b_ahead? "fetch ahead" : "fetch by column");
+#define BWD_LAUNCH(D_, W_) Launch_Backward_Simt<D_, W_>(b_ahead, chunks, n_chunks, n_lds_bytes, prog, t, L, w, x_out, stream, t_batch)
 #define BWD_WIDTHS(D_) do { if(n_width == 16) BWD_LAUNCH(D_, 16); else if(n_width == 32) BWD_LAUNCH(D_, 32); else BWD_LAUNCH(D_, 64); } while(0)
 	switch(n_dim) {
 	case 3:

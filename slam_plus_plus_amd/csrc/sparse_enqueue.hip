@@ -183,7 +183,8 @@ void slampp_hip_solver::Enqueue_Sparse(const double *p_values_dev, double *p_rhs
 			// wave-per-task kernel (their factor kernel stored the inverses)
 			const int n_chunks = lists.simt_chunk_ptr[s] - lists.simt_chunk_ptr[s - 1], n_rest = lists.simt_rest_ptr[s] - lists.simt_rest_ptr[s - 1];
 			if(!launch_backward_simt(d_simt_bwd_chunks.p() + lists.simt_chunk_ptr[s - 1], n_chunks, n_simt_width, lists.simt_bwd_lds_bytes[s - 1], n_lds_limit,
-				d_simt_bwd_prog.p(), d_simt_bwd_tab.p(), P.max_dim, d_L.p(), d_w.p(), p_rhs_dev, stream, t_batch))
+				(size_t(s - 1) < simt_bwd_ahead_waves.size())? simt_bwd_ahead_waves[s - 1] : 0, d_simt_bwd_prog.p(), d_simt_bwd_tab.p(), P.max_dim, d_L.p(), d_w.p(), p_rhs_dev, stream, t_batch,
+				dplan.p_timing != 0))
 				throw CDeviceError("lane-per-task backward launch refused: block size or LDS request outside what the analysis planned for");
 			if(n_rest > 0) {
 				TDevPlan t_rest = dplan;

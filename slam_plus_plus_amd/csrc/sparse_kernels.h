@@ -281,8 +281,17 @@ bool launch_factor_simt(const TSimtChunk *chunks, int n_chunks, int n_width /* t
 // backward substitution of the same tasks, a lane per task (chunk programs: n_cols, number of sub-diagonal blocks, nb per
 // column; tables: per column offset of its first factor block, scalar offsets in the workspace and in the caller's vector,
 // then the workspace offset of every sub-diagonal block's row): x_j from L_jj^T directly, no inverse
-bool launch_backward_simt(const TSimtChunk *chunks, int n_chunks, int n_width, int n_lds_bytes, size_t n_lds_limit /* plain_launch_lds_limit(), asked at analysis */, const int32_t *prog, const int64_t *tab,
-	int n_dim, const double *L, double *w, double *x_out, hipStream_t stream, const TBatch &t_batch = t_No_Batch());
+// Launches that fit the chip in one round at one wave a SIMD take the form that fetches a column ahead (simt_kernel.hip:
+// backward_simt_ahead_kernel): a column's register set holds the first SIMT_BWD_AHEAD blocks below the diagonal, the others
+// come as many to a trip.  n_ahead_waves: backward_simt_ahead_waves() of the stage, asked at analysis; b_report: say on
+// stderr which form the launch takes (development aid SLAMPP_HIP_STAGE_TIMING)
+enum { SIMT_BWD_AHEAD = 2 };
+bool launch_backward_simt(const TSimtChunk *chunks, int n_chunks, int n_width, int n_lds_bytes, size_t n_lds_limit /* plain_launch_lds_limit(), asked at analysis */,
+	int n_ahead_waves, const int32_t *prog, const int64_t *tab,
+	int n_dim, const double *L, double *w, double *x_out, hipStream_t stream, const TBatch &t_batch = t_No_Batch(), bool b_report = false);
+// waves (= workgroups) of the fetch-ahead form the device holds at once with this LDS request: CUs x the runtime's occupancy answer;
+// 0: the block size has no such form, or the device does not answer
+int backward_simt_ahead_waves(int n_dim, int n_width, int n_lds_bytes);
 // inv(L_jj) of the columns cols[col_begin .. col_end) (schedule order) from their factor blocks: for callers that need the
 // inverses the lane-per-task factorization did not store (another right-hand side, covariances)
 bool launch_invert_diagonals(const TDevPlan &p, int64_t col_begin, int64_t col_end, const double *L, double *Linv, hipStream_t stream);

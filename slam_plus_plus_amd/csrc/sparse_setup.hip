@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <string>
 #include <unordered_map>
 #include <thread>
 #include <mutex>
@@ -392,6 +393,47 @@ void slampp_hip_solver::Ensure_Leaf_Inverses()
 	b_leaf_linv_valid = true;
 }
 
+// development print (SLAMPP_HIP_PLAN_TIMING): what the column loop of the lane-per-task backward kernels meets, per stage, counted in tasks
+// (the spare lanes of a chunk repeat its last task: not counted)
+void slampp_hip_solver::Report_Simt_Backward(const SparseRecords &r_rec) const
+{
+	enum { N_MAX = 16 }; // (the last bin collects everything beyond)
+	for(size_t s = 0; s + 1 < lists.simt_chunk_ptr.size(); ++ s) {
+		long long n_by_cols[N_MAX + 1] = {0}, n_by_blocks[N_MAX + 1] = {0}, n_by_outside[SIMT_BWD_AHEAD + 1] = {0}, n_inside = 0, n_outside = 0, n_tasks = 0;
+		int n_spare_chunks = 0;
+		for(int32_t c = lists.simt_chunk_ptr[s]; c < lists.simt_chunk_ptr[s + 1]; ++ c) {
+			const TSimtChunk &ch = r_rec.simt_bwd_chunks[size_t(c)];
+			const int32_t *P = &r_rec.simt_bwd_prog[size_t(ch.prog_off)]; // n_cols, blocks below the diagonals, nb per column, the rows' places
+			const int n_cols = P[0], n_below = P[1];
+			n_tasks += ch.n_tasks;
+			n_spare_chunks += ch.n_tasks < n_simt_width;
+			n_by_cols[std::min(n_cols, int(N_MAX))] += ch.n_tasks;
+			for(int i = 0, n_blk0 = 0; i < n_cols; n_blk0 += P[2 + i] - 1, ++ i) {
+				n_by_blocks[std::min(P[2 + i] - 1, int(N_MAX))] += ch.n_tasks;
+				int n_set_outside = 0; // rows outside the task among the blocks a register set of the fetch-ahead form holds
+				for(int k = 0; k < SIMT_BWD_AHEAD && k < P[2 + i] - 1; ++ k)
+					n_set_outside += P[2 + n_cols + n_blk0 + k] < 0;
+				n_by_outside[n_set_outside] += ch.n_tasks;
+			}
+			for(int b = 0; b < n_below; ++ b)
+				((P[2 + n_cols + b] >= 0)? n_inside : n_outside) += ch.n_tasks;
+		}
+		std::string s_cols, s_blocks, s_outside;
+		for(int i = 0; i <= SIMT_BWD_AHEAD; ++ i)
+			s_outside += " " + std::to_string(i) + ":" + std::to_string(n_by_outside[i]);
+		for(int i = 0; i <= N_MAX; ++ i) {
+			if(n_by_cols[i])
+				s_cols += " " + std::to_string(i) + ":" + std::to_string(n_by_cols[i]);
+			if(n_by_blocks[i])
+				s_blocks += " " + std::to_string(i) + ":" + std::to_string(n_by_blocks[i]);
+		}
+		fprintf(stderr, "[setup] stage %zu backward lanes: %lld tasks in %d chunks of width %d, %d chunks with spare lanes, fetch ahead holds %d blocks, one round holds %d waves; "
+			"tasks by columns:%s; columns by sub-diagonal blocks:%s; columns by rows outside the task among the blocks held:%s; blocks with the row inside the task: %lld, outside: %lld\n", s, n_tasks,
+			lists.simt_chunk_ptr[s + 1] - lists.simt_chunk_ptr[s], n_simt_width, n_spare_chunks, int(SIMT_BWD_AHEAD),
+			(s < simt_bwd_ahead_waves.size())? simt_bwd_ahead_waves[s] : 0, s_cols.c_str(), s_blocks.c_str(), s_outside.c_str(), n_inside, n_outside);
+	}
+}
+
 // the lane-per-task tables build_simt_tables() made
 void slampp_hip_solver::Upload_Simt(const SparseRecords &r_rec)
 {
@@ -406,7 +448,11 @@ void slampp_hip_solver::Upload_Simt(const SparseRecords &r_rec)
 	d_simt_bwd_prog.Upload(r_rec.simt_bwd_prog, stream);
 	d_simt_bwd_tab.Upload(r_rec.simt_bwd_tab, stream);
 	SLAMPP_HIP_CHECK(hipStreamSynchronize(stream)); // (the host copies are no longer needed)
+	simt_bwd_ahead_waves.clear();
+	for(size_t s = 0; s < lists.simt_bwd_lds_bytes.size(); ++ s)
+		simt_bwd_ahead_waves.push_back(backward_simt_ahead_waves(P.max_dim, n_simt_width, lists.simt_bwd_lds_bytes[s]));
 	if(getenv("SLAMPP_HIP_PLAN_TIMING")) {
+		Report_Simt_Backward(r_rec);
 		for(size_t s = 0; s + 1 < lists.simt_chunk_ptr.size(); ++ s) {
 			fprintf(stderr, "[setup] stage %zu: %d tasks -> %d chunks of 64 lanes, %d tasks left to the wave-per-task kernel\n", s,
 				P.stage_ptr[s + 1] - P.stage_ptr[s], lists.simt_chunk_ptr[s + 1] - lists.simt_chunk_ptr[s], lists.simt_rest_ptr[s + 1] - lists.simt_rest_ptr[s]);
