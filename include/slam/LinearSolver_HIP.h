@@ -67,6 +67,7 @@ protected:
 	std::vector<int64_t> m_cumsum, m_bcol_ptr; /**< @brief structure handed to the library */
 	std::vector<int32_t> m_brow;
 	std::vector<size_t> m_order; /**< @brief new block column -> old (empty = identity) */
+	std::string m_s_half_solve_refusal; /**< @brief why the library refused the last Solve_L_Columns() / Solve_Lt_Columns() (empty: it did not) */
 	struct TGatherEntry { uint32_t n_col, n_blk; int64_t n_dest; int32_t n_rows, n_cols; uint32_t n_row; bool b_transpose; };
 	std::vector<TGatherEntry> m_gather; /**< @brief where every block of lambda goes in the packed values */
 	std::vector<uint32_t> m_col_block_num, m_col_width; /**< @brief blocks and width of every block column of lambda when it was analyzed (its own order) */
@@ -662,6 +663,73 @@ protected:
 		return true;
 	}
 
+	/**
+	 *	@brief Solve_L_Columns() / Solve_Lt_Columns() on the handle's kept factor: one slampp_hip_solve_half_columns, after the
+	 *		checks of Solve_Again_Columns_Kept().  Where the library's block order is lambda's own, the call runs on the caller's
+	 *		matrix itself (column-major: leading dimension rows()).  Where the analysis reordered lambda's block columns (m_order:
+	 *		the guided ordering of the Schur class, which matters for a handle whose analysis went to the sparse path), the side of
+	 *		the call that is in the caller's order is permuted by blocks, as Solve_Again_Columns_Kept() does: the input of the
+	 *		forward half on its way in, the output of the backward half on its way out.  The factor-order side is the library's as
+	 *		it stands: block j there is the LIBRARY's block perm[j] of slampp_hip_factor_structure, which is lambda's block
+	 *		m_order[perm[j]] (lambda's block perm[j] where m_order is empty).
+	 *	@return Returns true on success, false where the library refuses the call (SLAMPP_HIP_ERR_INVALID: no kept factor;
+	 *		SLAMPP_HIP_ERR_UNSUPPORTED: Schur mode, block columns wider than 8); its message is then in r_s_Half_Solve_Refusal()
+	 *		and r_columns is as it was.
+	 */
+	bool Solve_Half_Columns_Kept(int n_half, Eigen::MatrixXd &r_columns) // throw(std::bad_alloc, std::runtime_error)
+	{
+		if(!m_p_solver || !m_b_structure_valid)
+			throw std::runtime_error("CLinearSolver_HIP: Solve_L_Columns() / Solve_Lt_Columns() need a solve before them");
+		if(size_t(r_columns.rows()) != size_t(m_cumsum.back()))
+			throw std::runtime_error("CLinearSolver_HIP: the columns do not match lambda");
+		if(r_columns.cols() > long(SLAMPP_HIP_SOLVE_MAX_COLUMNS))
+			throw std::runtime_error("CLinearSolver_HIP: more than SLAMPP_HIP_SOLVE_MAX_COLUMNS columns");
+		m_s_half_solve_refusal.clear();
+		if(!r_columns.cols() || !r_columns.rows())
+			return true;
+		const long n = long(m_cumsum.size()) - 1;
+		const bool b_forward = n_half == SLAMPP_HIP_HALF_FORWARD;
+		std::vector<size_t> base; // where the library's block column i begins in the caller's rows
+		Eigen::MatrixXd work;
+		if(!m_order.empty()) {
+			std::vector<size_t> orig_cumsum(size_t(n) + 1, 0);
+			for(long i = 0; i < n; ++ i)
+				orig_cumsum[m_order[i] + 1] = size_t(m_cumsum[i + 1] - m_cumsum[i]);
+			for(long i = 0; i < n; ++ i)
+				orig_cumsum[i + 1] += orig_cumsum[i];
+			base.resize(size_t(n));
+			for(long i = 0; i < n; ++ i)
+				base[i] = orig_cumsum[m_order[i]];
+			if(b_forward) { // b: lambda's rows -> the library's
+				work.resize(r_columns.rows(), r_columns.cols());
+				for(long i = 0; i < n; ++ i) {
+					for(int64_t d = 0, w = m_cumsum[i + 1] - m_cumsum[i]; d < w; ++ d)
+						work.row(int(m_cumsum[i] + d)) = r_columns.row(int(base[i] + size_t(d)));
+				}
+			} else
+				work = r_columns; // (y is in the factor's order already; a copy, so that a refusal leaves the caller's matrix alone)
+		}
+		Eigen::MatrixXd &r_work = m_order.empty()? r_columns : work;
+		const int n_result = slampp_hip_solve_half_columns(m_p_solver, n_half, r_work.data(), int64_t(r_work.rows()),
+			int(r_work.cols()));
+		if(n_result == SLAMPP_HIP_ERR_INVALID || n_result == SLAMPP_HIP_ERR_UNSUPPORTED) {
+			m_s_half_solve_refusal = slampp_hip_last_error(m_p_solver);
+			return false;
+		}
+		Throw_On_Error(n_result);
+		if(!m_order.empty()) {
+			if(b_forward)
+				r_columns.swap(work); // y, in the factor's order
+			else { // x: the library's rows -> lambda's
+				for(long i = 0; i < n; ++ i) {
+					for(int64_t d = 0, w = m_cumsum[i + 1] - m_cumsum[i]; d < w; ++ d)
+						r_columns.row(int(base[i] + size_t(d))) = work.row(int(m_cumsum[i] + d));
+				}
+			}
+		}
+		return true;
+	}
+
 	/** @brief Marginal_Blocks() on the gathered values */
 	bool Marginal_Blocks_Gathered(std::vector<Eigen::MatrixXd> &r_blocks, const CUberBlockMatrix &r_lambda,
 		const std::vector<std::pair<size_t, size_t> > &r_pairs, TBlocksEntry p_blocks, const char *p_s_class) // throw(std::bad_alloc, std::runtime_error)
@@ -1146,6 +1214,44 @@ public:
 	}
 
 	/**
+	 *	@brief the forward half of Solve_Again_Columns() alone: column c becomes y = L^-1 P b (slampp_hip_solve_half_columns
+	 *		with SLAMPP_HIP_HALF_FORWARD; cholmod_solve with CHOLMOD_P + CHOLMOD_L, the reference's
+	 *		UpperTriangularTranspose_Solve_FBS, NonlinearSolver_FastL.h:1101) -- b^T lambda^-1 b is then the squared norm of the column
+	 *
+	 *	@param[in,out] r_columns holds a vector per column (rows as lambda's) on entry, y in the factor's order (the block
+	 *		permutation of slampp_hip_factor_structure over the blocks as the library was given them: Solve_Half_Columns_Kept())
+	 *		on return; at most SLAMPP_HIP_SOLVE_MAX_COLUMNS columns
+	 *
+	 *	@return Returns true on success, false where the library refuses (no kept factor, block columns wider than 8);
+	 *		r_s_Half_Solve_Refusal() then says why.
+	 *	@note This function throws std::bad_alloc and std::runtime_error (no analysis, mismatched dimensions, device errors).
+	 */
+	bool Solve_L_Columns(Eigen::MatrixXd &r_columns) // throw(std::bad_alloc, std::runtime_error)
+	{
+		return Solve_Half_Columns_Kept(SLAMPP_HIP_HALF_FORWARD, r_columns);
+	}
+
+	/**
+	 *	@brief the backward half alone: column c, y in the factor's order, becomes x = P^T L^-T y in lambda's order
+	 *		(SLAMPP_HIP_HALF_BACKWARD; CHOLMOD_Lt + CHOLMOD_Pt, the reference's UpperTriangular_Solve_FBS,
+	 *		NonlinearSolver_FastL.h:1693) -- of standard normal columns it makes samples of covariance lambda^-1
+	 *
+	 *	@param[in,out] r_columns as in Solve_L_Columns(), the orders the other way around
+	 *
+	 *	@return As Solve_L_Columns().
+	 */
+	bool Solve_Lt_Columns(Eigen::MatrixXd &r_columns) // throw(std::bad_alloc, std::runtime_error)
+	{
+		return Solve_Half_Columns_Kept(SLAMPP_HIP_HALF_BACKWARD, r_columns);
+	}
+
+	/** @brief the library's message where the last Solve_L_Columns() / Solve_Lt_Columns() returned false */
+	const std::string &r_s_Half_Solve_Refusal() const
+	{
+		return m_s_half_solve_refusal;
+	}
+
+	/**
 	 *	@brief calculates the requested parts of the covariance matrix (the inverse of lambda): the parts of the reference's
 	 *		CMarginals::Calculate_DenseMarginals_Recurrent_FBS(margs, R, ordering, n_part), which CNonlinearSolver_Lambda calls
 	 *		after ordering and factoring lambda once more (NonlinearSolver_Lambda.h:690-752), with the matrix parts of
@@ -1406,6 +1512,42 @@ public:
 		if(!this->m_b_structure_valid) // (SymbolicDecomposition_Blocky: a lambda without a landmark part went to the sparse solver)
 			return m_sparse_fallback.Solve_Again_Columns(r_eta_columns);
 		return this->Solve_Again_Columns_Kept(r_eta_columns);
+	}
+
+	/**
+	 *	@brief the forward half of Solve_Again_Columns() alone (CLinearSolver_HIP::Solve_L_Columns()).  In Schur mode the
+	 *		library refuses it: the factor there is the block factor [L_S, U L_C^-T; 0, L_C], whose halves need the Cholesky
+	 *		factor of every landmark block -- this returns false and r_s_Half_Solve_Refusal() holds the library's message.
+	 *		Where the last lambda had no landmark part, the sparse solver that answered for it answers here.  Where the library
+	 *		took the sparse path for a lambda the Schur kernels do not take (option "schur_fallback"), the call is valid: b is
+	 *		handed over in the guided ordering this class gave the library, and y's factor order is over those blocks
+	 *		(Solve_Half_Columns_Kept()).
+	 */
+	bool Solve_L_Columns(Eigen::MatrixXd &r_columns) // throw(std::bad_alloc, std::runtime_error)
+	{
+		if(!this->m_b_structure_valid) {
+			const bool b_result = m_sparse_fallback.Solve_L_Columns(r_columns);
+			this->m_s_half_solve_refusal = m_sparse_fallback.r_s_Half_Solve_Refusal();
+			return b_result;
+		}
+		return this->Solve_Half_Columns_Kept(SLAMPP_HIP_HALF_FORWARD, r_columns);
+	}
+
+	/** @brief the backward half alone (CLinearSolver_HIP::Solve_Lt_Columns()); refused in Schur mode as Solve_L_Columns() is */
+	bool Solve_Lt_Columns(Eigen::MatrixXd &r_columns) // throw(std::bad_alloc, std::runtime_error)
+	{
+		if(!this->m_b_structure_valid) {
+			const bool b_result = m_sparse_fallback.Solve_Lt_Columns(r_columns);
+			this->m_s_half_solve_refusal = m_sparse_fallback.r_s_Half_Solve_Refusal();
+			return b_result;
+		}
+		return this->Solve_Half_Columns_Kept(SLAMPP_HIP_HALF_BACKWARD, r_columns);
+	}
+
+	/** @brief the library's message where the last Solve_L_Columns() / Solve_Lt_Columns() returned false */
+	const std::string &r_s_Half_Solve_Refusal() const
+	{
+		return this->m_s_half_solve_refusal;
 	}
 
 	/**

@@ -276,6 +276,42 @@ int slampp_hip_solve_again_device_async(slampp_hip_solver *p_solver, double *p_r
 int slampp_hip_solve_columns_device_async(slampp_hip_solver *p_solver, double *p_rhs_inout_dev, int64_t n_ld, int n_columns);
 int slampp_hip_solve_columns(slampp_hip_solver *p_solver, double *p_rhs_inout, int64_t n_ld, int n_columns);
 
+/* The two substitutions of the call above one at a time: y = L^-1 P b and x = P^T L^-T y -- cholmod_solve with CHOLMOD_P +
+ * CHOLMOD_L and with CHOLMOD_Lt + CHOLMOD_Pt, and what the reference's L / FastL solvers are built on:
+ * UpperTriangularTranspose_Solve_FBS gives d = R^-T eta and UpperTriangular_Solve_FBS gives dx = R^-1 d, each on its own
+ * (include/slam/NonlinearSolver_FastL.h:1101, 1693, 2305-2406, NonlinearSolver_L.h:941-1136, 2254-2458,
+ * BlockMatrix.h:3284-3580).  With the forward half alone: b^T Lambda^-1 b = |L^-1 P b|^2 (the chi^2 of a candidate loop
+ * closure, the Newton decrement eta^T Lambda^-1 eta), whitened residuals, and B Lambda^-1 B^T = Y^T Y for k linear
+ * functionals (slampp_hip_gram_device_async below); with the backward half alone: samples x = P^T L^-T z of covariance
+ * Lambda^-1 from standard normal z.
+ * Columns as in slampp_hip_solve_columns: column c is the n_scalars doubles at p_inout_dev + c * n_ld, 1 <= n_columns <=
+ * SLAMPP_HIP_SOLVE_MAX_COLUMNS, the n_ld - n_scalars doubles behind a column are not touched, n_ld is not read for one column.
+ *   SLAMPP_HIP_HALF_FORWARD:  b in the caller's scalar order on entry, y = L^-1 P b in the factor's order on return;
+ *   SLAMPP_HIP_HALF_BACKWARD: y in the factor's order on entry, x = P^T L^-T y in the caller's scalar order on return.
+ * The factor's order: new block j is the caller's block perm[j] of slampp_hip_factor_structure, its dim[j] scalars next to
+ * each other, the blocks one after the other (j ascending); L is the factor slampp_hip_factorize hands back for the same
+ * values, so L L^T = P Lambda P^T in that order.
+ * Valid when slampp_hip_solve_again_device_async is valid in sparse mode (a Schur handle whose analysis went to the sparse
+ * path included), with its SLAMPP_HIP_ERR_INVALID and texts under the name solve_half_columns; SLAMPP_HIP_ERR_INVALID also
+ * for another n_half, a null pointer, n_columns out of range, n_ld < n_scalars with more than one column.
+ * SLAMPP_HIP_ERR_UNSUPPORTED, slampp_hip_last_error saying why: Schur mode (the factor there is the block factor
+ * [L_S, U L_C^-T; 0, L_C]; its halves need L_C of every landmark, where the handle keeps C^-1), block columns wider than 8
+ * (factored in pieces), landmark shards.
+ * The launches are those of slampp_hip_solve_columns_device_async in its order, in passes of 48 columns, cut in two between
+ * the substitutions; the forward half then copies y out of the interleaved workspace into the caller's columns (a dense
+ * top's rows out of the tile solves' array), the backward half first copies it in -- transposes through an LDS tile, whole
+ * lines on both sides.  (The forward kernels cannot write y into the caller's array themselves: they still read b there, in
+ * the caller's order, while other tasks write y in the factor's.)  So a forward call followed by a backward call on its
+ * result gives the bits of slampp_hip_solve_columns_device_async, with or without a dense top.  No atomics; column c depends
+ * on column c alone (a NaN stays in its column); the same call twice gives the same bits; installs no factor.  Enqueue-only
+ * but for the first call after an analysis (the host-side lists of slampp_hip_solve_columns).
+ * slampp_hip_solve_half_columns: host array, through device memory in groups of 48 columns; it waits. */
+#define SLAMPP_HIP_HALF_FORWARD  0
+#define SLAMPP_HIP_HALF_BACKWARD 1
+int slampp_hip_solve_half_columns_device_async(slampp_hip_solver *p_solver, int n_half, double *p_inout_dev, int64_t n_ld,
+	int n_columns);
+int slampp_hip_solve_half_columns(slampp_hip_solver *p_solver, int n_half, double *p_inout, int64_t n_ld, int n_columns);
+
 /* y = alpha Lambda x + beta y with Lambda's packed values as slampp_hip_factor_solve_device reads them -- what the
  * reference's LM and dog-leg solvers compute on the host after every linear solve: the gain ratio's dx^T (alpha dx + eta)
  * and the Cauchy step's g^T Lambda g (include/slam/NonlinearSolver_Lambda_LM.h:207, NonlinearSolver_Lambda_DL.h:1175-1177 and 1270:
@@ -342,6 +378,23 @@ int slampp_hip_pattern_outer_sum_device_async(slampp_hip_solver *p_solver, int n
  * NonlinearSolver_Lambda_LM.h:207, NonlinearSolver_Lambda_DL.h:1270, 1510) stay on the device.  Enqueue-only; any handle. */
 int slampp_hip_dot_device_async(slampp_hip_solver *p_solver, const double *p_a_dev, const double *p_b_dev, int64_t n,
 	double *p_out_dev);
+
+/* The same grown to a block: out(i, j) = sum over r < n_rows of a_i[r] b_j[r], a_i = p_a_dev + i * n_lda (i < n_ka), b_j =
+ * p_b_dev + j * n_ldb (j < n_kb), out(i, j) = p_out_dev[i + j * n_ldo] -- n_ka x n_kb, column-major; 1 <= n_ka, n_kb <=
+ * SLAMPP_HIP_GRAM_MAX_COLUMNS.  With a == b == Y, the columns slampp_hip_solve_half_columns_device_async left of B^T, it is the
+ * Gram matrix Y^T Y = B Lambda^-1 B^T (Eigen's products around the triangular solves in the reference's L solvers,
+ * NonlinearSolver_FastL.h:2305-2406).  Two launches whose shape depends on n_rows, n_ka and n_kb alone: the rows in chunks of
+ * 2 048 (longer ones, in whole tiles of 64 rows, once that would be more than 256 chunks), a workgroup per chunk that stages
+ * 64 rows of both operands in LDS at a time and sums its partial block on the matrix cores (v_mfma_f64_16x16x4: four rows to
+ * an instruction, the rows in order, four row groups added in a fixed order); then the partial blocks are added in chunk order.  No atomics: two calls give the same bits, and
+ * with a == b out(i, j) and out(j, i) have the same bits.  The partial blocks live in a workspace of 256 x 48 x 48 doubles
+ * (4.5 MiB) that the first call allocates.  Any handle, no structure or factor needed; enqueue-only.  SLAMPP_HIP_ERR_INVALID:
+ * a null pointer, n_rows < 0, n_ka or n_kb out of range, n_lda or n_ldb below n_rows (not read for one column), n_ldo < n_ka,
+ * out overlapping a or b; landmark shards: SLAMPP_HIP_ERR_UNSUPPORTED, as slampp_hip_dot_device_async. */
+#define SLAMPP_HIP_GRAM_MAX_COLUMNS 48
+#define SLAMPP_HIP_GRAM_CHUNK_ROWS 2048
+int slampp_hip_gram_device_async(slampp_hip_solver *p_solver, const double *p_a_dev, int64_t n_lda, int n_ka,
+	const double *p_b_dev, int64_t n_ldb, int n_kb, int64_t n_rows, double *p_out_dev, int64_t n_ldo);
 
 /* Iterative refinement of a solution x of Lambda x = eta with the kept factor: n_steps (1 .. 8) times r = eta - Lambda x,
  * d = solve_again(r), x += d -- the classical loop around cholmod_solve (LinearSolver_CholMod.cpp:322-347; the reference

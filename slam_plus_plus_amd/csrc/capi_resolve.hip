@@ -1,10 +1,12 @@
 // capi_resolve.hip -- the entry points of the C ABI (include/slampp_hip.h) that work with a factor or beside one: the factor
 // handed out (slampp_hip_factorize, slampp_hip_factor_structure), further right-hand sides with the kept factor
-// (slampp_hip_solve_again; several at once: slampp_hip_solve_columns), y = alpha Lambda x + beta y and its adjoint in the values (the outer product on Lambda's pattern),
+// (slampp_hip_solve_again; several at once: slampp_hip_solve_columns; one substitution at a time: slampp_hip_solve_half_columns,
+// with the Gram product slampp_hip_gram_device_async), y = alpha Lambda x + beta y and its adjoint in the values (the outer product on Lambda's pattern),
 // dot products and iterative refinement
 #include "capi_util.h"
 #include "covariance.h"
 #include "multiply.h"
+#include "gram.h"
 #include "pattern_outer.h"
 
 #include <algorithm>
@@ -340,6 +342,75 @@ int slampp_hip_solve_columns(slampp_hip_solver *p_solver, double *p_rhs_inout, i
 	return SLAMPP_HIP_OK;
 }
 
+// ---- one substitution at a time on the kept factor (covariance.hip: solve_half_columns_enqueue) ----
+
+namespace {
+
+// the checks of both solve_half_columns entry points (inside guarded())
+int solve_half_columns_checks(slampp_hip_solver *p_solver, int n_half, const double *p_inout, int64_t n_ld, int n_columns)
+{
+	int n_source = 0;
+	const int n_check = resolve_checks(p_solver, "solve_half_columns", &n_source);
+	if(n_check != SLAMPP_HIP_OK)
+		return n_check;
+	if(n_half != SLAMPP_HIP_HALF_FORWARD && n_half != SLAMPP_HIP_HALF_BACKWARD)
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_half_columns: n_half is SLAMPP_HIP_HALF_FORWARD or SLAMPP_HIP_HALF_BACKWARD");
+	if(!p_inout)
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_half_columns: null pointer");
+	if(n_columns < 1 || n_columns > SLAMPP_HIP_SOLVE_MAX_COLUMNS)
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_half_columns: between 1 and SLAMPP_HIP_SOLVE_MAX_COLUMNS columns");
+	if(n_columns > 1 && n_ld < p_solver->n_scalars)
+		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "solve_half_columns: the columns overlap (leading dimension below n_scalars)");
+	if(p_solver->n_mode != SLAMPP_HIP_MODE_SPARSE)
+		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, "solve_half_columns: not in Schur mode: the factor there is the block factor "
+			"[L_S, U L_C^-T; 0, L_C], whose halves need the Cholesky factor L_C of every landmark block (kept is C^-1)");
+	if(!solve_columns_applies(*p_solver))
+		return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, "solve_half_columns: block columns wider than 8 are factored in pieces: "
+			"no k-column kernels run on them, and the factor's row order is not the caller's blocks'");
+	return SLAMPP_HIP_OK;
+}
+
+} // anonymous namespace
+
+int slampp_hip_solve_half_columns_device_async(slampp_hip_solver *p_solver, int n_half, double *p_inout_dev, int64_t n_ld, int n_columns)
+{
+	return guarded(p_solver, [&]() -> int {
+		const int n_check = solve_half_columns_checks(p_solver, n_half, p_inout_dev, n_ld, n_columns);
+		if(n_check != SLAMPP_HIP_OK)
+			return n_check;
+		solve_half_columns_enqueue(*p_solver, n_half == SLAMPP_HIP_HALF_BACKWARD, p_inout_dev, n_ld, n_columns);
+		return SLAMPP_HIP_OK;
+	});
+}
+
+int slampp_hip_solve_half_columns(slampp_hip_solver *p_solver, int n_half, double *p_inout, int64_t n_ld, int n_columns)
+{
+	// groups of at most COV_K_PASS columns through the device array of the covariance columns, as slampp_hip_solve_columns
+	int n_group0 = 0, n_group = n_columns;
+	do {
+		const int n_result = host_round_trip(p_solver, [&]() -> int {
+			slampp_hip_solver &s = *p_solver;
+			const int n_check = solve_half_columns_checks(p_solver, n_half, p_inout, n_ld, n_columns);
+			if(n_check != SLAMPP_HIP_OK)
+				return n_check;
+			n_group = std::min(n_columns - n_group0, int(COV_K_PASS));
+			s.d_cov.Alloc(size_t(s.n_scalars) * n_group);
+			SLAMPP_HIP_CHECK(hipMemcpy2DAsync(s.d_cov.p(), size_t(s.n_scalars) * sizeof(double), p_inout + int64_t(n_group0) * n_ld,
+				size_t(std::max(n_ld, s.n_scalars)) * sizeof(double) /* (one column: n_ld is of no meaning) */, size_t(s.n_scalars) * sizeof(double), size_t(n_group), hipMemcpyHostToDevice, s.stream));
+			return SLAMPP_HIP_OK;
+		}, [&](slampp_hip_solver &s) {
+			return slampp_hip_solve_half_columns_device_async(p_solver, n_half, s.d_cov.p(), s.n_scalars, n_group);
+		}, false, [&](slampp_hip_solver &s) {
+			SLAMPP_HIP_CHECK(hipMemcpy2DAsync(p_inout + int64_t(n_group0) * n_ld, size_t(std::max(n_ld, s.n_scalars)) * sizeof(double), s.d_cov.p(),
+				size_t(s.n_scalars) * sizeof(double), size_t(s.n_scalars) * sizeof(double), size_t(n_group), hipMemcpyDeviceToHost, s.stream));
+		});
+		if(n_result != SLAMPP_HIP_OK)
+			return n_result;
+		n_group0 += n_group;
+	} while(n_group0 < n_columns);
+	return SLAMPP_HIP_OK;
+}
+
 // ---- y = alpha Lambda x + beta y, dot products, iterative refinement (multiply.hip) ----
 
 namespace {
@@ -509,6 +580,33 @@ int slampp_hip_dot_device_async(slampp_hip_solver *p_solver, const double *p_a_d
 			return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, "dot: this handle solves with landmark shards on several devices");
 		s.d_reduce.Alloc(reduce_MAX_PARTIALS);
 		dot_enqueue(p_a_dev, p_b_dev, n, s.d_reduce.p(), p_out_dev, s.stream);
+		return SLAMPP_HIP_OK;
+	});
+}
+
+static_assert(SLAMPP_HIP_GRAM_MAX_COLUMNS == gram_MAX_COLUMNS && SLAMPP_HIP_GRAM_CHUNK_ROWS == gram_CHUNK_ROWS, "include/slampp_hip.h and gram.h disagree");
+
+int slampp_hip_gram_device_async(slampp_hip_solver *p_solver, const double *p_a_dev, int64_t n_lda, int n_ka, const double *p_b_dev,
+	int64_t n_ldb, int n_kb, int64_t n_rows, double *p_out_dev, int64_t n_ldo)
+{
+	return guarded(p_solver, [&]() -> int {
+		slampp_hip_solver &s = *p_solver;
+		if(!p_a_dev || !p_b_dev || !p_out_dev || n_rows < 0)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "gram: null pointer or negative length");
+		if(n_ka < 1 || n_ka > SLAMPP_HIP_GRAM_MAX_COLUMNS || n_kb < 1 || n_kb > SLAMPP_HIP_GRAM_MAX_COLUMNS)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "gram: between 1 and SLAMPP_HIP_GRAM_MAX_COLUMNS columns of a and of b");
+		if((n_ka > 1 && n_lda < n_rows) || (n_kb > 1 && n_ldb < n_rows))
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "gram: the columns of a or b overlap (leading dimension below n_rows)");
+		if(n_ldo < n_ka)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "gram: the columns of out overlap (leading dimension below n_ka)");
+		const int64_t n_out_span = int64_t(n_kb - 1) * n_ldo + n_ka;
+		if(ranges_overlap(p_a_dev, int64_t(n_ka - 1) * n_lda + n_rows, p_out_dev, n_out_span) ||
+		   ranges_overlap(p_b_dev, int64_t(n_kb - 1) * n_ldb + n_rows, p_out_dev, n_out_span))
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "gram: out overlaps a or b");
+		if(s.b_group_active)
+			return fail(p_solver, SLAMPP_HIP_ERR_UNSUPPORTED, "gram: this handle solves with landmark shards on several devices");
+		s.d_gram.Alloc(gram_PARTIAL_DOUBLES);
+		gram_enqueue(p_a_dev, n_lda, n_ka, p_b_dev, n_ldb, n_kb, n_rows, s.d_gram.p(), p_out_dev, n_ldo, s.stream);
 		return SLAMPP_HIP_OK;
 	});
 }

@@ -63,4 +63,13 @@ void covariance_columns_rhs_enqueue(slampp_hip_solver &s, int n_src, const int64
 bool solve_columns_applies(const slampp_hip_solver &s);
 void solve_columns_enqueue(slampp_hip_solver &s, double *p_rhs_dev, int64_t n_ld, int n_columns);
 
+// One of the two substitutions alone, on the same columns (slampp_hip_solve_half_columns; needs solve_columns_applies).
+// Forward: column c holds b in the caller's scalar order on entry and y = L^-1 P b in the factor's order (Plan::cs_new) on
+// return; backward: y in the factor's order on entry, x = P^T L^-T y in the caller's order on return.  The launches of
+// solve_columns_enqueue, in its order, cut in two: the forward half ends with y copied out of the interleaved workspace (the
+// dense top's rows out of the tile solves' array), the backward half begins with y copied in.  The workspace stays in
+// between because the forward kernels read b at cs_src while other tasks already write y at cs_new.  One after the other
+// they give solve_columns_enqueue's bits.  Throws.
+void solve_half_columns_enqueue(slampp_hip_solver &s, bool b_backward, double *p_inout_dev, int64_t n_ld, int n_columns);
+
 } // namespace slampp

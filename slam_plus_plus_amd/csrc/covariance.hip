@@ -949,7 +949,71 @@ bool solve_columns_applies(const slampp_hip_solver &s)
 	return !s.b_refined && s.plan.max_dim <= 8;
 }
 
-void solve_columns_enqueue(slampp_hip_solver &s, double *p_rhs_dev, int64_t n_ld, int n_columns)
+// ---- the way in and out between the two substitutions (slampp_hip_solve_half_columns) ----
+//
+// Transposes between the interleaved workspace (row * kp + c) and the caller's columns (c * n_ld + row), HALF_TILE_ROWS rows
+// to a workgroup through an LDS tile, so that both sides move whole lines: the interleaved side as one contiguous run of
+// HALF_TILE_ROWS * kp doubles, the caller's side as HALF_TILE_ROWS consecutive doubles of every column.  A tile row is kp | 1
+// doubles long: the side that walks down a tile column then has an odd stride in doubles, which puts the 32 lanes of a
+// ds_read_b64 group (and the 16 of a write's 128 bytes per clock) on banks of their own.  p_map = 0: interleaved row i is the
+// caller's row i (the workspace X).  Otherwise the interleaved rows are the dense top's positions (Zb) and p_map[i].x the
+// permuted row of position i, negative for padding and gaps: those are skipped on the way out and zero on the way in.
+
+enum { HALF_TILE_ROWS = 64, HALF_TILE_LD = COV_K_PASS | 1 };
+
+// factor order out: p_cols[c * n_ld + row] = p_inter[i * kp + c]
+__global__ void __launch_bounds__(256)
+half_export_kernel(const double *__restrict__ p_inter, int64_t n_rows, int kp, const longlong2 *__restrict__ p_map,
+	double *__restrict__ p_cols, int64_t n_ld)
+{
+	__shared__ double s_tile[HALF_TILE_ROWS * HALF_TILE_LD];
+	const int64_t r0 = int64_t(blockIdx.x) * HALF_TILE_ROWS;
+	const int n_here = int((n_rows - r0 < HALF_TILE_ROWS)? n_rows - r0 : int64_t(HALF_TILE_ROWS));
+	for(int e = threadIdx.x; e < n_here * kp; e += blockDim.x) {
+		const int i = e / kp, c = e - i * kp;
+		s_tile[i * HALF_TILE_LD + c] = p_inter[r0 * kp + e];
+	}
+	__syncthreads();
+	for(int e = threadIdx.x; e < kp * HALF_TILE_ROWS; e += blockDim.x) {
+		const int c = e / HALF_TILE_ROWS, i = e - c * HALF_TILE_ROWS;
+		if(i >= n_here)
+			continue;
+		const int64_t row = p_map? int64_t(p_map[r0 + i].x) : r0 + i;
+		if(row >= 0)
+			p_cols[int64_t(c) * n_ld + row] = s_tile[i * HALF_TILE_LD + c];
+	}
+}
+
+// factor order in: p_inter[i * kp + c] = p_cols[c * n_ld + row], zero where the position has no row
+__global__ void __launch_bounds__(256)
+half_import_kernel(const double *__restrict__ p_cols, int64_t n_ld, int64_t n_rows, int kp, const longlong2 *__restrict__ p_map,
+	double *__restrict__ p_inter)
+{
+	__shared__ double s_tile[HALF_TILE_ROWS * HALF_TILE_LD];
+	const int64_t r0 = int64_t(blockIdx.x) * HALF_TILE_ROWS;
+	const int n_here = int((n_rows - r0 < HALF_TILE_ROWS)? n_rows - r0 : int64_t(HALF_TILE_ROWS));
+	for(int e = threadIdx.x; e < kp * HALF_TILE_ROWS; e += blockDim.x) {
+		const int c = e / HALF_TILE_ROWS, i = e - c * HALF_TILE_ROWS;
+		if(i >= n_here)
+			continue;
+		const int64_t row = p_map? int64_t(p_map[r0 + i].x) : r0 + i;
+		s_tile[i * HALF_TILE_LD + c] = (row >= 0)? p_cols[int64_t(c) * n_ld + row] : 0.0;
+	}
+	__syncthreads();
+	for(int e = threadIdx.x; e < n_here * kp; e += blockDim.x) {
+		const int i = e / kp, c = e - i * kp;
+		p_inter[r0 * kp + e] = s_tile[i * HALF_TILE_LD + c];
+	}
+}
+
+namespace {
+enum { SOLVE_COLS_FORWARD = 1, SOLVE_COLS_BACKWARD = 2 }; // which substitutions a call of Solve_Columns_Passes runs
+}
+
+// The passes of slampp_hip_solve_columns (both halves: the forward substitution leaves y in the workspace, the backward one
+// picks it up there) and of slampp_hip_solve_half_columns (one half: y leaves the workspace through half_export_kernel, or
+// enters it through half_import_kernel; the substitutions' launches are the same ones in the same order).
+static void Solve_Columns_Passes(slampp_hip_solver &s, double *p_rhs_dev, int64_t n_ld, int n_columns, int n_halves, const char *p_s_phase)
 {
 	const Plan &P = s.plan;
 	CCovariance &cv = Covariance_State(s);
@@ -962,13 +1026,15 @@ void solve_columns_enqueue(slampp_hip_solver &s, double *p_rhs_dev, int64_t n_ld
 	const int n_per_wave = 64 / (D? D : 8);
 	const int n_stages = int(P.stage_ptr.size()) - 1;
 	const int ld = s.n_dense_pad, n_dense = s.n_dense_dim, n_tiles = ld / COV_NB;
-	s.Phase_Begin("solve_columns");
+	const bool b_forward = (n_halves & SOLVE_COLS_FORWARD) != 0, b_backward = (n_halves & SOLVE_COLS_BACKWARD) != 0;
+	const unsigned n_row_tiles = unsigned((s.n_scalars + HALF_TILE_ROWS - 1) / HALF_TILE_ROWS);
+	s.Phase_Begin(p_s_phase);
 	for(int col0 = 0; col0 < n_columns; col0 += COV_K_PASS) {
 		const int kp = std::min(int(COV_K_PASS), n_columns - col0);
 		const unsigned n_groups = unsigned((kp + n_per_wave - 1) / n_per_wave);
 		double *p_pass = p_rhs_dev + int64_t(col0) * n_ld;
 #define SOLVE_COLS_DISPATCH(LAUNCH) switch(D) { case 3: LAUNCH(3); break; case 6: LAUNCH(6); break; case 7: LAUNCH(7); break; default: LAUNCH(0); break; }
-		for(int st = 0; st < n_stages; ++ st) {
+		for(int st = 0; b_forward && st < n_stages; ++ st) {
 			const int n_tasks = P.stage_ptr[size_t(st + 1)] - P.stage_ptr[size_t(st)];
 			if(n_tasks <= 0)
 				continue;
@@ -977,7 +1043,7 @@ void solve_columns_enqueue(slampp_hip_solver &s, double *p_rhs_dev, int64_t n_ld
 			SOLVE_COLS_DISPATCH(SOLVE_COLS_FWD)
 #undef SOLVE_COLS_FWD
 		}
-		if(n_dense) {
+		if(n_dense && b_forward) {
 			SLAMPP_HIP_CHECK(hipMemsetAsync(cv.d_Bd.p(), 0, size_t(ld) * kp * sizeof(double), s.stream)); // (gaps between the columns' positions)
 			if(cv.n_top_cols) {
 #define SOLVE_COLS_TOP(DD) hipLaunchKernelGGL(solve_cols_top_kernel<DD>, dim3(unsigned(cv.n_top_cols), n_groups), dim3(64), 0, s.stream, cv.d_top_cols.p(), \
@@ -988,6 +1054,23 @@ void solve_columns_enqueue(slampp_hip_solver &s, double *p_rhs_dev, int64_t n_ld
 			for(int t = 0; t < n_tiles; ++ t)
 				hipLaunchKernelGGL(cov_dense_forward_kernel, dim3(n_tiles - t), dim3(256), 0, s.stream, s.d_dense.p(), ld, n_dense, t,
 					s.d_dense_invdiag.p(), cv.d_Bd.p(), cv.d_Zb.p(), kp);
+		}
+		if(!b_backward) { // y out: the block-eliminated rows from X (its dense-top rows hold nothing), then the top's from Zb over them
+			hipLaunchKernelGGL(half_export_kernel, dim3(n_row_tiles), dim3(256), 0, s.stream, cv.d_X.p(), s.n_scalars, kp,
+				(const longlong2*)0, p_pass, n_ld);
+			if(n_dense)
+				hipLaunchKernelGGL(half_export_kernel, dim3(unsigned(n_tiles)), dim3(256), 0, s.stream, cv.d_Zb.p(), int64_t(ld), kp,
+					s.d_dense_dst.p(), p_pass, n_ld);
+			continue;
+		}
+		if(!b_forward) { // y in: every row into X (the top's x replaces its rows there), the top's into Zb
+			hipLaunchKernelGGL(half_import_kernel, dim3(n_row_tiles), dim3(256), 0, s.stream, p_pass, n_ld, s.n_scalars, kp,
+				(const longlong2*)0, cv.d_X.p());
+			if(n_dense)
+				hipLaunchKernelGGL(half_import_kernel, dim3(unsigned(n_tiles)), dim3(256), 0, s.stream, p_pass, n_ld, int64_t(ld), kp,
+					s.d_dense_dst.p(), cv.d_Zb.p());
+		}
+		if(n_dense) {
 			for(int t = n_tiles - 1; t >= 0; -- t)
 				hipLaunchKernelGGL(cov_dense_backward_kernel, dim3(t + 1), dim3(256), 0, s.stream, s.d_dense.p(), ld, n_dense, t,
 					s.d_dense_invdiag.p(), cv.d_Zb.p(), kp, s.d_dense_dst.p(), cv.d_X.p(), p_pass, n_ld, 0);
@@ -1005,6 +1088,17 @@ void solve_columns_enqueue(slampp_hip_solver &s, double *p_rhs_dev, int64_t n_ld
 	}
 	s.Phase_End();
 	SLAMPP_HIP_CHECK(hipGetLastError());
+}
+
+void solve_columns_enqueue(slampp_hip_solver &s, double *p_rhs_dev, int64_t n_ld, int n_columns)
+{
+	Solve_Columns_Passes(s, p_rhs_dev, n_ld, n_columns, SOLVE_COLS_FORWARD | SOLVE_COLS_BACKWARD, "solve_columns");
+}
+
+void solve_half_columns_enqueue(slampp_hip_solver &s, bool b_backward, double *p_inout_dev, int64_t n_ld, int n_columns)
+{
+	Solve_Columns_Passes(s, p_inout_dev, n_ld, n_columns, b_backward? SOLVE_COLS_BACKWARD : SOLVE_COLS_FORWARD,
+		b_backward? "solve_half_backward" : "solve_half_forward");
 }
 
 // ---- blocks at arbitrary pairs: Y_r^T Y_c over the rows the two paths share ----

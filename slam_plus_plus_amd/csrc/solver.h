@@ -145,6 +145,7 @@ struct slampp_hip_solver {
 	bool b_mul_valid = false;
 	int n_multiply_long_row = SLAMPP_HIP_MULTIPLY_LONG_ROW;
 	slampp::CDevArray<double> d_reduce, d_refine_r, d_mul_x, d_mul_y, d_refine_resid;
+	slampp::CDevArray<double> d_gram; // the per-chunk partial blocks of slampp_hip_gram_device_async (gram.h: gram_PARTIAL_DOUBLES), allocated at its first call
 	void Require_Multiply(); // throws
 	// out = alpha P(a, b) + beta out on Lambda's pattern (pattern_outer.hip): its lookup tables live as the row lists above do;
 	// the output array of the host entry point

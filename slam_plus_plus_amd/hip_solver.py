@@ -34,6 +34,9 @@ OK, NOT_POSDEF = 0, 1
 ERR_INVALID, ERR_ALLOC, ERR_DEVICE, ERR_UNSUPPORTED = -1, -2, -3, -4
 MODE_SPARSE, MODE_SCHUR = 0, 1
 SOLVE_MAX_COLUMNS = 256    # SLAMPP_HIP_SOLVE_MAX_COLUMNS
+HALF_FORWARD, HALF_BACKWARD = 0, 1   # SLAMPP_HIP_HALF_FORWARD, SLAMPP_HIP_HALF_BACKWARD
+GRAM_MAX_COLUMNS = 48      # SLAMPP_HIP_GRAM_MAX_COLUMNS
+GRAM_CHUNK_ROWS = 2048     # SLAMPP_HIP_GRAM_CHUNK_ROWS
 # slampp_hip_multiply: block rows with more blocks than MULTIPLY_LONG_ROW are cut into chunks of MULTIPLY_CHUNK
 # (SLAMPP_HIP_MULTIPLY_* in include/slampp_hip.h; the development option "multiply_long_row" lowers the threshold)
 MULTIPLY_LONG_ROW, MULTIPLY_CHUNK = 256, 256
@@ -121,6 +124,9 @@ ABI = {
     "slampp_hip_solve_again_device_async": (C.c_int, [_P, _P]),
     "slampp_hip_solve_columns_device_async": (C.c_int, [_P, _P, C.c_int64, C.c_int]),
     "slampp_hip_solve_columns": (C.c_int, [_P, _P, C.c_int64, C.c_int]),
+    "slampp_hip_solve_half_columns_device_async": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int]),
+    "slampp_hip_solve_half_columns": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int]),
+    "slampp_hip_gram_device_async": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int, C.c_int64, _P, C.c_int64]),
     "slampp_hip_pattern_outer_sum_device_async": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64, _P, C.c_double,
                                                             C.c_double]),
     "slampp_hip_multiply_device_async": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double]),
@@ -489,6 +495,21 @@ class _SolverBase:
             raise ValueError(f"B must be a C-contiguous float64 array of the shape (k, n_scalars), 1 <= k <= {SOLVE_MAX_COLUMNS}")
         return self._check(self._lib.slampp_hip_solve_columns(self._h, _ptr(B), n_scalars, int(B.shape[0])))
 
+    def Solve_Half_Columns(self, B: np.ndarray, half: int) -> bool:
+        """One of the two substitutions of Solve_Columns alone (slampp_hip_solve_half_columns: cholmod_solve with CHOLMOD_P +
+        CHOLMOD_L, or with CHOLMOD_Lt + CHOLMOD_Pt), on a C-contiguous float64 ``(k, n_scalars)`` array as Solve_Columns takes.
+        ``half=HALF_FORWARD``: row c holds b in the caller's scalar order on entry and ``y = L^-1 P b`` in the factor's order
+        (the block permutation of factor_structure()) on return; ``half=HALF_BACKWARD``: y in the factor's order on entry,
+        ``x = P^T L^-T y`` in the caller's order on return.  Sparse mode with block columns of at most 8; NotImplementedError
+        in Schur mode (the factor there is a block factor over the landmarks' own Cholesky factors) and for wider blocks."""
+        if self._structure_key is None or not self._analyzed:
+            raise ValueError("Solve_Half_Columns: there is no factorization")
+        n_scalars = self._structure_key[2]
+        if (not isinstance(B, np.ndarray) or B.dtype != np.float64 or not B.flags.c_contiguous or B.ndim != 2
+                or B.shape[1] != n_scalars or not 1 <= B.shape[0] <= SOLVE_MAX_COLUMNS):
+            raise ValueError(f"B must be a C-contiguous float64 array of the shape (k, n_scalars), 1 <= k <= {SOLVE_MAX_COLUMNS}")
+        return self._check(self._lib.slampp_hip_solve_half_columns(self._h, int(half), _ptr(B), n_scalars, int(B.shape[0])))
+
     def Log_Determinant(self, lam, reuse_factor: bool = False) -> float:
         """log det Lambda = 2 sum log L_ii from the Cholesky factor on the device (slampp_hip_logdet).  ``reuse_factor=False``:
         analyzes a new structure, factors ``lam.values`` and leaves the handle as Solve_PosDef_Blocky leaves it (Solve_Again
@@ -684,6 +705,20 @@ class _SolverBase:
         (slampp_hip_solve_columns_device_async): column c is the n_scalars doubles at rhs_ptr + 8 c ld; valid where
         solve_again_device is."""
         self._check(self._lib.slampp_hip_solve_columns_device_async(self._h, rhs_ptr or None, int(ld), int(k)))
+
+    def solve_half_columns_device(self, rhs_ptr: int, ld: int, k: int, half: int) -> None:
+        """One of the two substitutions of solve_columns_device alone, device-resident and enqueue-only
+        (slampp_hip_solve_half_columns_device_async): ``half=HALF_FORWARD`` turns column c, b in the caller's scalar order, into
+        ``L^-1 P b`` in the factor's order; ``half=HALF_BACKWARD`` turns y in the factor's order into ``P^T L^-T y`` in the
+        caller's.  One after the other they give solve_columns_device's bits.  Sparse mode, block columns of at most 8."""
+        self._check(self._lib.slampp_hip_solve_half_columns_device_async(self._h, int(half), rhs_ptr or None, int(ld), int(k)))
+
+    def gram_device(self, a_ptr: int, lda: int, ka: int, b_ptr: int, ldb: int, kb: int, n_rows: int, out_ptr: int, ldo: int) -> None:
+        """out(i, j) = a_i . b_j over n_rows device-resident doubles, in a fixed order (slampp_hip_gram_device_async): a_i at
+        a_ptr + 8 i lda, b_j at b_ptr + 8 j ldb, out(i, j) at out_ptr + 8 (i + j ldo); ka, kb <= GRAM_MAX_COLUMNS.
+        Enqueue-only; any handle."""
+        self._check(self._lib.slampp_hip_gram_device_async(self._h, a_ptr or None, int(lda), int(ka), b_ptr or None, int(ldb), int(kb),
+                                                           int(n_rows), out_ptr or None, int(ldo)))
 
     def multiply_device(self, values_ptr: int, x_ptr: int, y_ptr: int, alpha: float = 1.0, beta: float = 0.0) -> None:
         """y = alpha Lambda x + beta y on device-resident arrays, enqueue-only (slampp_hip_multiply_device_async); the

@@ -66,6 +66,23 @@ factorization plus the covariance recursion, and it leaves the handle's factor a
 call is unsupported (sparse mode: block columns wider than 8), backward raises a RuntimeError naming the limit; the forward
 pass works regardless.
 
+``quad_form(solver, lam, values, B[k, n_scalars])`` returns ``G = B M^-1 B^T`` (k x k, k <= 48), differentiable in ``values`` and
+``B``; sparse mode with block columns of at most 8 (the library refuses anything else: NotImplementedError in Schur mode).
+Forward: the values are factored as ``solve`` factors them (slampp_hip_factor_solve_device_async on a zero vector, which
+leaves the kept factor), ``Y = L^-1 P B^T`` by the forward half alone (slampp_hip_solve_half_columns_device_async) on a copy
+of B, ``G = Y^T Y`` by slampp_hip_gram_device_async -- bitwise symmetric --, and ``X = P^T L^-T Y = M^-1 B^T`` by the backward
+half on a copy of Y, saved for backward (skipped where neither input requires a gradient); one wait.  Backward, with an
+upstream ``G_bar``: ``B_bar = (G_bar + G_bar^T) X`` and ``v_bar = -sum_a P(x_a, w_a)`` with ``W = G_bar X`` in one slampp_hip_pattern_outer_sum_device_async, because
+``dG_ab = -x_a^T dM x_b = -<dv, P(x_a, x_b)>``.  Everything backward needs is in X: it reads no factor, so it does not matter
+whose factor the handle holds by then, and nothing is factored again; a handle that has been given another structure since
+is given this one again (analyzed, as the other backward passes do), because the outer products run on the handle's structure.
+
+``sample(solver, lam, values, Z[k, n_scalars])`` returns rows ``x = P^T L^-T z`` (the backward half alone): for standard
+normal z, samples of covariance ``M^-1``.  ``whiten(solver, lam, values, B[k, n_scalars])`` returns rows ``L^-1 P b`` (the
+forward half alone; their squared norms are ``b^T M^-1 b``) and the block permutation P (``factor_structure()["perm"]``: new
+block j is the caller's block perm[j]).  Neither is differentiable: the derivative of the Cholesky factor is not built
+here.  Both return detached tensors and raise if ``values`` requires a gradient; k <= 256.
+
 ``dense_from_packed`` and ``pattern_outer_reference`` restate M(v) and the outer product in plain torch / numpy: the
 yardsticks of the tests.
 """
@@ -75,7 +92,7 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
-from .hip_solver import CLinearSolver_HIP, CLinearSolver_Schur_HIP, MODE_SPARSE
+from .hip_solver import CLinearSolver_HIP, CLinearSolver_Schur_HIP, MODE_SPARSE, HALF_FORWARD, HALF_BACKWARD, GRAM_MAX_COLUMNS
 
 MAX_BATCH = 64     # SLAMPP_HIP_MAX_BATCH
 MAX_COLUMNS = 256  # SLAMPP_HIP_SOLVE_MAX_COLUMNS
@@ -132,8 +149,10 @@ def _enqueue(solver, fn) -> None:
     """fn() enqueues on the solver's stream, behind what torch's current stream holds and ahead of what it gets next."""
     ours, theirs = _solver_stream(solver), torch.cuda.current_stream(torch.device("cuda", solver._device))
     ours.wait_stream(theirs)
-    fn()
-    theirs.wait_stream(ours)
+    try:
+        fn()
+    finally:                                    # (also where fn() raised after it had enqueued something)
+        theirs.wait_stream(ours)
 
 
 # ---- checks (before any call into the library) ----
@@ -386,3 +405,110 @@ def logdet(solver, lam, values: torch.Tensor) -> torch.Tensor:
     _check_tensor(solver, values, "values", (int(lam.values.shape[0]),))
     _require_analysis(solver, lam)
     return _Logdet.apply(values, solver, lam)
+
+
+# ---- the two substitutions one at a time: B M^-1 B^T, samples, whitening ----
+
+def _check_rows(solver, lam, rows, name: str, n_max: int) -> None:
+    n_scalars = int(lam.cumsum[-1])
+    if isinstance(rows, torch.Tensor) and (rows.dim() != 2 or not 1 <= rows.shape[0] <= n_max):
+        raise ValueError(f"{name} must be a tensor of the shape (k, n_scalars), 1 <= k <= {n_max}")
+    _check_tensor(solver, rows, name, (rows.shape[0] if isinstance(rows, torch.Tensor) else 1, n_scalars))
+
+
+def _factor(solver, values, zero) -> None:
+    """Enqueues the factorization a solve makes, on the zero vector ``zero``: it leaves the kept factor."""
+    solver.factor_solve_device_async(values.data_ptr(), zero.data_ptr())
+
+
+def _factored_half(solver, values, rows, half: int, who: str):
+    """Factors ``values`` and runs one substitution on a packed copy of ``rows``; waits.  Returns the copy."""
+    out = rows.detach().clone(memory_format=torch.contiguous_format)
+    v = values.detach()
+    zero = torch.zeros(out.shape[1], dtype=torch.float64, device=out.device)
+
+    def work():
+        _factor(solver, v, zero)
+        solver.solve_half_columns_device(out.data_ptr(), out.stride(0), out.shape[0], half)
+    _enqueue(solver, work)
+    if not solver.sync():
+        raise torch.linalg.LinAlgError(f"{who}: the matrix is not positive definite")
+    return out
+
+
+class _QuadForm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, values, B, solver, lam):
+        k, n = B.shape
+        y = B.detach().clone(memory_format=torch.contiguous_format)
+        v = values.detach()
+        zero = torch.zeros(n, dtype=torch.float64, device=y.device)
+        G = torch.empty((k, k), dtype=torch.float64, device=y.device)
+
+        def forward_half():
+            _factor(solver, v, zero)
+            solver.solve_half_columns_device(y.data_ptr(), n, k, HALF_FORWARD)
+            solver.gram_device(y.data_ptr(), n, k, y.data_ptr(), n, k, n, G.data_ptr(), k)
+        _enqueue(solver, forward_half)
+        b_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        if b_grad:                                  # X for backward; nobody to differentiate for: the forward half is all there is to do
+            x = y.clone()
+            _enqueue(solver, lambda: solver.solve_half_columns_device(x.data_ptr(), n, k, HALF_BACKWARD))
+        if not solver.sync():
+            raise torch.linalg.LinAlgError("quad_form: the matrix is not positive definite")
+        if b_grad:
+            ctx.solver, ctx.lam = solver, lam
+            ctx.save_for_backward(values, x)
+        return G
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G_bar):
+        values, x = ctx.saved_tensors
+        solver = ctx.solver
+        v_bar = None
+        if ctx.needs_input_grad[0]:
+            _require_analysis(solver, ctx.lam)      # (the outer products are on the handle's structure: it may have been given another since)
+            v_bar = torch.empty_like(values)
+            w = (G_bar @ x).contiguous()
+            _enqueue(solver, lambda: solver.pattern_outer_sum_device(x.shape[0], x.data_ptr(), x.stride(0), w.data_ptr(),
+                                                                     w.stride(0), v_bar.data_ptr(), -1.0, 0.0))
+        B_bar = (G_bar + G_bar.transpose(0, 1)) @ x if ctx.needs_input_grad[1] else None
+        return v_bar, B_bar, None, None
+
+
+def quad_form(solver, lam, values: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+    """G = B M(values)^-1 B^T for B of the shape (k, n_scalars), k <= 48: a (k, k) tensor, bitwise symmetric, differentiable in
+    ``values`` and ``B`` (module docstring).  Sparse mode, block columns of at most 8."""
+    _check_solver(solver)
+    _check_tensor(solver, values, "values", (int(lam.values.shape[0]),))
+    _check_rows(solver, lam, B, "B", GRAM_MAX_COLUMNS)
+    _require_analysis(solver, lam)
+    return _QuadForm.apply(values, B, solver, lam)
+
+
+def sample(solver, lam, values: torch.Tensor, Z: torch.Tensor) -> torch.Tensor:
+    """Rows x = P^T L^-T z for the rows z of Z (k, n_scalars), L L^T = P M(values) P^T: standard normal z give samples of
+    covariance M^-1.  NOT differentiable in ``values`` -- the derivative of the Cholesky factor is not built here --: the
+    result is detached, and the call raises if ``values`` requires a gradient."""
+    _check_solver(solver)
+    _check_tensor(solver, values, "values", (int(lam.values.shape[0]),))
+    _check_rows(solver, lam, Z, "Z", MAX_COLUMNS)
+    if values.requires_grad:
+        raise ValueError("sample: not differentiable in values (the derivative of the Cholesky factor is not built): detach them")
+    _require_analysis(solver, lam)
+    return _factored_half(solver, values, Z, HALF_BACKWARD, "sample")
+
+
+def whiten(solver, lam, values: torch.Tensor, B: torch.Tensor):
+    """(Y, perm): rows y = L^-1 P b for the rows b of B (k, n_scalars) -- whitened coordinates: |y|^2 = b^T M(values)^-1 b --
+    in the factor's order, and the block permutation as an int64 CPU tensor: new block j is the caller's block perm[j].
+    Detached, and raises if ``values`` requires a gradient, as ``sample``."""
+    _check_solver(solver)
+    _check_tensor(solver, values, "values", (int(lam.values.shape[0]),))
+    _check_rows(solver, lam, B, "B", MAX_COLUMNS)
+    if values.requires_grad:
+        raise ValueError("whiten: not differentiable in values (the derivative of the Cholesky factor is not built): detach them")
+    _require_analysis(solver, lam)
+    Y = _factored_half(solver, values, B, HALF_FORWARD, "whiten")
+    return Y, torch.from_numpy(solver.factor_structure()["perm"].astype(np.int64))
