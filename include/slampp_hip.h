@@ -741,6 +741,69 @@ typedef struct slampp_hip_edge_set {
 int slampp_hip_assemble_sets_device_async(const slampp_hip_edge_set *p_sets, int n_sets, int64_t n_unary_vertex,
 	const double *p_unary_factor, const double *p_unary_error, double *p_values_dev, double *p_eta_dev, int b_accumulate);
 
+/* The two ends of a Gauss-Newton / LM iteration, so that the loop
+ *   linearize -> assemble -> (damp) -> factor_solve -> state_plus -> chi_squared
+ * runs without the states, the Jacobians, Lambda or dx leaving the device.
+ *
+ * linearize: every edge's error and Jacobians from the vertex states -- Calculate_Jacobians_Expectation_Error of the
+ * reference's three workhorse edges -- for the edge set of an assembly handle, which knows the edges' vertices and dimensions:
+ *   SLAMPP_HIP_EDGE_SE2      CEdgePose2D (SE2_Types.h:308-318, 2DSolverBase.h:372-424): h = (R^T(th0) (p1 - p0),
+ *                            f_ClampAngle_2Pi(th1 - th0)), err = z - h, its angle through f_ClampAngularError_2Pi
+ *                            (2DSolverBase.h:44-94); the Jacobians are the closed forms of lines 412-423, derivatives with
+ *                            respect to an additive perturbation of the state;
+ *   SLAMPP_HIP_EDGE_SE3      CEdgePose3D (SE3_Types.h:265-287, 3DSolverBase.h:806-946): h = (R0^T (t1 - t0), Log(R0^T R1)), Log
+ *                            the principal logarithm (the quaternion with w >= 0: f_AxisAngle_to_Quat, 3DSolverBase.h:476-519),
+ *                            err = (z_t - h_t, Log(Exp(z_r) Exp(h_r)^T)); J0 = dh(x0 (+) e, x1) / de and J1 = dh(x0, x1 (+) e) / de
+ *                            at e = 0, (+) being Relative_to_Absolute: t <- t + R e_t, R <- R Exp(e_r);
+ *   SLAMPP_HIP_EDGE_P2C_XYZ  CEdgeP2C3D (BA_Types.h:403-505, BASolverBase.h:259-327, 558-619; DATA_UPSIDE_DOWN off): x = R X + t,
+ *                            pinhole projection with the camera's intrinsics (fx, fy, cx, cy, k), then the one-coefficient
+ *                            radial term with k / ((fx + fy) / 2); err = z - projection; the camera moves by the SE(3) (+)
+ *                            above, the point additively.
+ * Where the reference differences forwards with a step of 1e-9 (SE3, P2C_XYZ: 3DSolverBase.h:1331-1371, BASolverBase.h:577-619;
+ * good to about 1e-7), these are the exact derivatives of the same functions in closed form.
+ *   p_state_dev        n_scalars doubles in Lambda's scalar order -- the layout of eta and dx: the state of block column v at
+ *                      its scalar offset (for these vertex types the state dimension is the block dimension);
+ *   p_measurement_dev  [n_edges][3 | 6 (xyz, axis-angle) | 2];
+ *   p_params_dev       NULL but for P2C_XYZ: the five intrinsics of the camera at block column c at p_params_dev + 5 c (only
+ *                      the entries of block columns that are some edge's vertex 0 are read);
+ *   p_J0_dev [n_edges][rd x d0], p_J1_dev [n_edges][rd x d1], p_error_dev [n_edges][rd]: written, in the layout
+ *                      slampp_hip_assemble_device_async reads (edge-major, matrices column-major).
+ * A lane computes an edge; a workgroup stages the outputs of its 64 edges in LDS and writes whole lines.  No atomics: the same
+ * call twice gives the same bits, and an edge's results do not depend on the other edges of the set.
+ * SLAMPP_HIP_ERR_INVALID (text under "linearize"): a null handle or a null required pointer, an assembly that a set_structure
+ * has outdated, an unknown type, a type whose (d0, d1, rd) are not the handle's, P2C_XYZ without p_params_dev.
+ * Enqueue-only on the solver's stream. */
+#define SLAMPP_HIP_EDGE_SE2      1  /* CEdgePose2D: d0 = d1 = 3, rd = 3, measurement 3 doubles          */
+#define SLAMPP_HIP_EDGE_SE3      2  /* CEdgePose3D: d0 = d1 = 6, rd = 6, measurement 6 (xyz, axis-angle) */
+#define SLAMPP_HIP_EDGE_P2C_XYZ  3  /* CEdgeP2C3D:  d0 = 6 (camera), d1 = 3 (point), rd = 2, measurement 2 */
+int slampp_hip_linearize_device_async(slampp_hip_assembly *p_assembly, int n_edge_type, const double *p_state_dev,
+	const double *p_measurement_dev, const double *p_params_dev, double *p_J0_dev, double *p_J1_dev, double *p_error_dev);
+
+/* out = state (+) f_scale dx on block columns [n_first_vertex, n_last_vertex) -- the range convention of
+ * slampp_hip_apply_damping_device_async -- on the manifold of the vertex type: Operator_Plus of the reference's vertices, which
+ * PushValuesInGraphSystem runs over the vertex pool (NonlinearSolver_Base.h); f_scale = -1 is Operator_Minus, the LM roll-back.
+ * State and dx in the layout of eta.  p_state_out_dev may be p_state_dev (in place, to the bits of out of place); otherwise the
+ * two must not overlap, and dx overlaps neither.  Block columns outside the range are not written (a graph with cameras and
+ * points takes two calls).  Needs slampp_hip_set_structure only.  A lane per block column; no atomics.
+ * SLAMPP_HIP_ERR_INVALID (text under "state_plus"): a null pointer, no structure, an unknown type, a range outside
+ * [0, n_bcols] or with first > last, a block column in the range whose dimension is not the type's (3 for SE2, 6 for SE3, above 8
+ * for EUCLIDEAN), arrays that overlap in part.  Enqueue-only on the solver's stream, but for the first call after a
+ * set_structure, which uploads the block columns' offsets and waits for that copy. */
+#define SLAMPP_HIP_VERTEX_EUCLIDEAN 0  /* x += s dx (CVertexXYZ; any block dimension up to 8)                      */
+#define SLAMPP_HIP_VERTEX_SE2       1  /* x += s dx, theta = f_ClampAngle_2Pi(theta)   (SE2_Types.h:70-74)          */
+#define SLAMPP_HIP_VERTEX_SE3       2  /* Relative_to_Absolute(x, s dx) (CVertexPose3D, CVertexCam: SE3_Types.h:45-48) */
+int slampp_hip_state_plus_device_async(slampp_hip_solver *p_solver, int n_vertex_type, int64_t n_first_vertex,
+	int64_t n_last_vertex, const double *p_state_dev, const double *p_dx_dev, double f_scale, double *p_state_out_dev);
+
+/* *p_out_dev = sum over the edges of the handle of w_e err_e^T Sigma_e^-1 err_e (p_weight_dev NULL: w = 1) -- f_Chi_Squared_Error
+ * of the edges summed over the edge pool (NonlinearSolver_Lambda.h f_Chi_Squared_Error_Denorm), on the error array
+ * slampp_hip_linearize_device_async wrote and the Sigma^-1 array the assembly reads.  Two passes as in
+ * slampp_hip_dot_device_async: a lane adds the terms of its edges, then the sums are added in a fixed order that depends on
+ * n_edges alone -- bit-reproducible, no atomics.  Any edge set (rd <= 8).  SLAMPP_HIP_ERR_INVALID (text under "chi2"): a null
+ * handle or pointer, an outdated assembly.  Enqueue-only on the solver's stream. */
+int slampp_hip_chi_squared_device_async(slampp_hip_assembly *p_assembly, const double *p_sigma_inv_dev,
+	const double *p_error_dev, const double *p_weight_dev /* or NULL */, double *p_out_dev);
+
 /* Multi-GPU BA (new functionality, no reference counterpart -- SURVEY.md section 8e): every rank
  * holds a landmark shard (its own points + all cameras); the partial reduced camera systems
  * [S | rhs] are summed over ranks by this callback (RCCL all-reduce over xGMI) between the Schur

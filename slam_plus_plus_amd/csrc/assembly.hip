@@ -43,6 +43,7 @@ struct CAssemblyState {
 	int n_long_dim;                 // their common dimension (0: none qualify)
 	int n_off_elems;                // largest off-diagonal block, in elements: 64 / that many blocks share a wave
 	CDevArray<int32_t> d_entries;   // edge index * 2 + (off-diagonal: flipped; diagonal: side)
+	CDevArray<int64_t> d_edge_state; // three planes of n_edges: scalar offset of vertex 0 and of vertex 1 in the state vector (eta's layout), block column of vertex 0 (linearize.hip)
 	// groups of consecutive vertices whose edges fit in LDS together: every edge record is read once for the off-diagonal
 	// block and both diagonal contributions (assemble_group_kernel)
 	int64_t n_groups;
@@ -330,6 +331,13 @@ CAssemblyState *assembly_setup(slampp_hip_solver &s, int64_t n_edges, const int6
 			p->d_diag_vertex.Upload(plain_vertex, s.stream);
 		}
 		p->d_entries.Upload(entries, s.stream);
+		std::vector<int64_t> edge_state(size_t(3 * n_edges));
+		for(int64_t e = 0; e < n_edges; ++ e) {
+			edge_state[e] = cs[v0[e]];
+			edge_state[n_edges + e] = cs[v1[e]];
+			edge_state[2 * n_edges + e] = v0[e];
+		}
+		p->d_edge_state.Upload(edge_state, s.stream); // (the synchronization below ends the copy before the vector goes)
 		p->d_unary.Alloc(72);
 		p->b_unary_valid = false;
 		p->p_solver = &s;
@@ -1157,7 +1165,16 @@ size_t assembly_device_bytes(const CAssemblyState *p)
 {
 	return p->d_offdiag.n_Bytes() + p->d_diag.n_Bytes() + p->d_diag_vertex.n_Bytes() + p->d_long.n_Bytes() + p->d_long_vertex.n_Bytes() +
 		p->d_small.n_Bytes() + p->d_small_vertex.n_Bytes() +
-		p->d_entries.n_Bytes() + p->d_unary.n_Bytes() + p->d_grp_words.n_Bytes();
+		p->d_entries.n_Bytes() + p->d_unary.n_Bytes() + p->d_grp_words.n_Bytes() + p->d_edge_state.n_Bytes();
+}
+
+void assembly_edge_view(const CAssemblyState &a, TAsmEdgeView &r_view)
+{
+	r_view.n_edges = a.n_edges;
+	r_view.d0 = a.d0; r_view.d1 = a.d1; r_view.rd = a.rd;
+	r_view.p_state_off0 = a.d_edge_state.p();
+	r_view.p_state_off1 = a.d_edge_state.p() + a.n_edges;
+	r_view.p_vertex0 = a.d_edge_state.p() + 2 * a.n_edges;
 }
 
 } // namespace slampp

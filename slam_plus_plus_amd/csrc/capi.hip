@@ -511,6 +511,7 @@ int slampp_hip_set_structure(slampp_hip_solver *p_solver, int64_t n_bcols, const
 		s.b_analyzed = false;
 		s.Factor_Dropped(); // (what the Schur covariance calls left in place is stale now)
 		s.b_damp_valid = false;
+		s.b_state_cumsum_valid = false;
 		s.b_mul_valid = false; // (the row lists of slampp_hip_multiply belong to the previous structure)
 		s.b_outer_valid = false; // (and so do the tables of slampp_hip_pattern_outer)
 		s.n_uploaded = 0;

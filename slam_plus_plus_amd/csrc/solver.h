@@ -270,6 +270,8 @@ struct slampp_hip_solver {
 	slampp::CDevArray<int64_t> d_diag_out_off; // ... and where its block goes in the output
 	slampp::CDevArray<int64_t> d_damp_off; // (offset of the diagonal block's first element, dimension) per block column: apply_damping
 	bool b_damp_valid = false;
+	slampp::CDevArray<int64_t> d_state_cumsum; // the block columns' scalar offsets (n_bcols + 1): state_plus
+	bool b_state_cumsum_valid = false;
 	slampp::CDevArray<int> d_flag;
 	int *p_flag_shared = 0; // the reduced camera system's solver: the not-positive-definite flag of the solver it serves (not zeroed here)
 	int *p_host_flag; // pinned
@@ -422,6 +424,13 @@ void assembly_enqueue(CAssemblyState &a, const double *J0, const double *J1, con
 	const double *wgt, int64_t n_unary_vertex, const double *p_unary_factor, const double *p_unary_error,
 	double *values_out, double *eta_out, int b_accumulate); // throws
 size_t assembly_device_bytes(const CAssemblyState *p);
+// what the edge kernels of linearize.hip need of an edge set: its shape and, per edge, where its vertices' states lie
+struct TAsmEdgeView {
+	int64_t n_edges;
+	int d0, d1, rd;
+	const int64_t *p_state_off0, *p_state_off1, *p_vertex0; // device arrays of n_edges: scalar offsets of both vertices, block column of vertex 0
+};
+void assembly_edge_view(const CAssemblyState &a, TAsmEdgeView &r_view);
 
 } // namespace slampp
 

@@ -89,6 +89,8 @@ void slampp_hip_solver::Free_Device(bool b_keep_multiply)
 	d_cov.Free(); d_damp_off.Free(); d_timing.Free();
 	d_refine_map.Free(); d_refined.Free();
 	b_damp_valid = false;
+	d_state_cumsum.Free();
+	b_state_cumsum_valid = false;
 	dplan.p_timing = 0;
 	n_uploaded = 0;
 	if(p_sinv) {

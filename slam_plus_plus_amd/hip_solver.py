@@ -12,6 +12,9 @@ same error behaviour (``False`` = not positive definite, ``MemoryError`` = std::
 * ``CLinearSolver_Schur``  (LinearSolver_Schur.h:1423-1935)  ->  :class:`CLinearSolver_Schur_HIP`
 * ``CNonlinearSolver_Lambda::Refresh_Lambda`` (NonlinearSolver_Lambda_Base.h:1634-1688) for one edge set
   ->  :class:`CLambdaAssembly_HIP`
+* the two ends of its iteration -- the edges' ``Calculate_Jacobians_Expectation_Error`` and ``f_Chi_Squared_Error``, the
+  vertices' ``Operator_Plus`` / ``Operator_Minus`` -- on device-resident states  ->  ``CLambdaAssembly_HIP.Linearize_device``,
+  ``.Chi2_device`` and ``State_Plus_device`` of the solver classes
 
 There is no CPU fallback: if the shared library is missing, or there is no GPU, construction raises.
 """
@@ -40,6 +43,9 @@ GRAM_CHUNK_ROWS = 2048     # SLAMPP_HIP_GRAM_CHUNK_ROWS
 # slampp_hip_multiply: block rows with more blocks than MULTIPLY_LONG_ROW are cut into chunks of MULTIPLY_CHUNK
 # (SLAMPP_HIP_MULTIPLY_* in include/slampp_hip.h; the development option "multiply_long_row" lowers the threshold)
 MULTIPLY_LONG_ROW, MULTIPLY_CHUNK = 256, 256
+EDGE_SE2, EDGE_SE3, EDGE_P2C_XYZ = 1, 2, 3             # SLAMPP_HIP_EDGE_*: CEdgePose2D, CEdgePose3D, CEdgeP2C3D
+VERTEX_EUCLIDEAN, VERTEX_SE2, VERTEX_SE3 = 0, 1, 2     # SLAMPP_HIP_VERTEX_*: x + dx, x + dx with the angle clamped, SE(3) (+)
+LINEARIZE_TILE_EDGES = 64   # edges of a workgroup of slampp_hip_linearize_device_async (their outputs leave through one LDS tile)
 
 
 def _hash_array(a: np.ndarray) -> int:
@@ -176,6 +182,9 @@ ABI = {
     "slampp_hip_assembly_destroy": (None, [_P]),
     "slampp_hip_assemble_device_async": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int]),
     "slampp_hip_assemble_sets_device_async": (C.c_int, [C.POINTER(EdgeSetPtrs), C.c_int, C.c_int64, _P, _P, _P, _P, C.c_int]),
+    "slampp_hip_linearize_device_async": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "slampp_hip_state_plus_device_async": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P, _P, C.c_double, _P]),
+    "slampp_hip_chi_squared_device_async": (C.c_int, [_P, _P, _P, _P, _P]),
     "slampp_hip_get_plan": (C.c_int, [_P, C.POINTER(PlanView)]),
     "slampp_hip_plan_create": (C.c_int, [C.POINTER(_P), C.c_int64, _P, _P, _P, C.c_int, C.c_int, C.c_int]),
     "slampp_hip_plan_get": (C.c_int, [_P, C.POINTER(PlanView), C.POINTER(Stats)]),
@@ -776,6 +785,15 @@ class _SolverBase:
         self._check(self._lib.slampp_hip_apply_damping_device_async(self._h, values_ptr, float(f_alpha), int(n_first_vertex),
                                                                     int(n_last_vertex)))
 
+    def State_Plus_device(self, vertex_type: int, first: int, last: int, state_ptr: int, dx_ptr: int, out_ptr: int,
+                          scale: float = 1.0) -> None:
+        """out = state (+) scale dx on block columns [first, last), on the manifold of ``vertex_type`` (VERTEX_*): the
+        reference's Operator_Plus over the vertex pool, ``scale=-1`` its Operator_Minus (slampp_hip_state_plus_device_async).
+        ``out_ptr`` may be ``state_ptr``; block columns outside the range are not written.  Needs the structure only: set it
+        with SymbolicDecomposition_Blocky, or create a CLambdaAssembly_HIP first.  Enqueue-only."""
+        self._check(self._lib.slampp_hip_state_plus_device_async(self._h, int(vertex_type), int(first), int(last), state_ptr or None,
+                                                                 dx_ptr or None, float(scale), out_ptr or None))
+
     def stream(self) -> int:
         return int(self._lib.slampp_hip_stream(self._h) or 0)
 
@@ -1039,6 +1057,22 @@ class CLambdaAssembly_HIP:
         self._solver._check(self._lib.slampp_hip_assemble_device_async(
             self._a, J0_ptr, J1_ptr, sigma_inv_ptr, error_ptr, weight_ptr or None, int(unary_vertex),
             None if uf is None else _ptr(uf), None if ue is None else _ptr(ue), values_ptr, eta_ptr, int(bool(accumulate))))
+
+    def Linearize_device(self, edge_type: int, state_ptr: int, measurement_ptr: int, J0_ptr: int, J1_ptr: int, error_ptr: int,
+                         params_ptr: int = 0) -> None:
+        """Every edge's error and Jacobians from the vertex states, written where Refresh_Lambda_device reads them
+        (slampp_hip_linearize_device_async; the reference's Calculate_Jacobians_Expectation_Error).  ``edge_type``: EDGE_SE2,
+        EDGE_SE3 or EDGE_P2C_XYZ, matching this edge set's dimensions; ``state_ptr``: the states in the layout of eta;
+        ``params_ptr``: five intrinsics per block column (EDGE_P2C_XYZ only).  Enqueue-only."""
+        self._solver._check(self._lib.slampp_hip_linearize_device_async(
+            self._a, int(edge_type), state_ptr or None, measurement_ptr or None, params_ptr or None, J0_ptr or None, J1_ptr or None,
+            error_ptr or None))
+
+    def Chi2_device(self, sigma_inv_ptr: int, error_ptr: int, weight_ptr: int, out_ptr: int) -> None:
+        """*out = sum over the edges of w err^T Sigma^-1 err in a fixed order (slampp_hip_chi_squared_device_async);
+        ``weight_ptr`` 0 = no robust weights.  Enqueue-only."""
+        self._solver._check(self._lib.slampp_hip_chi_squared_device_async(self._a, sigma_inv_ptr or None, error_ptr or None,
+                                                                          weight_ptr or None, out_ptr or None))
 
 
 def Refresh_Lambda_sets_device(assemblies, pointer_sets, values_ptr: int, eta_ptr: int, unary_vertex: int = 0, unary_factor=None,
