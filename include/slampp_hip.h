@@ -804,6 +804,138 @@ int slampp_hip_state_plus_device_async(slampp_hip_solver *p_solver, int n_vertex
 int slampp_hip_chi_squared_device_async(slampp_hip_assembly *p_assembly, const double *p_sigma_inv_dev,
 	const double *p_error_dev, const double *p_weight_dev /* or NULL */, double *p_out_dev);
 
+/* The Levenberg-Marquardt loop decided on the device: accept or reject,
+ * the next alpha and nu, convergence and the budget of extra iterations are decided by kernels on a caller-owned block of
+ * SLAMPP_HIP_LM_SCALARS doubles in device memory, so that a caller enqueues N iterations and waits once.  The rule is the
+ * reference's CLevenbergMarquardt_Baseline (include/slam/NonlinearSolver_Lambda_LM.h:151-223) inside the loop of
+ * CNonlinearSolver_Lambda_LM::Optimize (:915-1115).  Counters and flags are stored as doubles holding integers. */
+#define SLAMPP_HIP_LM_ALPHA        0  /* the damping the next solve uses                                              */
+#define SLAMPP_HIP_LM_NU           1  /* the factor of the next rejected step (m_nu)                                  */
+#define SLAMPP_HIP_LM_LAST_ERROR   2  /* chi^2 at the state (f_last_error)                                            */
+#define SLAMPP_HIP_LM_ERROR        3  /* chi^2 at the trial state of the last decision                                */
+#define SLAMPP_HIP_LM_DX_DX        4  /* dx^T dx of the last solve                                                    */
+#define SLAMPP_HIP_LM_DX_ETA       5  /* dx^T eta of the last solve                                                   */
+#define SLAMPP_HIP_LM_RHO          6  /* the gain ratio of the last decision (0 where none was formed)                */
+#define SLAMPP_HIP_LM_ACCEPTED     7  /* 1: the last decision accepted its step (slampp_hip_lm_commit_device_async copies) */
+#define SLAMPP_HIP_LM_STATUS       8  /* SLAMPP_HIP_LM_STATUS_*                                                       */
+#define SLAMPP_HIP_LM_N_ROUNDS     9  /* decisions entered with status 0                                              */
+#define SLAMPP_HIP_LM_N_ACCEPTED   10
+#define SLAMPP_HIP_LM_N_REJECTED   11
+#define SLAMPP_HIP_LM_ROUNDS_LEFT  12 /* iterations left (n_max_iteration_num - n_iteration)                          */
+#define SLAMPP_HIP_LM_EXTRA_LEFT   13 /* extra iterations still to be granted on rejected steps (fail)                */
+#define SLAMPP_HIP_LM_MIN_DX_NORM  14 /* f_min_dx_norm                                                                */
+#define SLAMPP_HIP_LM_N_RECORDS    15 /* trace records appended (those beyond the capacity were counted and dropped)  */
+#define SLAMPP_HIP_LM_SCALARS      16
+#define SLAMPP_HIP_LM_STATUS_RUNNING     0
+#define SLAMPP_HIP_LM_STATUS_CONVERGED   1  /* |dx| <= f_min_dx_norm: the step was not applied (:1054)                */
+#define SLAMPP_HIP_LM_STATUS_NOT_POSDEF  2  /* the factorization failed (:972)                                        */
+#define SLAMPP_HIP_LM_STATUS_BUDGET      3  /* n_max_iteration_num iterations, and the extra ones granted, are used up */
+/* a trace record: SLAMPP_HIP_LM_TRACE_RECORD doubles per decision entered with status 0 */
+#define SLAMPP_HIP_LM_TRACE_ALPHA       0  /* the alpha the solve used   */
+#define SLAMPP_HIP_LM_TRACE_ERROR       1  /* chi^2 at the trial state   */
+#define SLAMPP_HIP_LM_TRACE_RHO         2
+#define SLAMPP_HIP_LM_TRACE_DX_NORM     3  /* sqrt(dx^T dx)              */
+#define SLAMPP_HIP_LM_TRACE_ACCEPTED    4
+#define SLAMPP_HIP_LM_TRACE_STATUS      5  /* the status after           */
+#define SLAMPP_HIP_LM_TRACE_LAST_ERROR  6  /* LAST_ERROR after           */
+#define SLAMPP_HIP_LM_TRACE_NU          7  /* nu after                   */
+#define SLAMPP_HIP_LM_TRACE_RECORD      8
+#define SLAMPP_HIP_LM_MAX_SETS          8
+
+/* The building blocks; each is enqueue-only on the solver's stream, refuses on the host before anything is enqueued
+ * (SLAMPP_HIP_ERR_INVALID, text under "lm"), uses no atomics, and gives the same bits when called twice.
+ *
+ * edge_errors: the error array of slampp_hip_linearize_device_async, to its bits, without the Jacobians -- all that the
+ * reference's f_Chi_Squared_Error evaluates at a trial state.  The same kernels with the Jacobian stores compiled out.
+ *
+ * apply_damping_scalar: slampp_hip_apply_damping_device_async with the damping f_scale * *p_alpha_dev, *p_alpha_dev read
+ * on the device when the kernel runs (f_scale = -1 takes the same damping back out).
+ *
+ * lm_initial_damping: *p_alpha_out_dev = f_tau * max over the edges of all n_sets (<= SLAMPP_HIP_LM_MAX_SETS) sets of the
+ * largest diagonal entry of w_e J0^T Omega J0 and of w_e J1^T Omega J1 -- f_InitialDamping (:151-199) through
+ * f_Max_VertexHessianDiagValue (BaseTypes_Binary.h:1200-1222): the maximum starts from 0, a NaN does not enter it, the unary
+ * factor is no edge and does not count.  Any sets with rd, d0, d1 <= 8; the Jacobians are those the sets' arrays hold.
+ *
+ * lm_gain: p_lm_dev[DX_DX] = dx^T dx and p_lm_dev[DX_ETA] = dx^T eta over the solver's n_scalars entries in one pass, with
+ * the partition and the summation trees of slampp_hip_dot_device_async (they depend on n alone).  Writes nothing when
+ * p_lm_dev[STATUS] is not 0.
+ *
+ * lm_decide: one decision by one lane.  With STATUS != 0 it clears ACCEPTED and returns.  Otherwise ERROR = the n_parts
+ * chi^2 parts added in index order, N_ROUNDS counts up, and in this order:
+ *   the handle's not-positive-definite flag is set (the one slampp_hip_sync reports; in Schur mode the outer solver's)
+ *                                        -> STATUS = 2, ACCEPTED = 0, RHO = 0;
+ *   sqrt(DX_DX) <= MIN_DX_NORM           -> STATUS = 1, ACCEPTED = 0, RHO = 0  (the step is not applied);
+ *   rho = (LAST_ERROR - ERROR) / (ALPHA * DX_DX + DX_ETA); if(rho > 0), the only test -- a NaN rejects:
+ *     accepted:  t = 2 rho - 1, ALPHA *= max(1 / 3., 1 - t * t * t), NU = 2, LAST_ERROR = ERROR, N_ACCEPTED counts up
+ *                (the cube is two multiplications where the reference calls pow(t, 3): at most an ulp apart);
+ *     rejected:  ALPHA *= NU, NU *= 2, N_REJECTED counts up, and while EXTRA_LEFT > 0 one unit moves from it to ROUNDS_LEFT;
+ *   ROUNDS_LEFT counts down; at 0, STATUS = 3.
+ * Every decision entered with STATUS = 0 writes one record (SLAMPP_HIP_LM_TRACE_*) at index N_RECORDS of p_trace_dev where
+ * p_trace_dev is not NULL and N_RECORDS < n_trace_capacity, and counts N_RECORDS up either way.  Needs an analyzed handle.
+ *
+ * lm_commit: state = trial (n_scalars doubles) where ACCEPTED != 0; otherwise nothing is written, so that a rejected step
+ * leaves the state's bits alone -- the reference's Save_State / Load_State (:1062, 1100) without the round trip through
+ * x (+) dx (-) dx, which is not x to the bit on SE(3).  16 bytes per lane where the two arrays share their alignment. */
+int slampp_hip_edge_errors_device_async(slampp_hip_assembly *p_assembly, int n_edge_type, const double *p_state_dev,
+	const double *p_measurement_dev, const double *p_params_dev, double *p_error_dev);
+int slampp_hip_apply_damping_scalar_device_async(slampp_hip_solver *p_solver, double *p_values_dev, const double *p_alpha_dev,
+	double f_scale, int64_t n_first_vertex, int64_t n_last_vertex);
+int slampp_hip_lm_initial_damping_device_async(const slampp_hip_edge_set *p_sets, int n_sets, double f_tau, double *p_alpha_out_dev);
+int slampp_hip_lm_gain_device_async(slampp_hip_solver *p_solver, const double *p_dx_dev, const double *p_eta_dev, double *p_lm_dev);
+int slampp_hip_lm_decide_device_async(slampp_hip_solver *p_solver, double *p_lm_dev, const double *p_chi_parts_dev, int n_parts,
+	double *p_trace_dev /* or NULL */, int64_t n_trace_capacity);
+int slampp_hip_lm_commit_device_async(slampp_hip_solver *p_solver, const double *p_lm_dev, double *p_state_dev,
+	const double *p_trial_dev);
+
+/* The loop.  A problem names everything an iteration touches; the arrays are the caller's, in device memory but for the
+ * unary factor and error (host, as in slampp_hip_assemble_device_async) and the lists of sets and ranges (host). */
+typedef struct slampp_hip_lm_edge_set {
+	slampp_hip_assembly *p_assembly;
+	int n_edge_type;                               /* SLAMPP_HIP_EDGE_*, fitting the assembly's dimensions */
+	const double *p_measurement_dev, *p_params_dev /* P2C_XYZ only */, *p_sigma_inv_dev, *p_weight_dev /* or NULL */;
+	double *p_J0_dev, *p_J1_dev, *p_error_dev;     /* scratch: written by every iteration */
+} slampp_hip_lm_edge_set;
+typedef struct slampp_hip_lm_vertex_range {
+	int n_vertex_type;                             /* SLAMPP_HIP_VERTEX_* */
+	int64_t n_first_vertex, n_last_vertex;
+} slampp_hip_lm_vertex_range;
+typedef struct slampp_hip_lm_problem {
+	slampp_hip_solver *p_solver;
+	int n_sets;                                    /* 1 to SLAMPP_HIP_LM_MAX_SETS */
+	const slampp_hip_lm_edge_set *p_sets;
+	int n_ranges;                                  /* together the ranges cover [0, n_bcols) exactly once */
+	const slampp_hip_lm_vertex_range *p_ranges;
+	int64_t n_unary_vertex;                        /* -1: none */
+	const double *p_unary_factor, *p_unary_error;  /* host, or NULL */
+	double *p_state_dev, *p_trial_dev;             /* n_scalars each; trial is scratch */
+	double *p_values_dev, *p_eta_dev, *p_dx_dev;   /* scratch: Lambda's packed values, eta and the step */
+	double *p_lm_dev;                              /* SLAMPP_HIP_LM_SCALARS */
+	double *p_chi_parts_dev;                       /* n_sets */
+	double *p_trace_dev;                           /* n_trace_capacity records, or NULL */
+	int64_t n_trace_capacity;
+} slampp_hip_lm_problem;
+/* begin: the scalars of a new loop.  ALPHA = f_tau * the initial damping of a linearization of the start state where
+ * f_tau > 0 (the reference: 1e-3), otherwise f_alpha; NU = 2; LAST_ERROR = chi^2 of the start state; MIN_DX_NORM, ROUNDS_LEFT =
+ * n_max_iterations (STATUS = 3 at once where that is not positive) and EXTRA_LEFT = n_extra_on_reject (the reference: 10);
+ * everything else 0.  The trace starts over.
+ *
+ * iterate: n_rounds times  linearize the state -> assemble -> dx = eta -> damping from ALPHA -> factor_solve -> gain ->
+ * state_plus into trial over every range -> errors at trial -> chi^2 per set -> decide -> commit.  The sequence is fixed:
+ * after a rejected step the unchanged state is linearized again where the reference keeps its Jacobians (DESIGN.md section
+ * 4.10 has the cost).  Once STATUS is not 0 the remaining rounds change nothing the caller can see: state, scalars and trace
+ * keep their bits, the scratch arrays are rewritten with the same system's values.  The caller waits with slampp_hip_sync,
+ * which reports SLAMPP_HIP_NOT_POSDEF as after any factorization.  CNonlinearSolver_Lambda_LM::Optimize(n_max, f_min_dx_norm)
+ * is begin(0, 1e-3, f_min_dx_norm, n_max, 10) and iterate(n_max + 10).
+ *
+ * SLAMPP_HIP_ERR_INVALID (text under "lm"): a null handle or required pointer, an outdated assembly or one of another
+ * solver, no set or more than SLAMPP_HIP_LM_MAX_SETS, an edge type that does not fit its assembly, vertex ranges that do not
+ * cover [0, n_bcols) exactly once or whose types do not fit the block dimensions, state, trial and dx overlapping, a handle
+ * that was not analyzed, n_rounds <= 0.  SLAMPP_HIP_ERR_UNSUPPORTED: a handle over several devices, or one with an all-reduce
+ * callback (landmark shards).  Both sparse and Schur mode are served. */
+int slampp_hip_lm_begin_device_async(const slampp_hip_lm_problem *p_problem, double f_alpha, double f_tau, double f_min_dx_norm,
+	int n_max_iterations, int n_extra_on_reject);
+int slampp_hip_lm_iterate_device_async(const slampp_hip_lm_problem *p_problem, int n_rounds);
+
 /* Multi-GPU BA (new functionality, no reference counterpart -- SURVEY.md section 8e): every rank
  * holds a landmark shard (its own points + all cameras); the partial reduced camera systems
  * [S | rhs] are summed over ranks by this callback (RCCL all-reduce over xGMI) between the Schur

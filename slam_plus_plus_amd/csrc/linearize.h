@@ -9,7 +9,8 @@ namespace slampp {
 enum { linearize_TILE_EDGES = 64 }; // edges of a workgroup: a lane each, their outputs staged in LDS and written as whole lines
 
 // error and Jacobians of every edge of the set (n_edge_type: SLAMPP_HIP_EDGE_*, matching the view's dimensions: the caller
-// checks) into the arrays the assembly reads; p_params only for SLAMPP_HIP_EDGE_P2C_XYZ.  Throws.
+// checks) into the arrays the assembly reads; p_params only for SLAMPP_HIP_EDGE_P2C_XYZ.  p_J0 and p_J1 both null: the
+// errors alone, to the bits of the call that writes all three (edge_errors of the C ABI).  Throws.
 void linearize_enqueue(int n_edge_type, const TAsmEdgeView &r_edges, const double *p_state, const double *p_measurement,
 	const double *p_params, double *p_J0, double *p_J1, double *p_error, hipStream_t stream);
 

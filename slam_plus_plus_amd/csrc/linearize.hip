@@ -43,14 +43,17 @@ __device__ __forceinline__ void store_through_tile(double *p_tile, const double 
 
 // a lane per edge, linearize_TILE_EDGES edges per workgroup.  Nothing an edge computes depends on its neighbours in the tile:
 // a call on the first n edges of a set gives those edges the bits of the call on the whole set.
-template <int n_edge_type>
+// b_jacobians = false: the errors alone (the reference's f_Chi_Squared_Error evaluates no more), by the same arithmetic --
+// the Jacobians are not stored, p_J0 and p_J1 are not read, and what only they need is left to the compiler to drop.
+template <int n_edge_type, bool b_jacobians>
 __global__ void __launch_bounds__(linearize_TILE_EDGES)
 linearize_kernel(int64_t n_edges, const int64_t *__restrict__ p_off0, const int64_t *__restrict__ p_off1,
 	const int64_t *__restrict__ p_vertex0, const double *__restrict__ p_state, const double *__restrict__ p_measurement,
 	const double *__restrict__ p_params, double *__restrict__ p_J0, double *__restrict__ p_J1, double *__restrict__ p_error)
 {
 	typedef TEdgeShape<n_edge_type> S;
-	enum { D0 = S::D0, D1 = S::D1, RD = S::RD, MD = S::MD, N0 = RD * D0, N1 = RD * D1, N_MAX = (N0 > N1)? N0 : N1 };
+	enum { D0 = S::D0, D1 = S::D1, RD = S::RD, MD = S::MD, N0 = RD * D0, N1 = RD * D1,
+		N_MAX = (!b_jacobians)? RD : (N0 > N1)? N0 : N1 };
 	__shared__ double p_tile[linearize_TILE_EDGES * (N_MAX | 1)];
 	const int64_t n_first = int64_t(blockIdx.x) * linearize_TILE_EDGES, e = n_first + threadIdx.x;
 	const int n_here = (n_edges - n_first < linearize_TILE_EDGES)? int(n_edges - n_first) : int(linearize_TILE_EDGES);
@@ -81,8 +84,10 @@ linearize_kernel(int64_t n_edges, const int64_t *__restrict__ p_off0, const int6
 			lin::edge_p2c_xyz(x0, x1, z, k5, J0, J1, err);
 		}
 	}
-	store_through_tile<N0>(p_tile, J0, b_mine, p_J0 + n_first * N0, n_here);
-	store_through_tile<N1>(p_tile, J1, b_mine, p_J1 + n_first * N1, n_here);
+	if(b_jacobians) {
+		store_through_tile<N0>(p_tile, J0, b_mine, p_J0 + n_first * N0, n_here);
+		store_through_tile<N1>(p_tile, J1, b_mine, p_J1 + n_first * N1, n_here);
+	}
 	store_through_tile<RD>(p_tile, err, b_mine, p_error + n_first * RD, n_here);
 }
 
@@ -92,8 +97,13 @@ void linearize_enqueue(int n_edge_type, const TAsmEdgeView &v, const double *p_s
 	const int64_t n_grid = (v.n_edges + linearize_TILE_EDGES - 1) / linearize_TILE_EDGES;
 	if(n_grid < 1 || n_grid > 0x7fffffff)
 		throw std::domain_error("linearize: too many edges");
-#define LAUNCH_LINEARIZE(T) hipLaunchKernelGGL((linearize_kernel<T>), dim3(unsigned(n_grid)), dim3(linearize_TILE_EDGES), 0, stream, \
-	v.n_edges, v.p_state_off0, v.p_state_off1, v.p_vertex0, p_state, p_measurement, p_params, p_J0, p_J1, p_error)
+#define LAUNCH_LINEARIZE(T) do { if(p_J0) hipLaunchKernelGGL((linearize_kernel<T, true>), dim3(unsigned(n_grid)), \
+		dim3(linearize_TILE_EDGES), 0, stream, v.n_edges, v.p_state_off0, v.p_state_off1, v.p_vertex0, p_state, p_measurement, p_params, \
+		p_J0, p_J1, p_error); \
+	else hipLaunchKernelGGL((linearize_kernel<T, false>), dim3(unsigned(n_grid)), dim3(linearize_TILE_EDGES), 0, stream, v.n_edges, \
+		v.p_state_off0, v.p_state_off1, v.p_vertex0, p_state, p_measurement, p_params, p_J0, p_J1, p_error); } while(0)
+	if(!p_J0 != !p_J1)
+		throw std::invalid_argument("linearize: one Jacobian array without the other");
 	switch(n_edge_type) {
 	case SLAMPP_HIP_EDGE_SE2: LAUNCH_LINEARIZE(SLAMPP_HIP_EDGE_SE2); break;
 	case SLAMPP_HIP_EDGE_SE3: LAUNCH_LINEARIZE(SLAMPP_HIP_EDGE_SE3); break;

@@ -270,6 +270,8 @@ struct slampp_hip_solver {
 	slampp::CDevArray<int64_t> d_diag_out_off; // ... and where its block goes in the output
 	slampp::CDevArray<int64_t> d_damp_off; // (offset of the diagonal block's first element, dimension) per block column: apply_damping
 	bool b_damp_valid = false;
+	bool Require_Damping_Offsets(); // uploads d_damp_off after a set_structure (and waits for the copy); false: a block column has no diagonal block.  Throws.
+	slampp::CDevArray<double> d_lm_reduce; // the partial results of the LM loop's reductions (lm.h), allocated at its first call
 	slampp::CDevArray<int64_t> d_state_cumsum; // the block columns' scalar offsets (n_bcols + 1): state_plus
 	bool b_state_cumsum_valid = false;
 	slampp::CDevArray<int> d_flag;

@@ -121,7 +121,7 @@ void slampp_hip_solver::Free_Device(bool b_keep_multiply)
 	d_logdet_tab.Free();
 	std::vector<int64_t>().swap(logdet_tab_host);
 	b_logdet_valid = false;
-	d_reduce.Free(); d_gram.Free(); d_refine_r.Free(); d_mul_x.Free(); d_mul_y.Free(); d_refine_resid.Free();
+	d_reduce.Free(); d_lm_reduce.Free(); d_gram.Free(); d_refine_r.Free(); d_mul_x.Free(); d_mul_y.Free(); d_refine_resid.Free();
 	b_analyzed = false;
 	Factor_Dropped();
 }
@@ -136,7 +136,7 @@ size_t slampp_hip_solver::n_Device_Bytes() const
 		d_panel_pkg.n_Bytes() + d_panel_off.n_Bytes() + d_panel_out_off.n_Bytes() + d_handup.n_Bytes() + d_panel_rest.n_Bytes() + d_bwd_rec.n_Bytes() + d_bwd_off.n_Bytes() + d_panel_upd_slots.n_Bytes() + d_panel_upd_ents.n_Bytes() +
 		d_rhs.n_Bytes() + d_L.n_Bytes() + d_Linv.n_Bytes() + d_w.n_Bytes() + d_cov.n_Bytes() + d_flag.n_Bytes() +
 		d_Z.n_Bytes() + d_diag_zoff.n_Bytes() + d_Zd.n_Bytes() + d_Zd_work.n_Bytes() + sparse_inverse_bytes(p_sinv) + covariance_bytes(p_cov) +
-		(p_schur? schur_device_bytes(p_schur) : 0) + multiply_device_bytes(p_mul) + pattern_outer_device_bytes(p_outer) + d_outer_out.n_Bytes() + d_logdet_tab.n_Bytes() +d_reduce.n_Bytes() + d_refine_r.n_Bytes() +
+		(p_schur? schur_device_bytes(p_schur) : 0) + multiply_device_bytes(p_mul) + pattern_outer_device_bytes(p_outer) + d_outer_out.n_Bytes() + d_logdet_tab.n_Bytes() +d_reduce.n_Bytes() + d_lm_reduce.n_Bytes() + d_refine_r.n_Bytes() +
 		d_mul_x.n_Bytes() + d_mul_y.n_Bytes() + d_refine_resid.n_Bytes() + d_gram.n_Bytes();
 }
 

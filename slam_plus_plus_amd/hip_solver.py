@@ -46,6 +46,13 @@ MULTIPLY_LONG_ROW, MULTIPLY_CHUNK = 256, 256
 EDGE_SE2, EDGE_SE3, EDGE_P2C_XYZ = 1, 2, 3             # SLAMPP_HIP_EDGE_*: CEdgePose2D, CEdgePose3D, CEdgeP2C3D
 VERTEX_EUCLIDEAN, VERTEX_SE2, VERTEX_SE3 = 0, 1, 2     # SLAMPP_HIP_VERTEX_*: x + dx, x + dx with the angle clamped, SE(3) (+)
 LINEARIZE_TILE_EDGES = 64   # edges of a workgroup of slampp_hip_linearize_device_async (their outputs leave through one LDS tile)
+# SLAMPP_HIP_LM_*: the scalars of the device-decided Levenberg-Marquardt loop, its status values and its trace record
+(LM_ALPHA, LM_NU, LM_LAST_ERROR, LM_ERROR, LM_DX_DX, LM_DX_ETA, LM_RHO, LM_ACCEPTED, LM_STATUS, LM_N_ROUNDS, LM_N_ACCEPTED,
+ LM_N_REJECTED, LM_ROUNDS_LEFT, LM_EXTRA_LEFT, LM_MIN_DX_NORM, LM_N_RECORDS, LM_SCALARS) = range(17)
+LM_STATUS_RUNNING, LM_STATUS_CONVERGED, LM_STATUS_NOT_POSDEF, LM_STATUS_BUDGET = range(4)
+(LM_TRACE_ALPHA, LM_TRACE_ERROR, LM_TRACE_RHO, LM_TRACE_DX_NORM, LM_TRACE_ACCEPTED, LM_TRACE_STATUS, LM_TRACE_LAST_ERROR,
+ LM_TRACE_NU, LM_TRACE_RECORD) = range(9)
+LM_MAX_SETS = 8
 
 
 def _hash_array(a: np.ndarray) -> int:
@@ -99,6 +106,27 @@ class ShardView(C.Structure):
 class EdgeSetPtrs(C.Structure):
     _fields_ = [("p_assembly", C.c_void_p), ("p_J0_dev", C.c_void_p), ("p_J1_dev", C.c_void_p), ("p_sigma_inv_dev", C.c_void_p),
                 ("p_error_dev", C.c_void_p), ("p_weight_dev", C.c_void_p)]
+
+
+class LmEdgeSet(C.Structure):
+    """slampp_hip_lm_edge_set"""
+    _fields_ = [("p_assembly", C.c_void_p), ("n_edge_type", C.c_int), ("p_measurement_dev", C.c_void_p), ("p_params_dev", C.c_void_p),
+                ("p_sigma_inv_dev", C.c_void_p), ("p_weight_dev", C.c_void_p), ("p_J0_dev", C.c_void_p), ("p_J1_dev", C.c_void_p),
+                ("p_error_dev", C.c_void_p)]
+
+
+class LmVertexRange(C.Structure):
+    """slampp_hip_lm_vertex_range"""
+    _fields_ = [("n_vertex_type", C.c_int), ("n_first_vertex", C.c_int64), ("n_last_vertex", C.c_int64)]
+
+
+class LmProblem(C.Structure):
+    """slampp_hip_lm_problem"""
+    _fields_ = [("p_solver", C.c_void_p), ("n_sets", C.c_int), ("p_sets", C.POINTER(LmEdgeSet)), ("n_ranges", C.c_int),
+                ("p_ranges", C.POINTER(LmVertexRange)), ("n_unary_vertex", C.c_int64), ("p_unary_factor", C.c_void_p),
+                ("p_unary_error", C.c_void_p), ("p_state_dev", C.c_void_p), ("p_trial_dev", C.c_void_p), ("p_values_dev", C.c_void_p),
+                ("p_eta_dev", C.c_void_p), ("p_dx_dev", C.c_void_p), ("p_lm_dev", C.c_void_p), ("p_chi_parts_dev", C.c_void_p),
+                ("p_trace_dev", C.c_void_p), ("n_trace_capacity", C.c_int64)]
 
 
 class PhaseTime(C.Structure):
@@ -185,6 +213,14 @@ ABI = {
     "slampp_hip_linearize_device_async": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "slampp_hip_state_plus_device_async": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P, _P, C.c_double, _P]),
     "slampp_hip_chi_squared_device_async": (C.c_int, [_P, _P, _P, _P, _P]),
+    "slampp_hip_edge_errors_device_async": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
+    "slampp_hip_apply_damping_scalar_device_async": (C.c_int, [_P, _P, _P, C.c_double, C.c_int64, C.c_int64]),
+    "slampp_hip_lm_initial_damping_device_async": (C.c_int, [C.POINTER(EdgeSetPtrs), C.c_int, C.c_double, _P]),
+    "slampp_hip_lm_gain_device_async": (C.c_int, [_P, _P, _P, _P]),
+    "slampp_hip_lm_decide_device_async": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int64]),
+    "slampp_hip_lm_commit_device_async": (C.c_int, [_P, _P, _P, _P]),
+    "slampp_hip_lm_begin_device_async": (C.c_int, [C.POINTER(LmProblem), C.c_double, C.c_double, C.c_double, C.c_int, C.c_int]),
+    "slampp_hip_lm_iterate_device_async": (C.c_int, [C.POINTER(LmProblem), C.c_int]),
     "slampp_hip_get_plan": (C.c_int, [_P, C.POINTER(PlanView)]),
     "slampp_hip_plan_create": (C.c_int, [C.POINTER(_P), C.c_int64, _P, _P, _P, C.c_int, C.c_int, C.c_int]),
     "slampp_hip_plan_get": (C.c_int, [_P, C.POINTER(PlanView), C.POINTER(Stats)]),
@@ -197,7 +233,7 @@ _FACTOR_CHANGING = frozenset(
     ["slampp_hip_free_memory", "slampp_hip_set_structure", "slampp_hip_analyze", "slampp_hip_factor_solve",
      "slampp_hip_factor_solve_device", "slampp_hip_factor_solve_device_async", "slampp_hip_factor_solve_batch_device_async",
      "slampp_hip_factorize", "slampp_hip_solve_marginal_poses", "slampp_hip_solve_marginal_poses_device_async",
-     "slampp_hip_logdet", "slampp_hip_logdet_device_async"] +
+     "slampp_hip_logdet", "slampp_hip_logdet_device_async", "slampp_hip_lm_iterate_device_async"] +
     [n for n in ABI if "marginal" in n and "poses" not in n])
 
 
@@ -1090,3 +1126,112 @@ def Refresh_Lambda_sets_device(assemblies, pointer_sets, values_ptr: int, eta_pt
     solver._check(solver._lib.slampp_hip_assemble_sets_device_async(
         sets, len(assemblies), int(unary_vertex), None if uf is None else _ptr(uf), None if ue is None else _ptr(ue),
         values_ptr, eta_ptr, int(bool(accumulate))))
+
+
+_EDGE_DIMS = {EDGE_SE2: (3, 3, 3, 3), EDGE_SE3: (6, 6, 6, 6), EDGE_P2C_XYZ: (6, 3, 2, 2)}   # d0, d1, rd, measurement
+
+
+class CLevenbergMarquardt_HIP:
+    """The reference's ``CNonlinearSolver_Lambda_LM`` with ``CLevenbergMarquardt_Baseline`` (NonlinearSolver_Lambda_LM.h:151-223,
+    915-1115) decided on the device: ``Begin`` initialises the scalars, ``Iterate(n)`` enqueues n rounds of linearize ->
+    assemble -> damp -> factor_solve -> gain -> plus -> errors -> chi^2 -> decide -> commit, and nothing is waited for until
+    ``Sync`` (slampp_hip_lm_begin_device_async, slampp_hip_lm_iterate_device_async).
+
+    ``edge_sets``: a list of dicts with ``assembly`` (a CLambdaAssembly_HIP of ``solver``), ``edge_type`` (EDGE_*),
+    ``measurement`` [E, 3 | 6 | 2], ``sigma_inv`` [E, rd, rd] (every matrix column-major, as the assembly reads them), and
+    optionally ``params`` (five intrinsics per block column, EDGE_P2C_XYZ) and ``weight`` [E]; arrays or CUDA tensors.
+    ``lam``: Lambda's block structure, as CLambdaAssembly_HIP takes it.
+    ``vertex_ranges``: (VERTEX_*, first, last) triples covering every block column once.  ``unary``: (vertex, factor, error)
+    with host arrays (error may be None), or None.  The object owns the state (``self.state``, a CUDA tensor of n_scalars
+    doubles, a copy of ``state``) and every scratch array; memory comes from torch."""
+
+    def __init__(self, solver: _SolverBase, lam, edge_sets, vertex_ranges, state, unary=None, trace_capacity: int = 256):
+        import torch
+        self._torch, self._solver, self._lib = torch, solver, solver._lib
+        if not solver._analyzed or solver._structure_key != solver._key(lam):
+            solver.SymbolicDecomposition_Blocky(lam)
+        stats = Stats()
+        solver._check(self._lib.slampp_hip_get_stats(solver._h, C.byref(stats)))
+        n = int(stats.n_scalars)
+        dev = torch.device("cuda", solver._device)
+
+        def tensor(a):
+            if a is None:
+                return None
+            if isinstance(a, torch.Tensor):
+                return a.to(device=dev, dtype=torch.float64).contiguous()
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+
+        def scratch(k):
+            return torch.zeros(max(int(k), 1), dtype=torch.float64, device=dev)
+
+        def ptr(t):
+            return None if t is None else t.data_ptr()
+        self.state = tensor(state).clone()
+        if self.state.numel() != n:
+            raise ValueError("state must hold n_scalars doubles")
+        self._keep = []                                   # the tensors and handles the problem points at
+        self._sets = (LmEdgeSet * max(len(edge_sets), 1))()
+        for i, s in enumerate(edge_sets[:LM_MAX_SETS]):
+            d0, d1, rd, md = _EDGE_DIMS.get(int(s["edge_type"]), (8, 8, 8, 8))
+            z, sigma = tensor(s["measurement"]), tensor(s["sigma_inv"])
+            e = z.numel() // md
+            params, weight = tensor(s.get("params")), tensor(s.get("weight"))
+            J0, J1, err = scratch(e * rd * d0), scratch(e * rd * d1), scratch(e * rd)
+            self._keep += [s["assembly"], z, sigma, params, weight, J0, J1, err]
+            t = self._sets[i]
+            t.p_assembly, t.n_edge_type = s["assembly"]._a, int(s["edge_type"])
+            t.p_measurement_dev, t.p_params_dev, t.p_sigma_inv_dev, t.p_weight_dev = ptr(z), ptr(params), ptr(sigma), ptr(weight)
+            t.p_J0_dev, t.p_J1_dev, t.p_error_dev = ptr(J0), ptr(J1), ptr(err)
+        self._ranges = (LmVertexRange * max(len(vertex_ranges), 1))()
+        for i, (kind, first, last) in enumerate(vertex_ranges):
+            self._ranges[i].n_vertex_type, self._ranges[i].n_first_vertex, self._ranges[i].n_last_vertex = int(kind), int(first), int(last)
+        self.trial, self.eta, self.dx = scratch(n), scratch(n), scratch(n)
+        self.values = scratch(lam.values.shape[0])
+        self.scalars_dev, self.chi_parts = scratch(LM_SCALARS), scratch(LM_MAX_SETS)
+        self.trace_capacity = int(trace_capacity)
+        self.trace_dev = scratch(self.trace_capacity * LM_TRACE_RECORD)
+        p = self._problem = LmProblem()
+        p.p_solver = solver._h
+        p.n_sets, p.p_sets = len(edge_sets), self._sets
+        p.n_ranges, p.p_ranges = len(vertex_ranges), self._ranges
+        p.n_unary_vertex = -1
+        if unary is not None:
+            vertex, factor, error = unary
+            self._unary = (np.ascontiguousarray(factor, dtype=np.float64),
+                           None if error is None else np.ascontiguousarray(error, dtype=np.float64))
+            p.n_unary_vertex, p.p_unary_factor = int(vertex), self._unary[0].ctypes.data
+            p.p_unary_error = None if error is None else self._unary[1].ctypes.data
+        p.p_state_dev, p.p_trial_dev, p.p_values_dev = self.state.data_ptr(), self.trial.data_ptr(), self.values.data_ptr()
+        p.p_eta_dev, p.p_dx_dev, p.p_lm_dev = self.eta.data_ptr(), self.dx.data_ptr(), self.scalars_dev.data_ptr()
+        p.p_chi_parts_dev, p.p_trace_dev, p.n_trace_capacity = self.chi_parts.data_ptr(), self.trace_dev.data_ptr(), self.trace_capacity
+        torch.cuda.synchronize(dev)                       # (torch filled the arrays on its own stream)
+
+    def Begin(self, f_alpha: float = 0.0, f_tau: float = 1e-3, f_min_dx_norm: float = 0.0, n_max_iterations: int = 1 << 30,
+              n_extra_on_reject: int = 10) -> None:
+        """The scalars of a new loop from ``self.state``: alpha = f_tau max diag of the edges' Hessians where f_tau > 0,
+        else f_alpha; nu = 2; chi^2 of the state.  Enqueue-only."""
+        self._solver._check(self._lib.slampp_hip_lm_begin_device_async(
+            C.byref(self._problem), float(f_alpha), float(f_tau), float(f_min_dx_norm), int(n_max_iterations), int(n_extra_on_reject)))
+
+    def Iterate(self, n_rounds: int) -> None:
+        """Enqueues n_rounds rounds; those after the status left 0 change nothing the caller can see.  Enqueue-only."""
+        self._solver._check(self._lib.slampp_hip_lm_iterate_device_async(C.byref(self._problem), int(n_rounds)))
+
+    def Sync(self):
+        """Waits once (slampp_hip_sync) and returns (positive definite, scalars [LM_SCALARS], trace [records, LM_TRACE_RECORD])
+        as numpy arrays; False is slampp_hip_sync's SLAMPP_HIP_NOT_POSDEF, and the scalars' status says the same."""
+        ok = self._solver.sync()
+        scalars = self.scalars_dev.cpu().numpy().copy()
+        n = min(int(scalars[LM_N_RECORDS]), self.trace_capacity)
+        trace = self.trace_dev[:n * LM_TRACE_RECORD].cpu().numpy().reshape(n, LM_TRACE_RECORD).copy()
+        return ok, scalars, trace
+
+    def Optimize(self, n_max_iterations: int = 5, f_min_dx_norm: float = 0.01, f_tau: float = 1e-3, f_alpha: float = 0.0,
+                 n_extra_on_reject: int = 10):
+        """CNonlinearSolver_Lambda_LM::Optimize(n_max_iteration_num, f_min_dx_norm): every round it can take is enqueued at
+        once, then one wait.  Returns what ``Sync`` returns."""
+        self.Begin(f_alpha, f_tau, f_min_dx_norm, n_max_iterations, n_extra_on_reject)
+        if n_max_iterations > 0:
+            self.Iterate(n_max_iterations + max(int(n_extra_on_reject), 0))
+        return self.Sync()
