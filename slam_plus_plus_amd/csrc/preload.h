@@ -14,6 +14,7 @@
 namespace slampp {
 
 void preload_simt_kernel(hipStream_t stream);
+void preload_simt_factor_ahead(hipStream_t stream);
 void preload_panel_kernel(hipStream_t stream);
 void preload_sparse_kernels(hipStream_t stream);
 void preload_subtree_kernel(hipStream_t stream);
@@ -26,6 +27,7 @@ void preload_schur_tiles(hipStream_t stream);
 inline void preload_device_code(hipStream_t stream)
 {
 	preload_simt_kernel(stream);
+	preload_simt_factor_ahead(stream);
 	preload_panel_kernel(stream);
 	preload_sparse_kernels(stream);
 	preload_subtree_kernel(stream);

@@ -27,115 +27,7 @@
 
 namespace slampp {
 
-__device__ __forceinline__ double simt_rsqrt(double x)
-{
-	double y = __builtin_amdgcn_rsq(x);
-	const double h = 0.5 * x;
-	y = y * (1.5 - h * y * y);
-	y = y * (1.5 - h * y * y);
-	return y;
-}
-
-// D consecutive doubles at p (16-byte aligned when D is even: block offsets are multiples of D * D)
-template <int D>
-__device__ __forceinline__ void load_column(const double *__restrict__ p, double (&v)[D])
-{
-	if(D % 2 == 0) {
-		const double2 *p2 = reinterpret_cast<const double2*>(p);
-		#pragma unroll
-		for(int i = 0; i < D / 2; ++ i) {
-			const double2 t = p2[i];
-			v[2 * i] = t.x;
-			v[2 * i + 1] = t.y;
-		}
-	} else {
-		#pragma unroll
-		for(int i = 0; i < D; ++ i)
-			v[i] = p[i];
-	}
-}
-
-template <int D>
-__device__ __forceinline__ void load_block(const double *__restrict__ p, double (&v)[D][D]) // v[c][r] = p[r + c D]
-{
-	if(D % 2 == 0) {
-		const double2 *p2 = reinterpret_cast<const double2*>(p);
-		#pragma unroll
-		for(int i = 0; i < D * D / 2; ++ i) {
-			const double2 t = p2[i];
-			v[(2 * i) / D][(2 * i) % D] = t.x;
-			v[(2 * i + 1) / D][(2 * i + 1) % D] = t.y;
-		}
-	} else {
-		#pragma unroll
-		for(int i = 0; i < D * D; ++ i)
-			v[i / D][i % D] = p[i];
-	}
-}
-
-// the lower triangle of a block: v[q][r] = p[r + q D] for r >= q (even D: 16-byte loads; the element above the diagonal that
-// shares one with the diagonal element of an odd column comes along)
-template <int D>
-__device__ __forceinline__ void load_lower(const double *__restrict__ p, double (&v)[D][D])
-{
-	#pragma unroll
-	for(int q = 0; q < D; ++ q) {
-		if(D % 2 == 0) {
-			#pragma unroll
-			for(int r = q & ~1; r < D; r += 2) {
-				const double2 t = *reinterpret_cast<const double2*>(p + r + q * D);
-				v[q][r] = t.x;
-				v[q][r + 1] = t.y;
-			}
-		} else {
-			#pragma unroll
-			for(int r = q; r < D; ++ r)
-				v[q][r] = p[r + q * D];
-		}
-	}
-}
-
-template <int D>
-__device__ __forceinline__ void store_block(double *p, const double (&m)[D][D]) // m[r][q] -> p[r + q D]
-{
-	if(D % 2 == 0) {
-		double2 *p2 = reinterpret_cast<double2*>(p);
-		#pragma unroll
-		for(int q = 0; q < D; ++ q) {
-			#pragma unroll
-			for(int r = 0; r < D; r += 2)
-				p2[(r + q * D) / 2] = double2{m[r][q], m[r + 1][q]};
-		}
-	} else {
-		#pragma unroll
-		for(int q = 0; q < D; ++ q) {
-			#pragma unroll
-			for(int r = 0; r < D; ++ r)
-				p[r + q * D] = m[r][q];
-		}
-	}
-}
-
-// rows [r0, r0 + D / 2) of a block: v[c][i] = p[r0 + i + c D] (two lanes per task: each takes half the rows)
-template <int D>
-__device__ __forceinline__ void load_half_rows(const double *__restrict__ p, int r0, double (&v)[D][D / 2])
-{
-	#pragma unroll
-	for(int c = 0; c < D; ++ c) {
-		#pragma unroll
-		for(int i = 0; i < D / 2; ++ i)
-			v[c][i] = p[r0 + i + c * D];
-	}
-}
-
-// position of the next column's header in the program, given the position right behind this column's touch list
-__device__ __forceinline__ int pc_next_column(const int32_t *P, int pc, int nb, int nr)
-{
-	pc += 2 * nr;
-	for(int kb = 1; kb < nb; ++ kb)
-		pc += 1 + 2 * P[pc];
-	return pc;
-}
+#include "simt_device.inl"
 
 template <int D, int W, int LPT, bool b_linv> // W = tasks per wave, LPT = lanes per task (1, or 2 for even D: the lanes of a pair compute the
 // diagonal block of a column both, and each half the rows of the blocks below it -- no traffic between them); b_linv: inv(L_jj)
@@ -405,7 +297,8 @@ factor_simt_kernel(const TSimtChunk *__restrict__ chunks, const int32_t *__restr
 }
 
 bool launch_factor_simt(const TSimtChunk *chunks, int n_chunks, int n_width, int n_lds_bytes, const int32_t *prog, const int64_t *tab, int n_dim,
-	const double *A, double *L, double *Linv, const double *b, double *w, int *p_flag, hipStream_t stream, long long *p_timing, const TBatch &t_batch)
+	const double *A, double *L, double *Linv, const double *b, double *w, int *p_flag, hipStream_t stream, long long *p_timing, const TBatch &t_batch,
+	int n_ahead_waves)
 {
 	if(n_chunks <= 0)
 		return true;
@@ -422,6 +315,19 @@ bool launch_factor_simt(const TSimtChunk *chunks, int n_chunks, int n_width, int
 	// waves on 1 024 SIMDs, 120 -> 100 us) and costs where they are full (a million poses: 716 -> 779 us).
 	const int n_pairs_env = dev_knob("SLAMPP_HIP_DEV_SIMT_PAIRS", -1); // development aid (plan.h)
 	const bool b_pairs = (n_pairs_env >= 0)? n_pairs_env != 0 : n_chunks <= 2048;
+	// The fetch-ahead form (simt_factor_ahead.hip) runs at one wave a SIMD: it is for paired launches that fit the chip in one
+	// round at that occupancy and so could not hide a wave's waits behind other waves anyway (C3's leaves: 592 waves).  Larger
+	// launches -- a batch of eight, a million poses -- keep the kernel above, where the waits are hidden and registers would cost
+	// residency.  Development aid (plan.h): 0 = never, 1 = wherever the form exists; the results are the same bits.
+	const int n_ahead_env = dev_knob("SLAMPP_HIP_DEV_SIMT_FACTOR_AHEAD", -1);
+	const int n_lpt = (b_pairs && n_dim % 2 == 0 && (n_width == 16 || n_width == 32))? 2 : 1;
+	const bool b_ahead = n_lpt == 2 && factor_simt_ahead_exists(n_dim, n_width) &&
+		((n_ahead_env >= 0)? n_ahead_env != 0 : int64_t(n_chunks) * std::max<int64_t>(t_batch.n, 1) <= n_ahead_waves);
+	if(p_timing) // (development aid SLAMPP_HIP_STAGE_TIMING: which form the launch takes, for the tests)
+		fprintf(stderr, "stage_timing lane-per-task factor launch: %d chunks, width %d, block size %d, %d members, LPT %d, %s\n", n_chunks, n_width, n_dim,
+			int(t_batch.n), n_lpt, b_ahead? "fetch ahead" : "fetch by column");
+	if(b_ahead)
+		return launch_factor_simt_ahead(chunks, n_chunks, n_width, n_lds_bytes, prog, tab, n_dim, A, L, Linv, b, w, p_flag, stream, p_timing, t_batch);
 	switch(n_dim) {
 	case 3:
 		SIMT_WIDTHS(3);

@@ -224,6 +224,7 @@ struct slampp_hip_solver {
 	slampp::CDevArray<slampp::TSimtChunk> d_simt_bwd_chunks;
 	slampp::CDevArray<int32_t> d_simt_bwd_prog;
 	slampp::CDevArray<int64_t> d_simt_bwd_tab;
+	std::vector<int32_t> simt_factor_ahead_waves; // per lane-per-task stage: factor_simt_ahead_waves() of its LDS request, asked at analysis: factor launches of at most that many waves fetch a column ahead
 	std::vector<int32_t> simt_bwd_ahead_waves; // per lane-per-task stage: backward_simt_ahead_waves() of its LDS request, asked at analysis (as n_lds_limit): launches of at most that many waves fetch a column ahead
 	// inv(L_jj) of the columns the lane-per-task kernel factors is not on the solve's path any more (its backward kernel solves with
 	// L_jj^T): stored only once something has asked for it (another right-hand side, covariances) -- from then on always
@@ -246,6 +247,7 @@ struct slampp_hip_solver {
 	                       // single separator columns whose operands other waves wrote: no gain there, measured)
 	void Upload_Simt(const slampp::SparseRecords &r_rec); // throws; what build_simt_tables() made (sparse_records.h)
 	void Report_Simt_Backward(const slampp::SparseRecords &r_rec) const; // development print (SLAMPP_HIP_PLAN_TIMING)
+	void Report_Simt_Factor(const slampp::SparseRecords &r_rec) const; // development print (SLAMPP_HIP_PLAN_TIMING)
 	// dense top of the sparse path (plan.h): assembled Schur complement + dense factor workspaces
 	slampp::CDevArray<slampp::TDenseBlk> d_dense_blks;
 	slampp::CDevArray<int64_t> d_dense_blk_loff; // where each of those blocks lives in the factor's block layout (slampp_hip_factorize)

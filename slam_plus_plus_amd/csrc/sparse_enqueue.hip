@@ -92,7 +92,8 @@ void slampp_hip_solver::Enqueue_Sparse(const double *p_values_dev, double *p_rhs
 				const int n_chunks = lists.simt_chunk_ptr[s + 1] - lists.simt_chunk_ptr[s], n_rest = lists.simt_rest_ptr[s + 1] - lists.simt_rest_ptr[s];
 				const bool b_store_linv = b_leaf_linv_wanted || !b_simt_backward_wanted; // (the wave-per-task backward kernel reads the inverses)
 				launch_factor_simt(d_simt_chunks.p() + lists.simt_chunk_ptr[s], n_chunks, n_simt_width, lists.simt_lds_bytes[s], d_simt_prog.p(), d_simt_tab.p(), P.max_dim,
-					p_values_dev, d_L.p(), b_store_linv? d_Linv.p() : 0, p_rhs_dev, d_w.p(), p_flag, stream, dplan.p_timing, t_batch);
+					p_values_dev, d_L.p(), b_store_linv? d_Linv.p() : 0, p_rhs_dev, d_w.p(), p_flag, stream, dplan.p_timing, t_batch,
+					(size_t(s) < simt_factor_ahead_waves.size())? simt_factor_ahead_waves[size_t(s)] : 0);
 				b_leaf_linv_valid = b_leaf_linv_valid && b_store_linv;
 				if(n_rest > 0) {
 					TDevPlan t_rest = dplan;

@@ -277,7 +277,18 @@ bool launch_factor_simt(const TSimtChunk *chunks, int n_chunks, int n_width /* t
 	int n_lds_bytes /* the largest table of the chunks: fields x width x 8 */,
 	const int32_t *prog, const int64_t *tab, int n_dim,
 	const double *A, double *L, double *Linv /* null: inv(L_jj) is not stored */, const double *b, double *w, int *p_flag, hipStream_t stream,
-	long long *p_timing = 0 /* development aid, as TDevPlan::p_timing */, const TBatch &t_batch = t_No_Batch());
+	long long *p_timing = 0 /* development aid, as TDevPlan::p_timing */, const TBatch &t_batch = t_No_Batch(),
+	int n_ahead_waves = 0 /* factor_simt_ahead_waves() of the stage, asked at analysis */);
+// The same kernel for launches that fit the chip in one round at one wave a SIMD (simt_factor_ahead.hip: factor_simt_kernel_ahead):
+// what a column reads of Lambda and b -- the diagonal block, b_j, the first SIMT_FACTOR_AHEAD blocks below the diagonal -- is
+// requested a column ahead; same arguments, same bits.  Block size 6, two lanes per task (widths 16 and 32) only:
+// launch_factor_simt() decides, these answer false / 0 where the form does not exist.
+enum { SIMT_FACTOR_AHEAD = 2 };
+bool factor_simt_ahead_exists(int n_dim, int n_width);
+bool launch_factor_simt_ahead(const TSimtChunk *chunks, int n_chunks, int n_width, int n_lds_bytes, const int32_t *prog, const int64_t *tab, int n_dim,
+	const double *A, double *L, double *Linv, const double *b, double *w, int *p_flag, hipStream_t stream, long long *p_timing, const TBatch &t_batch);
+// waves (= workgroups) of that form the device holds at once with this LDS request (as backward_simt_ahead_waves())
+int factor_simt_ahead_waves(int n_dim, int n_width, int n_lds_bytes);
 // backward substitution of the same tasks, a lane per task (chunk programs: n_cols, number of sub-diagonal blocks, nb per
 // column; tables: per column offset of its first factor block, scalar offsets in the workspace and in the caller's vector,
 // then the workspace offset of every sub-diagonal block's row): x_j from L_jj^T directly, no inverse

@@ -434,6 +434,61 @@ void slampp_hip_solver::Report_Simt_Backward(const SparseRecords &r_rec) const
 	}
 }
 
+// development print (SLAMPP_HIP_PLAN_TIMING): what the column loop of the lane-per-task factor kernels meets, per stage, counted in tasks
+// (the spare lanes of a chunk repeat its last task: not counted).  A block below the diagonal either has a source in Lambda or is
+// fill-in (enc < 0 in the task's table: tasks of one shape may differ in it)
+void slampp_hip_solver::Report_Simt_Factor(const SparseRecords &r_rec) const
+{
+	enum { N_MAX = 16 }; // (the last bin collects everything beyond)
+	for(size_t s = 0; s + 1 < lists.simt_chunk_ptr.size(); ++ s) {
+		long long n_by_cols[N_MAX + 1] = {0}, n_by_blocks[N_MAX + 1] = {0}, n_by_sources[N_MAX + 1] = {0}, n_by_fill[N_MAX + 1] = {0}, n_held_fill = 0, n_tasks = 0;
+		int n_spare_chunks = 0;
+		for(int32_t c = lists.simt_chunk_ptr[s]; c < lists.simt_chunk_ptr[s + 1]; ++ c) {
+			const TSimtChunk &ch = r_rec.simt_chunks[size_t(c)];
+			const int32_t *P = &r_rec.simt_prog[size_t(ch.prog_off)]; // n_cols, n_blocks, n_ops, n_y, then the columns
+			const int64_t *T = &r_rec.simt_tab[size_t(ch.tab_off)]; // [field][width]
+			const int n_cols = P[0];
+			n_tasks += ch.n_tasks;
+			n_spare_chunks += ch.n_tasks < n_simt_width;
+			n_by_cols[std::min(n_cols, int(N_MAX))] += ch.n_tasks;
+			for(int i = 0, pc = 4, n_blk0 = 0; i < n_cols; ++ i) {
+				const int nb = P[pc], nr = P[pc + 1], n_touch = P[pc + 2];
+				pc += 3 + n_touch + 2 * nr;
+				for(int kb = 1; kb < nb; ++ kb)
+					pc += 1 + 2 * P[pc];
+				n_by_blocks[std::min(nb - 1, int(N_MAX))] += ch.n_tasks;
+				for(int t = 0; t < ch.n_tasks; ++ t) {
+					int n_sources = 0, n_fill = 0;
+					for(int kb = 1; kb < nb; ++ kb) {
+						const bool b_fill = T[size_t(4 * n_cols + n_blk0 + kb) * size_t(n_simt_width) + size_t(t)] < 0;
+						(b_fill? n_fill : n_sources) ++;
+						n_held_fill += b_fill && kb <= int(SIMT_FACTOR_AHEAD);
+					}
+					n_by_sources[std::min(n_sources, int(N_MAX))] ++;
+					n_by_fill[std::min(n_fill, int(N_MAX))] ++;
+				}
+				n_blk0 += nb;
+			}
+		}
+		std::string s_cols, s_blocks, s_sources, s_fill;
+		for(int i = 0; i <= N_MAX; ++ i) {
+			if(n_by_cols[i])
+				s_cols += " " + std::to_string(i) + ":" + std::to_string(n_by_cols[i]);
+			if(n_by_blocks[i])
+				s_blocks += " " + std::to_string(i) + ":" + std::to_string(n_by_blocks[i]);
+			if(n_by_sources[i])
+				s_sources += " " + std::to_string(i) + ":" + std::to_string(n_by_sources[i]);
+			if(n_by_fill[i])
+				s_fill += " " + std::to_string(i) + ":" + std::to_string(n_by_fill[i]);
+		}
+		fprintf(stderr, "[setup] stage %zu factor lanes: %lld tasks in %d chunks of width %d, %d chunks with spare lanes, fetch ahead holds %d blocks, one round holds %d waves; "
+			"tasks by columns:%s; columns by sub-diagonal blocks:%s; columns by sub-diagonal blocks with a source in Lambda:%s; columns by fill-in blocks:%s; "
+			"fill-in blocks among the blocks held: %lld\n", s, n_tasks, lists.simt_chunk_ptr[s + 1] - lists.simt_chunk_ptr[s], n_simt_width, n_spare_chunks,
+			int(SIMT_FACTOR_AHEAD), (s < simt_factor_ahead_waves.size())? simt_factor_ahead_waves[s] : 0, s_cols.c_str(), s_blocks.c_str(), s_sources.c_str(),
+			s_fill.c_str(), n_held_fill);
+	}
+}
+
 // the lane-per-task tables build_simt_tables() made
 void slampp_hip_solver::Upload_Simt(const SparseRecords &r_rec)
 {
@@ -451,8 +506,12 @@ void slampp_hip_solver::Upload_Simt(const SparseRecords &r_rec)
 	simt_bwd_ahead_waves.clear();
 	for(size_t s = 0; s < lists.simt_bwd_lds_bytes.size(); ++ s)
 		simt_bwd_ahead_waves.push_back(backward_simt_ahead_waves(P.max_dim, n_simt_width, lists.simt_bwd_lds_bytes[s]));
+	simt_factor_ahead_waves.clear();
+	for(size_t s = 0; s < lists.simt_lds_bytes.size(); ++ s)
+		simt_factor_ahead_waves.push_back(factor_simt_ahead_waves(P.max_dim, n_simt_width, lists.simt_lds_bytes[s]));
 	if(getenv("SLAMPP_HIP_PLAN_TIMING")) {
 		Report_Simt_Backward(r_rec);
+		Report_Simt_Factor(r_rec);
 		for(size_t s = 0; s + 1 < lists.simt_chunk_ptr.size(); ++ s) {
 			fprintf(stderr, "[setup] stage %zu: %d tasks -> %d chunks of 64 lanes, %d tasks left to the wave-per-task kernel\n", s,
 				P.stage_ptr[s + 1] - P.stage_ptr[s], lists.simt_chunk_ptr[s + 1] - lists.simt_chunk_ptr[s], lists.simt_rest_ptr[s + 1] - lists.simt_rest_ptr[s]);
