@@ -9,6 +9,7 @@
 #include <unistd.h>
 #include <pthread.h>
 #include "capi_util.h"
+#include "host_threads.h"
 
 #include <algorithm>
 #include <atomic>
@@ -461,15 +462,14 @@ int slampp_hip_set_structure(slampp_hip_solver *p_solver, int64_t n_bcols, const
 		// (the pointer array is checked before anything is read through it)
 		if(p_bcol_ptr[n_bcols] < 0)
 			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "set_structure: malformed cumsum / pointer arrays");
-		// the copy of the block rows and the check of every block: on a few threads from 65 536 block columns on (round 6: one
+		// the copy of the block rows and the check of every block: on four threads from 65 536 block columns on, a thread per 16 384 below that (round 6: one
 		// thread took 5.6 ms at the Venice-like C4 and 8.2 ms at C5 -- a sixth of those analyses)
 		const int64_t n_blocks_all = p_bcol_ptr[n_bcols];
 		s.brow.resize(size_t(n_blocks_all));
-		const int n_check_threads = (n_bcols >= 65536)? 4 : 1;
+		const int n_check_threads = host_thread_count(n_bcols, 16384, 4);
 		std::vector<int64_t> values_of(size_t(n_check_threads), 0);
 		std::vector<int> error_of(size_t(n_check_threads), 0); // 1: malformed arrays, 2: a block outside the upper triangle
-		auto Check = [&](int t) {
-			const int64_t c0 = n_bcols * t / n_check_threads, c1 = n_bcols * (t + 1) / n_check_threads;
+		for_ranges(0, n_bcols, n_check_threads, [&](int t, int64_t c0, int64_t c1) {
 			int64_t n_sum = 0;
 			for(int64_t c = c0; c < c1; ++ c) {
 				const int64_t w = s.cumsum[c + 1] - s.cumsum[c], k0 = s.bcol_ptr[c], k1 = s.bcol_ptr[c + 1];
@@ -488,15 +488,7 @@ int slampp_hip_set_structure(slampp_hip_solver *p_solver, int64_t n_bcols, const
 				}
 			}
 			values_of[size_t(t)] = n_sum;
-		};
-		{
-			std::vector<std::thread> threads;
-			for(int t = 1; t < n_check_threads; ++ t)
-				threads.emplace_back(Check, t);
-			Check(0);
-			for(size_t t = 0; t < threads.size(); ++ t)
-				threads[t].join();
-		}
+		});
 		int64_t n_values = 0;
 		for(int t = 0; t < n_check_threads; ++ t) {
 			if(error_of[size_t(t)] == 1)
@@ -591,7 +583,7 @@ int slampp_hip_analyze(slampp_hip_solver *p_solver, int n_mode, int64_t n_matrix
 		// pinned staging for Lambda's values -- 10 ms of page faults and registration at C3's 58 MB, more at C4's 336 MB --
 		// comes up on a thread of its own while this one orders and analyzes
 		std::exception_ptr p_staging_error;
-		struct TJoin { std::thread t; ~TJoin() { if(t.joinable()) t.join(); } } t_staging_thread;
+		CJoinedThread t_staging_thread;
 		// (a thread only where the staging is worth one: below 8 MB of values it is pinned on this thread, by whoever asks for it)
 		if(s.n_staging_ahead && s.group_devices.empty() && s.n_values >= (int64_t(1) << 20) && !dev_knob_set("SLAMPP_HIP_DEV_NO_STAGING_AHEAD")) { // (the variable: a development aid, plan.h)
 			t_staging_thread.t = std::thread([&s, &p_staging_error]() {

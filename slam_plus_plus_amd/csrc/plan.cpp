@@ -1,15 +1,14 @@
 // plan.cpp -- ordering + symbolic factorization + schedule, see plan.h
 #include "plan.h"
+#include "host_threads.h"
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <thread>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
-#include <mutex>
 #include <numeric>
 
 namespace slampp {
@@ -118,9 +117,12 @@ private:
 	void Order_Both(size_t b, size_t n_lower, size_t n_upper, int n_depth)
 	{
 		if(n_depth < parallel_max_depth && std::min(n_lower, n_upper) >= parallel_min_size) {
-			std::thread other([&]() { Order(b + n_lower, b + n_lower + n_upper, n_depth + 1); });
-			Order(b, b + n_lower, n_depth + 1);
-			other.join();
+			run_on_threads(2, [&](int n_part) {
+				if(n_part)
+					Order(b + n_lower, b + n_lower + n_upper, n_depth + 1);
+				else
+					Order(b, b + n_lower, n_depth + 1);
+			});
 		} else {
 			Order(b, b + n_lower, n_depth + 1);
 			Order(b + n_lower, b + n_lower + n_upper, n_depth + 1);
@@ -1224,36 +1226,6 @@ private:
 		return m_opt.natural_order? std::make_pair(0, 0) : std::make_pair(r_k.n_balance, r_k.n_bank);
 	}
 
-	template <class CJob>
-	static void Run_Side_By_Side(size_t n_jobs, CJob job)
-	{
-		if(!n_jobs)
-			return;
-		std::vector<std::thread> threads;
-		std::exception_ptr p_error;
-		std::mutex t_mutex;
-		auto guarded = [&](size_t i) {
-			try {
-				job(i);
-			} catch(...) {
-				std::lock_guard<std::mutex> t_lock(t_mutex);
-				p_error = std::current_exception();
-			}
-		};
-		try {
-			for(size_t i = 1; i < n_jobs; ++ i)
-				threads.emplace_back(guarded, i);
-		} catch(...) { // no more threads: the rest on this one
-			for(size_t i = threads.size() + 1; i < n_jobs; ++ i)
-				guarded(i);
-		}
-		guarded(0);
-		for(size_t t = 0; t < threads.size(); ++ t)
-			threads[t].join();
-		if(p_error)
-			std::rethrow_exception(p_error);
-	}
-
 public:
 	CPlanSearch(const TBlockGraph &r_graph, const int64_t *p_cumsum, const int64_t *p_bcol_ptr, const int32_t *p_brow,
 		const PlanOptions &r_opt)
@@ -1276,7 +1248,7 @@ public:
 			}
 		}
 		const double t0 = now_ms();
-		Run_Side_By_Side(todo.size(), [&](size_t i) {
+		run_on_threads(int(todo.size()), [&](int i) {
 			PlanOptions t_opt = m_opt;
 			t_opt.nd_balance_pct = todo[i].first.first;
 			t_opt.nd_other_bank = todo[i].first.second;
@@ -1303,7 +1275,7 @@ public:
 			}
 		}
 		const double t0 = now_ms();
-		Run_Side_By_Side(todo.size(), [&](size_t i) {
+		run_on_threads(int(todo.size()), [&](int i) {
 			const TKey &r_k = todo[i].first;
 			TCandidate &r_c = *todo[i].second;
 			const TOrdered &r_o = m_ordered.find(t_Ordering_Key(r_k))->second; // (there since Ensure_Orderings(); find(): nothing is inserted under the threads' feet)

@@ -5,13 +5,13 @@
 #include "schur_state.h"
 #include "dense_chol.h"
 #include "covariance.h"
+#include "host_threads.h"
 
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <thread>
 
 namespace slampp {
@@ -107,12 +107,12 @@ CSchurState *schur_analyze(slampp_hip_solver &s)
 		// the shape of the system, column by column -- on a few threads from 65 536 block columns on (round 6: two passes over
 		// C5's two million columns were 5 - 7 ms on one); what is reported is what the serial passes reported: a block size out of
 		// line first, then the first landmark that is wrong and how, then the first camera
-		const int n_check_threads = (n >= 65536)? 4 : 1;
+		const int n_check_threads = host_thread_count(n, 16384, 4); // (four from 65 536 block columns on)
 		struct TFirst { int64_t n_size, n_landmark, n_camera; int n_landmark_error; };
 		std::vector<TFirst> first(size_t(n_check_threads), TFirst{-1, -1, -1, 0});
-		auto Check = [&](int t) {
+		for_ranges(0, n, n_check_threads, [&](int t, int64_t c0, int64_t c1) {
 			TFirst &r_first = first[size_t(t)];
-			for(int64_t c = n * t / n_check_threads, c1 = n * (t + 1) / n_check_threads; c < c1; ++ c) {
+			for(int64_t c = c0; c < c1; ++ c) {
 				if(r_first.n_size < 0 && cs[c + 1] - cs[c] != (c < nc? DC : DP))
 					r_first.n_size = c;
 				const bool b_no_diagonal = ptr[c + 1] == ptr[c] || brow[ptr[c + 1] - 1] != c;
@@ -129,13 +129,7 @@ CSchurState *schur_analyze(slampp_hip_solver &s)
 					}
 				}
 			}
-		};
-		std::vector<std::thread> threads;
-		for(int t = 1; t < n_check_threads; ++ t)
-			threads.emplace_back(Check, t);
-		Check(0);
-		for(size_t t = 0; t < threads.size(); ++ t)
-			threads[t].join();
+		});
 		for(int t = 0; t < n_check_threads; ++ t) {
 			if(first[size_t(t)].n_size >= 0)
 				throw std::domain_error("Schur path: cameras and landmarks must each have one block size");
@@ -175,23 +169,11 @@ CSchurState *schur_analyze(slampp_hip_solver &s)
 		// (round 4: the passes over the landmarks run on a few threads, a range of landmarks each -- C5's two million landmarks
 		// and eight million observations were 34 + 19 ms here on one core; the camera-major list is a counting sort with one
 		// counter array per thread, so every observation still lands where the serial pass put it)
-		const int n_setup_workers = int(std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, std::max(1u, std::thread::hardware_concurrency())), np / 65536)));
-		auto For_Landmark_Ranges = [np, n_setup_workers](const std::function<void(int, int64_t, int64_t)> &r_work) {
-			std::vector<std::thread> threads;
-			for(int t = 0; t < n_setup_workers; ++ t) {
-				const int64_t n_first = np * t / n_setup_workers, n_last = np * (t + 1) / n_setup_workers;
-				if(t + 1 < n_setup_workers)
-					threads.emplace_back(r_work, t, n_first, n_last);
-				else
-					r_work(t, n_first, n_last);
-			}
-			for(size_t t = 0; t < threads.size(); ++ t)
-				threads[t].join();
-		};
+		const int n_setup_workers = host_thread_count(np, 65536);
 		raw_vector<int32_t> obs_pt(S.n_obs), obs_cam(S.n_obs); // (written in full by the pass below)
 		std::vector<int64_t> cam_ptr(nc + 1, 0);
 		std::vector<std::vector<int64_t> > cam_count(n_setup_workers, std::vector<int64_t>(size_t(nc), 0));
-		For_Landmark_Ranges([&](int t, int64_t n_first, int64_t n_last) {
+		for_ranges(0, np, n_setup_workers, [&](int t, int64_t n_first, int64_t n_last) {
 			std::vector<int64_t> &r_count = cam_count[t];
 			for(int64_t pt = n_first; pt < n_last; ++ pt) {
 				const int64_t c = nc + pt, o0 = ptr[c] - ptr[nc] - pt;
@@ -213,7 +195,7 @@ CSchurState *schur_analyze(slampp_hip_solver &s)
 			cam_ptr[c + 1] = n_sum;
 		}
 		raw_vector<int32_t> cam_obs(S.n_obs);
-		For_Landmark_Ranges([&](int t, int64_t n_first, int64_t n_last) {
+		for_ranges(0, np, n_setup_workers, [&](int t, int64_t n_first, int64_t n_last) {
 			std::vector<int64_t> &r_fill = cam_count[t];
 			const int64_t o_first = ptr[nc + n_first] - ptr[nc] - n_first, o_last = ptr[nc + n_last] - ptr[nc] - n_last;
 			for(int64_t o = o_first; o < o_last; ++ o)
@@ -223,7 +205,7 @@ CSchurState *schur_analyze(slampp_hip_solver &s)
 		// what is ready goes to the device from here on, beside the rest of the analysis (round 6: 130 MB out of pageable
 		// vectors at C5, 7 ms at the end of the analysis; the vectors are not written again, and joined before the final sync)
 		std::exception_ptr p_early_upload_error;
-		struct TJoinEarly { std::thread t; ~TJoinEarly() { if(t.joinable()) t.join(); } } t_early_upload;
+		CJoinedThread t_early_upload;
 		s.Join_Bringup(); // (a handle fresh from slampp_hip_create: its streams came up beside the checks and the observation lists -- solver.h)
 		{
 			const int n_device = s.n_device;
@@ -266,7 +248,7 @@ CSchurState *schur_analyze(slampp_hip_solver &s)
 				// where the landmarks cannot be taken one by one: below)
 				const int64_t n_words = (nc * nc + 63) / 64;
 				std::vector<std::vector<uint64_t> > pair_bits(n_setup_workers, std::vector<uint64_t>(size_t(n_words), 0));
-				For_Landmark_Ranges([&](int t, int64_t n_first, int64_t n_last) {
+				for_ranges(0, np, n_setup_workers, [&](int t, int64_t n_first, int64_t n_last) {
 					std::vector<uint64_t> &r_bits = pair_bits[t];
 					for(int64_t pt = n_first; pt < n_last; ++ pt) {
 						const int64_t o0 = ptr[nc + pt] - ptr[nc] - pt, o1 = ptr[nc + pt + 1] - ptr[nc] - (pt + 1);
@@ -303,20 +285,8 @@ CSchurState *schur_analyze(slampp_hip_solver &s)
 					// pass put it: inside a block in landmark order
 					const int64_t n_keys = nc * nc;
 					const int n_list_workers = int(std::max<int64_t>(1, std::min<int64_t>(n_setup_workers, (int64_t(1) << 26) / std::max<int64_t>(n_keys, 1)))); // (at most 512 MB of counters)
-					auto For_List_Ranges = [&](int64_t n, const std::function<void(int, int64_t, int64_t)> &r_work) {
-						std::vector<std::thread> threads;
-						for(int t = 0; t < n_list_workers; ++ t) {
-							const int64_t n_first = n * t / n_list_workers, n_last = n * (t + 1) / n_list_workers;
-							if(t + 1 < n_list_workers)
-								threads.emplace_back(r_work, t, n_first, n_last);
-							else
-								r_work(t, n_first, n_last);
-						}
-						for(size_t t = 0; t < threads.size(); ++ t)
-							threads[t].join();
-					};
 					std::vector<raw_vector<int64_t> > cnt(n_list_workers);
-					For_List_Ranges(np, [&](int t, int64_t n_first, int64_t n_last) {
+					for_ranges(0, np, n_list_workers, [&](int t, int64_t n_first, int64_t n_last) {
 						raw_vector<int64_t> &r_cnt = cnt[t];
 						r_cnt.assign(size_t(n_keys), 0);
 						for(int64_t pt = n_first; pt < n_last; ++ pt) {
@@ -330,7 +300,7 @@ CSchurState *schur_analyze(slampp_hip_solver &s)
 					// the ranges of blocks first by themselves, then shifted by what the ranges before them hold
 					std::vector<int64_t> range_total(n_list_workers, 0);
 					std::vector<std::vector<int64_t> > range_starts(n_list_workers); // start of every nonzero block of the range
-					For_List_Ranges(n_keys, [&](int r, int64_t n_first, int64_t n_last) {
+					for_ranges(0, n_keys, n_list_workers, [&](int r, int64_t n_first, int64_t n_last) {
 						int64_t n_sum = 0;
 						for(int64_t key = n_first; key < n_last; ++ key) {
 							const int64_t n_before = n_sum;
@@ -347,7 +317,7 @@ CSchurState *schur_analyze(slampp_hip_solver &s)
 					std::vector<int64_t> range_base(n_list_workers + 1, 0);
 					for(int r = 0; r < n_list_workers; ++ r)
 						range_base[r + 1] = range_base[r] + range_total[r];
-					For_List_Ranges(n_keys, [&](int r, int64_t n_first, int64_t n_last) {
+					for_ranges(0, n_keys, n_list_workers, [&](int r, int64_t n_first, int64_t n_last) {
 						if(!range_base[r])
 							return;
 						for(int t = 0; t < n_list_workers; ++ t) {
@@ -365,7 +335,7 @@ CSchurState *schur_analyze(slampp_hip_solver &s)
 						throw std::logic_error("reduced camera system: the block list and the contribution counts disagree");
 					ent_a.resize(n_entries);
 					ent_uoff.resize(n_entries);
-					For_List_Ranges(np, [&](int t, int64_t n_first, int64_t n_last) {
+					for_ranges(0, np, n_list_workers, [&](int t, int64_t n_first, int64_t n_last) {
 						int64_t *p_fill = cnt[t].data();
 						for(int64_t pt = n_first; pt < n_last; ++ pt) {
 							const int64_t o0 = ptr[nc + pt] - ptr[nc] - pt, o1 = ptr[nc + pt + 1] - ptr[nc] - (pt + 1);

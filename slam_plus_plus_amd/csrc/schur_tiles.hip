@@ -18,14 +18,13 @@
 // SLAMPP_HIP_DEV_TILE_POINTS / SLAMPP_HIP_DEV_RUN_PIECE (environment, with SLAMPP_HIP_DEV=1: plan.h) are development knobs for the landmarks per tile / per run piece.
 #include "schur_tiles.h"
 #include "schur_state.h"
+#include "host_threads.h"
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <thread>
 #include <atomic>
-#include <functional>
 #include <chrono>
 
 namespace slampp {
@@ -863,23 +862,11 @@ void radix_sort_items(raw_vector<TItem> &r_items, raw_vector<TItem> &r_tmp, int 
 	enum { DIGIT_BITS = 11, DIGITS = 1 << DIGIT_BITS };
 	const int64_t n = int64_t(r_items.size());
 	r_tmp.resize(size_t(n));
-	const int n_workers = int(std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, std::max(1u, std::thread::hardware_concurrency())), n / 32768)));
+	const int n_workers = host_thread_count(n, 32768);
 	std::vector<std::vector<int64_t> > cnt(n_workers, std::vector<int64_t>(DIGITS));
-	auto For_Ranges = [&](const std::function<void(int, int64_t, int64_t)> &r_work) {
-		std::vector<std::thread> threads;
-		for(int t = 0; t < n_workers; ++ t) {
-			const int64_t n_first = n * t / n_workers, n_last = n * (t + 1) / n_workers;
-			if(t + 1 < n_workers)
-				threads.emplace_back(r_work, t, n_first, n_last);
-			else
-				r_work(t, n_first, n_last);
-		}
-		for(size_t t = 0; t < threads.size(); ++ t)
-			threads[t].join();
-	};
 	for(int n_shift = n_first_bit; n_shift < n_last_bit; n_shift += DIGIT_BITS) {
 		const uint64_t n_mask = (n_last_bit - n_shift >= DIGIT_BITS)? uint64_t(DIGITS - 1) : (uint64_t(1) << (n_last_bit - n_shift)) - 1;
-		For_Ranges([&](int t, int64_t n_first, int64_t n_last) {
+		for_ranges(0, n, n_workers, [&](int t, int64_t n_first, int64_t n_last) {
 			std::vector<int64_t> &r_cnt = cnt[t];
 			std::fill(r_cnt.begin(), r_cnt.end(), 0);
 			for(int64_t i = n_first; i < n_last; ++ i)
@@ -893,7 +880,7 @@ void radix_sort_items(raw_vector<TItem> &r_items, raw_vector<TItem> &r_tmp, int 
 				n_sum += n_here;
 			}
 		}
-		For_Ranges([&](int t, int64_t n_first, int64_t n_last) {
+		for_ranges(0, n, n_workers, [&](int t, int64_t n_first, int64_t n_last) {
 			std::vector<int64_t> &r_cnt = cnt[t];
 			for(int64_t i = n_first; i < n_last; ++ i)
 				r_tmp[r_cnt[(key_of(r_items[i]) >> n_shift) & n_mask] ++] = r_items[i];
@@ -935,19 +922,8 @@ void schur_tiles_build(CSchurTiles &T, int n_mode, int DC, int DP, int64_t nc, i
 	if(b_use_runs) {
 		// (the passes over the landmarks that do not depend on each other run on a few threads: at C5's two million landmarks
 		// telling the classes apart was 98 ms of a 250 ms analysis on one core, a cache miss per list)
-		auto For_Landmark_Ranges = [np](int64_t n_begin, const std::function<void(int64_t, int64_t)> &r_work) {
-			const int64_t n = np - n_begin;
-			const int n_workers = int(std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, std::max(1u, std::thread::hardware_concurrency())), n / 65536)));
-			std::vector<std::thread> threads;
-			for(int t = 0; t < n_workers; ++ t) {
-				const int64_t n_first = n_begin + n * t / n_workers, n_last = n_begin + n * (t + 1) / n_workers;
-				if(t + 1 < n_workers)
-					threads.emplace_back(r_work, n_first, n_last);
-				else
-					r_work(n_first, n_last);
-			}
-			for(size_t t = 0; t < threads.size(); ++ t)
-				threads[t].join();
+		auto For_Landmark_Ranges = [np](int64_t n_begin, auto work) {
+			for_ranges(n_begin, np, host_thread_count(np - n_begin, 65536), [&](int, int64_t n_first, int64_t n_last) { work(n_first, n_last); });
 		};
 		raw_vector<uint64_t> hash(np), hash2(np); // (hash2: a second, independent hash of the same list -- see "same lists" below; raw_vector: not zero-filled, host_pool.h)
 		raw_vector<int32_t> k_of(np); // observations per landmark (8 MB that stay in the caches better than two reads of ptr[] per use)
@@ -1215,26 +1191,17 @@ void schur_tiles_build(CSchurTiles &T, int n_mode, int DC, int DP, int64_t nc, i
 			const int n_fields = std::max(1, 64 / n_field_bits), n_key_bits = n_fields * n_field_bits;
 			struct TClassItem { uint64_t n_key; TClass t_class; };
 			raw_vector<TClassItem> class_items(n_classes), class_items_tmp;
-			const int n_class_workers = int(std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, std::max(1u, std::thread::hardware_concurrency())), n_classes / 16384)));
-			{
-				std::vector<std::thread> threads;
-				auto Keys = [&](int64_t n_first, int64_t n_last) {
-					for(int64_t c = n_first; c < n_last; ++ c) {
-						const int32_t p = order[classes[c].n_first];
-						const int64_t k0 = ptr[nc + p], k = ptr[nc + p + 1] - k0 - 1;
-						uint64_t n_key = 0;
-						for(int f = 0; f < n_fields; ++ f)
-							n_key = (n_key << n_field_bits) | ((f < k)? uint64_t(brow[k0 + f]) + 1 : 0);
-						class_items[c].n_key = n_key;
-						class_items[c].t_class = classes[c];
-					}
-				};
-				for(int t = 0; t + 1 < n_class_workers; ++ t)
-					threads.emplace_back(Keys, n_classes * t / n_class_workers, n_classes * (t + 1) / n_class_workers);
-				Keys(n_classes * (n_class_workers - 1) / n_class_workers, n_classes);
-				for(size_t t = 0; t < threads.size(); ++ t)
-					threads[t].join();
-			}
+			for_ranges(0, n_classes, host_thread_count(n_classes, 16384), [&](int, int64_t n_first, int64_t n_last) {
+				for(int64_t c = n_first; c < n_last; ++ c) {
+					const int32_t p = order[classes[c].n_first];
+					const int64_t k0 = ptr[nc + p], k = ptr[nc + p + 1] - k0 - 1;
+					uint64_t n_key = 0;
+					for(int f = 0; f < n_fields; ++ f)
+						n_key = (n_key << n_field_bits) | ((f < k)? uint64_t(brow[k0 + f]) + 1 : 0);
+					class_items[c].n_key = n_key;
+					class_items[c].t_class = classes[c];
+				}
+			});
 			radix_sort_items(class_items, class_items_tmp, 0, n_key_bits, [](const TClassItem &r_item) { return r_item.n_key; }); // (stable: classes of one key stay in the order they were found in)
 			std::vector<TClass> sorted(classes.size());
 			for(int64_t c = 0; c < n_classes; ++ c)
@@ -1259,23 +1226,14 @@ void schur_tiles_build(CSchurTiles &T, int n_mode, int DC, int DP, int64_t nc, i
 		const int64_t n_classes_all = int64_t(classes.size());
 		raw_vector<int32_t> class_k(n_classes_all);
 		raw_vector<uint8_t> class_tiles(n_classes_all), class_continues(n_classes_all);
-		{
-			const int n_workers = int(std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, std::max(1u, std::thread::hardware_concurrency())), n_classes_all / 16384)));
-			auto Look = [&](int64_t n_first, int64_t n_last) {
-				for(int64_t c = n_first; c < n_last; ++ c) {
-					const int32_t p = order[classes[c].n_first];
-					class_k[c] = int32_t(ptr[nc + p + 1] - ptr[nc + p] - 1);
-					class_tiles[c] = uint8_t(Tile_Class(p));
-					class_continues[c] = b_chains && c > 0 && Is_Prefix(order[classes[c - 1].n_first], p);
-				}
-			};
-			std::vector<std::thread> threads;
-			for(int t = 0; t + 1 < n_workers; ++ t)
-				threads.emplace_back(Look, n_classes_all * t / n_workers, n_classes_all * (t + 1) / n_workers);
-			Look(n_classes_all * (n_workers - 1) / n_workers, n_classes_all);
-			for(size_t t = 0; t < threads.size(); ++ t)
-				threads[t].join();
-		}
+		for_ranges(0, n_classes_all, host_thread_count(n_classes_all, 16384), [&](int, int64_t n_first, int64_t n_last) {
+			for(int64_t c = n_first; c < n_last; ++ c) {
+				const int32_t p = order[classes[c].n_first];
+				class_k[c] = int32_t(ptr[nc + p + 1] - ptr[nc + p] - 1);
+				class_tiles[c] = uint8_t(Tile_Class(p));
+				class_continues[c] = b_chains && c > 0 && Is_Prefix(order[classes[c - 1].n_first], p);
+			}
+		});
 		BUILD_PHASE("  class lists");
 		std::vector<int32_t> members, members_k; // (kept for the discard list below)
 		struct TGroup { size_t c0, c1; int64_t n_members; };
@@ -1316,7 +1274,7 @@ void schur_tiles_build(CSchurTiles &T, int n_mode, int DC, int DP, int64_t nc, i
 			}
 		};
 		{
-			const int n_emit_workers = int(std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(dev_knob("SLAMPP_HIP_DEV_EMIT_THREADS", 8), std::max(1u, std::thread::hardware_concurrency())), n_emit_members / 65536))); // (development aid, plan.h: 1 = one thread, for comparing the tables)
+			const int n_emit_workers = host_thread_count(n_emit_members, 65536, dev_knob("SLAMPP_HIP_DEV_EMIT_THREADS", 8)); // (development aid, plan.h: 1 = one thread, for comparing the tables)
 			std::vector<TEmitOut> outs;
 			outs.resize(size_t(n_emit_workers));
 			std::vector<size_t> g_begin(size_t(n_emit_workers) + 1, groups.size());
@@ -1330,30 +1288,13 @@ void schur_tiles_build(CSchurTiles &T, int n_mode, int DC, int DP, int64_t nc, i
 						g_begin[size_t(t ++)] = g + 1;
 				}
 			}
-			std::exception_ptr p_emit_error;
-			std::mutex t_error_mutex;
-			{
-				std::vector<std::thread> threads;
-				auto Work = [&](int t) {
-					try {
-						outs[size_t(t)].run_lm.reserve(size_t(n_emit_members / n_emit_workers + 65536));
-						outs[size_t(t)].run_k.reserve(size_t(n_emit_members / n_emit_workers + 65536));
-						Emit_Groups(outs[size_t(t)], g_begin[size_t(t)], g_begin[size_t(t) + 1]);
-						for(int32_t n_landmark : outs[size_t(t)].run_lm)
-							handled[size_t(n_landmark)] = 1; // (a landmark is in one run: no two threads write the same byte)
-					} catch(...) {
-						std::lock_guard<std::mutex> t_lock(t_error_mutex);
-						p_emit_error = std::current_exception();
-					}
-				};
-				for(int t = 1; t < n_emit_workers; ++ t)
-					threads.emplace_back(Work, t);
-				Work(0);
-				for(size_t t = 0; t < threads.size(); ++ t)
-					threads[t].join();
-			}
-			if(p_emit_error)
-				std::rethrow_exception(p_emit_error);
+			run_on_threads(n_emit_workers, [&](int t) {
+				outs[size_t(t)].run_lm.reserve(size_t(n_emit_members / n_emit_workers + 65536));
+				outs[size_t(t)].run_k.reserve(size_t(n_emit_members / n_emit_workers + 65536));
+				Emit_Groups(outs[size_t(t)], g_begin[size_t(t)], g_begin[size_t(t) + 1]);
+				for(int32_t n_landmark : outs[size_t(t)].run_lm)
+					handled[size_t(n_landmark)] = 1; // (a landmark is in one run: no two threads write the same byte)
+			});
 			// behind each other, in the order of the runs: positions in the run list and offsets of the partial blocks become global
 			if(n_emit_workers == 1) {
 				run_lm.swap(outs[0].run_lm);
@@ -1486,7 +1427,8 @@ void schur_tiles_build(CSchurTiles &T, int n_mode, int DC, int DP, int64_t nc, i
 				order[i] = int32_t(uint32_t(items[i]));
 		}
 		const int64_t n_rest = int64_t(order.size());
-		// built piecewise by a few threads (a piece boundary is a tile boundary)
+		// built piecewise by a few threads (a piece boundary is a tile boundary: the pieces are counted from the landmarks
+		// alone, not by host_thread_count() -- the tiles must not depend on the machine or on a knob)
 		const int n_pieces = int(std::max<int64_t>(1, std::min<int64_t>(8, n_rest / 32768)));
 		// Round 6: where the library decides by itself (n_mode < 0) and the runs alone do not carry half of the contributions, the
 		// tiles are tried on a sample first -- the first 4 096 landmarks of every piece -- and left alone if runs and tiles
@@ -1497,23 +1439,14 @@ void schur_tiles_build(CSchurTiles &T, int n_mode, int DC, int DP, int64_t nc, i
 			const int64_t n_sample = 4096;
 			std::vector<TTileRun> sample(n_pieces);
 			std::vector<int64_t> sample_pairs(n_pieces, 0);
-			std::vector<std::thread> threads;
-			for(int t = 0; t < n_pieces; ++ t) {
-				const int64_t n_first = n_rest * t / n_pieces, n_last = std::min(n_first + n_sample, n_rest * (t + 1) / n_pieces);
-				auto Work = [&sample, &sample_pairs, &order, t, n_first, n_last, n_mode, nc, ptr, brow]() {
-					build_run(sample[t], order.data(), n_first, n_last, n_mode, nc, ptr, brow);
-					for(int64_t i = n_first; i < n_last; ++ i) {
-						const int64_t k = ptr[nc + order[i] + 1] - ptr[nc + order[i]] - 1;
-						sample_pairs[t] += k * (k + 1) / 2;
-					}
-				};
-				if(t + 1 < n_pieces)
-					threads.emplace_back(Work);
-				else
-					Work();
-			}
-			for(size_t t = 0; t < threads.size(); ++ t)
-				threads[t].join();
+			for_ranges(0, n_rest, n_pieces, [&](int t, int64_t n_first, int64_t n_piece_end) {
+				const int64_t n_last = std::min(n_first + n_sample, n_piece_end);
+				build_run(sample[t], order.data(), n_first, n_last, n_mode, nc, ptr, brow);
+				for(int64_t i = n_first; i < n_last; ++ i) {
+					const int64_t k = ptr[nc + order[i] + 1] - ptr[nc + order[i]] - 1;
+					sample_pairs[t] += k * (k + 1) / 2;
+				}
+			});
 			int64_t n_sample_all = 0, n_sample_tiled = 0;
 			for(int t = 0; t < n_pieces; ++ t) {
 				n_sample_all += sample_pairs[t];
@@ -1532,19 +1465,9 @@ void schur_tiles_build(CSchurTiles &T, int n_mode, int DC, int DP, int64_t nc, i
 			}
 		}
 		runs.resize(n_pieces);
-		std::vector<std::thread> threads;
-		for(int t = 0; t < n_pieces; ++ t) {
-			const int64_t n_first = n_rest * t / n_pieces, n_last = n_rest * (t + 1) / n_pieces;
-			auto Work = [&runs, &order, t, n_first, n_last, n_mode, nc, ptr, brow]() {
-				build_run(runs[t], order.data(), n_first, n_last, n_mode, nc, ptr, brow);
-			};
-			if(t + 1 < n_pieces)
-				threads.emplace_back(Work);
-			else
-				Work();
-		}
-		for(size_t t = 0; t < threads.size(); ++ t)
-			threads[t].join();
+		for_ranges(0, n_rest, n_pieces, [&](int t, int64_t n_first, int64_t n_last) {
+			build_run(runs[t], order.data(), n_first, n_last, n_mode, nc, ptr, brow);
+		});
 		for(int t = 0; t < n_pieces; ++ t) {
 			n_tiles += int64_t(runs[t].tile_size.size());
 			n_tile_slots += int64_t(runs[t].slot_key.size());
@@ -1579,21 +1502,14 @@ void schur_tiles_build(CSchurTiles &T, int n_mode, int DC, int DP, int64_t nc, i
 				raw_vector<int64_t> run_rec(p_up->run_lm.size());
 				{ // offset of every landmark's first U block in the values (a read of ptr[] per landmark, in hash order: a few threads)
 					const int64_t n = int64_t(run_rec.size());
-					const int n_workers = int(std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, std::max(1u, std::thread::hardware_concurrency())), n / 65536))); // (round 6: eight -- the analysis waits for this thread at its end)
 					int64_t *p_rec = run_rec.data();
 					const int32_t *p_lm = p_up->run_lm.data();
-					auto Fill = [=](int64_t n_first, int64_t n_last) {
+					for_ranges(0, n, host_thread_count(n, 65536), [=](int, int64_t n_first, int64_t n_last) { // (eight threads: the analysis waits for this thread at its end)
 						for(int64_t i = n_first; i < n_last; ++ i) {
 							const int64_t pt = p_lm[i], o0 = ptr[nc + pt] - ptr[nc] - pt;
 							p_rec[i] = n_ablocks * DC * DC + o0 * DC * DP + pt * DP * DP;
 						}
-					};
-					std::vector<std::thread> threads;
-					for(int t = 0; t + 1 < n_workers; ++ t)
-						threads.emplace_back(Fill, n * t / n_workers, n * (t + 1) / n_workers);
-					Fill(n * (n_workers - 1) / n_workers, n);
-					for(size_t t = 0; t < threads.size(); ++ t)
-						threads[t].join();
+					});
 				}
 				p_tiles->d_run_rec.Upload(run_rec, stream);
 				SLAMPP_HIP_CHECK(hipStreamSynchronize(stream)); // (run_rec lives in this scope)
@@ -1733,22 +1649,10 @@ void schur_tiles_build(CSchurTiles &T, int n_mode, int DC, int DP, int64_t nc, i
 				list_points.push_back(int32_t(pt));
 		}
 		const int64_t n_list = int64_t(list_points.size());
-		const int n_workers = int(std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, std::max(1u, std::thread::hardware_concurrency())), n_list / 2048)));
+		const int n_workers = host_thread_count(n_list, 2048);
 		std::vector<std::vector<int64_t> > cnt_t(n_workers, std::vector<int64_t>(size_t(n_sblocks), 0)), cam_t(n_workers, std::vector<int64_t>(size_t(nc), 0));
-		auto For_Ranges = [&](const std::function<void(int, int64_t, int64_t)> &r_work) {
-			std::vector<std::thread> threads;
-			for(int t = 0; t < n_workers; ++ t) {
-				const int64_t n_first = n_list * t / n_workers, n_last = n_list * (t + 1) / n_workers;
-				if(t + 1 < n_workers)
-					threads.emplace_back(r_work, t, n_first, n_last);
-				else
-					r_work(t, n_first, n_last);
-			}
-			for(size_t t = 0; t < threads.size(); ++ t)
-				threads[t].join();
-		};
 		std::atomic<int> n_missing(0);
-		For_Ranges([&](int t, int64_t n_first, int64_t n_last) {
+		for_ranges(0, n_list, n_workers, [&](int t, int64_t n_first, int64_t n_last) {
 			for(int64_t i = n_first; i < n_last; ++ i) {
 				const int64_t pt = list_points[i], k0 = ptr[nc + pt], k = ptr[nc + pt + 1] - k0 - 1;
 				for(int64_t a = 0; a < k; ++ a) {
@@ -1796,7 +1700,7 @@ void schur_tiles_build(CSchurTiles &T, int n_mode, int DC, int DP, int64_t nc, i
 		xent_a.resize(size_t(xsb_ptr.back()));
 		xent_uoff.resize(size_t(xsb_ptr.back()));
 		xcam_obs.resize(size_t(xcam_ptr[nc]));
-		For_Ranges([&](int t, int64_t n_first, int64_t n_last) {
+		for_ranges(0, n_list, n_workers, [&](int t, int64_t n_first, int64_t n_last) {
 			for(int64_t i = n_first; i < n_last; ++ i) {
 				const int64_t pt = list_points[i], k0 = ptr[nc + pt], k = ptr[nc + pt + 1] - k0 - 1, o0 = k0 - ptr[nc] - pt;
 				for(int64_t a = 0; a < k; ++ a) {

@@ -5,11 +5,9 @@
 #include "plan.h"
 #include "sparse_kernels.h"
 #include "host_pool.h"
+#include "host_threads.h"
 
 #include <algorithm>
-#include <exception>
-#include <mutex>
-#include <thread>
 
 namespace slampp {
 
@@ -77,34 +75,7 @@ struct SparseRecords {
 template <class F>
 void Parallel_Ranges(int64_t n, int64_t n_min_per_thread, F f, int n_max_threads = 4)
 {
-	n_max_threads = std::min(n_max_threads, std::max(dev_knob("SLAMPP_HIP_DEV_SETUP_THREADS", n_max_threads), 1)); // (development knob, plan.h)
-	const int n_threads = int(std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_max_threads, std::max(1u, std::thread::hardware_concurrency())), n / std::max<int64_t>(n_min_per_thread, 1))));
-	if(n_threads <= 1) {
-		f(int64_t(0), n);
-		return;
-	}
-	std::vector<std::thread> threads;
-	std::exception_ptr p_error;
-	std::mutex t_mutex;
-	for(int t = 0; t < n_threads; ++ t) {
-		const int64_t b = n * t / n_threads, e = n * (t + 1) / n_threads;
-		auto job = [&, b, e]() {
-			try {
-				f(b, e);
-			} catch(...) {
-				std::lock_guard<std::mutex> t_lock(t_mutex);
-				p_error = std::current_exception();
-			}
-		};
-		if(t + 1 < n_threads)
-			threads.emplace_back(job);
-		else
-			job();
-	}
-	for(size_t t = 0; t < threads.size(); ++ t)
-		threads[t].join();
-	if(p_error)
-		std::rethrow_exception(p_error);
+	for_ranges(0, n, host_thread_count(n, n_min_per_thread, n_max_threads), [&](int, int64_t n_b, int64_t n_e) { f(n_b, n_e); });
 }
 
 // The builders, one per job.  Each reads the plan, the options and what earlier builders left, and writes the parts named;

@@ -88,9 +88,6 @@ void slampp_hip_solver::Refine_Structure()
 
 namespace {
 
-// a thread that is joined when its scope ends, however it ends
-struct TJoinedThread { std::thread t; ~TJoinedThread() { if(t.joinable()) t.join(); } };
-
 // the phases of the analysis on stderr (SLAMPP_HIP_PLAN_TIMING)
 struct TSetupPhases {
 	bool b_timing;
@@ -228,7 +225,7 @@ void slampp_hip_solver::Analyze_Sparse()
 	// 2. the shape grouping of the leaf kernel (13 ms of host work at 100 000 poses, plan in, tables out) runs beside the
 	// records, packages and uploads below
 	std::exception_ptr p_simt_error;
-	TJoinedThread t_simt_thread;
+	CJoinedThread t_simt_thread;
 	const double t_simt = wall_ms();
 	if(b_small)
 		build_simt_tables(P, t_opt, rec, lists);
@@ -251,7 +248,7 @@ void slampp_hip_solver::Analyze_Sparse()
 
 	// 4. the panel packages of the separator stages
 	std::exception_ptr p_panel_error;
-	TJoinedThread t_panel_thread;
+	CJoinedThread t_panel_thread;
 	if(b_small)
 		build_panel_packages(P, t_opt, rec, lists);
 	else {
@@ -279,7 +276,7 @@ void slampp_hip_solver::Analyze_Sparse()
 	// and an upload from a std::vector is a staged copy that keeps its thread): a thread of its own, joined before the rest
 	// of the uploads.  The vectors it reads are not written from here on.
 	std::exception_ptr p_upload_error;
-	TJoinedThread t_upload_thread;
+	CJoinedThread t_upload_thread;
 	if(b_small) {
 		Upload_Records(*this, rec);
 		Phase("record uploads");

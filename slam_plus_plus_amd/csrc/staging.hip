@@ -8,6 +8,7 @@
 #include <pthread.h>
 #include "solver.h"
 #include "sparse_inverse.h"
+#include "host_threads.h"
 
 #include <algorithm>
 #include <atomic>
@@ -30,9 +31,10 @@ static size_t pinned_bytes(size_t n_doubles) // what Alloc_Pinned maps for that 
 	return (std::max<size_t>(n_doubles, 1) * sizeof(double) + n_huge - 1) / n_huge * n_huge;
 }
 
-// worker threads that are joined on every way out of the scope that started them: a std::thread destroyed while
-// joinable is std::terminate (a wordless abort), and that is what an exception thrown between two emplace_back calls --
-// std::system_error when the process is out of threads -- would otherwise leave behind
+// The copy workers of Staged_Upload(), joined on every way out of the scope that started them: a std::thread destroyed
+// while joinable is std::terminate (a wordless abort), and that is what an exception thrown between two emplace_back
+// calls -- std::system_error when the process is out of threads -- would otherwise leave behind.  (Not a fork-join,
+// host_threads.h: the calling thread does not take a share, it sends off the chunks the workers have finished.)
 struct CJoiningThreads {
 	std::vector<std::thread> v;
 	~CJoiningThreads() { Join(); }
@@ -122,24 +124,11 @@ static double *Alloc_Pinned(size_t n_doubles, bool &r_b_registered, bool b_defer
 		}
 		if(p) {
 			(void)madvise(p, n_bytes, MADV_HUGEPAGE);
-			const size_t n_threads = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(8, std::thread::hardware_concurrency()), n_bytes / (8 * n_huge)));
-			try {
-				CJoiningThreads threads;
-				for(size_t t = 0; t < n_threads; ++ t) {
-					const size_t n_begin = n_bytes / n_huge * t / n_threads * n_huge, n_end = n_bytes / n_huge * (t + 1) / n_threads * n_huge;
-					auto touch = [p, n_begin, n_end]() {
-						for(size_t i = n_begin; i < n_end; i += 4096)
-							((volatile char*)p)[i] = 0;
-					};
-					if(t + 1 < n_threads)
-						threads.v.emplace_back(touch);
-					else
-						touch();
-				}
-				threads.Join();
-			} catch(std::system_error&) {
-				// no more threads to be had: the registration below touches the pages itself
-			}
+			const int64_t n_pages = int64_t(n_bytes / n_huge);
+			for_ranges(0, n_pages, host_thread_count(n_pages, 8), [p](int, int64_t n_first, int64_t n_last) { // a thread per eight huge pages
+				for(size_t i = size_t(n_first) * n_huge, n_end = size_t(n_last) * n_huge; i < n_end; i += 4096)
+					((volatile char*)p)[i] = 0;
+			});
 			if(hipHostRegister(p, n_bytes, hipHostRegisterPortable | hipHostRegisterMapped) == hipSuccess) {
 				r_b_registered = true;
 				return (double*)p;
