@@ -26,6 +26,7 @@
 #include <cstring>
 #include <atomic>
 #include <chrono>
+#include <map>
 
 namespace slampp {
 
@@ -37,6 +38,29 @@ constexpr int tile_max_k(int n_cap)
 	while((k + 1) * (k + 2) / 2 <= n_cap)
 		++ k;
 	return k;
+}
+
+// What a launch takes from the analysis' counts, in one place each: tiles_enqueue_t launches by these, and schur_tiles_build
+// reports them (SLAMPP_HIP_PLAN_TIMING: the "[schur report]" lines tests/test_schur_variants_gpu.py reads) -- the report
+// cannot say one thing and the launch do another.
+// Quads of landmarks wherever a job stages a multiple of four landmarks at a time: all but the off-diagonal jobs of three
+// and four tiles a side, which stage two.  (Those with four staged and quads need 286 registers, one wave per SIMD instead
+// of two: Venice-like C4 1.513 against 1.502 ms, not kept.  Quads also for the diagonal jobs of three and four tiles a side,
+// four landmarks staged at a time: Venice-like C4 1.545 -> 1.486 ms.)
+inline bool run_launch_quad(int n_tiles_a_side, bool b_diag)
+{
+	const bool b_quad = !dev_knob_set("SLAMPP_HIP_DEV_NO_QUAD_RUNS"); // (development: the one-landmark-per-step form, for A/B timing)
+	const bool b_quad_wide = !dev_knob_set("SLAMPP_HIP_DEV_NO_QUAD_WIDE"); // (development: no quads for the diagonal jobs of three and four tiles a side)
+	return (n_tiles_a_side <= 2 || (b_diag && b_quad_wide)) && b_quad;
+}
+
+// 64-lane loads that fetch the blocks of a tile launch's largest landmark (NL of schur_tile_kernel): at most what the
+// largest landmark a tile takes needs
+inline int tile_launch_loads(int DC, int DP, int64_t n_max_k)
+{
+	const int BLK = DC * DP, NL_MAX = (tile_max_k(SCHUR_TILE_SLOTS) * BLK + 63) / 64;
+	const int64_t n_loads = (n_max_k * BLK + 63) / 64;
+	return int(std::max<int64_t>(1, std::min<int64_t>(n_loads, std::min(4, NL_MAX))));
 }
 
 __device__ __forceinline__ int64_t readlane64(int64_t v, int n_lane)
@@ -671,16 +695,12 @@ static void tiles_enqueue_t(const CSchurTiles &T, const int64_t *ptr, int64_t nc
 {
 	{
 		const TRunJob *p_jobs = T.d_run_jobs.p();
-		const bool b_quad = !dev_knob_set("SLAMPP_HIP_DEV_NO_QUAD_RUNS"); // (development: the one-landmark-per-step form, for A/B timing)
-		// (the off-diagonal jobs of three and four tiles a side stage two landmarks; with four staged and quads they need 286
-		// registers, one wave per SIMD instead of two: Venice-like C4 1.513 against 1.502 ms, not kept)
-		const bool b_quad_wide = !dev_knob_set("SLAMPP_HIP_DEV_NO_QUAD_WIDE"); // (quads also for the diagonal jobs of three and four tiles a side, four landmarks staged at a time: Venice-like C4 1.545 -> 1.486 ms; the off-diagonal ones stage two and stay as they were)
 #define LAUNCH_RUNS_Q(NT, DIAG, PFX, QUAD) hipLaunchKernelGGL((schur_run_kernel<DC, DP, NT, DIAG != 0, PFX != 0, QUAD>), \
 			dim3(unsigned(T.n_run_jobs[NT][DIAG][PFX])), dim3(64), 0, stream, p_jobs + T.n_run_job_first[NT][DIAG][PFX], T.d_run_lm.p(), \
 			T.d_run_rec.p(), T.d_run_k.p(), ubase, A, eta, n, Cinv, p_W, int(b_store), T.d_P.p(), T.d_R.p(), p_flag)
-		// (quads of landmarks wherever a job stages a multiple of four landmarks at a time: all but the off-diagonal jobs of
-		// three and four tiles a side, which stage two)
-#define LAUNCH_RUNS(NT, DIAG, PFX) do { if(T.n_run_jobs[NT][DIAG][PFX]) { if((NT <= 2 || (DIAG && b_quad_wide)) && b_quad) LAUNCH_RUNS_Q(NT, DIAG, PFX, (NT <= 2 || DIAG)); \
+		// (run_launch_quad says which jobs take quads of landmarks: never the off-diagonal jobs of three and four tiles a side,
+		// whose quad form is not instantiated)
+#define LAUNCH_RUNS(NT, DIAG, PFX) do { if(T.n_run_jobs[NT][DIAG][PFX]) { if(run_launch_quad(NT, DIAG != 0)) LAUNCH_RUNS_Q(NT, DIAG, PFX, (NT <= 2 || DIAG)); \
 			else LAUNCH_RUNS_Q(NT, DIAG, PFX, false); } } while(0)
 #define LAUNCH_RUNS_D(NT, DIAG) do { LAUNCH_RUNS(NT, DIAG, 0); LAUNCH_RUNS(NT, DIAG, 1); } while(0)
 		LAUNCH_RUNS_D(1, 1);
@@ -699,7 +719,7 @@ static void tiles_enqueue_t(const CSchurTiles &T, const int64_t *ptr, int64_t nc
 	enum { BLK = DC * DP, MAXK = tile_max_k(SCHUR_TILE_SLOTS), OPS = (MAXK * BLK > 320)? (MAXK * BLK + 63) / 64 * 64 : 320,
 		NL_MAX = (MAXK * BLK + 63) / 64 };
 	const size_t n_lds = (2 * OPS + size_t(T.n_max_slots) * (DC * DC + DC)) * sizeof(double) + 128;
-	const int n_loads = int((T.n_max_k * BLK + 63) / 64); // 64-lane loads that fetch the blocks of the largest landmark
+	const int n_loads = tile_launch_loads(DC, DP, T.n_max_k); // 64-lane loads that fetch the blocks of the largest landmark
 #define LAUNCH_TILES(NL) hipLaunchKernelGGL((schur_tile_kernel<DC, DP, SCHUR_TILE_SLOTS, (NL <= NL_MAX)? NL : NL_MAX>), \
 		dim3(unsigned(T.n_tiles)), dim3(64), n_lds, stream, T.d_tile_ptr.p(), T.d_tile_lm.p(), T.d_tile_slot_ptr.p(), \
 		T.d_pair_ptr.p(), T.d_lm_slot.p(), ptr, nc, ubase, A, eta, n, Cinv, p_W, int(b_store), T.d_P.p(), T.d_R.p(), p_flag, \
@@ -919,6 +939,20 @@ void schur_tiles_build(CSchurTiles &T, int n_mode, int DC, int DP, int64_t nc, i
 	raw_vector<TRunJob> jobs;
 	raw_vector<int32_t> run_lm, run_k;
 	int64_t n_run_pairs = 0;
+	bool b_no_run_possible = false; // (for the report: every list as long as every other and no class large enough)
+	// the machine-readable report beside the "[schur] of N landmarks" line (SLAMPP_HIP_PLAN_TIMING; diagnostics only)
+	auto Report_Lists_Keep = [b_build_timing](const char *p_s_rule) {
+		if(b_build_timing)
+			fprintf(stderr, "[schur report] the lists keep everything: rule=%s\n", p_s_rule);
+	};
+	auto Report_Counts = [](const auto &r_counts, const char *p_s_end = "\n") { // "value x times, ..." of a histogram
+		const char *p_s_sep = "";
+		for(const auto &r_count : r_counts) {
+			fprintf(stderr, "%s%lldx%lld", p_s_sep, (long long)r_count.first, (long long)r_count.second);
+			p_s_sep = ",";
+		}
+		fprintf(stderr, "%s%s", r_counts.empty()? "-" : "", p_s_end);
+	};
 	if(b_use_runs) {
 		// (the passes over the landmarks that do not depend on each other run on a few threads: at C5's two million landmarks
 		// telling the classes apart was 98 ms of a 250 ms analysis on one core, a cache miss per list)
@@ -1144,6 +1178,7 @@ void schur_tiles_build(CSchurTiles &T, int n_mode, int DC, int DP, int64_t nc, i
 			}
 			const int64_t n_needed = (k_max > OB && n_min_run > 2)? 2 : n_min_run; // (what the emission below asks of a run)
 			b_runs_impossible = k_min == k_max && n_longest + 1 < n_needed;
+			b_no_run_possible = b_runs_impossible;
 		}
 		run_lm.reserve(b_runs_impossible? 0 : np);
 		run_k.reserve(b_runs_impossible? 0 : np);
@@ -1461,6 +1496,7 @@ void schur_tiles_build(CSchurTiles &T, int n_mode, int DC, int DP, int64_t nc, i
 				BUILD_PHASE("tiles (sample)");
 				memset(T.n_run_jobs, 0, sizeof(T.n_run_jobs));
 				memset(T.n_run_job_first, 0, sizeof(T.n_run_job_first));
+				Report_Lists_Keep("sample");
 				return; // the lists keep everything
 			}
 		}
@@ -1480,6 +1516,8 @@ void schur_tiles_build(CSchurTiles &T, int n_mode, int DC, int DP, int64_t nc, i
 	if((!n_tiles && jobs.empty()) || (n_mode < 0 && 2 * (n_tile_pairs + n_run_pairs) < n_all_pairs) || n_slots > INT32_MAX) {
 		memset(T.n_run_jobs, 0, sizeof(T.n_run_jobs));
 		memset(T.n_run_job_first, 0, sizeof(T.n_run_job_first));
+		Report_Lists_Keep((!n_tiles && jobs.empty())? ((b_no_run_possible)? "runs_impossible" : "no_jobs") :
+			(n_slots > INT32_MAX)? "partial_block_count" : "under_half");
 		return; // the lists keep everything
 	}
 	// the run tables go to the device from here on, beside the rest of this analysis and of the caller's (round 5: 19 ms of C5's
@@ -1544,6 +1582,36 @@ void schur_tiles_build(CSchurTiles &T, int n_mode, int DC, int DP, int64_t nc, i
 		fprintf(stderr, "[schur] of %lld landmarks %lld in runs (%zu jobs), %lld in %lld tiles (largest %lld blocks); %lld partial blocks; "
 			"%lld of %lld contributions\n", (long long)np, (long long)n_run_points, n_run_jobs_all, (long long)n_tile_points,
 			(long long)n_tiles, (long long)T.n_max_slots, (long long)n_slots, (long long)T.n_tile_pairs, (long long)n_all_pairs);
+		// one line per run launch that has jobs, in the order of tiles_enqueue_t; the quad flag is the enqueue's own rule
+		for(int d = 1; d >= 0; -- d) {
+			for(int nt = 1; nt <= 4; ++ nt) {
+				for(int x = 0; x < 2; ++ x) {
+					if(!T.n_run_jobs[nt][d][x])
+						continue;
+					int32_t n_max_points = 0;
+					const TRunJob *p_job = T.p_run_upload->jobs.data() + T.n_run_job_first[nt][d][x];
+					std::map<int32_t, int64_t> points; // landmarks of a job -> jobs
+					for(int64_t j = 0; j < T.n_run_jobs[nt][d][x]; ++ j) {
+						n_max_points = std::max(n_max_points, p_job[j].n_points);
+						++ points[p_job[j].n_points];
+					}
+					fprintf(stderr, "[schur report] runs: NT=%d diag=%d prefix=%d quad=%d jobs=%lld max_points=%d points=", nt, d, x,
+						int(run_launch_quad(nt, d != 0)), (long long)T.n_run_jobs[nt][d][x], int(n_max_points));
+					Report_Counts(points);
+				}
+			}
+		}
+		if(n_tiles) {
+			int32_t n_max_tile_points = 0;
+			for(size_t t = 0; t < runs.size(); ++ t) {
+				for(size_t i = 0; i < runs[t].tile_size.size(); ++ i)
+					n_max_tile_points = std::max(n_max_tile_points, runs[t].tile_size[i]);
+			}
+			fprintf(stderr, "[schur report] tiles: NL=%d tiles=%lld max_slots=%lld max_k=%lld max_points=%d\n", tile_launch_loads(DC, DP, T.n_max_k),
+				(long long)n_tiles, (long long)T.n_max_slots, (long long)T.n_max_k, int(n_max_tile_points));
+		}
+		fprintf(stderr, "[schur report] routes: runs=%lld prefix=%lld tiles=%lld lists=%lld\n", (long long)n_run_points,
+			(long long)T.n_prefix_points, (long long)n_tile_points, (long long)T.n_list_points);
 	}
 
 	std::vector<int32_t> tile_ptr(1, 0), tile_lm;
@@ -1616,6 +1684,17 @@ void schur_tiles_build(CSchurTiles &T, int n_mode, int DC, int DP, int64_t nc, i
 			rb_part[start[slot_sb[g]] ++] = int32_t(g);
 	}
 	T.n_rb = int64_t(rb_sb.size());
+	if(b_build_timing) {
+		int64_t n_longest_list = 0;
+		std::map<int64_t, int64_t> lengths[2]; // partial blocks of a block of S -> blocks, off the diagonal and on it
+		for(size_t b = 0; b + 1 < rb_ptr.size(); ++ b) {
+			n_longest_list = std::max(n_longest_list, rb_ptr[b + 1] - rb_ptr[b]);
+			++ lengths[sb_row[rb_sb[b]] == sb_col[rb_sb[b]]][rb_ptr[b + 1] - rb_ptr[b]];
+		}
+		fprintf(stderr, "[schur report] reduce: blocks=%lld longest=%lld off_diagonal=", (long long)T.n_rb, (long long)n_longest_list);
+		Report_Counts(lengths[0], " diagonal=");
+		Report_Counts(lengths[1]);
+	}
 	BUILD_PHASE("partial block lists");
 
 	if(T.n_tiles) { // (the tile kernel's tables: 16 bytes per landmark that nobody reads where every landmark is in a run -- 32 MB of C5's cold call)
