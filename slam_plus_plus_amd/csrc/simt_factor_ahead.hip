@@ -192,38 +192,39 @@ __device__ __forceinline__ void factor_ahead_block(double (&acc)[D / 2][D], cons
 	}
 }
 
-template <int D, int W, int LPT, bool b_linv, int AHEAD> // (the arguments, programs, tables and LDS layout of factor_simt_kernel)
-__global__ void __launch_bounds__(64)
-factor_simt_kernel_ahead(const TSimtChunk *__restrict__ chunks, const int32_t *__restrict__ prog, const long long *__restrict__ tab,
-	const double *__restrict__ A, double *L, double *Linv, const double *__restrict__ b, double *w, int *p_flag,
-	long long *p_timing, TBatch t_batch)
-{	{ const int64_t n_member = blockIdx.y; A += n_member * t_batch.a; L += n_member * t_batch.l; Linv = Linv? Linv + n_member * t_batch.linv : Linv; b += n_member * t_batch.b; w += n_member * t_batch.w; p_flag += n_member; } // (TBatch: sparse_kernels.h)
+// A chunk's table from memory to LDS, one wave: eight loads in flight a lane before the first is waited for.  (A loop of one load
+// and one store an entry is compiled to a wait per load: 27 trips to memory one after the other for a table of 1 700 entries, some
+// 6 us in front of the first column of every wave.)  n_lane: 0 .. 63
+__device__ __forceinline__ void factor_ahead_stage_table(long long *p_dst, const long long *__restrict__ p_src, int n_entries, int n_lane)
+{
+	enum { N_FLIGHT = 8 };
+	for(int n_base = 0; n_base < n_entries; n_base += N_FLIGHT * 64) { // (wave-uniform trip count)
+		long long v[N_FLIGHT];
+		#pragma unroll
+		for(int u = 0; u < N_FLIGHT; ++ u) {
+			const int i = n_base + u * 64 + n_lane;
+			v[u] = p_src[(i < n_entries)? i : n_entries - 1]; // (no lane masked out: the loads of a trip go out together)
+		}
+		#pragma unroll
+		for(int u = 0; u < N_FLIGHT; ++ u) {
+			const int i = n_base + u * 64 + n_lane;
+			if(i < n_entries)
+				p_dst[i] = v[u];
+		}
+	}
+}
 
-	static_assert(LPT == 2 && D % 2 == 0 && AHEAD >= 1, "two lanes per task, even block sizes");
-	enum { DD = D * D, DH = D / 2 };
-	extern __shared__ long long s_tab[]; // the chunk's table of per-lane offsets
-	const TSimtChunk ch = chunks[blockIdx.x];
-	{
-		const int n_entries = (4 * prog[ch.prog_off] + prog[ch.prog_off + 1] + prog[ch.prog_off + 2] + prog[ch.prog_off + 3]) * W;
-		for(int i = threadIdx.x; i < n_entries; i += 64)
-			s_tab[i] = tab[ch.tab_off + i];
-		__syncthreads();
-	}
-	if(int(threadIdx.x) >= W * LPT)
-		return; // (no barrier below)
-	const int n_half = int(threadIdx.x) & 1; // which half of the rows below the diagonal this lane takes
-	const int r0 = n_half * DH;
-	long long *p_tm = 0; // development aid (SLAMPP_HIP_STAGE_TIMING): clock samples of a wave in the middle of the grid
-	int n_tm = 0;
-	if(p_timing && blockIdx.x == gridDim.x / 2 && threadIdx.x == 0) {
-		const unsigned long long n_tm_record = atomicAdd((unsigned long long*)p_timing, 1ull);
-		p_tm = (n_tm_record < 4096)? p_timing + 1 + 32 * n_tm_record : 0; // the buffer holds 4096 launch records: later launches go unrecorded
-		if(p_tm)
-			p_tm[n_tm ++] = wall_clock64();
-	}
+// The column loop of one chunk -- a whole task a lane pair, or one segment of a split task: the one loop of both kernels below.
+// P: the chunk's program (wave-uniform: scalar loads); T: field f of this lane's task at T[W f]; n_half: which half of the rows
+// below the diagonal this lane takes; p_tm, n_tm: the clock samples of the wave that takes them (SIMT_TICK).  Returns whether
+// a pivot was not positive.
 #define SIMT_TICK() do { if(p_tm && n_tm < 32) p_tm[n_tm ++] = wall_clock64(); } while(0)
-	const int32_t *P = prog + ch.prog_off;                 // wave-uniform: scalar loads
-	const long long *T = s_tab + threadIdx.x / LPT;        // field f of this lane's task at T[W f]
+template <int D, int W, bool b_linv, int AHEAD>
+__device__ __forceinline__ bool factor_ahead_columns(const int32_t *P, const long long *T, const int n_half, const double *__restrict__ A, double *L, double *Linv,
+	const double *__restrict__ b, double *w, long long *p_tm, int &n_tm)
+{
+	enum { DD = D * D, DH = D / 2 };
+	const int r0 = n_half * DH;
 	const int n_cols = P[0], n_blocks = P[1], n_ops = P[2];
 	const int f_blk = 4 * n_cols, f_op = f_blk + n_blocks, f_y = f_op + n_ops;
 	int pc = 4, blk0 = 0;
@@ -400,9 +401,144 @@ factor_simt_kernel_ahead(const TSimtChunk *__restrict__ chunks, const int32_t *_
 		// (what a lane loads in the following columns is what the lane itself has stored, or what an earlier launch
 		// has: program order of one thread, no fence)
 	}
+	return b_bad;
+}
 #undef SIMT_TICK
+
+template <int D, int W, int LPT, bool b_linv, int AHEAD> // (the arguments, programs, tables and LDS layout of factor_simt_kernel)
+__global__ void __launch_bounds__(64)
+factor_simt_kernel_ahead(const TSimtChunk *__restrict__ chunks, const int32_t *__restrict__ prog, const long long *__restrict__ tab,
+	const double *__restrict__ A, double *L, double *Linv, const double *__restrict__ b, double *w, int *p_flag,
+	long long *p_timing, TBatch t_batch)
+{	{ const int64_t n_member = blockIdx.y; A += n_member * t_batch.a; L += n_member * t_batch.l; Linv = Linv? Linv + n_member * t_batch.linv : Linv; b += n_member * t_batch.b; w += n_member * t_batch.w; p_flag += n_member; } // (TBatch: sparse_kernels.h)
+
+	static_assert(LPT == 2 && D % 2 == 0 && AHEAD >= 1, "two lanes per task, even block sizes");
+	enum { DD = D * D, DH = D / 2 };
+	extern __shared__ long long s_tab[]; // the chunk's table of per-lane offsets
+	const TSimtChunk ch = chunks[blockIdx.x];
+	{
+		const int n_entries = (4 * prog[ch.prog_off] + prog[ch.prog_off + 1] + prog[ch.prog_off + 2] + prog[ch.prog_off + 3]) * W;
+		factor_ahead_stage_table(s_tab, tab + ch.tab_off, n_entries, int(threadIdx.x));
+		__syncthreads();
+	}
+	if(int(threadIdx.x) >= W * LPT)
+		return; // (no barrier below)
+	const int n_half = int(threadIdx.x) & 1; // which half of the rows below the diagonal this lane takes
+	long long *p_tm = 0; // development aid (SLAMPP_HIP_STAGE_TIMING): clock samples of a wave in the middle of the grid
+	int n_tm = 0;
+	if(p_timing && blockIdx.x == gridDim.x / 2 && threadIdx.x == 0) {
+		const unsigned long long n_tm_record = atomicAdd((unsigned long long*)p_timing, 1ull);
+		p_tm = (n_tm_record < 4096)? p_timing + 1 + 32 * n_tm_record : 0; // the buffer holds 4096 launch records: later launches go unrecorded
+		if(p_tm)
+			p_tm[n_tm ++] = wall_clock64();
+	}
+	const bool b_bad = factor_ahead_columns<D, W, b_linv, AHEAD>(prog + ch.prog_off, s_tab + threadIdx.x / LPT, n_half, A, L, Linv, b, w, p_tm, n_tm);
 	if(b_bad)
 		atomicOr(p_flag, 1);
+}
+
+// The launch whose longest tasks set its duration (C3's leaves: the waves of five-column tasks are through at 38 us, those of
+// eight-column tasks at 71 us, and most of the chip idles in between).  A leaf task is no chain: its branches are independent
+// until they meet.  A workgroup of two waves runs three segments (TSimtBranchGroup, sparse_kernels.h): waves 0 and 1 the two
+// bins of whole branch chains of one chunk of split tasks, side by side; behind the barrier wave 0 the join columns above them,
+// the same tasks in the same lanes.  Chunks of whole tasks ride two to a workgroup and have no third segment.  The join columns
+// read blocks and entries of w that wave 1 stored: both waves are in one CU (one vector cache), and the barrier with its
+// workgroup-scope fence orders the stores in front of the loads.  A wave stages its segment's table into its own LDS region of
+// n_region entries; the column loop is factor_simt_kernel_ahead's, and so is every bit stored.
+template <int D, int W, bool b_linv, int AHEAD>
+__global__ void __launch_bounds__(128)
+factor_simt_kernel_branches(const TSimtBranchGroup *__restrict__ groups, const int32_t *__restrict__ prog, const long long *__restrict__ tab,
+	const double *__restrict__ A, double *L, double *Linv, const double *__restrict__ b, double *w, int *p_flag,
+	long long *p_timing, TBatch t_batch, int n_region)
+{	{ const int64_t n_member = blockIdx.y; A += n_member * t_batch.a; L += n_member * t_batch.l; Linv = Linv? Linv + n_member * t_batch.linv : Linv; b += n_member * t_batch.b; w += n_member * t_batch.w; p_flag += n_member; } // (TBatch: sparse_kernels.h)
+
+	static_assert(D % 2 == 0 && AHEAD >= 1 && W * 2 <= 64, "two lanes per task, even block sizes");
+	extern __shared__ long long s_tab[]; // two regions: a wave's segment table of per-lane offsets
+	const int n_wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6), n_lane = int(threadIdx.x) & 63; // (n_wave in a scalar register: what follows from it stays wave-uniform)
+	long long *s_mine = s_tab + n_wave * n_region;
+	long long *p_tm = 0; // development aid (SLAMPP_HIP_STAGE_TIMING): clock samples of the first wave of a workgroup in the middle of the grid
+	int n_tm = 0;
+	if(p_timing && blockIdx.x == gridDim.x / 2 && threadIdx.x == 0) {
+		const unsigned long long n_tm_record = atomicAdd((unsigned long long*)p_timing, 1ull);
+		p_tm = (n_tm_record < 4096)? p_timing + 1 + 32 * n_tm_record : 0; // the buffer holds 4096 launch records: later launches go unrecorded
+		if(p_tm)
+			p_tm[n_tm ++] = wall_clock64();
+	}
+	bool b_bad = false;
+	for(int n_pass = 0; n_pass < 2; ++ n_pass) { // the bins side by side, then the joins on wave 0
+		const TSimtChunk ch = groups[blockIdx.x].seg[n_pass? 2 : n_wave];
+		if(ch.n_tasks > 0 && (n_pass == 0 || n_wave == 0)) { // (wave-uniform)
+			const int32_t *P = prog + ch.prog_off;
+			const int n_entries = (4 * P[0] + P[1] + P[2] + P[3]) * W;
+			factor_ahead_stage_table(s_mine, tab + ch.tab_off, n_entries, n_lane);
+			__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); // (the region is this wave's own: its lanes' stores in front of its lanes' loads, no barrier)
+			__builtin_amdgcn_wave_barrier();
+			if(n_lane < W * 2) { // (idle lanes of a narrow wave go on to the barrier)
+				const bool b_bad_here = factor_ahead_columns<D, W, b_linv, AHEAD>(P, s_mine + n_lane / 2, n_lane & 1, A, L, Linv, b, w, p_tm, n_tm);
+				b_bad = b_bad || b_bad_here;
+			}
+		}
+		if(n_pass == 0)
+			__syncthreads(); // (what the bins stored of L, inv(L_jj) and w, in front of what the joins load)
+	}
+	if(b_bad)
+		atomicOr(p_flag, 1);
+}
+
+template <int W>
+static const void *p_Factor_Branches_Kernel(bool b_store_linv)
+{
+	return b_store_linv? reinterpret_cast<const void*>(&factor_simt_kernel_branches<6, W, true, SIMT_FACTOR_AHEAD>) :
+		reinterpret_cast<const void*>(&factor_simt_kernel_branches<6, W, false, SIMT_FACTOR_AHEAD>);
+}
+
+static const void *p_Factor_Branches_Kernel(int n_dim, int n_width, bool b_store_linv)
+{
+	if(n_dim != 6)
+		return 0;
+	return (n_width == 16)? p_Factor_Branches_Kernel<16>(b_store_linv) : (n_width == 32)? p_Factor_Branches_Kernel<32>(b_store_linv) : 0;
+}
+
+bool factor_simt_branches_exists(int n_dim, int n_width)
+{
+	return p_Factor_Branches_Kernel(n_dim, n_width, false) != 0;
+}
+
+int factor_simt_branches_groups(int n_dim, int n_width, int n_lds_bytes)
+{
+	int n_device = 0, n_cus = 0, n_groups = 0;
+	if(!factor_simt_branches_exists(n_dim, n_width) || n_lds_bytes <= 0 || hipGetDevice(&n_device) != hipSuccess ||
+	   hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, n_device) != hipSuccess || n_cus <= 0) {
+		(void)hipGetLastError();
+		return 0;
+	}
+	for(int b_store_linv = 0; b_store_linv < 2; ++ b_store_linv) { // (the smaller answer of the two instantiations)
+		int n_blocks = 0;
+		if(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_blocks, p_Factor_Branches_Kernel(n_dim, n_width, b_store_linv != 0), 128, size_t(n_lds_bytes)) != hipSuccess || n_blocks <= 0) {
+			(void)hipGetLastError();
+			return 0;
+		}
+		n_groups = (b_store_linv)? std::min(n_groups, n_cus * n_blocks) : n_cus * n_blocks;
+	}
+	return n_groups;
+}
+
+bool launch_factor_simt_branches(const TSimtBranchGroup *groups, int n_groups, int n_width, int n_lds_bytes, const int32_t *prog, const int64_t *tab, int n_dim,
+	const double *A, double *L, double *Linv, const double *b, double *w, int *p_flag, hipStream_t stream, long long *p_timing, const TBatch &t_batch)
+{
+	if(!factor_simt_branches_exists(n_dim, n_width) || n_groups <= 0 || n_lds_bytes <= 0 || n_lds_bytes % 16 != 0)
+		return false;
+	const long long *t = reinterpret_cast<const long long*>(tab);
+	const int n_region = n_lds_bytes / 16; // (entries of one of the two regions)
+#define BRANCHES_LAUNCH(W_, b_linv_) hipLaunchKernelGGL((factor_simt_kernel_branches<6, W_, b_linv_, SIMT_FACTOR_AHEAD>), dim3(n_groups, t_batch.n), dim3(128), n_lds_bytes, stream, \
+	groups, prog, t, A, L, Linv, b, w, p_flag, p_timing, t_batch, n_region)
+	if(n_width == 16) {
+		if(Linv) BRANCHES_LAUNCH(16, true); else BRANCHES_LAUNCH(16, false);
+	} else {
+		if(Linv) BRANCHES_LAUNCH(32, true); else BRANCHES_LAUNCH(32, false);
+	}
+#undef BRANCHES_LAUNCH
+	return true;
 }
 
 template <int W>

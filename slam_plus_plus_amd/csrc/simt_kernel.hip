@@ -298,7 +298,7 @@ factor_simt_kernel(const TSimtChunk *__restrict__ chunks, const int32_t *__restr
 
 bool launch_factor_simt(const TSimtChunk *chunks, int n_chunks, int n_width, int n_lds_bytes, const int32_t *prog, const int64_t *tab, int n_dim,
 	const double *A, double *L, double *Linv, const double *b, double *w, int *p_flag, hipStream_t stream, long long *p_timing, const TBatch &t_batch,
-	int n_ahead_waves)
+	int n_ahead_waves, const TSimtBranchLaunch *p_branches)
 {
 	if(n_chunks <= 0)
 		return true;
@@ -323,6 +323,22 @@ bool launch_factor_simt(const TSimtChunk *chunks, int n_chunks, int n_width, int
 	const int n_lpt = (b_pairs && n_dim % 2 == 0 && (n_width == 16 || n_width == 32))? 2 : 1;
 	const bool b_ahead = n_lpt == 2 && factor_simt_ahead_exists(n_dim, n_width) &&
 		((n_ahead_env >= 0)? n_ahead_env != 0 : int64_t(n_chunks) * std::max<int64_t>(t_batch.n, 1) <= n_ahead_waves);
+	// The two-wave form (simt_factor_ahead.hip: factor_simt_kernel_branches) shortens the launch where its longest tasks set its
+	// duration and everything else is through long before them (C3's leaves): the launch must be one the fetch-ahead form would
+	// take, fit one round of the two-wave form, have tasks longer than T* columns, the longest chain a wave then walks -- and
+	// be of a stage of at least 2 048 tasks, the size from which the analysis chooses the lane kernels by itself (below it only
+	// option simt = 1 gets here).  Development aid (plan.h): 0 = never, 1 = wherever the stage has records; the same bits.
+	const int n_branches_env = dev_knob("SLAMPP_HIP_DEV_SIMT_FACTOR_BRANCHES", -1);
+	const bool b_branches = p_branches && p_branches->n_groups > 0 && n_lpt == 2 && factor_simt_branches_exists(n_dim, n_width) &&
+		((n_branches_env >= 0)? n_branches_env != 0 : b_ahead && int64_t(p_branches->n_groups) * std::max<int64_t>(t_batch.n, 1) <= p_branches->n_round_groups &&
+		p_branches->n_tstar < p_branches->n_longest_task && p_branches->n_stage_tasks >= 2048);
+	if(b_branches) {
+		if(p_timing)
+			fprintf(stderr, "stage_timing lane-per-task factor branches launch: %d workgroups of two waves, %d split chunks, %d whole chunks, width %d, block size %d, %d members\n",
+				p_branches->n_groups, p_branches->n_split_chunks, p_branches->n_whole_chunks, n_width, n_dim, int(t_batch.n));
+		return launch_factor_simt_branches(p_branches->groups, p_branches->n_groups, n_width, p_branches->n_lds_bytes, prog, tab, n_dim, A, L, Linv, b, w, p_flag,
+			stream, p_timing, t_batch);
+	}
 	if(p_timing) // (development aid SLAMPP_HIP_STAGE_TIMING: which form the launch takes, for the tests)
 		fprintf(stderr, "stage_timing lane-per-task factor launch: %d chunks, width %d, block size %d, %d members, LPT %d, %s\n", n_chunks, n_width, n_dim,
 			int(t_batch.n), n_lpt, b_ahead? "fetch ahead" : "fetch by column");

@@ -91,9 +91,16 @@ void slampp_hip_solver::Enqueue_Sparse(const double *p_values_dev, double *p_rhs
 			if(b_simt && s + 1 < int(lists.simt_chunk_ptr.size())) {
 				const int n_chunks = lists.simt_chunk_ptr[s + 1] - lists.simt_chunk_ptr[s], n_rest = lists.simt_rest_ptr[s + 1] - lists.simt_rest_ptr[s];
 				const bool b_store_linv = b_leaf_linv_wanted || !b_simt_backward_wanted; // (the wave-per-task backward kernel reads the inverses)
+				TSimtBranchLaunch t_branches = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+				if(size_t(s) < lists.simt_br.size() && size_t(s) < simt_branches_round_groups.size() && lists.simt_br[size_t(s)].n_groups > 0 && d_simt_br_groups.p()) {
+					const TSimtBranchStage &r_br = lists.simt_br[size_t(s)];
+					const TSimtBranchLaunch t_have = {d_simt_br_groups.p() + r_br.n_first, r_br.n_groups, r_br.n_split_chunks, r_br.n_whole_chunks, r_br.n_lds_bytes,
+						simt_branches_round_groups[size_t(s)], r_br.n_tstar, r_br.n_longest_task, r_br.n_stage_tasks};
+					t_branches = t_have;
+				}
 				launch_factor_simt(d_simt_chunks.p() + lists.simt_chunk_ptr[s], n_chunks, n_simt_width, lists.simt_lds_bytes[s], d_simt_prog.p(), d_simt_tab.p(), P.max_dim,
 					p_values_dev, d_L.p(), b_store_linv? d_Linv.p() : 0, p_rhs_dev, d_w.p(), p_flag, stream, dplan.p_timing, t_batch,
-					(size_t(s) < simt_factor_ahead_waves.size())? simt_factor_ahead_waves[size_t(s)] : 0);
+					(size_t(s) < simt_factor_ahead_waves.size())? simt_factor_ahead_waves[size_t(s)] : 0, t_branches.n_groups? &t_branches : 0);
 				b_leaf_linv_valid = b_leaf_linv_valid && b_store_linv;
 				if(n_rest > 0) {
 					TDevPlan t_rest = dplan;

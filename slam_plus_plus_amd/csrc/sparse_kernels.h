@@ -278,7 +278,8 @@ bool launch_factor_simt(const TSimtChunk *chunks, int n_chunks, int n_width /* t
 	const int32_t *prog, const int64_t *tab, int n_dim,
 	const double *A, double *L, double *Linv /* null: inv(L_jj) is not stored */, const double *b, double *w, int *p_flag, hipStream_t stream,
 	long long *p_timing = 0 /* development aid, as TDevPlan::p_timing */, const TBatch &t_batch = t_No_Batch(),
-	int n_ahead_waves = 0 /* factor_simt_ahead_waves() of the stage, asked at analysis */);
+	int n_ahead_waves = 0 /* factor_simt_ahead_waves() of the stage, asked at analysis */,
+	const struct TSimtBranchLaunch *p_branches = 0 /* the stage's workgroup records of the two-wave form, if it has any (below) */);
 // The same kernel for launches that fit the chip in one round at one wave a SIMD (simt_factor_ahead.hip: factor_simt_kernel_ahead):
 // what a column reads of Lambda and b -- the diagonal block, b_j, the first SIMT_FACTOR_AHEAD blocks below the diagonal -- is
 // requested a column ahead; same arguments, same bits.  Block size 6, two lanes per task (widths 16 and 32) only:
@@ -289,6 +290,28 @@ bool launch_factor_simt_ahead(const TSimtChunk *chunks, int n_chunks, int n_widt
 	const double *A, double *L, double *Linv, const double *b, double *w, int *p_flag, hipStream_t stream, long long *p_timing, const TBatch &t_batch);
 // waves (= workgroups) of that form the device holds at once with this LDS request (as backward_simt_ahead_waves())
 int factor_simt_ahead_waves(int n_dim, int n_width, int n_lds_bytes);
+// The fetch-ahead form for launches whose longest tasks set their duration (simt_factor_ahead.hip: factor_simt_kernel_branches): a
+// workgroup of two waves runs three segments, each a chunk -- a program in the format above over the segment's own columns and
+// its table.  Segments 0 and 1 run side by side on waves 0 and 1; behind a barrier wave 0 runs segment 2.  A chunk of split tasks
+// gives one record: the two bins of whole branch chains of its tasks, and the join columns above them, the same tasks in the
+// same lanes of all three (sparse_records.h: simt_task_segments()).  Chunks of whole tasks ride two to a record, as segments 0
+// and 1.  n_tasks = 0: no such segment.  Per column the operations and their order are the same: the same bits.
+struct TSimtBranchGroup { // 48 B
+	TSimtChunk seg[3];
+};
+// what launch_factor_simt() needs to know of a stage's records to decide for the form (null: the stage has none)
+struct TSimtBranchLaunch {
+	const TSimtBranchGroup *groups; // (device)
+	int n_groups, n_split_chunks, n_whole_chunks;
+	int n_lds_bytes;       // two regions of the stage's largest segment table
+	int n_round_groups;    // factor_simt_branches_groups() of the stage, asked at analysis
+	int n_tstar, n_longest_task, n_stage_tasks; // the longest chain of columns a wave walks in this form and in the other; the stage's tasks
+};
+bool factor_simt_branches_exists(int n_dim, int n_width);
+// workgroups of that form the device holds at once with this LDS request
+int factor_simt_branches_groups(int n_dim, int n_width, int n_lds_bytes);
+bool launch_factor_simt_branches(const TSimtBranchGroup *groups, int n_groups, int n_width, int n_lds_bytes, const int32_t *prog, const int64_t *tab, int n_dim,
+	const double *A, double *L, double *Linv, const double *b, double *w, int *p_flag, hipStream_t stream, long long *p_timing, const TBatch &t_batch);
 // backward substitution of the same tasks, a lane per task (chunk programs: n_cols, number of sub-diagonal blocks, nb per
 // column; tables: per column offset of its first factor block, scalar offsets in the workspace and in the caller's vector,
 // then the workspace offset of every sub-diagonal block's row): x_j from L_jj^T directly, no inverse

@@ -905,11 +905,14 @@ struct TSimtChunkJob { int32_t n_group; size_t n_first; int n_fields, n_bwd_fiel
 
 // the program of task t, its operands and its y columns in order of first use, whether it fits the kernel, the program's hash
 // (op_index, y_index: per factor block and per column, all -1 when called and when left; touch, body: scratch)
-void Simt_Task_Program(const Plan &P, int32_t t, size_t W, int32_t *op_index, int32_t *y_index, std::vector<int32_t> &touch,
-	std::vector<int32_t> &body, TSimtTask &tt)
+// (p_cols: the columns the program walks, in elimination order -- a whole task's, or one segment's of a split task: below)
+void Simt_Task_Program(const Plan &P, int32_t t, const int32_t *p_cols, int32_t n_cols, size_t W, int32_t *op_index, int32_t *y_index,
+	std::vector<int32_t> &touch, std::vector<int32_t> &body, TSimtTask &tt)
 {
 	std::vector<int32_t> &prog = tt.prog;
 	prog.assign(4, 0);
+	tt.ops.clear();
+	tt.ys.clear();
 	tt.n_task = t;
 	int32_t n_blocks = 0;
 	bool b_fits = true;
@@ -920,8 +923,8 @@ void Simt_Task_Program(const Plan &P, int32_t t, size_t W, int32_t *op_index, in
 		}
 		return op_index[n_blk];
 	};
-	for(int64_t i = P.task_ptr[t]; i < P.task_ptr[t + 1] && b_fits; ++ i) {
-		const int32_t j = P.task_cols[i];
+	for(int32_t i = 0; i < n_cols && b_fits; ++ i) {
+		const int32_t j = p_cols[i];
 		const int32_t nb = int32_t(P.lptr[j + 1] - P.lptr[j]), nr = int32_t(P.rptr[j + 1] - P.rptr[j]);
 		prog.push_back(nb);
 		prog.push_back(nr);
@@ -960,17 +963,16 @@ void Simt_Task_Program(const Plan &P, int32_t t, size_t W, int32_t *op_index, in
 		op_index[tt.ops[k]] = -1;
 	for(size_t k = 0; k < tt.ys.size(); ++ k)
 		y_index[tt.ys[k]] = -1;
-	const int32_t n_cols = int32_t(P.task_ptr[t + 1] - P.task_ptr[t]);
 	// (round 6) behind the program proper: for every block below a diagonal, which of the task's columns its row is, or
 	// -1 for a row outside the task -- what the backward kernel keeps x of in LDS.  Implied by the program (a block whose
 	// row is column m of the task is a row entry of m), and part of the shape's key all the same
-	for(int64_t i = P.task_ptr[t]; i < P.task_ptr[t + 1] && b_fits; ++ i) {
-		const int32_t j = P.task_cols[i];
+	for(int32_t i = 0; i < n_cols && b_fits; ++ i) {
+		const int32_t j = p_cols[i];
 		for(int64_t k = P.lptr[j] + 1; k < P.lptr[j + 1]; ++ k) {
 			int32_t n_local = -1;
-			for(int64_t i2 = i + 1; i2 < P.task_ptr[t + 1] && n_local < 0; ++ i2) {
-				if(P.task_cols[i2] == P.lrow[k])
-					n_local = int32_t(i2 - P.task_ptr[t]);
+			for(int32_t i2 = i + 1; i2 < n_cols && n_local < 0; ++ i2) {
+				if(p_cols[i2] == P.lrow[k])
+					n_local = i2;
 			}
 			prog.push_back(n_local);
 		}
@@ -1069,6 +1071,31 @@ std::pair<int32_t, int32_t> Layout_Simt_Chunks(const Plan &P, size_t W, const st
 	return std::make_pair(n_stage_lds, n_stage_bwd_lds);
 }
 
+// one lane of a forward table, [field][lane]: the fields of the columns p_cols (a whole task's, or a segment's), then of the
+// operands and y columns of their program; returns the number of fields written
+int Fill_Simt_Forward_Lane(const Plan &P, size_t W, int64_t *p_tab, int n_lane, const int32_t *p_cols, int32_t n_cols,
+	const std::vector<int32_t> &r_ops, const std::vector<int32_t> &r_ys)
+{
+	int f = 0;
+	for(int32_t i = 0; i < n_cols; ++ i) {
+		const int32_t j = p_cols[i];
+		p_tab[W * (f ++) + n_lane] = P.loff[P.lptr[j]];
+		p_tab[W * (f ++) + n_lane] = P.linv_off[j];
+		p_tab[W * (f ++) + n_lane] = P.cs_new[j];
+		p_tab[W * (f ++) + n_lane] = P.cs_src[j];
+	}
+	for(int32_t i = 0; i < n_cols; ++ i) {
+		const int32_t j = p_cols[i];
+		for(int64_t k = P.lptr[j]; k < P.lptr[j + 1]; ++ k)
+			p_tab[W * (f ++) + n_lane] = (P.asrc[k] < 0)? -1 : P.asrc[k] * 2 + P.atrans[k];
+	}
+	for(int32_t n_blk : r_ops)
+		p_tab[W * (f ++) + n_lane] = P.loff[n_blk];
+	for(int32_t c : r_ys)
+		p_tab[W * (f ++) + n_lane] = P.cs_new[c];
+	return f;
+}
+
 // the forward and the backward table of one chunk, [field][lane]
 void Fill_Simt_Chunk_Tables(const Plan &P, size_t W, const std::vector<TSimtTask> &tasks_all, const std::vector<std::vector<int32_t> > &groups,
 	const TSimtChunkJob &r_job, SparseRecords &r_rec)
@@ -1079,23 +1106,8 @@ void Fill_Simt_Chunk_Tables(const Plan &P, size_t W, const std::vector<TSimtTask
 	int64_t *p_tab = &r_rec.simt_tab[size_t(r_job.n_tab_off)];
 	for(int n_lane = 0; n_lane < int(W); ++ n_lane) {
 		const TSimtTask &tt = tasks_all[size_t(r_members[n_first + std::min<size_t>(n_lane, n_in_chunk - 1)])]; // spare lanes repeat the last task
-		int f = 0;
-		for(int64_t i = P.task_ptr[tt.n_task]; i < P.task_ptr[tt.n_task + 1]; ++ i) {
-			const int32_t j = P.task_cols[i];
-			p_tab[W * (f ++) + n_lane] = P.loff[P.lptr[j]];
-			p_tab[W * (f ++) + n_lane] = P.linv_off[j];
-			p_tab[W * (f ++) + n_lane] = P.cs_new[j];
-			p_tab[W * (f ++) + n_lane] = P.cs_src[j];
-		}
-		for(int64_t i = P.task_ptr[tt.n_task]; i < P.task_ptr[tt.n_task + 1]; ++ i) {
-			const int32_t j = P.task_cols[i];
-			for(int64_t k = P.lptr[j]; k < P.lptr[j + 1]; ++ k)
-				p_tab[W * (f ++) + n_lane] = (P.asrc[k] < 0)? -1 : P.asrc[k] * 2 + P.atrans[k];
-		}
-		for(int32_t n_blk : tt.ops)
-			p_tab[W * (f ++) + n_lane] = P.loff[n_blk];
-		for(int32_t c : tt.ys)
-			p_tab[W * (f ++) + n_lane] = P.cs_new[c];
+		const int f = Fill_Simt_Forward_Lane(P, W, p_tab, n_lane, P.task_cols.data() + P.task_ptr[tt.n_task],
+			int32_t(P.task_ptr[tt.n_task + 1] - P.task_ptr[tt.n_task]), tt.ops, tt.ys);
 		if(f != n_fields)
 			throw std::logic_error("lane-per-task tables: field count mismatch");
 	}
@@ -1124,6 +1136,243 @@ void Fill_Simt_Chunk_Tables(const Plan &P, size_t W, const std::vector<TSimtTask
 
 } // anonymous namespace
 
+void simt_task_parents(const Plan &P, int32_t t, std::vector<int32_t> &r_parent)
+{
+	const int32_t *p_cols = P.task_cols.data() + P.task_ptr[t];
+	const int32_t n_cols = int32_t(P.task_ptr[t + 1] - P.task_ptr[t]);
+	r_parent.assign(size_t(n_cols), -1);
+	for(int32_t i = 0; i < n_cols; ++ i) { // the first of the task's columns among the rows below the diagonal
+		const int32_t j = p_cols[i];
+		for(int64_t k = P.lptr[j] + 1; k < P.lptr[j + 1]; ++ k) {
+			for(int32_t i2 = i + 1; i2 < n_cols && (r_parent[size_t(i)] < 0 || i2 < r_parent[size_t(i)]); ++ i2) {
+				if(p_cols[i2] == P.lrow[k])
+					r_parent[size_t(i)] = i2;
+			}
+		}
+	}
+}
+
+int32_t simt_task_segments(const std::vector<int32_t> &r_parent, TSimtSegments &r_seg)
+{
+	const int32_t n = int32_t(r_parent.size());
+	std::vector<int32_t> n_children(size_t(n), 0);
+	std::vector<char> b_join(size_t(n), 0);
+	for(int32_t i = 0; i < n; ++ i) {
+		if(r_parent[size_t(i)] >= 0)
+			++ n_children[size_t(r_parent[size_t(i)])];
+	}
+	for(int32_t i = 0; i < n; ++ i) { // (ascending: a parent lies behind its children)
+		b_join[size_t(i)] = b_join[size_t(i)] || n_children[size_t(i)] >= 2;
+		if(b_join[size_t(i)] && r_parent[size_t(i)] >= 0)
+			b_join[size_t(r_parent[size_t(i)])] = 1;
+	}
+	std::vector<std::vector<int32_t> > chains;
+	for(int32_t i = 0; i < n; ++ i) {
+		if(n_children[size_t(i)] != 0)
+			continue;
+		chains.push_back(std::vector<int32_t>());
+		for(int32_t c = i; c >= 0 && !b_join[size_t(c)]; c = r_parent[size_t(c)])
+			chains.back().push_back(c);
+	}
+	r_seg.n_tips = int32_t(chains.size());
+	for(int k = 0; k < 3; ++ k)
+		r_seg.seg[k].clear();
+	std::stable_sort(chains.begin(), chains.end(), [](const std::vector<int32_t> &r_a, const std::vector<int32_t> &r_b) { return r_a.size() > r_b.size(); });
+	for(size_t c = 0; c < chains.size(); ++ c) {
+		std::vector<int32_t> &r_bin = r_seg.seg[(r_seg.seg[1].size() < r_seg.seg[0].size() && chains.size() > 1)? 1 : 0];
+		r_bin.insert(r_bin.end(), chains[c].begin(), chains[c].end());
+	}
+	for(int32_t i = 0; i < n; ++ i) {
+		if(b_join[size_t(i)])
+			r_seg.seg[2].push_back(i);
+	}
+	std::sort(r_seg.seg[0].begin(), r_seg.seg[0].end());
+	std::sort(r_seg.seg[1].begin(), r_seg.seg[1].end());
+	return int32_t(std::max(r_seg.seg[0].size(), r_seg.seg[1].size()) + r_seg.seg[2].size());
+}
+
+namespace {
+
+// The workgroup records of one stage for the two-wave factor form (sparse_kernels.h: TSimtBranchGroup).  Shapes stay grouped by
+// the whole task's program, so a chunk of split tasks has one program per segment, shared by its lanes; the segments' programs
+// and tables go to br_prog and br_tab (build_simt_tables() puts them behind the chunks' own and moves the offsets), the
+// chunks of whole tasks are named as they are.  b_split_all: every shape with two bins splits (the development knob at 1: how
+// small systems reach the form); otherwise the shapes with more columns than T* do, since splitting others would not shorten
+// the launch -- and a stage where none does gets no records.
+// n_chunk0: the stage's first chunk; jobs: one per chunk of the stage, in the chunks' order
+void Build_Simt_Branches(const Plan &P, size_t W, bool b_split_all, int32_t n_stage_tasks, const std::vector<TSimtTask> &tasks_all,
+	const std::vector<std::vector<int32_t> > &groups, const std::vector<TSimtChunkJob> &jobs, size_t n_chunk0, raw_vector<int32_t> &index_pool,
+	SparseRecords &r_rec, TSimtBranchStage &r_stage, std::vector<int32_t> &br_prog, raw_vector<int64_t> &br_tab, std::vector<char> &br_split)
+{
+	r_stage = TSimtBranchStage();
+	r_stage.n_first = int32_t(r_rec.simt_br_groups.size());
+	r_stage.n_stage_tasks = n_stage_tasks;
+	// 1. the segments of every shape, T*, which shapes split
+	std::vector<TSimtSegments> segs(groups.size());
+	std::vector<int32_t> chain(groups.size(), 0), parent;
+	for(size_t g = 0; g < groups.size(); ++ g) {
+		const TSimtTask &tt = tasks_all[size_t(groups[g][0])];
+		simt_task_parents(P, tt.n_task, parent);
+		chain[g] = simt_task_segments(parent, segs[g]);
+		const int32_t n_cols = int32_t(parent.size());
+		if(segs[g].seg[1].empty())
+			chain[g] = n_cols;
+		r_stage.n_tstar = std::max(r_stage.n_tstar, std::min(n_cols, chain[g]));
+		r_stage.n_longest_task = std::max(r_stage.n_longest_task, n_cols);
+	}
+	std::vector<char> split(groups.size(), 0);
+	bool b_any_split = false;
+	for(size_t g = 0; g < groups.size(); ++ g) {
+		const int32_t n_cols = tasks_all[size_t(groups[g][0])].prog[0];
+		split[g] = !segs[g].seg[1].empty() && chain[g] < n_cols && (b_split_all || n_cols > r_stage.n_tstar);
+		b_any_split = b_any_split || split[g];
+	}
+	if(!b_any_split && !b_split_all)
+		return;
+	// 2. the segments' programs, from the first task of every split shape.  Tasks of one program differ in nothing but where their
+	// blocks live, so a segment's operand (or y column) is the same entry of the whole task's list in every task of the shape: the
+	// other tasks' tables are filled through that map, and no program but the first task's is built
+	std::vector<TSimtTask> seg_tasks(groups.size() * 3);
+	std::vector<std::vector<int32_t> > seg_op_map(groups.size() * 3), seg_y_map(groups.size() * 3);
+	{
+		int32_t *op_index = &index_pool[0], *y_index = op_index + P.lrow.size(); // (all -1: as the programs' pass left them)
+		std::vector<int32_t> touch, body, cols;
+		for(size_t g = 0; g < groups.size(); ++ g) {
+			if(!split[g])
+				continue;
+			const TSimtTask &r_first = tasks_all[size_t(groups[g][0])];
+			for(size_t k = 0; k < 3; ++ k) {
+				const std::vector<int32_t> &r_local = segs[g].seg[k];
+				cols.resize(r_local.size());
+				for(size_t i = 0; i < r_local.size(); ++ i)
+					cols[i] = P.task_cols[size_t(P.task_ptr[r_first.n_task] + r_local[i])];
+				TSimtTask &r_seg = seg_tasks[g * 3 + k];
+				Simt_Task_Program(P, r_first.n_task, cols.data(), int32_t(cols.size()), W, op_index, y_index, touch, body, r_seg);
+				for(int32_t n_blk : r_seg.ops) {
+					const size_t n_at = size_t(std::find(r_first.ops.begin(), r_first.ops.end(), n_blk) - r_first.ops.begin());
+					if(n_at == r_first.ops.size())
+						throw std::logic_error("lane-per-task segments: an operand the whole task does not have");
+					seg_op_map[g * 3 + k].push_back(int32_t(n_at));
+				}
+				for(int32_t c : r_seg.ys) {
+					const size_t n_at = size_t(std::find(r_first.ys.begin(), r_first.ys.end(), c) - r_first.ys.begin());
+					if(n_at == r_first.ys.size())
+						throw std::logic_error("lane-per-task segments: a y column the whole task does not have");
+					seg_y_map[g * 3 + k].push_back(int32_t(n_at));
+				}
+			}
+		}
+	}
+	// 3. layout: a program per segment of a split shape, a table per segment of its chunks; the records
+	struct TItem { int32_t n_chain; TSimtBranchGroup t_group; char b_split; };
+	struct TSegJob { size_t n_group, n_first; int n_seg, n_fields; int64_t n_tab_off; };
+	std::vector<TItem> items;
+	std::vector<std::pair<int32_t, size_t> > whole; // columns, chunk
+	std::vector<TSegJob> seg_jobs;
+	std::map<std::pair<int32_t, int32_t>, int32_t> split_by;
+	int32_t n_region_bytes = 0;
+	const TSimtChunk t_none = {0, 0, 0};
+	for(size_t n_job = 0; n_job < jobs.size(); ) {
+		const size_t g = size_t(jobs[n_job].n_group);
+		const int32_t n_cols = tasks_all[size_t(groups[g][0])].prog[0];
+		if(!split[g]) {
+			for(; n_job < jobs.size() && size_t(jobs[n_job].n_group) == g; ++ n_job) {
+				whole.push_back(std::make_pair(n_cols, n_chunk0 + n_job));
+				n_region_bytes = std::max(n_region_bytes, int32_t(jobs[n_job].n_fields * W * 8));
+			}
+			continue;
+		}
+		int32_t n_seg_prog_off[3] = {0, 0, 0};
+		int n_seg_fields[3] = {0, 0, 0};
+		for(size_t k = 0; k < 3; ++ k) {
+			const std::vector<int32_t> &prog = seg_tasks[g * 3 + k].prog;
+			n_seg_prog_off[k] = int32_t(br_prog.size());
+			n_seg_fields[k] = 4 * prog[0] + prog[1] + prog[2] + prog[3];
+			if(prog[0] > 0) {
+				br_prog.insert(br_prog.end(), prog.begin(), prog.end());
+				n_region_bytes = std::max(n_region_bytes, int32_t(n_seg_fields[k] * W * 8));
+			}
+		}
+		const int32_t n_bin = int32_t(std::max(segs[g].seg[0].size(), segs[g].seg[1].size())), n_joins = int32_t(segs[g].seg[2].size());
+		split_by[std::make_pair(n_bin, n_joins)] += int32_t(groups[g].size());
+		r_stage.n_split_tasks += int32_t(groups[g].size());
+		for(; n_job < jobs.size() && size_t(jobs[n_job].n_group) == g; ++ n_job) {
+			const size_t n_first = jobs[n_job].n_first;
+			TItem t_item;
+			t_item.n_chain = chain[g];
+			t_item.b_split = 1;
+			for(size_t k = 0; k < 3; ++ k) {
+				TSimtChunk &ch = t_item.t_group.seg[k];
+				ch = t_none;
+				if(!n_seg_fields[k])
+					continue;
+				ch.prog_off = n_seg_prog_off[k];
+				ch.n_tasks = int32_t(std::min<size_t>(W, groups[g].size() - n_first));
+				ch.tab_off = int64_t(br_tab.size());
+				const TSegJob t_seg_job = {g, n_first, int(k), n_seg_fields[k], ch.tab_off};
+				seg_jobs.push_back(t_seg_job);
+				br_tab.resize(br_tab.size() + size_t(n_seg_fields[k]) * W);
+			}
+			items.push_back(t_item);
+			++ r_stage.n_split_chunks;
+		}
+	}
+	Parallel_Ranges(int64_t(seg_jobs.size()), 32, [&](int64_t n_b, int64_t n_e) {
+		std::vector<int32_t> cols, ops, ys;
+		for(int64_t n_j = n_b; n_j < n_e; ++ n_j) {
+			const TSegJob &r_job = seg_jobs[size_t(n_j)];
+			const std::vector<int32_t> &r_local = segs[r_job.n_group].seg[r_job.n_seg], &r_members = groups[r_job.n_group];
+			const std::vector<int32_t> &r_op_map = seg_op_map[r_job.n_group * 3 + size_t(r_job.n_seg)], &r_y_map = seg_y_map[r_job.n_group * 3 + size_t(r_job.n_seg)];
+			const size_t n_in_chunk = std::min<size_t>(W, r_members.size() - r_job.n_first);
+			cols.resize(r_local.size());
+			ops.resize(r_op_map.size());
+			ys.resize(r_y_map.size());
+			for(int n_lane = 0; n_lane < int(W); ++ n_lane) {
+				const TSimtTask &tt = tasks_all[size_t(r_members[r_job.n_first + std::min<size_t>(size_t(n_lane), n_in_chunk - 1)])]; // spare lanes repeat the last task
+				for(size_t i = 0; i < r_local.size(); ++ i)
+					cols[i] = P.task_cols[size_t(P.task_ptr[tt.n_task] + r_local[i])];
+				for(size_t i = 0; i < r_op_map.size(); ++ i)
+					ops[i] = tt.ops[size_t(r_op_map[i])];
+				for(size_t i = 0; i < r_y_map.size(); ++ i)
+					ys[i] = tt.ys[size_t(r_y_map[i])];
+				if(Fill_Simt_Forward_Lane(P, W, &br_tab[size_t(r_job.n_tab_off)], n_lane, cols.data(), int32_t(cols.size()), ops, ys) != r_job.n_fields)
+					throw std::logic_error("lane-per-task segments: field count mismatch");
+			}
+		}
+	}, 8);
+	// chunks of whole tasks two to a record, neighbours in length; the records by their chain, longest first (as Sort_Launch_Order())
+	std::stable_sort(whole.begin(), whole.end(), [](const std::pair<int32_t, size_t> &r_a, const std::pair<int32_t, size_t> &r_b) { return r_a.first > r_b.first; });
+	for(size_t i = 0; i < whole.size(); i += 2) {
+		TItem t_item;
+		t_item.n_chain = whole[i].first;
+		t_item.b_split = 0;
+		t_item.t_group.seg[0] = r_rec.simt_chunks[whole[i].second];
+		t_item.t_group.seg[1] = (i + 1 < whole.size())? r_rec.simt_chunks[whole[i + 1].second] : t_none;
+		t_item.t_group.seg[2] = t_none;
+		items.push_back(t_item);
+	}
+	r_stage.n_whole_chunks = int32_t(whole.size());
+	std::stable_sort(items.begin(), items.end(), [](const TItem &r_a, const TItem &r_b) { return r_a.n_chain > r_b.n_chain; });
+	if(2 * int64_t(n_region_bytes) > 64 * 1024) { // (beyond a plain launch's LDS: the stage keeps the one-wave forms; what went to br_prog and br_tab is not referred to)
+		r_stage.n_split_tasks = r_stage.n_split_chunks = r_stage.n_whole_chunks = 0;
+		return;
+	}
+	for(size_t i = 0; i < items.size(); ++ i) {
+		r_rec.simt_br_groups.push_back(items[i].t_group);
+		br_split.push_back(items[i].b_split);
+		r_stage.n_longest_chain = std::max(r_stage.n_longest_chain, items[i].n_chain);
+	}
+	r_stage.n_groups = int32_t(items.size());
+	r_stage.n_lds_bytes = 2 * n_region_bytes;
+	for(std::map<std::pair<int32_t, int32_t>, int32_t>::const_iterator p = split_by.begin(); p != split_by.end(); ++ p) {
+		r_stage.split_by.push_back(p->first.first);
+		r_stage.split_by.push_back(p->first.second);
+		r_stage.split_by.push_back(p->second);
+	}
+}
+
+} // anonymous namespace
+
 // Sorts the tasks of the wide bottom stages by shape for the lane-per-task kernel.  A shape is the task's whole program --
 // counts and operand indices, the operands numbered in order of first use -- so two tasks of one shape differ in nothing
 // but where their blocks live.  (No HIP call: runs on a thread of its own next to the rest of the analysis; sparse_setup.hip
@@ -1135,6 +1384,8 @@ void build_simt_tables(const Plan &P, const SparseRecordOptions &t_opt, SparseRe
 	r_lists.simt_lds_bytes.clear();
 	r_rec.simt_chunks.clear(); r_rec.simt_prog.clear(); r_rec.simt_tab.clear(); r_rec.simt_rest.clear();
 	r_lists.simt_bwd_lds_bytes.clear();
+	r_lists.simt_br.clear();
+	r_rec.simt_br_groups.clear();
 	r_rec.simt_bwd_chunks.clear(); r_rec.simt_bwd_prog.clear(); r_rec.simt_bwd_tab.clear();
 	if(!t_opt.n_simt || !b_Package_Dim(P))
 		return;
@@ -1154,6 +1405,14 @@ void build_simt_tables(const Plan &P, const SparseRecordOptions &t_opt, SparseRe
 	r_lists.simt_chunk_ptr.push_back(0);
 	r_lists.simt_rest_ptr.push_back(0);
 	const size_t W = size_t(t_opt.n_simt_width);
+	// the workgroup records of the two-wave factor form, where the fetch-ahead form exists for the stage (block size 6, two lanes
+	// a task: widths 16 and 32).  Development aid SLAMPP_HIP_DEV_SIMT_FACTOR_BRANCHES (plan.h): 0 = none, 1 = every shape with two
+	// bins splits; the launches read the knob again (simt_kernel.hip)
+	const int n_branches_env = dev_knob("SLAMPP_HIP_DEV_SIMT_FACTOR_BRANCHES", -1);
+	const bool b_branches = n_branches_env != 0 && P.uniform_dim && P.max_dim == 6 && (W == 16 || W == 32);
+	std::vector<int32_t> br_prog;
+	raw_vector<int64_t> br_tab; // (written in full by Build_Simt_Branches())
+	std::vector<char> br_split; // per record: its segments are in br_prog and br_tab
 	for(int s = 0; s < r_lists.n_bottom_stages && s < n_stages && s < t_opt.n_simt_stages; ++ s) {
 		const int32_t t0 = P.stage_ptr[s], n_stage_tasks = P.stage_ptr[s + 1] - P.stage_ptr[s];
 		double t_simt_phase = wall_ms();
@@ -1171,7 +1430,8 @@ void build_simt_tables(const Plan &P, const SparseRecordOptions &t_opt, SparseRe
 			std::fill(op_index, op_index + P.lrow.size() + size_t(P.n), -1);
 			std::vector<int32_t> touch, body;
 			for(int64_t n_i = n_b; n_i < n_e; ++ n_i)
-				Simt_Task_Program(P, t0 + int32_t(n_i), W, op_index, y_index, touch, body, tasks_all[size_t(n_i)]);
+				Simt_Task_Program(P, t0 + int32_t(n_i), P.task_cols.data() + P.task_ptr[t0 + n_i], int32_t(P.task_ptr[t0 + n_i + 1] - P.task_ptr[t0 + n_i]), W,
+					op_index, y_index, touch, body, tasks_all[size_t(n_i)]);
 		}, 8);
 		Simt_Phase("programs");
 		std::vector<std::vector<int32_t> > groups;
@@ -1179,6 +1439,10 @@ void build_simt_tables(const Plan &P, const SparseRecordOptions &t_opt, SparseRe
 		Simt_Phase("grouping");
 		std::vector<TSimtChunkJob> jobs;
 		const std::pair<int32_t, int32_t> t_stage_lds = Layout_Simt_Chunks(P, W, tasks_all, groups, r_rec, n_tab_size, n_bwd_tab_size, jobs);
+		if(b_branches) { // (the segments' tables are at most the size of the tasks' own: room for them now, so that nothing is moved when they are put behind)
+			r_rec.simt_tab.reserve(2 * n_tab_size);
+			br_tab.reserve(n_tab_size);
+		}
 		r_rec.simt_tab.resize(n_tab_size); // (raw_vector: what was there stays, the new part is written in full below)
 		r_rec.simt_bwd_tab.resize(n_bwd_tab_size);
 		Simt_Phase("layout");
@@ -1187,6 +1451,12 @@ void build_simt_tables(const Plan &P, const SparseRecordOptions &t_opt, SparseRe
 				Fill_Simt_Chunk_Tables(P, W, tasks_all, groups, jobs[size_t(n_job)], r_rec);
 		}, 8);
 		Simt_Phase("tables");
+		r_lists.simt_br.push_back(TSimtBranchStage());
+		if(b_branches) {
+			Build_Simt_Branches(P, W, n_branches_env == 1, n_stage_tasks, tasks_all, groups, jobs, r_rec.simt_chunks.size() - jobs.size(), index_pool,
+				r_rec, r_lists.simt_br.back(), br_prog, br_tab, br_split);
+			Simt_Phase("branches");
+		}
 		std::sort(rest.begin() + r_lists.simt_rest_ptr.back(), rest.end());
 		r_lists.simt_chunk_ptr.push_back(int32_t(r_rec.simt_chunks.size()));
 		r_lists.simt_rest_ptr.push_back(int32_t(rest.size()));
@@ -1196,6 +1466,24 @@ void build_simt_tables(const Plan &P, const SparseRecordOptions &t_opt, SparseRe
 	if(r_rec.simt_chunks.empty()) {
 		r_lists.simt_chunk_ptr.clear();
 		r_lists.simt_rest_ptr.clear();
+	}
+	if(r_rec.simt_br_groups.empty())
+		r_lists.simt_br.clear();
+	else { // the segments' programs and tables behind the chunks' own, which stay where they were
+		const int32_t n_prog_base = int32_t(r_rec.simt_prog.size());
+		const int64_t n_tab_base = int64_t(r_rec.simt_tab.size());
+		r_rec.simt_prog.insert(r_rec.simt_prog.end(), br_prog.begin(), br_prog.end());
+		r_rec.simt_tab.resize(size_t(n_tab_base) + br_tab.size());
+		std::copy(br_tab.begin(), br_tab.end(), r_rec.simt_tab.begin() + n_tab_base);
+		for(size_t i = 0; i < r_rec.simt_br_groups.size(); ++ i) {
+			for(int k = 0; k < 3 && br_split[i]; ++ k) {
+				TSimtChunk &ch = r_rec.simt_br_groups[i].seg[k];
+				if(ch.n_tasks > 0) {
+					ch.prog_off += n_prog_base;
+					ch.tab_off += n_tab_base;
+				}
+			}
+		}
 	}
 }
 

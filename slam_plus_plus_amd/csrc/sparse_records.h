@@ -24,6 +24,17 @@ struct SparseRecordOptions {
 	bool b_timing;        // SLAMPP_HIP_PLAN_TIMING: the builders print what they decided
 };
 
+// a lane-per-task stage's workgroup records of the two-wave factor form (sparse_kernels.h: TSimtBranchGroup)
+struct TSimtBranchStage {
+	int32_t n_first = 0, n_groups = 0;  // the stage's records in SparseRecords::simt_br_groups (none: the stage keeps the one-wave forms)
+	int32_t n_split_tasks = 0, n_split_chunks = 0, n_whole_chunks = 0;
+	int32_t n_tstar = 0;                // T*: the largest, over the stage's shapes, of min(columns, chain)
+	int32_t n_longest_chain = 0;        // the longest chain of columns a wave walks with these records
+	int32_t n_longest_task = 0, n_stage_tasks = 0;
+	int32_t n_lds_bytes = 0;            // two regions of the largest segment table
+	std::vector<int32_t> split_by;      // triples: longer bin, join columns, tasks
+};
+
 // what the launches of a step read on the host (sparse_enqueue.hip)
 struct SparseLaunchLists {
 	int n_bottom_stages = 1; // leading stages launched with one wave per task
@@ -36,6 +47,7 @@ struct SparseLaunchLists {
 	// lane-per-task kernels of the wide bottom stages (simt_kernel.hip)
 	std::vector<int32_t> simt_chunk_ptr, simt_rest_ptr; // [n_bottom_stages + 1] each; empty = not in use
 	std::vector<int32_t> simt_lds_bytes, simt_bwd_lds_bytes; // per stage: the largest chunk table (it is staged in LDS)
+	std::vector<TSimtBranchStage> simt_br; // per stage (empty: no stage has records)
 };
 
 // the host arrays of one analysis, until they are on the device
@@ -69,6 +81,7 @@ struct SparseRecords {
 	std::vector<TSimtChunk> simt_chunks, simt_bwd_chunks;
 	std::vector<int32_t> simt_prog, simt_rest, simt_bwd_prog;
 	raw_vector<int64_t> simt_tab, simt_bwd_tab; // (raw_vector: written in full by the table pass, never zero-filled)
+	std::vector<TSimtBranchGroup> simt_br_groups; // (the segments' programs and tables lie behind the chunks' in simt_prog and simt_tab)
 };
 
 // index ranges on a few threads (the record loops of the cold path: every entry written once, from the plan alone)
@@ -102,6 +115,17 @@ void build_panel_packages(const Plan &P, const SparseRecordOptions &t_opt, Spars
 void build_column_packages(const Plan &P, const SparseLaunchLists &r_lists, SparseRecords &r_rec);
 // dense_blks .. dst; n_dense_pad: the padded dimension of the dense system
 void build_dense_top_records(const Plan &P, int n_dense_pad, SparseRecords &r_rec);
+// The segments of a leaf task for the two-wave factor form, from the parents of its columns inside the task (-1: none; columns
+// in elimination order, a parent behind its children).  Join columns: those with two or more children inside the task, and
+// their ancestors.  The others fall into chains, each from a tip up to just below the first join column; the chains go into two
+// bins, longest first, each into the currently shorter bin (ties: the first).  seg[0], seg[1]: the bins, seg[2]: the join
+// columns, all ascending.  A task with one tip has one bin and no joins.  Returns the task's chain: the longer bin plus the joins.
+struct TSimtSegments {
+	std::vector<int32_t> seg[3];
+	int32_t n_tips = 0;
+};
+void simt_task_parents(const Plan &P, int32_t t, std::vector<int32_t> &r_parent);
+int32_t simt_task_segments(const std::vector<int32_t> &r_parent, TSimtSegments &r_seg);
 // simt_* of both; reads n_bottom_stages
 void build_simt_tables(const Plan &P, const SparseRecordOptions &t_opt, SparseRecords &r_rec, SparseLaunchLists &r_lists);
 

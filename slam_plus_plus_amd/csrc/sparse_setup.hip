@@ -499,7 +499,11 @@ void slampp_hip_solver::Upload_Simt(const SparseRecords &r_rec)
 	d_simt_bwd_chunks.Upload(r_rec.simt_bwd_chunks, stream);
 	d_simt_bwd_prog.Upload(r_rec.simt_bwd_prog, stream);
 	d_simt_bwd_tab.Upload(r_rec.simt_bwd_tab, stream);
+	d_simt_br_groups.Upload(r_rec.simt_br_groups, stream);
 	SLAMPP_HIP_CHECK(hipStreamSynchronize(stream)); // (the host copies are no longer needed)
+	simt_branches_round_groups.clear();
+	for(size_t s = 0; s < lists.simt_br.size(); ++ s)
+		simt_branches_round_groups.push_back((lists.simt_br[s].n_groups > 0)? factor_simt_branches_groups(P.max_dim, n_simt_width, lists.simt_br[s].n_lds_bytes) : 0);
 	simt_bwd_ahead_waves.clear();
 	for(size_t s = 0; s < lists.simt_bwd_lds_bytes.size(); ++ s)
 		simt_bwd_ahead_waves.push_back(backward_simt_ahead_waves(P.max_dim, n_simt_width, lists.simt_bwd_lds_bytes[s]));
@@ -509,6 +513,18 @@ void slampp_hip_solver::Upload_Simt(const SparseRecords &r_rec)
 	if(getenv("SLAMPP_HIP_PLAN_TIMING")) {
 		Report_Simt_Backward(r_rec);
 		Report_Simt_Factor(r_rec);
+		for(size_t s = 0; s < lists.simt_br.size(); ++ s) { // the two-wave form's records (sparse_records.cpp: Build_Simt_Branches())
+			const TSimtBranchStage &r_br = lists.simt_br[s];
+			if(!r_br.n_groups)
+				continue;
+			std::string s_by;
+			for(size_t i = 0; i + 2 < r_br.split_by.size(); i += 3)
+				s_by += " (" + std::to_string(r_br.split_by[i]) + "," + std::to_string(r_br.split_by[i + 1]) + "):" + std::to_string(r_br.split_by[i + 2]);
+			fprintf(stderr, "[setup] stage %zu factor branches: %d split tasks in %d split chunks, %d whole chunks, %d workgroups of two waves, T* %d, longest chain %d, "
+				"longest task %d; split tasks by (longer bin, join columns):%s; LDS %d bytes, one round holds %d workgroups\n", s, r_br.n_split_tasks, r_br.n_split_chunks,
+				r_br.n_whole_chunks, r_br.n_groups, r_br.n_tstar, r_br.n_longest_chain, r_br.n_longest_task, s_by.c_str(), r_br.n_lds_bytes,
+				(s < simt_branches_round_groups.size())? simt_branches_round_groups[s] : 0);
+		}
 		for(size_t s = 0; s + 1 < lists.simt_chunk_ptr.size(); ++ s) {
 			fprintf(stderr, "[setup] stage %zu: %d tasks -> %d chunks of 64 lanes, %d tasks left to the wave-per-task kernel\n", s,
 				P.stage_ptr[s + 1] - P.stage_ptr[s], lists.simt_chunk_ptr[s + 1] - lists.simt_chunk_ptr[s], lists.simt_rest_ptr[s + 1] - lists.simt_rest_ptr[s]);
