@@ -930,11 +930,92 @@ typedef struct slampp_hip_lm_problem {
  * SLAMPP_HIP_ERR_INVALID (text under "lm"): a null handle or required pointer, an outdated assembly or one of another
  * solver, no set or more than SLAMPP_HIP_LM_MAX_SETS, an edge type that does not fit its assembly, vertex ranges that do not
  * cover [0, n_bcols) exactly once or whose types do not fit the block dimensions, state, trial and dx overlapping, a handle
- * that was not analyzed, n_rounds <= 0.  SLAMPP_HIP_ERR_UNSUPPORTED: a handle over several devices, or one with an all-reduce
+ * that was not analyzed, n_rounds <= 0, an edge set whose assembly has a robust kernel (slampp_hip_assembly_set_robust, below:
+ * the loop then computes the set's weights itself) and a weight array as well.  SLAMPP_HIP_ERR_UNSUPPORTED: a handle over several devices, or one with an all-reduce
  * callback (landmark shards).  Both sparse and Schur mode are served. */
 int slampp_hip_lm_begin_device_async(const slampp_hip_lm_problem *p_problem, double f_alpha, double f_tau, double f_min_dx_norm,
 	int n_max_iterations, int n_extra_on_reject);
 int slampp_hip_lm_iterate_device_async(const slampp_hip_lm_problem *p_problem, int n_rounds);
+
+/* Robust kernels on the device: the per-edge weight that the assembly, chi^2
+ * and the initial damping already take, computed where the errors are, so that the loop above stays on the device once an edge is
+ * an outlier.  The reference's CEdgePose3D is such an edge (SE3_Types.h:128-129: CBaseEdge::Robust with
+ * CRobustify_ErrorNorm_Default<CCTFraction<30, 100>, CHuberLossd>): every Calculate_Hessians_v2 multiplies its blocks by
+ * w = Huber(|err| / 0.3) (BaseTypes_Binary.h:759-848).
+ *
+ * A specification is set on an assembly handle; with one set the handle owns a device array of n_edges weights (freed by
+ * set_robust(NULL) and with the handle).  w(s), the expressions of the reference's operator () in include/geometry/RobustLoss.h,
+ * evaluated in their order without contraction, a = f_param:
+ *   SLAMPP_HIP_ROBUST_HUBER   s <= a ? 1 : a / s                     CHuberLoss, :103          (default a = 1.345)
+ *   SLAMPP_HIP_ROBUST_CAUCHY  a a / (a a + s s)                      CCauchyLoss, :153         (2.385)
+ *   SLAMPP_HIP_ROBUST_TUKEY   s <= a ? (1 - s s / (a a))^2 : 0       CTukeyBiweightLoss, :206  (4.685)
+ *   SLAMPP_HIP_ROBUST_WELSCH  exp(-s s / (a a))                      CWelschLoss, :433         (2.985)
+ * What s is:
+ *   SLAMPP_HIP_ROBUST_BASIS_ERROR_NORM   |err|_2 / f_scale            CRobustify_ErrorNorm_Default, slam/RobustUtils.h:397-399
+ *                                        (Sigma^-1 is not read)
+ *   SLAMPP_HIP_ROBUST_BASIS_CHI2         err^T Sigma^-1 err / f_scale CRobustify_Chi2_Default, :531-534 -- the squared form
+ *                                        handed to the kernel as it stands
+ *   SLAMPP_HIP_ROBUST_BASIS_MAHALANOBIS  sqrt(err^T Sigma^-1 err) / f_scale   no counterpart in the reference: the usual
+ *                                        convention, and the only basis for which w(s) Sigma^-1 err is the gradient of a cost
+ * How the loop of slampp_hip_lm_* uses the weight:
+ *   SLAMPP_HIP_ROBUST_MODE_REFERENCE  line for line with the reference: w is the assembly's weight array, so Lambda gets w and
+ *                                     vertex 0's eta gets w^2 (the reference's own doubling, BaseTypes_Binary.h:813-815); the
+ *                                     initial damping reads the weighted blocks (:1200-1222); chi^2 is not weighted
+ *                                     (f_Chi_Squared_Error of the robust edge, SE3_Types.h:323-331).  Any basis.
+ *   SLAMPP_HIP_ROBUST_MODE_LOSS       a robust cost is minimised: J0, J1 and err are scaled by sqrt(w) in place (the reference's
+ *                                     device for its A-solver, BaseTypes.h:1478-1483) and assembled without weights, so that
+ *                                     Lambda = sum w J^T Sigma^-1 J and eta = sum w J^T Sigma^-1 err on both vertices; the loop
+ *                                     compares sum 2 f_scale^2 rho(s) of the unscaled error.  MAHALANOBIS only.
+ * rho has rho' = s w(s) and rho(0) = 0 (not the reference's v_Loss, whose Welsch is a copy of Fair's):
+ *   Huber s s / 2 up to a, a (s - a / 2) beyond; Cauchy (a a / 2) log(1 + s s / (a a)); Tukey (a a / 6) (1 - (1 - s s / (a a))^3)
+ *   up to a, a a / 6 beyond; Welsch (a a / 2) (1 - exp(-s s / (a a))).  Below the threshold of Huber 2 f_scale^2 rho(s) is
+ *   err^T Sigma^-1 err.
+ *
+ * set_robust: copies the specification (NULL: none again) and allocates or frees the weight array; waits for the solver's
+ * stream before it frees.  robust_weights (the pointer of the handle's array in *pp_weight_dev, NULL where none is set).
+ *
+ * The three kernels are enqueue-only on the solver's stream, use no atomics and give the same bits when called twice; an edge's
+ * weight does not depend on the other edges of the set.  A workgroup stages the records of its 64 edges (contiguous in memory)
+ * through LDS as whole lines and a lane forms its edge's s from its row of the tile.
+ *   robust_weights      p_weight_out_dev[e] = w(s_e) (NULL: into the handle's array); p_sigma_inv_dev may be NULL with ERROR_NORM;
+ *   robust_scale        p_J0_dev, p_J1_dev and p_error_dev, each element times sqrt(w_e) of its edge, in place (p_weight_dev
+ *                       NULL: the handle's array);
+ *   robust_chi_squared  *p_out_dev = sum over the edges of 2 f_scale^2 rho(s_e), with the partition and the summation trees of
+ *                       slampp_hip_chi_squared_device_async (they depend on n_edges alone).  MAHALANOBIS only.
+ * SLAMPP_HIP_ERR_INVALID (text under "robust"), before anything is enqueued: a null handle or required pointer, an outdated
+ * assembly, an unknown kernel, basis or mode, a scale or parameter that is not positive (a NaN is not), LOSS with another basis
+ * than MAHALANOBIS, robust_chi_squared on another basis, a kernel call on a handle without a specification.
+ *
+ * In slampp_hip_lm_begin_device_async and slampp_hip_lm_iterate_device_async an edge set whose assembly has a specification
+ * gets, after its linearize, robust_weights into the handle's array and (LOSS) robust_scale on its scratch arrays; the assembly
+ * and the initial damping take the handle's array (REFERENCE) or none (LOSS); its chi^2 part is the unweighted chi^2 (REFERENCE)
+ * or robust_chi_squared (LOSS) of the unscaled errors.  Such a set must leave p_weight_dev NULL.  Sets without a specification
+ * run as before, and the two kinds mix in one problem.  The handle's array is scratch as J0, J1 and err are: once STATUS has left 0
+ * the rounds still enqueued write the weights of the final state into it, the same values every time. */
+#define SLAMPP_HIP_ROBUST_HUBER   1
+#define SLAMPP_HIP_ROBUST_CAUCHY  2
+#define SLAMPP_HIP_ROBUST_TUKEY   3
+#define SLAMPP_HIP_ROBUST_WELSCH  4
+#define SLAMPP_HIP_ROBUST_BASIS_ERROR_NORM   1
+#define SLAMPP_HIP_ROBUST_BASIS_CHI2         2
+#define SLAMPP_HIP_ROBUST_BASIS_MAHALANOBIS  3
+#define SLAMPP_HIP_ROBUST_MODE_REFERENCE  1
+#define SLAMPP_HIP_ROBUST_MODE_LOSS       2
+typedef struct slampp_hip_robust {
+	int n_kernel;   /* SLAMPP_HIP_ROBUST_HUBER | _CAUCHY | _TUKEY | _WELSCH */
+	int n_basis;    /* SLAMPP_HIP_ROBUST_BASIS_ERROR_NORM | _CHI2 | _MAHALANOBIS */
+	int n_mode;     /* SLAMPP_HIP_ROBUST_MODE_REFERENCE | _LOSS */
+	double f_scale; /* > 0 */
+	double f_param; /* > 0: the loss function's a */
+} slampp_hip_robust;
+int slampp_hip_assembly_set_robust(slampp_hip_assembly *p_assembly, const slampp_hip_robust *p_robust /* NULL: none again */);
+int slampp_hip_assembly_robust_weights(slampp_hip_assembly *p_assembly, const double **pp_weight_dev);
+int slampp_hip_robust_weights_device_async(slampp_hip_assembly *p_assembly, const double *p_sigma_inv_dev, const double *p_error_dev,
+	double *p_weight_out_dev /* NULL: the handle's own array */);
+int slampp_hip_robust_scale_device_async(slampp_hip_assembly *p_assembly, const double *p_weight_dev /* NULL: the handle's */,
+	double *p_J0_dev, double *p_J1_dev, double *p_error_dev);
+int slampp_hip_robust_chi_squared_device_async(slampp_hip_assembly *p_assembly, const double *p_sigma_inv_dev,
+	const double *p_error_dev, double *p_out_dev);
 
 /* Multi-GPU BA (new functionality, no reference counterpart -- SURVEY.md section 8e): every rank
  * holds a landmark shard (its own points + all cameras); the partial reduced camera systems

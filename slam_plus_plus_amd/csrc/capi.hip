@@ -252,6 +252,8 @@ void slampp_hip_destroy(slampp_hip_solver *p_solver)
 			(void)hipStreamSynchronize(p_solver->stream);
 		for(slampp_hip_assembly *p_assembly : p_solver->assemblies) { // orphaned, not freed: the caller owns the handles
 			assembly_destroy(p_assembly->p_state);
+			p_assembly->d_robust_weight.Release();
+			p_assembly->b_robust = false;
 			p_assembly->p_state = 0;
 			p_assembly->p_solver = 0;
 		}

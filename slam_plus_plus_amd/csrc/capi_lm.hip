@@ -69,6 +69,8 @@ int check_problem(const slampp_hip_lm_problem &r)
 			return n_check;
 		if(!t.p_measurement_dev || !t.p_sigma_inv_dev || !t.p_J0_dev || !t.p_J1_dev || !t.p_error_dev)
 			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "lm: null pointer");
+		if(t.p_assembly->b_robust && t.p_weight_dev)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "lm: an edge set has both a robust kernel and a weight array");
 	}
 	const int64_t n = int64_t(s.cumsum.size()) - 1;
 	if(r.n_unary_vertex < -1 || r.n_unary_vertex >= n)
@@ -108,7 +110,40 @@ int check_problem(const slampp_hip_lm_problem &r)
 	return SLAMPP_HIP_OK;
 }
 
-// errors at p_state_dev (with the Jacobians where b_jacobians is set) and chi^2 of every set into the parts
+// A set whose assembly has a robust specification (slampp_hip_assembly_set_robust): the loop computes
+// its weights.  In SLAMPP_HIP_ROBUST_MODE_LOSS the weights are in the set's scaled arrays and the cost is the robust one.
+bool is_robust(const slampp_hip_lm_edge_set &t)
+{
+	return t.p_assembly->b_robust;
+}
+
+bool is_robust_loss(const slampp_hip_lm_edge_set &t)
+{
+	return t.p_assembly->b_robust && t.p_assembly->t_robust.n_mode == SLAMPP_HIP_ROBUST_MODE_LOSS;
+}
+
+// the weight array the assembly and the initial damping take for a set: the caller's, or the handle's own (REFERENCE), or none
+const double *assembly_weights(const slampp_hip_lm_edge_set &t)
+{
+	if(!is_robust(t))
+		return t.p_weight_dev;
+	return (is_robust_loss(t))? 0 : t.p_assembly->d_robust_weight.p();
+}
+
+// behind a set's linearize: the weights into the handle's array, and in LOSS the set's Jacobians and errors times sqrt(w)
+int robustify(const slampp_hip_lm_edge_set &t)
+{
+	if(!is_robust(t))
+		return SLAMPP_HIP_OK;
+	const int n_result = slampp_hip_robust_weights_device_async(t.p_assembly, t.p_sigma_inv_dev, t.p_error_dev, 0);
+	if(n_result != SLAMPP_HIP_OK || !is_robust_loss(t))
+		return n_result;
+	return slampp_hip_robust_scale_device_async(t.p_assembly, 0, t.p_J0_dev, t.p_J1_dev, t.p_error_dev);
+}
+
+// errors at p_state_dev (with the Jacobians where b_jacobians is set) and the cost of every set into the parts: chi^2 with
+// the caller's weights, of a robust set chi^2 without weights (REFERENCE: SE3_Types.h:323-331) or the robust cost (LOSS), each
+// from the unscaled errors -- robustify() comes behind
 int errors_and_chi2(const slampp_hip_lm_problem &r, const double *p_state_dev, bool b_jacobians)
 {
 	for(int i = 0; i < r.n_sets; ++ i) {
@@ -117,9 +152,12 @@ int errors_and_chi2(const slampp_hip_lm_problem &r, const double *p_state_dev, b
 			t.p_params_dev, t.p_J0_dev, t.p_J1_dev, t.p_error_dev) : slampp_hip_edge_errors_device_async(t.p_assembly, t.n_edge_type,
 			p_state_dev, t.p_measurement_dev, t.p_params_dev, t.p_error_dev);
 		if(n_result == SLAMPP_HIP_OK) {
-			n_result = slampp_hip_chi_squared_device_async(t.p_assembly, t.p_sigma_inv_dev, t.p_error_dev, t.p_weight_dev,
-				r.p_chi_parts_dev + i);
+			n_result = (is_robust_loss(t))? slampp_hip_robust_chi_squared_device_async(t.p_assembly, t.p_sigma_inv_dev, t.p_error_dev,
+				r.p_chi_parts_dev + i) : slampp_hip_chi_squared_device_async(t.p_assembly, t.p_sigma_inv_dev, t.p_error_dev,
+				(is_robust(t))? 0 : t.p_weight_dev, r.p_chi_parts_dev + i);
 		}
+		if(n_result == SLAMPP_HIP_OK && b_jacobians)
+			n_result = robustify(t);
 		if(n_result != SLAMPP_HIP_OK)
 			return n_result;
 	}
@@ -135,7 +173,7 @@ void fill_edge_sets(const slampp_hip_lm_problem &r, slampp_hip_edge_set *p_sets)
 		p_sets[i].p_J1_dev = t.p_J1_dev;
 		p_sets[i].p_sigma_inv_dev = t.p_sigma_inv_dev;
 		p_sets[i].p_error_dev = t.p_error_dev;
-		p_sets[i].p_weight_dev = t.p_weight_dev;
+		p_sets[i].p_weight_dev = assembly_weights(t);
 	}
 }
 
@@ -313,6 +351,7 @@ int slampp_hip_lm_iterate_device_async(const slampp_hip_lm_problem *p_problem, i
 			const slampp_hip_lm_edge_set &t = r.p_sets[i];
 			LM_STEP(slampp_hip_linearize_device_async(t.p_assembly, t.n_edge_type, r.p_state_dev, t.p_measurement_dev, t.p_params_dev,
 				t.p_J0_dev, t.p_J1_dev, t.p_error_dev));
+			LM_STEP(robustify(t));
 		}
 		LM_STEP(slampp_hip_assemble_sets_device_async(p_sets, r.n_sets, r.n_unary_vertex, r.p_unary_factor, r.p_unary_error,
 			r.p_values_dev, r.p_eta_dev, 0));

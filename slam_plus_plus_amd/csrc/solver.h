@@ -105,6 +105,9 @@ struct slampp_hip_assembly {
 	slampp_hip_solver *p_solver;     // null once the solver is gone
 	slampp::CAssemblyState *p_state;
 	bool b_stale;                    // set_structure() was called since: the block offsets no longer apply
+	bool b_robust = false;           // slampp_hip_assembly_set_robust() left a specification (robust.h) ...
+	slampp_hip_robust t_robust;      // ... this one, checked ...
+	slampp::CDevArray<double> d_robust_weight; // ... and the handle's n_edges weights (released with the solver, which owns the device)
 };
 
 struct slampp_hip_solver {

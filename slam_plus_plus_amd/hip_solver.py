@@ -53,6 +53,12 @@ LM_STATUS_RUNNING, LM_STATUS_CONVERGED, LM_STATUS_NOT_POSDEF, LM_STATUS_BUDGET =
 (LM_TRACE_ALPHA, LM_TRACE_ERROR, LM_TRACE_RHO, LM_TRACE_DX_NORM, LM_TRACE_ACCEPTED, LM_TRACE_STATUS, LM_TRACE_LAST_ERROR,
  LM_TRACE_NU, LM_TRACE_RECORD) = range(9)
 LM_MAX_SETS = 8
+# SLAMPP_HIP_ROBUST_*: the loss functions (the reference's CHuberLoss, CCauchyLoss, CTukeyBiweightLoss, CWelschLoss), what their
+# argument is, and how the LM loop applies the weight; ROBUST_DEFAULT_PARAM: the reference's default a of each
+ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_TUKEY, ROBUST_WELSCH = 1, 2, 3, 4
+ROBUST_BASIS_ERROR_NORM, ROBUST_BASIS_CHI2, ROBUST_BASIS_MAHALANOBIS = 1, 2, 3
+ROBUST_MODE_REFERENCE, ROBUST_MODE_LOSS = 1, 2
+ROBUST_DEFAULT_PARAM = {ROBUST_HUBER: 1.345, ROBUST_CAUCHY: 2.385, ROBUST_TUKEY: 4.685, ROBUST_WELSCH: 2.985}
 
 
 def _hash_array(a: np.ndarray) -> int:
@@ -127,6 +133,11 @@ class LmProblem(C.Structure):
                 ("p_unary_error", C.c_void_p), ("p_state_dev", C.c_void_p), ("p_trial_dev", C.c_void_p), ("p_values_dev", C.c_void_p),
                 ("p_eta_dev", C.c_void_p), ("p_dx_dev", C.c_void_p), ("p_lm_dev", C.c_void_p), ("p_chi_parts_dev", C.c_void_p),
                 ("p_trace_dev", C.c_void_p), ("n_trace_capacity", C.c_int64)]
+
+
+class Robust(C.Structure):
+    """slampp_hip_robust"""
+    _fields_ = [("n_kernel", C.c_int), ("n_basis", C.c_int), ("n_mode", C.c_int), ("f_scale", C.c_double), ("f_param", C.c_double)]
 
 
 class PhaseTime(C.Structure):
@@ -221,6 +232,11 @@ ABI = {
     "slampp_hip_lm_commit_device_async": (C.c_int, [_P, _P, _P, _P]),
     "slampp_hip_lm_begin_device_async": (C.c_int, [C.POINTER(LmProblem), C.c_double, C.c_double, C.c_double, C.c_int, C.c_int]),
     "slampp_hip_lm_iterate_device_async": (C.c_int, [C.POINTER(LmProblem), C.c_int]),
+    "slampp_hip_assembly_set_robust": (C.c_int, [_P, C.POINTER(Robust)]),
+    "slampp_hip_assembly_robust_weights": (C.c_int, [_P, C.POINTER(_P)]),
+    "slampp_hip_robust_weights_device_async": (C.c_int, [_P, _P, _P, _P]),
+    "slampp_hip_robust_scale_device_async": (C.c_int, [_P, _P, _P, _P, _P]),
+    "slampp_hip_robust_chi_squared_device_async": (C.c_int, [_P, _P, _P, _P]),
     "slampp_hip_get_plan": (C.c_int, [_P, C.POINTER(PlanView)]),
     "slampp_hip_plan_create": (C.c_int, [C.POINTER(_P), C.c_int64, _P, _P, _P, C.c_int, C.c_int, C.c_int]),
     "slampp_hip_plan_get": (C.c_int, [_P, C.POINTER(PlanView), C.POINTER(Stats)]),
@@ -1110,6 +1126,46 @@ class CLambdaAssembly_HIP:
         self._solver._check(self._lib.slampp_hip_chi_squared_device_async(self._a, sigma_inv_ptr or None, error_ptr or None,
                                                                           weight_ptr or None, out_ptr or None))
 
+    def Set_Robust(self, kernel, basis: int = ROBUST_BASIS_ERROR_NORM, mode: int = ROBUST_MODE_REFERENCE, scale: float = 1.0,
+                   param: float = None) -> None:
+        """A robust kernel for this edge set (slampp_hip_assembly_set_robust): ``kernel`` ROBUST_HUBER, _CAUCHY, _TUKEY or
+        _WELSCH, w(s) of the reference's loss functions with a = ``param`` (None: the reference's default); ``basis`` what s is
+        -- ROBUST_BASIS_ERROR_NORM |err| / scale, _CHI2 err^T Sigma^-1 err / scale, _MAHALANOBIS sqrt(err^T Sigma^-1 err) /
+        scale; ``mode`` how the LM loop applies the weight -- ROBUST_MODE_REFERENCE as the reference's robust edges do, or
+        ROBUST_MODE_LOSS (MAHALANOBIS only), which minimises sum 2 scale^2 rho(s).  The reference's CEdgePose3D is
+        ``Set_Robust(ROBUST_HUBER, ROBUST_BASIS_ERROR_NORM, ROBUST_MODE_REFERENCE, 0.3, 1.345)``.  The handle then owns an
+        array of a weight per edge; ``Set_Robust(None)`` frees it and takes the kernel off."""
+        if kernel is None:
+            self._solver._check(self._lib.slampp_hip_assembly_set_robust(self._a, None))
+            return
+        spec = Robust(int(kernel), int(basis), int(mode), float(scale),
+                      float(ROBUST_DEFAULT_PARAM.get(int(kernel), 0.0) if param is None else param))
+        self._solver._check(self._lib.slampp_hip_assembly_set_robust(self._a, C.byref(spec)))
+
+    def Robust_Weights_ptr(self) -> int:
+        """The device pointer of the handle's weight array, 0 where no robust kernel is set (slampp_hip_assembly_robust_weights)."""
+        p = C.c_void_p()
+        self._solver._check(self._lib.slampp_hip_assembly_robust_weights(self._a, C.byref(p)))
+        return p.value or 0
+
+    def Robust_Weights_device(self, sigma_inv_ptr: int, error_ptr: int, weight_out_ptr: int = 0) -> None:
+        """w(s) of every edge into ``weight_out_ptr`` (0: the handle's array) from the errors Linearize_device wrote
+        (slampp_hip_robust_weights_device_async); ``sigma_inv_ptr`` may be 0 with ROBUST_BASIS_ERROR_NORM.  Enqueue-only."""
+        self._solver._check(self._lib.slampp_hip_robust_weights_device_async(self._a, sigma_inv_ptr or None, error_ptr or None,
+                                                                             weight_out_ptr or None))
+
+    def Robust_Scale_device(self, J0_ptr: int, J1_ptr: int, error_ptr: int, weight_ptr: int = 0) -> None:
+        """J0, J1 and the errors of every edge times sqrt(w) of the edge, in place (slampp_hip_robust_scale_device_async);
+        ``weight_ptr`` 0: the handle's array.  Enqueue-only."""
+        self._solver._check(self._lib.slampp_hip_robust_scale_device_async(self._a, weight_ptr or None, J0_ptr or None, J1_ptr or None,
+                                                                           error_ptr or None))
+
+    def Robust_Chi2_device(self, sigma_inv_ptr: int, error_ptr: int, out_ptr: int) -> None:
+        """*out = sum over the edges of 2 scale^2 rho(s) in a fixed order (slampp_hip_robust_chi_squared_device_async;
+        ROBUST_BASIS_MAHALANOBIS only).  Enqueue-only."""
+        self._solver._check(self._lib.slampp_hip_robust_chi_squared_device_async(self._a, sigma_inv_ptr or None, error_ptr or None,
+                                                                                 out_ptr or None))
+
 
 def Refresh_Lambda_sets_device(assemblies, pointer_sets, values_ptr: int, eta_ptr: int, unary_vertex: int = 0, unary_factor=None,
                                unary_error=None, accumulate: bool = False) -> None:
@@ -1139,7 +1195,9 @@ class CLevenbergMarquardt_HIP:
 
     ``edge_sets``: a list of dicts with ``assembly`` (a CLambdaAssembly_HIP of ``solver``), ``edge_type`` (EDGE_*),
     ``measurement`` [E, 3 | 6 | 2], ``sigma_inv`` [E, rd, rd] (every matrix column-major, as the assembly reads them), and
-    optionally ``params`` (five intrinsics per block column, EDGE_P2C_XYZ) and ``weight`` [E]; arrays or CUDA tensors.
+    optionally ``params`` (five intrinsics per block column, EDGE_P2C_XYZ) and ``weight`` [E]; arrays or CUDA tensors.  A set
+    may carry ``robust`` instead of ``weight``: a dict of the arguments of ``CLambdaAssembly_HIP.Set_Robust`` (``kernel``,
+    ``basis``, ``mode``, ``scale``, ``param``), which is set on the set's assembly; the loop then computes the weights itself.
     ``lam``: Lambda's block structure, as CLambdaAssembly_HIP takes it.
     ``vertex_ranges``: (VERTEX_*, first, last) triples covering every block column once.  ``unary``: (vertex, factor, error)
     with host arrays (error may be None), or None.  The object owns the state (``self.state``, a CUDA tensor of n_scalars
@@ -1177,6 +1235,10 @@ class CLevenbergMarquardt_HIP:
             z, sigma = tensor(s["measurement"]), tensor(s["sigma_inv"])
             e = z.numel() // md
             params, weight = tensor(s.get("params")), tensor(s.get("weight"))
+            if s.get("robust") is not None:
+                if weight is not None:
+                    raise ValueError("an edge set takes robust or weight, not both")
+                s["assembly"].Set_Robust(**s["robust"])
             J0, J1, err = scratch(e * rd * d0), scratch(e * rd * d1), scratch(e * rd)
             self._keep += [s["assembly"], z, sigma, params, weight, J0, J1, err]
             t = self._sets[i]
