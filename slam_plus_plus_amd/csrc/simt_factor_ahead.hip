@@ -14,8 +14,10 @@
 // -- some 330 dependent fp64 instructions with no load among them.  The loads of the column's own operands (L) further down
 // queue behind the fetch, which by then has had that stretch of arithmetic to arrive.  No touches, no second request of a line.
 //
-// The operations, their order and the selects on enc are factor_simt_kernel's, and so is what every store writes: L, inv(L_jj),
-// w and the flag are the same bits.  (Who stores the diagonal block differs: the lanes of a pair take half its columns each,
+// The operations and their order are factor_simt_kernel's because they are the same functions (simt_device.inl: row entries,
+// Cholesky and inverse, forward substitution, a block below the diagonal, the Lambda load of the blocks a set does not hold);
+// the selects on enc of a set's values are written here after simt_load_lambda_block's.  So is what every store writes: L,
+// inv(L_jj), w and the flag are the same bits.  (Who stores the diagonal block differs: the lanes of a pair take half its columns each,
 // where factor_simt_kernel leaves them to the first lane -- see there for why.)  Two lanes per task and even D only (the 8-byte loads of a half block stay apart; with one lane per task the
 // compiler merges the loads of a set past what a wait can count).  One wave a SIMD: VGPRs and AGPRs up to the file, no scratch.
 // Own translation unit (the register allocation of factor_simt_kernel moves with its neighbours: dense_tiles.hip says why).
@@ -37,8 +39,7 @@ struct TFactorAheadSet {
 };
 
 // requests of one fetch (16-byte loads of the diagonal block's columns down to their diagonal element and of b_j, 8-byte loads
-// of the half blocks), stores of half a block, and s_waitcnt's operand for "at most n vector memory operations outstanding"
-// (gfx9 layout: vmcnt in bits 3:0 and 15:14; expcnt and lgkmcnt left at their maxima: not waited for)
+// of the half blocks) and stores of half a block: what the written-out waits count (simt_wait_imm, simt_device.inl)
 template <int D, int AHEAD>
 constexpr int factor_ahead_fetch_loads()
 {
@@ -52,7 +53,6 @@ constexpr int factor_ahead_fetch_loads()
 template <int D> constexpr int factor_ahead_half_block_stores() { return D * ((D / 2) / 2 + (D / 2) % 2); }
 template <int D> constexpr int factor_ahead_diagonal_stores() { return D / 2 + (D / 2) * (D / 2); }
 template <int D> constexpr int factor_ahead_newer_stores() { return (factor_ahead_half_block_stores<D>() < factor_ahead_diagonal_stores<D>())? factor_ahead_half_block_stores<D>() : factor_ahead_diagonal_stores<D>(); }
-constexpr int factor_ahead_wait_imm(int n) { return ((n > 63)? 63 : n) % 16 | 7 << 4 | 15 << 8 | ((n > 63)? 63 : n) / 16 << 14; }
 
 // The set stays where its loads put it until the column's wait has passed: an empty asm that wants every value in the accumulation
 // half of the register file, which is where the allocator puts most of a set anyway -- without it the values were moved to
@@ -135,63 +135,6 @@ __device__ __forceinline__ void store_half_columns(double *p, const double (&m)[
 	}
 }
 
-// one block below the diagonal, from its Lambda values in acc: the update pairs, the product with inv(L_jj)^T, the store
-template <int D, int W>
-__device__ __forceinline__ void factor_ahead_block(double (&acc)[D / 2][D], const double (&x)[D][D], int &pc, int f_op, int r0, const int32_t *P,
-	const long long *T, double *L, double *p_out)
-{
-	enum { DH = D / 2 };
-	const int np = P[pc ++];
-	{
-		long long off_a = 0, off_b = 0;
-		if(np > 0) {
-			off_a = T[W * (f_op + P[pc])];
-			off_b = T[W * (f_op + P[pc + 1])];
-		}
-		for(int e = 0; e < np; ++ e) {
-			pc += 2;
-			double ca[D][DH], cb[D][D]; // ca[t][i] = L(i,c) element (r0 + i, t)
-			load_half_rows<D>(L + off_a, r0, ca);
-			load_block<D>(L + off_b, cb);
-			if(e + 1 < np) {
-				off_a = T[W * (f_op + P[pc])];
-				off_b = T[W * (f_op + P[pc + 1])];
-			}
-			#pragma unroll
-			for(int t = 0; t < D; ++ t) {
-				#pragma unroll
-				for(int i = 0; i < DH; ++ i) {
-					#pragma unroll
-					for(int q = 0; q < D; ++ q)
-						acc[i][q] -= ca[t][i] * cb[t][q];
-				}
-			}
-		}
-	}
-	// out = acc inv(L_jj)^T: out[i][q] = sum_{t <= q} acc[i][t] x[q][t] (x[r][c] = element (r, c) of the inverse)
-	#pragma unroll
-	for(int q = 0; q < D; ++ q) {
-		double out[DH];
-		#pragma unroll
-		for(int i = 0; i < DH; ++ i) {
-			double sum = 0;
-			#pragma unroll
-			for(int t = 0; t <= q; ++ t)
-				sum += acc[i][t] * x[q][t];
-			out[i] = sum;
-		}
-		if(DH % 2 == 0) {
-			#pragma unroll
-			for(int i = 0; i < DH; i += 2)
-				*reinterpret_cast<double2*>(p_out + r0 + i + q * D) = double2{out[i], out[i + 1]};
-		} else {
-			#pragma unroll
-			for(int i = 0; i < DH; ++ i)
-				p_out[r0 + i + q * D] = out[i];
-		}
-	}
-}
-
 // A chunk's table from memory to LDS, one wave: eight loads in flight a lane before the first is waited for.  (A loop of one load
 // and one store an entry is compiled to a wait per load: 27 trips to memory one after the other for a table of 1 700 entries, some
 // 6 us in front of the first column of every wave.)  n_lane: 0 .. 63
@@ -218,7 +161,6 @@ __device__ __forceinline__ void factor_ahead_stage_table(long long *p_dst, const
 // P: the chunk's program (wave-uniform: scalar loads); T: field f of this lane's task at T[W f]; n_half: which half of the rows
 // below the diagonal this lane takes; p_tm, n_tm: the clock samples of the wave that takes them (SIMT_TICK).  Returns whether
 // a pivot was not positive.
-#define SIMT_TICK() do { if(p_tm && n_tm < 32) p_tm[n_tm ++] = wall_clock64(); } while(0)
 template <int D, int W, bool b_linv, int AHEAD>
 __device__ __forceinline__ bool factor_ahead_columns(const int32_t *P, const long long *T, const int n_half, const double *__restrict__ A, double *L, double *Linv,
 	const double *__restrict__ b, double *w, long long *p_tm, int &n_tm)
@@ -231,7 +173,7 @@ __device__ __forceinline__ bool factor_ahead_columns(const int32_t *P, const lon
 	bool b_bad = false;
 	TFactorAheadSet<D, AHEAD> t_set;
 	factor_ahead_fetch<D, W, AHEAD>(t_set, 0, 0, P[pc], f_blk, r0, T, A, b); // prologue: the first column, waited for right away
-	__builtin_amdgcn_s_waitcnt(factor_ahead_wait_imm(0));
+	__builtin_amdgcn_s_waitcnt(simt_wait_imm(0));
 	factor_ahead_pin<D, AHEAD>(t_set); // (or the loads are moved past the wait, into the loop's preheader, and the loop is entered with the set pending)
 	for(int ci = 0; ci < n_cols; ++ ci) {
 		const int nb = P[pc], nr = P[pc + 1], n_touch = P[pc + 2];
@@ -242,7 +184,7 @@ __device__ __forceinline__ bool factor_ahead_columns(const int32_t *P, const lon
 		// the diagonal block and, of every block below it, operand loads (waited for where they were used: so was everything in
 		// front of them, the set included) and the stores of half a block: those may still be on their way -- the column before is
 		// not drained.  The compiler's own waits stay and add what correctness needs: with this one in front of them it adds none.
-		__builtin_amdgcn_s_waitcnt(factor_ahead_wait_imm(factor_ahead_newer_stores<D>()));
+		__builtin_amdgcn_s_waitcnt(simt_wait_imm(factor_ahead_newer_stores<D>()));
 		factor_ahead_pin<D, AHEAD>(t_set);
 		double a[D][D], y[D], acc[AHEAD][DH][D]; // a: lower triangle of the diagonal block
 		{
@@ -269,95 +211,18 @@ __device__ __forceinline__ bool factor_ahead_columns(const int32_t *P, const lon
 				}
 			}
 		}
-		{ // blocks L(j,c) of block row j: update of the diagonal block and of the right-hand side
-			long long off = 0, yoff = 0;
-			if(nr > 0) {
-				off = T[W * (f_op + P[pc])];
-				yoff = T[W * (f_y + P[pc + 1])];
-			}
-			for(int e = 0; e < nr; ++ e) {
-				pc += 2;
-				double c[D][D], yc[D];
-				load_block<D>(L + off, c);
-				load_column<D>(w + yoff, yc);
-				if(e + 1 < nr) {
-					off = T[W * (f_op + P[pc])];
-					yoff = T[W * (f_y + P[pc + 1])];
-				}
-				#pragma unroll
-				for(int t = 0; t < D; ++ t) {
-					#pragma unroll
-					for(int r = 0; r < D; ++ r) {
-						#pragma unroll
-						for(int q = 0; q <= r; ++ q)
-							a[r][q] -= c[t][r] * c[t][q];
-						y[r] -= c[t][r] * yc[t];
-					}
-				}
-			}
-		}
+		simt_row_entries<D, W>(a, y, pc, nr, f_op, f_y, P, T, L, w); // blocks L(j,c) of block row j
 		SIMT_TICK(); // Lambda, row entries
 		// the next column's set: requested here, where nothing but arithmetic follows for a while
 		if(ci + 1 < n_cols) {
 			asm volatile("" ::: "memory");
 			factor_ahead_fetch<D, W, AHEAD>(t_set, ci + 1, blk0 + nb, P[pc_next_column(P, pc, nb, 0)], f_blk, r0, T, A, b);
 		}
-		// Cholesky of the diagonal block, in place; rd[k] = 1 / L(k,k)
-		double rd[D];
-		#pragma unroll
-		for(int k = 0; k < D; ++ k) {
-			double piv = a[k][k];
-			const bool b_neg = !(piv > 0); // also catches NaN
-			b_bad = b_bad || b_neg;
-			piv = b_neg? 1.0 : piv;
-			const double s = simt_rsqrt(piv);
-			rd[k] = s;
-			a[k][k] = piv * s;
-			#pragma unroll
-			for(int r = k + 1; r < D; ++ r)
-				a[r][k] *= s;
-			#pragma unroll
-			for(int q = k + 1; q < D; ++ q) {
-				#pragma unroll
-				for(int r = q; r < D; ++ r)
-					a[r][q] -= a[r][k] * a[q][k];
-			}
-		}
-		// its inverse (lower triangular) and y_j = inv(L_jj) (b_j - sum L(j,c) y_c)
-		double x[D][D];
-		#pragma unroll
-		for(int c = 0; c < D; ++ c) {
-			#pragma unroll
-			for(int r = 0; r < D; ++ r) {
-				if(r < c)
-					x[r][c] = 0.0;
-				else if(r == c)
-					x[r][c] = rd[r];
-				else {
-					double sum = 0;
-					#pragma unroll
-					for(int t = c; t < r; ++ t)
-						sum += a[r][t] * x[t][c];
-					x[r][c] = -sum * rd[r];
-				}
-			}
-		}
+		double x[D][D]; // inv(L_jj)
+		simt_cholesky_inverse<D>(a, x, b_bad);
 		{
 			double yn[D];
-			#pragma unroll
-			for(int r = 0; r < D; ++ r) {
-				double sum = 0;
-				#pragma unroll
-				for(int t = 0; t <= r; ++ t)
-					sum += x[r][t] * y[t];
-				yn[r] = sum;
-			}
-			#pragma unroll
-			for(int r = 0; r < D; ++ r) {
-				#pragma unroll
-				for(int q = r + 1; q < D; ++ q)
-					a[r][q] = 0.0; // the factor block is stored whole, zeros above its diagonal
-			}
+			simt_forward_substitution<D>(yn, a, x, y);
 			// The lanes of a pair hold the same numbers: each stores half the columns of the diagonal block (and of its inverse), both
 			// store y_j -- the same values to the same place.  No lane is masked out, so no path goes round these stores, and the
 			// compiler can count them behind the fetch on every path to the next column's wait (with "if(n_half == 0)" around them it
@@ -375,26 +240,18 @@ __device__ __forceinline__ bool factor_ahead_columns(const int32_t *P, const lon
 		#pragma unroll
 		for(int k = 0; k < AHEAD; ++ k) {
 			if(k + 1 < nb) {
-				factor_ahead_block<D, W>(acc[k], x, pc, f_op, r0, P, T, L, L + l_base + (k + 1) * DD);
+				const int np = P[pc ++];
+				simt_update_pairs<D, W, 2>(acc[k], pc, np, f_op, r0, P, T, L);
+				simt_block_product<D, 2>(acc[k], x, r0, L + l_base + (k + 1) * DD);
 				SIMT_TICK(); // one sub-diagonal block
 			}
 		}
 		for(int kb = AHEAD + 1; kb < nb; ++ kb) { // the blocks the set does not hold: Lambda from memory, as factor_simt_kernel
-			const long long enc = T[W * (f_blk + blk0 + kb)];
+			const int np = P[pc ++];
 			double acc_more[DH][D];
-			{
-				const double *src = A + ((enc < 0)? 0 : (enc >> 1));
-				const bool b_trans = (enc & 1) != 0, b_have = enc >= 0;
-				#pragma unroll
-				for(int i = 0; i < DH; ++ i) {
-					#pragma unroll
-					for(int q = 0; q < D; ++ q) {
-						const double f = src[b_trans? q + (r0 + i) * D : (r0 + i) + q * D];
-						acc_more[i][q] = b_have? f : 0.0;
-					}
-				}
-			}
-			factor_ahead_block<D, W>(acc_more, x, pc, f_op, r0, P, T, L, L + l_base + kb * DD);
+			simt_load_lambda_block<D, 2>(acc_more, T[W * (f_blk + blk0 + kb)], r0, A);
+			simt_update_pairs<D, W, 2>(acc_more, pc, np, f_op, r0, P, T, L);
+			simt_block_product<D, 2>(acc_more, x, r0, L + l_base + kb * DD);
 			SIMT_TICK(); // one sub-diagonal block
 		}
 		blk0 += nb;
@@ -403,7 +260,6 @@ __device__ __forceinline__ bool factor_ahead_columns(const int32_t *P, const lon
 	}
 	return b_bad;
 }
-#undef SIMT_TICK
 
 template <int D, int W, int LPT, bool b_linv, int AHEAD> // (the arguments, programs, tables and LDS layout of factor_simt_kernel)
 __global__ void __launch_bounds__(64)
@@ -424,14 +280,8 @@ factor_simt_kernel_ahead(const TSimtChunk *__restrict__ chunks, const int32_t *_
 	if(int(threadIdx.x) >= W * LPT)
 		return; // (no barrier below)
 	const int n_half = int(threadIdx.x) & 1; // which half of the rows below the diagonal this lane takes
-	long long *p_tm = 0; // development aid (SLAMPP_HIP_STAGE_TIMING): clock samples of a wave in the middle of the grid
 	int n_tm = 0;
-	if(p_timing && blockIdx.x == gridDim.x / 2 && threadIdx.x == 0) {
-		const unsigned long long n_tm_record = atomicAdd((unsigned long long*)p_timing, 1ull);
-		p_tm = (n_tm_record < 4096)? p_timing + 1 + 32 * n_tm_record : 0; // the buffer holds 4096 launch records: later launches go unrecorded
-		if(p_tm)
-			p_tm[n_tm ++] = wall_clock64();
-	}
+	long long *p_tm = simt_timing_begin(p_timing, n_tm); // development aid (SLAMPP_HIP_STAGE_TIMING)
 	const bool b_bad = factor_ahead_columns<D, W, b_linv, AHEAD>(prog + ch.prog_off, s_tab + threadIdx.x / LPT, n_half, A, L, Linv, b, w, p_tm, n_tm);
 	if(b_bad)
 		atomicOr(p_flag, 1);
@@ -456,14 +306,8 @@ factor_simt_kernel_branches(const TSimtBranchGroup *__restrict__ groups, const i
 	extern __shared__ long long s_tab[]; // two regions: a wave's segment table of per-lane offsets
 	const int n_wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6), n_lane = int(threadIdx.x) & 63; // (n_wave in a scalar register: what follows from it stays wave-uniform)
 	long long *s_mine = s_tab + n_wave * n_region;
-	long long *p_tm = 0; // development aid (SLAMPP_HIP_STAGE_TIMING): clock samples of the first wave of a workgroup in the middle of the grid
 	int n_tm = 0;
-	if(p_timing && blockIdx.x == gridDim.x / 2 && threadIdx.x == 0) {
-		const unsigned long long n_tm_record = atomicAdd((unsigned long long*)p_timing, 1ull);
-		p_tm = (n_tm_record < 4096)? p_timing + 1 + 32 * n_tm_record : 0; // the buffer holds 4096 launch records: later launches go unrecorded
-		if(p_tm)
-			p_tm[n_tm ++] = wall_clock64();
-	}
+	long long *p_tm = simt_timing_begin(p_timing, n_tm); // development aid (SLAMPP_HIP_STAGE_TIMING): the first wave of the workgroup
 	bool b_bad = false;
 	for(int n_pass = 0; n_pass < 2; ++ n_pass) { // the bins side by side, then the joins on wave 0
 		const TSimtChunk ch = groups[blockIdx.x].seg[n_pass? 2 : n_wave];
@@ -506,21 +350,10 @@ bool factor_simt_branches_exists(int n_dim, int n_width)
 
 int factor_simt_branches_groups(int n_dim, int n_width, int n_lds_bytes)
 {
-	int n_device = 0, n_cus = 0, n_groups = 0;
-	if(!factor_simt_branches_exists(n_dim, n_width) || n_lds_bytes <= 0 || hipGetDevice(&n_device) != hipSuccess ||
-	   hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, n_device) != hipSuccess || n_cus <= 0) {
-		(void)hipGetLastError();
+	if(!factor_simt_branches_exists(n_dim, n_width) || n_lds_bytes <= 0)
 		return 0;
-	}
-	for(int b_store_linv = 0; b_store_linv < 2; ++ b_store_linv) { // (the smaller answer of the two instantiations)
-		int n_blocks = 0;
-		if(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_blocks, p_Factor_Branches_Kernel(n_dim, n_width, b_store_linv != 0), 128, size_t(n_lds_bytes)) != hipSuccess || n_blocks <= 0) {
-			(void)hipGetLastError();
-			return 0;
-		}
-		n_groups = (b_store_linv)? std::min(n_groups, n_cus * n_blocks) : n_cus * n_blocks;
-	}
-	return n_groups;
+	return std::min(simt_resident_workgroups(p_Factor_Branches_Kernel(n_dim, n_width, false), 128, n_lds_bytes),
+		simt_resident_workgroups(p_Factor_Branches_Kernel(n_dim, n_width, true), 128, n_lds_bytes)); // (the smaller answer of the two instantiations)
 }
 
 bool launch_factor_simt_branches(const TSimtBranchGroup *groups, int n_groups, int n_width, int n_lds_bytes, const int32_t *prog, const int64_t *tab, int n_dim,
@@ -562,21 +395,10 @@ bool factor_simt_ahead_exists(int n_dim, int n_width)
 
 int factor_simt_ahead_waves(int n_dim, int n_width, int n_lds_bytes)
 {
-	int n_device = 0, n_cus = 0, n_waves = 0;
-	if(!factor_simt_ahead_exists(n_dim, n_width) || n_lds_bytes < 0 || hipGetDevice(&n_device) != hipSuccess ||
-	   hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, n_device) != hipSuccess || n_cus <= 0) {
-		(void)hipGetLastError();
+	if(!factor_simt_ahead_exists(n_dim, n_width))
 		return 0;
-	}
-	for(int b_store_linv = 0; b_store_linv < 2; ++ b_store_linv) { // (the smaller answer of the two instantiations)
-		int n_blocks = 0;
-		if(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_blocks, p_Factor_Ahead_Kernel(n_dim, n_width, b_store_linv != 0), 64, size_t(n_lds_bytes)) != hipSuccess || n_blocks <= 0) {
-			(void)hipGetLastError();
-			return 0;
-		}
-		n_waves = (b_store_linv)? std::min(n_waves, n_cus * n_blocks) : n_cus * n_blocks; // (a workgroup is one wave)
-	}
-	return n_waves;
+	return std::min(simt_resident_workgroups(p_Factor_Ahead_Kernel(n_dim, n_width, false), 64, n_lds_bytes),
+		simt_resident_workgroups(p_Factor_Ahead_Kernel(n_dim, n_width, true), 64, n_lds_bytes)); // (the smaller answer of the two instantiations; a workgroup is one wave)
 }
 
 bool launch_factor_simt_ahead(const TSimtChunk *chunks, int n_chunks, int n_width, int n_lds_bytes, const int32_t *prog, const int64_t *tab, int n_dim,

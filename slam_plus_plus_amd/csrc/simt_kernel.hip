@@ -18,6 +18,9 @@
 //
 // Arithmetic as in the other factor kernels (left-looking, one writer per block, fixed summation order); results
 // differ from theirs in the last bits only through the order of the sums inside a 6-term dot product.
+// The sums themselves -- row entries, Cholesky and inverse, the blocks below the diagonal, the backward pass's products and
+// solve -- are written once, in simt_device.inl, for the kernels here and their forms in simt_factor_ahead.hip: that is why
+// the forms store the same bits.  The kernels hold what differs between the forms: where the operands come from and when.
 // Own translation unit (see dense_tiles.hip for why).
 #include <hip/hip_runtime.h>
 #include "sparse_kernels.h"
@@ -53,15 +56,8 @@ factor_simt_kernel(const TSimtChunk *__restrict__ chunks, const int32_t *__restr
 	const int n_half = (LPT == 2)? int(threadIdx.x) & 1 : 0; // which half of the rows below the diagonal this lane takes
 	enum { DH = (LPT == 2)? D / 2 : D };
 	const int r0 = n_half * DH;
-	long long *p_tm = 0; // development aid (SLAMPP_HIP_STAGE_TIMING): clock samples of a wave in the middle of the grid
 	int n_tm = 0;
-	if(p_timing && blockIdx.x == gridDim.x / 2 && threadIdx.x == 0) {
-		const unsigned long long n_tm_record = atomicAdd((unsigned long long*)p_timing, 1ull);
-		p_tm = (n_tm_record < 4096)? p_timing + 1 + 32 * n_tm_record : 0; // the buffer holds 4096 launch records: later launches go unrecorded
-		if(p_tm)
-			p_tm[n_tm ++] = wall_clock64();
-	}
-#define SIMT_TICK() do { if(p_tm && n_tm < 32) p_tm[n_tm ++] = wall_clock64(); } while(0)
+	long long *p_tm = simt_timing_begin(p_timing, n_tm); // development aid (SLAMPP_HIP_STAGE_TIMING)
 	const int32_t *P = prog + ch.prog_off;                 // wave-uniform: scalar loads
 	const long long *T = s_tab + threadIdx.x / LPT;        // field f of this lane's task at T[W f]
 	const int n_cols = P[0], n_blocks = P[1], n_ops = P[2];
@@ -101,94 +97,17 @@ factor_simt_kernel(const TSimtChunk *__restrict__ chunks, const int32_t *__restr
 			}
 			load_column<D>(b + cs_src, y);
 		}
-		{ // blocks L(j,c) of block row j: update of the diagonal block and of the right-hand side; the offsets of entry
-			// e + 1 are fetched while entry e is being worked on, and a block is requested whole before its first product
-			long long off = 0, yoff = 0;
-			if(nr > 0) {
-				off = T[W * (f_op + P[pc])];
-				yoff = T[W * (f_y + P[pc + 1])];
-			}
-			for(int e = 0; e < nr; ++ e) {
-				pc += 2;
-				double c[D][D], yc[D];
-				load_block<D>(L + off, c);
-				load_column<D>(w + yoff, yc);
-				if(e + 1 < nr) {
-					off = T[W * (f_op + P[pc])];
-					yoff = T[W * (f_y + P[pc + 1])];
-				}
-				#pragma unroll
-				for(int t = 0; t < D; ++ t) {
-					#pragma unroll
-					for(int r = 0; r < D; ++ r) {
-						#pragma unroll
-						for(int q = 0; q <= r; ++ q)
-							a[r][q] -= c[t][r] * c[t][q];
-						y[r] -= c[t][r] * yc[t];
-					}
-				}
-			}
-		}
+		simt_row_entries<D, W>(a, y, pc, nr, f_op, f_y, P, T, L, w);
 		SIMT_TICK(); // Lambda, row entries
-		// Cholesky of the diagonal block, in place; rd[k] = 1 / L(k,k)
-		double rd[D];
-		#pragma unroll
-		for(int k = 0; k < D; ++ k) {
-			double piv = a[k][k];
-			const bool b_neg = !(piv > 0); // also catches NaN
-			b_bad = b_bad || b_neg;
-			piv = b_neg? 1.0 : piv;
-			const double s = simt_rsqrt(piv);
-			rd[k] = s;
-			a[k][k] = piv * s;
-			#pragma unroll
-			for(int r = k + 1; r < D; ++ r)
-				a[r][k] *= s;
-			#pragma unroll
-			for(int q = k + 1; q < D; ++ q) {
-				#pragma unroll
-				for(int r = q; r < D; ++ r)
-					a[r][q] -= a[r][k] * a[q][k];
-			}
-		}
-		// its inverse (lower triangular) and y_j = inv(L_jj) (b_j - sum L(j,c) y_c)
-		double x[D][D];
-		#pragma unroll
-		for(int c = 0; c < D; ++ c) {
-			#pragma unroll
-			for(int r = 0; r < D; ++ r) {
-				if(r < c)
-					x[r][c] = 0.0;
-				else if(r == c)
-					x[r][c] = rd[r];
-				else {
-					double sum = 0;
-					#pragma unroll
-					for(int t = c; t < r; ++ t)
-						sum += a[r][t] * x[t][c];
-					x[r][c] = -sum * rd[r];
-				}
-			}
-		}
+		double x[D][D]; // inv(L_jj)
+		simt_cholesky_inverse<D>(a, x, b_bad);
 		{
 			double yn[D];
-			#pragma unroll
-			for(int r = 0; r < D; ++ r) {
-				double sum = 0;
-				#pragma unroll
-				for(int t = 0; t <= r; ++ t)
-					sum += x[r][t] * y[t];
-				yn[r] = sum;
-			}
-			#pragma unroll
-			for(int r = 0; r < D; ++ r) {
-				if(n_half == 0)
-					w[cs_new + r] = yn[r];
-				#pragma unroll
-				for(int q = r + 1; q < D; ++ q)
-					a[r][q] = 0.0; // the factor block is stored whole, zeros above its diagonal
-			}
+			simt_forward_substitution<D>(yn, a, x, y);
 			if(n_half == 0) { // (the lanes of a pair hold the same numbers)
+				#pragma unroll
+				for(int r = 0; r < D; ++ r)
+					w[cs_new + r] = yn[r];
 				store_block<D>(L + l_base, a);
 				if constexpr(b_linv)
 					store_block<D>(Linv + linv_off, x);
@@ -199,91 +118,32 @@ factor_simt_kernel(const TSimtChunk *__restrict__ chunks, const int32_t *__restr
 		// its DH rows of the block (inv(L_jj) is in its own registers: x above)
 		for(int kb = 1; kb < nb; ++ kb) {
 			const int np = P[pc ++];
-			const long long enc = T[W * (f_blk + blk0 + kb)];
 			double acc[DH][D];
-			{
-				const double *src = A + ((enc < 0)? 0 : (enc >> 1));
-				const bool b_trans = (enc & 1) != 0, b_have = enc >= 0;
-				if constexpr(LPT == 1) {
-					double v[D][D]; // v[c][r] = stored element (r, c)
-					#pragma unroll
-					for(int c = 0; c < D; ++ c)
-						load_column<D>(src + c * D, v[c]);
-					#pragma unroll
-					for(int r = 0; r < DH; ++ r) {
-						#pragma unroll
-						for(int q = 0; q < D; ++ q)
-							acc[r][q] = b_have? (b_trans? v[r][q] : v[q][r]) : 0.0;
-					}
-				} else {
-					// element (r0 + i, q) of the block: stored at (r0 + i) + q D, or transposed at q + (r0 + i) D
-					#pragma unroll
-					for(int i = 0; i < DH; ++ i) {
-						#pragma unroll
-						for(int q = 0; q < D; ++ q) {
-							const double f = src[b_trans? q + (r0 + i) * D : (r0 + i) + q * D];
-							acc[i][q] = b_have? f : 0.0;
-						}
-					}
-				}
-			}
-			{
-				long long off_a = 0, off_b = 0;
-				if(np > 0) {
-					off_a = T[W * (f_op + P[pc])];
-					off_b = T[W * (f_op + P[pc + 1])];
-				}
-				for(int e = 0; e < np; ++ e) {
-					pc += 2;
-					double ca[D][DH], cb[D][D]; // ca[t][i] = L(i,c) element (r0 + i, t)
-					if constexpr(LPT == 1) {
-						double full[D][D];
-						load_block<D>(L + off_a, full);
-						#pragma unroll
-						for(int t = 0; t < D; ++ t) {
-							#pragma unroll
-							for(int i = 0; i < DH; ++ i)
-								ca[t][i] = full[t][i];
-						}
-					} else
-						load_half_rows<D>(L + off_a, r0, ca);
-					load_block<D>(L + off_b, cb);
-					if(e + 1 < np) {
-						off_a = T[W * (f_op + P[pc])];
-						off_b = T[W * (f_op + P[pc + 1])];
-					}
-					#pragma unroll
-					for(int t = 0; t < D; ++ t) {
-						#pragma unroll
-						for(int i = 0; i < DH; ++ i) {
-							#pragma unroll
-							for(int q = 0; q < D; ++ q)
-								acc[i][q] -= ca[t][i] * cb[t][q];
-						}
-					}
-				}
-			}
-			// out = acc inv(L_jj)^T: out[i][q] = sum_{t <= q} acc[i][t] x[q][t] (x[r][c] = element (r, c) of the inverse)
+			simt_load_lambda_block<D, LPT>(acc, T[W * (f_blk + blk0 + kb)], r0, A);
+			simt_update_pairs<D, W, LPT>(acc, pc, np, f_op, r0, P, T, L);
 			double *p_out = L + l_base + kb * DD;
-			#pragma unroll
-			for(int q = 0; q < D; ++ q) {
-				double out[DH];
+			if constexpr(D % 2 == 0)
+				simt_block_product<D, LPT>(acc, x, r0, p_out);
+			else {
+				// Odd D (one lane per task, a whole block a lane, scalar stores) has no other form to agree with, and D = 7 fills the
+				// VGPR file: through simt_block_product the same sums reach the scheduler in another order and the allocator parks
+				// two to four more values in AGPRs (profiles/simt_shared_arith_isa.txt).  So these kernels keep the product as they
+				// had it: out[r][q] = sum_{t <= q} acc[r][t] x[q][t], the sums simt_block_product writes.
+				static_assert(LPT == 1, "odd D: one lane per task, the lane has all D rows of the block");
 				#pragma unroll
-				for(int i = 0; i < DH; ++ i) {
-					double sum = 0;
+				for(int q = 0; q < D; ++ q) {
+					double out[D];
 					#pragma unroll
-					for(int t = 0; t <= q; ++ t)
-						sum += acc[i][t] * x[q][t];
-					out[i] = sum;
-				}
-				if(DH % 2 == 0 && D % 2 == 0) {
+					for(int r = 0; r < D; ++ r) {
+						double sum = 0;
+						#pragma unroll
+						for(int t = 0; t <= q; ++ t)
+							sum += acc[r][t] * x[q][t];
+						out[r] = sum;
+					}
 					#pragma unroll
-					for(int i = 0; i < DH; i += 2)
-						*reinterpret_cast<double2*>(p_out + r0 + i + q * D) = double2{out[i], out[i + 1]};
-				} else {
-					#pragma unroll
-					for(int i = 0; i < DH; ++ i)
-						p_out[r0 + i + q * D] = out[i];
+					for(int r = 0; r < D; ++ r)
+						p_out[r + q * D] = out[r];
 				}
 			}
 			SIMT_TICK(); // one sub-diagonal block
@@ -420,57 +280,24 @@ backward_simt_kernel(const TSimtChunk *__restrict__ chunks, const int32_t *__res
 		asm volatile("" ::: "memory");
 		double rd[D];
 		#pragma unroll
-		for(int q = 0; q < D; ++ q) {
-			const double d = a[q][q];
-			double r = __builtin_amdgcn_rcp(d);
-			r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
-			r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
-			rd[q] = r;
-		}
+		for(int q = 0; q < D; ++ q)
+			rd[q] = simt_refined_rcp(a[q][q]);
 		for(int kb = 1; kb < nb; ++ kb) {
 			const long long xcs = T[W * (3 * n_cols + n_blk0 + kb - 1)];
 			const int n_local = p_local[n_blk0 + kb - 1]; // (wave-uniform)
 			double c[D][D], xi[D];
 			load_block<D>(L + l_base + kb * DD, c); // c[q][r] = L(i,j)(r, q)
-			if(n_local >= 0) {
-				#pragma unroll
-				for(int r = 0; r < D; ++ r)
-					xi[r] = s_x[(n_local * D + r) * W];
-			} else
+			if(n_local >= 0)
+				simt_local_x<D, W>(xi, s_x, n_local);
+			else
 				load_column<D>(w + xcs, xi);
-			#pragma unroll
-			for(int q = 0; q < D; ++ q) {
-				#pragma unroll
-				for(int r = 0; r < D; ++ r)
-					acc[q] -= c[q][r] * xi[r];
-			}
+			simt_backward_block<D>(acc, c, xi);
 		}
 		double x[D];
-		#pragma unroll
-		for(int q = D - 1; q >= 0; -- q) {
-			double sum = acc[q];
-			#pragma unroll
-			for(int r = q + 1; r < D; ++ r)
-				sum -= a[q][r] * x[r];
-			x[q] = sum * rd[q];
-		}
-		#pragma unroll
-		for(int q = 0; q < D; ++ q)
-			s_x[(ci * D + q) * W] = x[q];
+		simt_solve_transposed<D>(x, acc, a, rd);
+		simt_store_local_x<D, W>(s_x, ci, x);
 		f_touched += f_touch_now; // (used here: nothing of this column waits for the touches)
-		if(D % 2 == 0) {
-			#pragma unroll
-			for(int q = 0; q < D; q += 2) {
-				*reinterpret_cast<double2*>(w + cs_new + q) = double2{x[q], x[q + 1]};
-				*reinterpret_cast<double2*>(x_out + cs_src + q) = double2{x[q], x[q + 1]};
-			}
-		} else {
-			#pragma unroll
-			for(int q = 0; q < D; ++ q) {
-				w[cs_new + q] = x[q];
-				x_out[cs_src + q] = x[q];
-			}
-		}
+		simt_store_x<D>(w + cs_new, x_out + cs_src, x);
 		n_blk_end = n_blk0;
 	}
 	if(f_touched == 1.2345e301) // (never: the sum only has to be used)
@@ -490,7 +317,8 @@ backward_simt_kernel(const TSimtChunk *__restrict__ chunks, const int32_t *__res
 // registers (108 doubles each at D = 6 with two blocks: 512 registers in all, one wave a SIMD, no scratch; an x per block, 114
 // doubles a set, spilled -- DESIGN.md section 10).  Columns with more blocks fetch the rest themselves, SIMT_BWD_AHEAD at a time
 // into the set they are solving from, all before the first product: one more trip, and this one is waited for.  The arithmetic,
-// its order and every store are backward_simt_kernel's: the results are the same bits.  No touches.
+// its order and every store are backward_simt_kernel's, by way of the same functions of simt_device.inl (the solve with L_jj^T
+// excepted: see bwd_ahead_solve): the results are the same bits.  No touches.
 template <int D, int AHEAD>
 struct TBwdAheadSet {
 	double y[D], a[D][D], c[AHEAD][D][D], xs[D]; // xs: x of the first of those blocks' rows that lies outside the task; a[q][r] = L_jj(r, q), c[k][q][r] = L(i_k,j)(r, q)
@@ -533,9 +361,8 @@ __device__ __forceinline__ void bwd_ahead_fetch(TBwdAheadSet<D, AHEAD> &s, int c
 	asm volatile("" ::: "memory"); // (the requests go out here, not where the scheduler would like them: next to their use)
 }
 
-// requests of one fetch (even D: 16-byte loads, of L_jj those that hold an element of its lower triangle: load_lower), stores
-// of one solve, and s_waitcnt's operand for "at most n vector memory operations
-// outstanding" (gfx9 layout: vmcnt in bits 3:0 and 15:14; expcnt and lgkmcnt left at their maxima: not waited for)
+// requests of one fetch (even D: 16-byte loads, of L_jj those that hold an element of its lower triangle: load_lower) and
+// stores of one solve: what the written-out waits count (simt_wait_imm, simt_device.inl)
 template <int D, int AHEAD>
 constexpr int bwd_ahead_fetch_loads()
 {
@@ -547,7 +374,6 @@ constexpr int bwd_ahead_fetch_loads()
 	return n + AHEAD * (D * D / 2) + D / 2;
 }
 template <int D> constexpr int bwd_ahead_solve_stores() { return (D % 2 == 0)? D : 2 * D; }
-constexpr int bwd_ahead_wait_imm(int n) { return ((n > 63)? 63 : n) % 16 | 7 << 4 | 15 << 8 | ((n > 63)? 63 : n) / 16 << 14; }
 
 template <int D, int W, int AHEAD, int N_NEWER /* vector memory operations issued since the set's fetch, at the least */>
 __device__ __forceinline__ void bwd_ahead_solve(TBwdAheadSet<D, AHEAD> &s, int ci, int n_cols, const int32_t *p_local, const long long *T, double *s_x,
@@ -557,15 +383,10 @@ __device__ __forceinline__ void bwd_ahead_solve(TBwdAheadSet<D, AHEAD> &s, int c
 	// The one wait of the column, written out: everything older than the N_NEWER newest requests -- this set -- has arrived.  The
 	// compiler's own waits stay (it adds what correctness needs), but where paths of different load counts meet, behind the loop
 	// of the remaining blocks, it no longer finds this set pending and asks for nothing: it asked for vmcnt(1) there.
-	__builtin_amdgcn_s_waitcnt(bwd_ahead_wait_imm(N_NEWER));
+	__builtin_amdgcn_s_waitcnt(simt_wait_imm(N_NEWER));
 	#pragma unroll
-	for(int q = 0; q < D; ++ q) { // the reciprocals take the diagonal's place (registers)
-		const double d = s.a[q][q];
-		double r = __builtin_amdgcn_rcp(d);
-		r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
-		r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
-		s.a[q][q] = r;
-	}
+	for(int q = 0; q < D; ++ q) // the reciprocals take the diagonal's place (registers)
+		s.a[q][q] = simt_refined_rcp(s.a[q][q]);
 	double acc[D];
 	#pragma unroll
 	for(int q = 0; q < D; ++ q)
@@ -574,24 +395,17 @@ __device__ __forceinline__ void bwd_ahead_solve(TBwdAheadSet<D, AHEAD> &s, int c
 	for(int k = 0; k < AHEAD; ++ k) {
 		if(k + 1 < s.nb) {
 			double xi[D];
-			if(s.n_local[k] >= 0) { // a row inside the task: x from LDS
-				#pragma unroll
-				for(int r = 0; r < D; ++ r)
-					xi[r] = s_x[(s.n_local[k] * D + r) * W];
-			} else if(s.n_xk == k) {
+			if(s.n_local[k] >= 0) // a row inside the task: x from LDS
+				simt_local_x<D, W>(xi, s_x, s.n_local[k]);
+			else if(s.n_xk == k) {
 				#pragma unroll
 				for(int r = 0; r < D; ++ r)
 					xi[r] = s.xs[r];
 			} else { // a second row outside the task: fetched here, and waited for
 				load_column<D>(w + T[W * (3 * n_cols + s.n_blk0 + k)], xi);
-				__builtin_amdgcn_s_waitcnt(bwd_ahead_wait_imm(0));
+				__builtin_amdgcn_s_waitcnt(simt_wait_imm(0));
 			}
-			#pragma unroll
-			for(int q = 0; q < D; ++ q) {
-				#pragma unroll
-				for(int r = 0; r < D; ++ r)
-					acc[q] -= s.c[k][q][r] * xi[r];
-			}
+			simt_backward_block<D>(acc, s.c[k], xi);
 		}
 	}
 	const long long l_base = (s.nb > AHEAD + 1)? T[W * (3 * ci)] : 0;
@@ -602,29 +416,23 @@ __device__ __forceinline__ void bwd_ahead_solve(TBwdAheadSet<D, AHEAD> &s, int c
 			if(kb + i < s.nb) {
 				load_block<D>(L + l_base + (kb + i) * DD, s.c[i]);
 				const int n_local = p_local[s.n_blk0 + kb + i - 1];
-				if(n_local >= 0) {
-					#pragma unroll
-					for(int r = 0; r < D; ++ r)
-						xr[i][r] = s_x[(n_local * D + r) * W];
-				} else
+				if(n_local >= 0)
+					simt_local_x<D, W>(xr[i], s_x, n_local);
+				else
 					load_column<D>(w + T[W * (3 * n_cols + s.n_blk0 + kb + i - 1)], xr[i]);
 			}
 		}
 		asm volatile("" ::: "memory"); // (all of them requested before the first product)
-		__builtin_amdgcn_s_waitcnt(bwd_ahead_wait_imm(0)); // (written out for the same reason: no path leaves this loop with a request of its own pending)
+		__builtin_amdgcn_s_waitcnt(simt_wait_imm(0)); // (written out for the same reason: no path leaves this loop with a request of its own pending)
 		#pragma unroll
 		for(int i = 0; i < AHEAD; ++ i) {
-			if(kb + i < s.nb) {
-				#pragma unroll
-				for(int q = 0; q < D; ++ q) {
-					#pragma unroll
-					for(int r = 0; r < D; ++ r)
-						acc[q] -= s.c[i][q][r] * xr[i][r];
-				}
-			}
+			if(kb + i < s.nb)
+				simt_backward_block<D>(acc, s.c[i], xr[i]);
 		}
 	}
 	double x[D];
+	// (the solve of simt_solve_transposed, simt_device.inl, written out: with the reciprocals on s.a's diagonal the helper needs them in
+	// an array of their own or behind a pointer, and either form moved this kernel's waits -- profiles/simt_shared_arith_isa.txt)
 	#pragma unroll
 	for(int q = D - 1; q >= 0; -- q) {
 		double sum = acc[q];
@@ -633,23 +441,9 @@ __device__ __forceinline__ void bwd_ahead_solve(TBwdAheadSet<D, AHEAD> &s, int c
 			sum -= s.a[q][r] * x[r];
 		x[q] = sum * s.a[q][q];
 	}
-	#pragma unroll
-	for(int q = 0; q < D; ++ q)
-		s_x[(ci * D + q) * W] = x[q];
+	simt_store_local_x<D, W>(s_x, ci, x);
 	const long long cs_new = T[W * (3 * ci + 1)], cs_src = T[W * (3 * ci + 2)];
-	if(D % 2 == 0) {
-		#pragma unroll
-		for(int q = 0; q < D; q += 2) {
-			*reinterpret_cast<double2*>(w + cs_new + q) = double2{x[q], x[q + 1]};
-			*reinterpret_cast<double2*>(x_out + cs_src + q) = double2{x[q], x[q + 1]};
-		}
-	} else {
-		#pragma unroll
-		for(int q = 0; q < D; ++ q) {
-			w[cs_new + q] = x[q];
-			x_out[cs_src + q] = x[q];
-		}
-	}
+	simt_store_x<D>(w + cs_new, x_out + cs_src, x);
 }
 
 template <int D, int W, int AHEAD>
@@ -735,15 +529,7 @@ static void Launch_Backward_Simt(bool b_ahead, const TSimtChunk *chunks, int n_c
 
 int backward_simt_ahead_waves(int n_dim, int n_width, int n_lds_bytes)
 {
-	const void *p_kernel = p_Backward_Ahead_Kernel(n_dim, n_width);
-	int n_device = 0, n_cus = 0, n_blocks = 0;
-	if(!p_kernel || n_lds_bytes < 0 || hipGetDevice(&n_device) != hipSuccess ||
-	   hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, n_device) != hipSuccess ||
-	   hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_blocks, p_kernel, 64, size_t(n_lds_bytes)) != hipSuccess) {
-		(void)hipGetLastError();
-		return 0;
-	}
-	return (n_cus > 0 && n_blocks > 0)? n_cus * n_blocks : 0; // (a workgroup is one wave)
+	return simt_resident_workgroups(p_Backward_Ahead_Kernel(n_dim, n_width), 64, n_lds_bytes); // (a workgroup is one wave)
 }
 
 bool launch_backward_simt(const TSimtChunk *chunks, int n_chunks, int n_width, int n_lds_bytes, size_t n_lds_limit, int n_ahead_waves, const int32_t *prog, const int64_t *tab,

@@ -1,5 +1,7 @@
 """Dev helper: K value sets of the C3 structure in one pass of launches (slampp_hip_factor_solve_batch_device_async);
-under `rocprofv3 --kernel-trace --stats` this is the per-kernel picture of a batch (profiles/r05_c3_batch8_kernel_stats.csv)."""
+under `rocprofv3 --kernel-trace --stats` this is the per-kernel picture of a batch (profiles/r05_c3_batch8_kernel_stats.csv).
+POSES and BLOCK (block size, default 6) choose the chain; KEPT=1 solves once on a kept factor first, after which the factorizations
+store inv(L_jj) (the b_linv instantiations of the lane-per-task factor kernels)."""
 import os as _os; _os.environ.setdefault("SLAMPP_HIP_DEV", "1")  # development options and knobs are refused without it (csrc/plan.h)
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -10,9 +12,12 @@ from slam_plus_plus_amd.hip_solver import CLinearSolver_HIP
 
 K = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
-lam = synth.pose_chain(n=int(os.environ.get("POSES", "100000")))
+lam = synth.pose_chain(n=int(os.environ.get("POSES", "100000")), d=int(os.environ.get("BLOCK", "6")))
 s = CLinearSolver_HIP()
 s.SymbolicDecomposition_Blocky(lam)
+if os.environ.get("KEPT") == "1":
+    eta = lam.rhs.copy()
+    assert s.Solve_PosDef_Blocky(lam, eta) and s.Solve_Again(lam.rhs.copy())
 n_v, n_s = lam.values.shape[0] + lam.values.shape[0] % 2, lam.n_scalars + lam.n_scalars % 2
 vals = torch.zeros(K * n_v, dtype=torch.float64, device="cuda")
 for k in range(K):
