@@ -152,6 +152,28 @@ static int simt_resident_workgroups(const void *p_kernel, int n_threads, int n_l
 	return (n_cus > 0 && n_blocks > 0)? n_cus * n_blocks : 0;
 }
 
+// A chunk's table (forward or backward) from memory to LDS, one wave: eight loads in flight a lane before the first is waited for.  (A loop of one load
+// and one store an entry is compiled to a wait per load: 27 trips to memory one after the other for a table of 1 700 entries, some
+// 6 us in front of the first column of every wave.)  n_lane: 0 .. 63
+__device__ __forceinline__ void simt_stage_table(long long *p_dst, const long long *__restrict__ p_src, int n_entries, int n_lane)
+{
+	enum { N_FLIGHT = 8 };
+	for(int n_base = 0; n_base < n_entries; n_base += N_FLIGHT * 64) { // (wave-uniform trip count)
+		long long v[N_FLIGHT];
+		#pragma unroll
+		for(int u = 0; u < N_FLIGHT; ++ u) {
+			const int i = n_base + u * 64 + n_lane;
+			v[u] = p_src[(i < n_entries)? i : n_entries - 1]; // (no lane masked out: the loads of a trip go out together)
+		}
+		#pragma unroll
+		for(int u = 0; u < N_FLIGHT; ++ u) {
+			const int i = n_base + u * 64 + n_lane;
+			if(i < n_entries)
+				p_dst[i] = v[u];
+		}
+	}
+}
+
 // ---- the column arithmetic of the factor kernels (factor_simt_kernel, factor_simt_kernel_ahead, factor_simt_kernel_branches).
 // These kernels store the same bits because they run the code below: the one copy of every sum, in its one order.  What a form
 // owns is where a column's Lambda comes from and when (touches, register sets, waits) and who stores the diagonal block.

@@ -135,28 +135,6 @@ __device__ __forceinline__ void store_half_columns(double *p, const double (&m)[
 	}
 }
 
-// A chunk's table from memory to LDS, one wave: eight loads in flight a lane before the first is waited for.  (A loop of one load
-// and one store an entry is compiled to a wait per load: 27 trips to memory one after the other for a table of 1 700 entries, some
-// 6 us in front of the first column of every wave.)  n_lane: 0 .. 63
-__device__ __forceinline__ void factor_ahead_stage_table(long long *p_dst, const long long *__restrict__ p_src, int n_entries, int n_lane)
-{
-	enum { N_FLIGHT = 8 };
-	for(int n_base = 0; n_base < n_entries; n_base += N_FLIGHT * 64) { // (wave-uniform trip count)
-		long long v[N_FLIGHT];
-		#pragma unroll
-		for(int u = 0; u < N_FLIGHT; ++ u) {
-			const int i = n_base + u * 64 + n_lane;
-			v[u] = p_src[(i < n_entries)? i : n_entries - 1]; // (no lane masked out: the loads of a trip go out together)
-		}
-		#pragma unroll
-		for(int u = 0; u < N_FLIGHT; ++ u) {
-			const int i = n_base + u * 64 + n_lane;
-			if(i < n_entries)
-				p_dst[i] = v[u];
-		}
-	}
-}
-
 // The column loop of one chunk -- a whole task a lane pair, or one segment of a split task: the one loop of both kernels below.
 // P: the chunk's program (wave-uniform: scalar loads); T: field f of this lane's task at T[W f]; n_half: which half of the rows
 // below the diagonal this lane takes; p_tm, n_tm: the clock samples of the wave that takes them (SIMT_TICK).  Returns whether
@@ -274,7 +252,7 @@ factor_simt_kernel_ahead(const TSimtChunk *__restrict__ chunks, const int32_t *_
 	const TSimtChunk ch = chunks[blockIdx.x];
 	{
 		const int n_entries = (4 * prog[ch.prog_off] + prog[ch.prog_off + 1] + prog[ch.prog_off + 2] + prog[ch.prog_off + 3]) * W;
-		factor_ahead_stage_table(s_tab, tab + ch.tab_off, n_entries, int(threadIdx.x));
+		simt_stage_table(s_tab, tab + ch.tab_off, n_entries, int(threadIdx.x));
 		__syncthreads();
 	}
 	if(int(threadIdx.x) >= W * LPT)
@@ -314,7 +292,7 @@ factor_simt_kernel_branches(const TSimtBranchGroup *__restrict__ groups, const i
 		if(ch.n_tasks > 0 && (n_pass == 0 || n_wave == 0)) { // (wave-uniform)
 			const int32_t *P = prog + ch.prog_off;
 			const int n_entries = (4 * P[0] + P[1] + P[2] + P[3]) * W;
-			factor_ahead_stage_table(s_mine, tab + ch.tab_off, n_entries, n_lane);
+			simt_stage_table(s_mine, tab + ch.tab_off, n_entries, n_lane);
 			__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); // (the region is this wave's own: its lanes' stores in front of its lanes' loads, no barrier)
 			__builtin_amdgcn_wave_barrier();
 			if(n_lane < W * 2) { // (idle lanes of a narrow wave go on to the barrier)

@@ -47,8 +47,7 @@ factor_simt_kernel(const TSimtChunk *__restrict__ chunks, const int32_t *__restr
 	const TSimtChunk ch = chunks[blockIdx.x];
 	{
 		const int n_entries = (4 * prog[ch.prog_off] + prog[ch.prog_off + 1] + prog[ch.prog_off + 2] + prog[ch.prog_off + 3]) * W;
-		for(int i = threadIdx.x; i < n_entries; i += 64)
-			s_tab[i] = tab[ch.tab_off + i];
+		simt_stage_table(s_tab, tab + ch.tab_off, n_entries, int(threadIdx.x));
 		__syncthreads();
 	}
 	if(int(threadIdx.x) >= W * LPT)
@@ -240,8 +239,7 @@ backward_simt_kernel(const TSimtChunk *__restrict__ chunks, const int32_t *__res
 	const int n_cols = P[0], n_below = P[1];
 	{
 		const int n_entries = (3 * n_cols + n_below) * W;
-		for(int i = threadIdx.x; i < n_entries; i += 64)
-			s_tab[i] = tab[ch.tab_off + i];
+		simt_stage_table(s_tab, tab + ch.tab_off, n_entries, int(threadIdx.x));
 		__syncthreads();
 	}
 	if(int(threadIdx.x) >= W)
@@ -375,9 +373,10 @@ constexpr int bwd_ahead_fetch_loads()
 }
 template <int D> constexpr int bwd_ahead_solve_stores() { return (D % 2 == 0)? D : 2 * D; }
 
-template <int D, int W, int AHEAD, int N_NEWER /* vector memory operations issued since the set's fetch, at the least */>
+template <int D, int W, int AHEAD, int N_NEWER /* vector memory operations issued since the set's fetch, at the least */,
+	bool b_slots = false /* the columns are a segment of a task (backward_simt_kernel_branches): x goes to LDS at p_slot[ci], the column's place in the whole task */>
 __device__ __forceinline__ void bwd_ahead_solve(TBwdAheadSet<D, AHEAD> &s, int ci, int n_cols, const int32_t *p_local, const long long *T, double *s_x,
-	const double *__restrict__ L, double *w, double *x_out)
+	const double *__restrict__ L, double *w, double *x_out, const int32_t *p_slot = 0)
 {
 	enum { DD = D * D };
 	// The one wait of the column, written out: everything older than the N_NEWER newest requests -- this set -- has arrived.  The
@@ -441,9 +440,31 @@ __device__ __forceinline__ void bwd_ahead_solve(TBwdAheadSet<D, AHEAD> &s, int c
 			sum -= s.a[q][r] * x[r];
 		x[q] = sum * s.a[q][q];
 	}
-	simt_store_local_x<D, W>(s_x, ci, x);
+	simt_store_local_x<D, W>(s_x, b_slots? p_slot[ci] : ci, x);
 	const long long cs_new = T[W * (3 * ci + 1)], cs_src = T[W * (3 * ci + 2)];
 	simt_store_x<D>(w + cs_new, x_out + cs_src, x);
+}
+
+// The columns of a chunk behind the prologue fetch (t_even holds the last column), last to first: the one loop of both kernels
+// below.  b_slots, p_slot: as bwd_ahead_solve
+template <int D, int W, int AHEAD, bool b_slots>
+__device__ __forceinline__ void bwd_ahead_columns(TBwdAheadSet<D, AHEAD> &t_even, TBwdAheadSet<D, AHEAD> &t_odd, int n_cols, const int32_t *P, const int32_t *p_local,
+	const int32_t *p_slot, const long long *T, double *s_x, const double *__restrict__ L, double *w, double *x_out)
+{
+	enum { N_FETCH = bwd_ahead_fetch_loads<D, AHEAD>(), N_STORES = bwd_ahead_solve_stores<D>() };
+	int ci = n_cols - 1;
+	for(; ci >= 2; ci -= 2) { // steady state: every solve with one fetch in front of it
+		bwd_ahead_fetch<D, W, AHEAD>(t_odd, ci - 1, t_even.n_blk0, n_cols, P, p_local, T, L, w);
+		bwd_ahead_solve<D, W, AHEAD, N_FETCH, b_slots>(t_even, ci, n_cols, p_local, T, s_x, L, w, x_out, p_slot); // (in the first round no store lies between the two fetches)
+		bwd_ahead_fetch<D, W, AHEAD>(t_even, ci - 2, t_odd.n_blk0, n_cols, P, p_local, T, L, w);
+		bwd_ahead_solve<D, W, AHEAD, N_STORES + N_FETCH, b_slots>(t_odd, ci - 1, n_cols, p_local, T, s_x, L, w, x_out, p_slot);
+	}
+	if(ci == 1) { // epilogue: the columns left (t_even holds column ci), the last of them with nothing to fetch
+		bwd_ahead_fetch<D, W, AHEAD>(t_odd, 0, t_even.n_blk0, n_cols, P, p_local, T, L, w);
+		bwd_ahead_solve<D, W, AHEAD, N_FETCH, b_slots>(t_even, 1, n_cols, p_local, T, s_x, L, w, x_out, p_slot);
+		bwd_ahead_solve<D, W, AHEAD, N_STORES, b_slots>(t_odd, 0, n_cols, p_local, T, s_x, L, w, x_out, p_slot);
+	} else
+		bwd_ahead_solve<D, W, AHEAD, 0, b_slots>(t_even, 0, n_cols, p_local, T, s_x, L, w, x_out, p_slot);
 }
 
 template <int D, int W, int AHEAD>
@@ -458,8 +479,7 @@ backward_simt_ahead_kernel(const TSimtChunk *__restrict__ chunks, const int32_t 
 	const int n_cols = P[0], n_below = P[1];
 	{
 		const int n_entries = (3 * n_cols + n_below) * W;
-		for(int i = threadIdx.x; i < n_entries; i += 64)
-			s_tab[i] = tab[ch.tab_off + i];
+		simt_stage_table(s_tab, tab + ch.tab_off, n_entries, int(threadIdx.x));
 		__syncthreads();
 	}
 	if(int(threadIdx.x) >= W)
@@ -468,21 +488,84 @@ backward_simt_ahead_kernel(const TSimtChunk *__restrict__ chunks, const int32_t 
 	double *s_x = reinterpret_cast<double*>(s_tab + (3 * n_cols + n_below) * W) + threadIdx.x; // x of the task's own columns (backward_simt_kernel)
 	const int32_t *p_local = P + 2 + n_cols;
 	TBwdAheadSet<D, AHEAD> t_even, t_odd; // (two named sets and a loop unrolled by two: an index into an array of sets would be scratch)
-	enum { N_FETCH = bwd_ahead_fetch_loads<D, AHEAD>(), N_STORES = bwd_ahead_solve_stores<D>() };
-	int ci = n_cols - 1;
-	bwd_ahead_fetch<D, W, AHEAD>(t_even, ci, n_below, n_cols, P, p_local, T, L, w); // prologue: the last column
-	for(; ci >= 2; ci -= 2) { // steady state: every solve with one fetch in front of it
-		bwd_ahead_fetch<D, W, AHEAD>(t_odd, ci - 1, t_even.n_blk0, n_cols, P, p_local, T, L, w);
-		bwd_ahead_solve<D, W, AHEAD, N_FETCH>(t_even, ci, n_cols, p_local, T, s_x, L, w, x_out); // (in the first round no store lies between the two fetches)
-		bwd_ahead_fetch<D, W, AHEAD>(t_even, ci - 2, t_odd.n_blk0, n_cols, P, p_local, T, L, w);
-		bwd_ahead_solve<D, W, AHEAD, N_STORES + N_FETCH>(t_odd, ci - 1, n_cols, p_local, T, s_x, L, w, x_out);
+	bwd_ahead_fetch<D, W, AHEAD>(t_even, n_cols - 1, n_below, n_cols, P, p_local, T, L, w); // prologue: the last column
+	bwd_ahead_columns<D, W, AHEAD, false>(t_even, t_odd, n_cols, P, p_local, 0, T, s_x, L, w, x_out);
+}
+
+// The fetch-ahead substitution for the launch whose longest tasks set its duration (C3's leaves: 592 one-wave workgroups on
+// 1 024 SIMDs, the 30 % of the tasks with six to eight columns finish alone).  Backward substitution runs a task's tree from the
+// top: the join columns first, then the two bins of whole branch chains (sparse_records.h: simt_task_segments()), which no longer
+// depend on each other.  A workgroup of two waves runs one record (TSimtBranchGroup): wave 0 the joins (seg[2]), behind the one
+// barrier waves 0 and 1 the bins (seg[0], seg[1]), the same tasks in the same lanes.  The bins exchange nothing through memory:
+// x of the task's own columns is in LDS at the column's place in the whole task (the segment programs carry it: p_slot), the
+// "which column" entries of a segment's rows stay in the task's numbering, and x of rows outside the task is earlier launches'.
+// Chunks of whole tasks ride two to a record, as seg[0] and seg[1] with no joins, and then each wave has an x region of its own.
+// LDS: three table regions of n_tab_region entries (seg[0], seg[1], seg[2]: every wave stages what it reads itself, all at the
+// start), then two x regions of n_x_region doubles (a split record uses the first only).  One barrier, reached by every thread:
+// idle lanes of a narrow chunk, a wave without a segment and the odd whole chunk without a partner included; no return in front
+// of it.  Per column the operations and their order are backward_simt_ahead_kernel's (bwd_ahead_fetch, bwd_ahead_solve, the one
+// column loop bwd_ahead_columns): the same bits.  (Wave 1 waits at the barrier with nothing requested: a first set fetched in
+// front of the barrier and carried across it costs 324 bytes of scratch a lane -- the two sets fill the register file, and the
+// set then has to sit in the same registers on both sides.  DESIGN.md section 10.)
+template <int D, int W, int AHEAD>
+__global__ void __launch_bounds__(128)
+backward_simt_kernel_branches(const TSimtBranchGroup *__restrict__ groups, const int32_t *__restrict__ prog, const long long *__restrict__ tab,
+	const double *__restrict__ L, double *w, double *x_out, TBatch t_batch, int n_tab_region, int n_x_region)
+{	{ const int64_t n_member = blockIdx.y; L += n_member * t_batch.l; w += n_member * t_batch.w; x_out += n_member * t_batch.b; } // (TBatch: sparse_kernels.h)
+
+	extern __shared__ long long s_tab[];
+	const int n_wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6), n_lane = int(threadIdx.x) & 63; // (n_wave in a scalar register: what follows from it stays wave-uniform)
+	const TSimtBranchGroup &r_group = groups[blockIdx.x];
+	const bool b_shared_x = r_group.seg[2].n_tasks > 0; // (a record of split tasks: one x region for the task, written by both waves)
+	for(int k = n_wave; k < 3; k += 2) { // wave 0: the tables of seg[0] and seg[2], wave 1: of seg[1]
+		const TSimtChunk ch = r_group.seg[k];
+		if(ch.n_tasks > 0) { // (wave-uniform)
+			const int32_t *P = prog + ch.prog_off;
+			simt_stage_table(s_tab + k * n_tab_region, tab + ch.tab_off, (3 * P[0] + P[1]) * W, n_lane);
+		}
 	}
-	if(ci == 1) { // epilogue: the columns left (t_even holds column ci), the last of them with nothing to fetch
-		bwd_ahead_fetch<D, W, AHEAD>(t_odd, 0, t_even.n_blk0, n_cols, P, p_local, T, L, w);
-		bwd_ahead_solve<D, W, AHEAD, N_FETCH>(t_even, 1, n_cols, p_local, T, s_x, L, w, x_out);
-		bwd_ahead_solve<D, W, AHEAD, N_STORES>(t_odd, 0, n_cols, p_local, T, s_x, L, w, x_out);
-	} else
-		bwd_ahead_solve<D, W, AHEAD, 0>(t_even, 0, n_cols, p_local, T, s_x, L, w, x_out);
+	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); // (the regions a wave reads are its own: its lanes' stores in front of its lanes' loads, no barrier)
+	__builtin_amdgcn_wave_barrier();
+	TBwdAheadSet<D, AHEAD> t_even, t_odd; // (as backward_simt_ahead_kernel)
+	t_even.nb = t_even.n_blk0 = t_even.n_xk = 0; // (see between the two regions below)
+	#pragma unroll
+	for(int i = 0; i < AHEAD; ++ i)
+		t_even.n_local[i] = 0;
+	const bool b_my_lane = (int(threadIdx.x) & 63) < W; // (idle lanes of a narrow wave and a wave without a segment go on to the barrier)
+	double *s_x = reinterpret_cast<double*>(s_tab + 3 * n_tab_region) + (b_shared_x? 0 : n_wave * n_x_region) + n_lane;
+	{ // wave 0: the joins
+		const TSimtChunk ch = r_group.seg[2];
+		if(ch.n_tasks > 0 && !n_wave && b_my_lane) {
+			const int32_t *P = prog + ch.prog_off; // n_cols, n_below, nb per column, per block which of the task's columns its row is, per column its place in the task
+			const int n_cols = P[0], n_below = P[1];
+			const long long *T = s_tab + 2 * n_tab_region + n_lane;
+			const int32_t *p_local = P + 2 + n_cols;
+			bwd_ahead_fetch<D, W, AHEAD>(t_even, n_cols - 1, n_below, n_cols, P, p_local, T, L, w); // prologue: the last column
+			bwd_ahead_columns<D, W, AHEAD, true>(t_even, t_odd, n_cols, P, p_local, p_local + n_below, T, s_x, L, w, x_out);
+		}
+	}
+	// What a set holds of the program (wave-uniform) leaves the region above, which only the chunk's lanes of wave 0 enter, in
+	// vector registers.  The region below writes all of it anew, so nothing here changes a result; but the two sets fill the
+	// register file, and with those words left where they are the kernel needs 20 bytes of scratch a lane, with them back in
+	// scalar registers none (tests/test_simt_bwd_branches_resources.py)
+	t_even.nb = __builtin_amdgcn_readfirstlane(t_even.nb);
+	t_even.n_blk0 = __builtin_amdgcn_readfirstlane(t_even.n_blk0);
+	t_even.n_xk = __builtin_amdgcn_readfirstlane(t_even.n_xk);
+	#pragma unroll
+	for(int i = 0; i < AHEAD; ++ i)
+		t_even.n_local[i] = __builtin_amdgcn_readfirstlane(t_even.n_local[i]);
+	__syncthreads(); // (x of the joins, in LDS, in front of the bins' loads of it)
+	{ // both waves: their bins, or their chunks of whole tasks
+		const TSimtChunk ch = r_group.seg[n_wave];
+		if(ch.n_tasks > 0 && b_my_lane) {
+			const int32_t *P = prog + ch.prog_off;
+			const int n_cols = P[0], n_below = P[1];
+			const long long *T = s_tab + (n_wave * n_tab_region - n_wave * 64) + int(threadIdx.x); // (= region n_wave + n_lane, from threadIdx.x itself: a register less)
+			const int32_t *p_local = P + 2 + n_cols;
+			bwd_ahead_fetch<D, W, AHEAD>(t_even, n_cols - 1, n_below, n_cols, P, p_local, T, L, w);
+			bwd_ahead_columns<D, W, AHEAD, true>(t_even, t_odd, n_cols, P, p_local, p_local + n_below, T, s_x, L, w, x_out);
+		}
+	}
 }
 
 // the fetch-ahead form exists for the block sizes listed here (which compile without scratch)
@@ -532,14 +615,62 @@ int backward_simt_ahead_waves(int n_dim, int n_width, int n_lds_bytes)
 	return simt_resident_workgroups(p_Backward_Ahead_Kernel(n_dim, n_width), 64, n_lds_bytes); // (a workgroup is one wave)
 }
 
+// the two-wave form exists where the fetch-ahead form does, for the widths that leave a wave idle lanes or none (16, 32)
+static const void *p_Backward_Branches_Kernel(int n_dim, int n_width)
+{
+	if(n_dim != 6)
+		return 0;
+	return (n_width == 16)? reinterpret_cast<const void*>(&backward_simt_kernel_branches<6, 16, SIMT_BWD_AHEAD>) :
+		(n_width == 32)? reinterpret_cast<const void*>(&backward_simt_kernel_branches<6, 32, SIMT_BWD_AHEAD>) : 0;
+}
+
+bool backward_simt_branches_exists(int n_dim, int n_width)
+{
+	return p_Backward_Branches_Kernel(n_dim, n_width) != 0;
+}
+
+int backward_simt_branches_groups(int n_dim, int n_width, int n_lds_bytes)
+{
+	if(!backward_simt_branches_exists(n_dim, n_width) || n_lds_bytes <= 0)
+		return 0;
+	return simt_resident_workgroups(p_Backward_Branches_Kernel(n_dim, n_width), 128, n_lds_bytes);
+}
+
 bool launch_backward_simt(const TSimtChunk *chunks, int n_chunks, int n_width, int n_lds_bytes, size_t n_lds_limit, int n_ahead_waves, const int32_t *prog, const int64_t *tab,
-	int n_dim, const double *L, double *w, double *x_out, hipStream_t stream, const TBatch &t_batch, bool b_report)
+	int n_dim, const double *L, double *w, double *x_out, hipStream_t stream, const TBatch &t_batch, bool b_report, const TSimtBwdBranchLaunch *p_branches)
 {
 	if(n_chunks <= 0)
 		return true;
 	if(n_lds_bytes < 0 || size_t(n_lds_bytes) > n_lds_limit)
 		return false; // (the chunk tables are staged in LDS: a launch over the limit would fail without a word)
 	const long long *t = reinterpret_cast<const long long*>(tab);
+	// The two-wave form (backward_simt_kernel_branches) under the rule of the factor form (launch_factor_simt()): the launch is one
+	// the fetch-ahead form would take, fits one round of the two-wave form, has tasks longer than T* columns and is of a stage
+	// of at least 2 048 tasks.  Development aid (plan.h): 0 = never, 1 = wherever the stage has records; the same bits.  A launch
+	// whose LDS request is over the limit keeps the forms below.
+	{
+		const int n_branches_env = dev_knob("SLAMPP_HIP_DEV_SIMT_BWD_BRANCHES", -1);
+		const int n_ahead_knob = dev_knob("SLAMPP_HIP_DEV_SIMT_BWD_AHEAD", -1);
+		const bool b_would_fetch_ahead = p_Backward_Ahead_Kernel(n_dim, n_width) &&
+			((n_ahead_knob >= 0)? n_ahead_knob != 0 : int64_t(n_chunks) * std::max<int64_t>(t_batch.n, 1) <= n_ahead_waves);
+		const bool b_branches = p_branches && p_branches->n_groups > 0 && backward_simt_branches_exists(n_dim, n_width) &&
+			p_branches->n_lds_bytes > 0 && size_t(p_branches->n_lds_bytes) <= n_lds_limit &&
+			((n_branches_env >= 0)? n_branches_env != 0 : b_would_fetch_ahead &&
+			int64_t(p_branches->n_groups) * std::max<int64_t>(t_batch.n, 1) <= p_branches->n_round_groups &&
+			p_branches->n_tstar < p_branches->n_longest_task && p_branches->n_stage_tasks >= 2048);
+		if(b_branches) {
+			if(b_report)
+				fprintf(stderr, "stage_timing lane-per-task backward branches launch: %d workgroups of two waves, %d split chunks, %d whole chunks, width %d, block size %d, %d members\n",
+					p_branches->n_groups, p_branches->n_split_chunks, p_branches->n_whole_chunks, n_width, n_dim, int(t_batch.n));
+			if(n_width == 16)
+				hipLaunchKernelGGL((backward_simt_kernel_branches<6, 16, SIMT_BWD_AHEAD>), dim3(p_branches->n_groups, t_batch.n), dim3(128), p_branches->n_lds_bytes, stream,
+					p_branches->groups, prog, t, L, w, x_out, t_batch, p_branches->n_tab_region, p_branches->n_x_region);
+			else
+				hipLaunchKernelGGL((backward_simt_kernel_branches<6, 32, SIMT_BWD_AHEAD>), dim3(p_branches->n_groups, t_batch.n), dim3(128), p_branches->n_lds_bytes, stream,
+					p_branches->groups, prog, t, L, w, x_out, t_batch, p_branches->n_tab_region, p_branches->n_x_region);
+			return hipGetLastError() == hipSuccess;
+		}
+	}
 	// The fetch-ahead form runs at one wave a SIMD: it is for launches that fit the chip in one round at that occupancy and so
 	// could not hide a wave's waits behind other waves anyway (C3's leaves: 592 waves, 41.7 -> 30.3 us).  Larger
 	// launches -- a batch of eight (4 736 waves), a million poses -- keep the kernel above, where many waves a SIMD already hide

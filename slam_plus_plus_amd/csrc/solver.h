@@ -229,6 +229,8 @@ struct slampp_hip_solver {
 	slampp::CDevArray<int64_t> d_simt_bwd_tab;
 	std::vector<int32_t> simt_factor_ahead_waves; // per lane-per-task stage: factor_simt_ahead_waves() of its LDS request, asked at analysis: factor launches of at most that many waves fetch a column ahead
 	slampp::CDevArray<slampp::TSimtBranchGroup> d_simt_br_groups; // the workgroup records of the two-wave factor form (sparse_kernels.h); their segments' programs and tables are in d_simt_prog and d_simt_tab
+	slampp::CDevArray<slampp::TSimtBranchGroup> d_simt_bwd_br_groups; // the same records of the two-wave backward form; their segments' programs and tables are in d_simt_bwd_prog and d_simt_bwd_tab
+	std::vector<int32_t> simt_bwd_branches_round_groups; // per lane-per-task stage: backward_simt_branches_groups() of its LDS request, asked at analysis (0: no records)
 	std::vector<int32_t> simt_branches_round_groups; // per lane-per-task stage: factor_simt_branches_groups() of its LDS request, asked at analysis (0: no records)
 	std::vector<int32_t> simt_bwd_ahead_waves; // per lane-per-task stage: backward_simt_ahead_waves() of its LDS request, asked at analysis (as n_lds_limit): launches of at most that many waves fetch a column ahead
 	// inv(L_jj) of the columns the lane-per-task kernel factors is not on the solve's path any more (its backward kernel solves with

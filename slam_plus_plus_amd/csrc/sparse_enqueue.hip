@@ -190,9 +190,16 @@ void slampp_hip_solver::Enqueue_Sparse(const double *p_values_dev, double *p_rhs
 			// a lane-per-task stage: its chunks by backward_simt_kernel (no inverses read), the tasks of rare shapes by the
 			// wave-per-task kernel (their factor kernel stored the inverses)
 			const int n_chunks = lists.simt_chunk_ptr[s] - lists.simt_chunk_ptr[s - 1], n_rest = lists.simt_rest_ptr[s] - lists.simt_rest_ptr[s - 1];
+			TSimtBwdBranchLaunch t_branches = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+			if(size_t(s - 1) < lists.simt_br.size() && size_t(s - 1) < simt_bwd_branches_round_groups.size() && lists.simt_br[size_t(s - 1)].n_bwd_groups > 0 && d_simt_bwd_br_groups.p()) {
+				const TSimtBranchStage &r_br = lists.simt_br[size_t(s - 1)];
+				const TSimtBwdBranchLaunch t_have = {d_simt_bwd_br_groups.p() + r_br.n_bwd_first, r_br.n_bwd_groups, r_br.n_split_chunks, r_br.n_whole_chunks, r_br.n_bwd_lds_bytes,
+					r_br.n_bwd_tab_region, r_br.n_bwd_x_region, simt_bwd_branches_round_groups[size_t(s - 1)], r_br.n_tstar, r_br.n_longest_task, r_br.n_stage_tasks};
+				t_branches = t_have;
+			}
 			if(!launch_backward_simt(d_simt_bwd_chunks.p() + lists.simt_chunk_ptr[s - 1], n_chunks, n_simt_width, lists.simt_bwd_lds_bytes[s - 1], n_lds_limit,
 				(size_t(s - 1) < simt_bwd_ahead_waves.size())? simt_bwd_ahead_waves[s - 1] : 0, d_simt_bwd_prog.p(), d_simt_bwd_tab.p(), P.max_dim, d_L.p(), d_w.p(), p_rhs_dev, stream, t_batch,
-				dplan.p_timing != 0))
+				dplan.p_timing != 0, t_branches.n_groups? &t_branches : 0))
 				throw CDeviceError("lane-per-task backward launch refused: block size or LDS request outside what the analysis planned for");
 			if(n_rest > 0) {
 				TDevPlan t_rest = dplan;

@@ -320,9 +320,30 @@ bool launch_factor_simt_branches(const TSimtBranchGroup *groups, int n_groups, i
 // come as many to a trip.  n_ahead_waves: backward_simt_ahead_waves() of the stage, asked at analysis; b_report: say on
 // stderr which form the launch takes (development aid SLAMPP_HIP_STAGE_TIMING)
 enum { SIMT_BWD_AHEAD = 2 };
+// The fetch-ahead form for launches whose longest tasks set their duration (simt_kernel.hip: backward_simt_kernel_branches): a
+// workgroup of two waves runs one TSimtBranchGroup of backward chunks.  Wave 0 runs seg[2], the join columns of a chunk of
+// split tasks; behind a barrier waves 0 and 1 run seg[0] and seg[1], the two bins of whole branch chains.  Chunks of whole
+// tasks ride two to a record, as seg[0] and seg[1].  A segment's program is the backward program above over the segment's
+// columns -- the "which column" entries in the whole task's numbering -- followed by the place of each of its columns in the whole
+// task: where its x goes in LDS.  Its table is the backward table over its columns.  Programs and tables lie behind the
+// chunks' own (a whole chunk's table is the chunk's).  LDS: three table regions, then two x regions (a split record uses one).
+struct TSimtBwdBranchLaunch {
+	const TSimtBranchGroup *groups; // (device)
+	int n_groups, n_split_chunks, n_whole_chunks;
+	int n_lds_bytes;       // (3 n_tab_region + 2 n_x_region) * 8
+	int n_tab_region;      // entries of the stage's largest segment table
+	int n_x_region;        // doubles: columns of the stage's longest task x block size x width
+	int n_round_groups;    // backward_simt_branches_groups() of the stage, asked at analysis
+	int n_tstar, n_longest_task, n_stage_tasks; // as TSimtBranchLaunch
+};
+bool backward_simt_branches_exists(int n_dim, int n_width);
+// workgroups of that form the device holds at once with this LDS request
+int backward_simt_branches_groups(int n_dim, int n_width, int n_lds_bytes);
+// p_branches: the stage's records of the two-wave form, if it has any; launch_backward_simt() decides (knob SLAMPP_HIP_DEV_SIMT_BWD_BRANCHES)
 bool launch_backward_simt(const TSimtChunk *chunks, int n_chunks, int n_width, int n_lds_bytes, size_t n_lds_limit /* plain_launch_lds_limit(), asked at analysis */,
 	int n_ahead_waves, const int32_t *prog, const int64_t *tab,
-	int n_dim, const double *L, double *w, double *x_out, hipStream_t stream, const TBatch &t_batch = t_No_Batch(), bool b_report = false);
+	int n_dim, const double *L, double *w, double *x_out, hipStream_t stream, const TBatch &t_batch = t_No_Batch(), bool b_report = false,
+	const TSimtBwdBranchLaunch *p_branches = 0);
 // waves (= workgroups) of the fetch-ahead form the device holds at once with this LDS request: CUs x the runtime's occupancy answer;
 // 0: the block size has no such form, or the device does not answer
 int backward_simt_ahead_waves(int n_dim, int n_width, int n_lds_bytes);

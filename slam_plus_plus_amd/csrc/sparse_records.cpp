@@ -1193,6 +1193,116 @@ int32_t simt_task_segments(const std::vector<int32_t> &r_parent, TSimtSegments &
 
 namespace {
 
+// an item of a stage's launch order in the two-wave forms: a chunk of split tasks, or two chunks of whole tasks
+struct TSimtBranchItem {
+	int32_t n_chain;          // the longest chain of columns a wave walks in it
+	TSimtBranchGroup t_group; // the factor record
+	char b_split;
+	size_t n_group;           // split: the shape
+	size_t n_chunk[2];        // the chunk of the split tasks, or the two chunks of whole tasks (size_t(-1): none), in simt_chunks / simt_bwd_chunks
+};
+
+// The same items in the same order as backward records (sparse_kernels.h: TSimtBwdBranchLaunch).  A segment's program is cut out
+// of the whole task's backward program: n_cols, blocks below the diagonals, nb per column, per block which of the task's columns
+// its row is (in the task's numbering: unchanged), and per column its place in the task.  Its table is the rows of the chunk's
+// backward table that belong to its columns, [field][lane] as they are (spare lanes repeat the last task there already).  A chunk
+// of whole tasks keeps its table and gets its program with the places 0 .. n_cols - 1 behind it.  Programs and tables go to
+// bwd_prog and bwd_tab (build_simt_tables() puts them behind the chunks' own and moves the offsets); nothing the one-wave
+// forms read is touched.  A stage whose LDS request -- three table regions and two x regions -- is beyond a plain launch's gets none.
+void Build_Simt_Bwd_Branches(const Plan &P, size_t W, const std::vector<TSimtSegments> &segs, const std::vector<TSimtBranchItem> &items,
+	SparseRecords &r_rec, TSimtBranchStage &r_stage, std::vector<int32_t> &bwd_prog, std::vector<int64_t> &bwd_tab, std::vector<char> &bwd_split)
+{
+	const size_t n_prog0 = bwd_prog.size(), n_tab0 = bwd_tab.size();
+	std::map<std::pair<int32_t, int>, int32_t> prog_of; // (the whole task's program, segment or 3 for the whole task) -> where its program is
+	std::vector<TSimtBranchGroup> records;
+	std::vector<int32_t> blk0;
+	size_t n_tab_region = 0;
+	int32_t n_x_cols = 0;
+	const TSimtChunk t_none = {0, 0, 0};
+	for(size_t n_item = 0; n_item < items.size(); ++ n_item) {
+		const TSimtBranchItem &r_item = items[n_item];
+		TSimtBranchGroup t_record = {{t_none, t_none, t_none}};
+		for(int n_half = 0; n_half < 2; ++ n_half) {
+			if(r_item.n_chunk[n_half] == size_t(-1))
+				continue;
+			const TSimtChunk ch = r_rec.simt_bwd_chunks[r_item.n_chunk[n_half]];
+			const int32_t *p_whole = &r_rec.simt_bwd_prog[size_t(ch.prog_off)];
+			const int32_t n_cols = p_whole[0], n_below = p_whole[1];
+			const int32_t *p_nb = p_whole + 2, *p_local = p_nb + n_cols;
+			n_x_cols = std::max(n_x_cols, n_cols);
+			r_stage.n_bwd_spare_chunks += size_t(ch.n_tasks) < W;
+			blk0.assign(size_t(n_cols) + 1, 0); // the column's first block below the diagonal among the task's
+			for(int32_t i = 0; i < n_cols; ++ i)
+				blk0[size_t(i) + 1] = blk0[size_t(i)] + p_nb[i] - 1;
+			for(int32_t i = 0; i < n_cols; ++ i) {
+				int n_outside = 0;
+				for(int32_t b = blk0[size_t(i)]; b < blk0[size_t(i) + 1]; ++ b)
+					n_outside += p_local[b] < 0;
+				r_stage.n_bwd_two_outside_columns += (n_outside >= 2)? ch.n_tasks : 0;
+			}
+			if(!r_item.b_split) {
+				std::pair<std::map<std::pair<int32_t, int>, int32_t>::iterator, bool> t_at = prog_of.insert(std::make_pair(std::make_pair(ch.prog_off, 3), int32_t(bwd_prog.size())));
+				if(t_at.second) {
+					bwd_prog.insert(bwd_prog.end(), p_whole, p_whole + 2 + n_cols + n_below);
+					for(int32_t i = 0; i < n_cols; ++ i)
+						bwd_prog.push_back(i);
+				}
+				const TSimtChunk t_seg = {t_at.first->second, ch.n_tasks, ch.tab_off};
+				t_record.seg[n_half] = t_seg;
+				n_tab_region = std::max(n_tab_region, size_t(3 * n_cols + n_below) * W);
+				continue;
+			}
+			const TSimtSegments &r_segs = segs[r_item.n_group];
+			r_stage.n_bwd_tip3_tasks += (r_segs.n_tips >= 3)? ch.n_tasks : 0;
+			for(int k = 0; k < 3; ++ k) {
+				const std::vector<int32_t> &r_cols = r_segs.seg[k]; // (columns of the task, ascending)
+				if(r_cols.empty())
+					continue;
+				int32_t n_seg_below = 0;
+				for(int32_t c : r_cols) {
+					n_seg_below += p_nb[c] - 1;
+					r_stage.n_bwd_long_columns += (p_nb[c] > int32_t(SIMT_BWD_AHEAD) + 1)? ch.n_tasks : 0;
+				}
+				std::pair<std::map<std::pair<int32_t, int>, int32_t>::iterator, bool> t_at = prog_of.insert(std::make_pair(std::make_pair(ch.prog_off, k), int32_t(bwd_prog.size())));
+				if(t_at.second) {
+					bwd_prog.push_back(int32_t(r_cols.size()));
+					bwd_prog.push_back(n_seg_below);
+					for(int32_t c : r_cols)
+						bwd_prog.push_back(p_nb[c]);
+					for(int32_t c : r_cols)
+						bwd_prog.insert(bwd_prog.end(), p_local + blk0[size_t(c)], p_local + blk0[size_t(c) + 1]);
+					bwd_prog.insert(bwd_prog.end(), r_cols.begin(), r_cols.end());
+				}
+				const TSimtChunk t_seg = {t_at.first->second, ch.n_tasks, int64_t(bwd_tab.size())};
+				t_record.seg[k] = t_seg;
+				const int64_t *p_tab = &r_rec.simt_bwd_tab[size_t(ch.tab_off)];
+				for(int32_t c : r_cols) // per column: its first factor block, its place in the workspace and in the caller's vector
+					bwd_tab.insert(bwd_tab.end(), p_tab + size_t(3 * c) * W, p_tab + size_t(3 * c + 3) * W);
+				for(int32_t c : r_cols) // per block below a diagonal: its row's place in the workspace
+					bwd_tab.insert(bwd_tab.end(), p_tab + size_t(3 * n_cols + blk0[size_t(c)]) * W, p_tab + size_t(3 * n_cols + blk0[size_t(c) + 1]) * W);
+				n_tab_region = std::max(n_tab_region, (3 * r_cols.size() + size_t(n_seg_below)) * W);
+			}
+		}
+		records.push_back(t_record);
+	}
+	const size_t n_x_region = size_t(n_x_cols) * size_t(P.max_dim) * W;
+	const size_t n_lds_bytes = (3 * n_tab_region + 2 * n_x_region) * 8;
+	if(n_lds_bytes > 64 * 1024) { // (beyond a plain launch's LDS: the stage keeps the one-wave backward forms)
+		bwd_prog.resize(n_prog0);
+		bwd_tab.resize(n_tab0);
+		r_stage.n_bwd_tip3_tasks = r_stage.n_bwd_long_columns = r_stage.n_bwd_two_outside_columns = r_stage.n_bwd_spare_chunks = 0;
+		return;
+	}
+	r_stage.n_bwd_first = int32_t(r_rec.simt_bwd_br_groups.size());
+	r_stage.n_bwd_groups = int32_t(records.size());
+	r_stage.n_bwd_tab_region = int32_t(n_tab_region);
+	r_stage.n_bwd_x_region = int32_t(n_x_region);
+	r_stage.n_bwd_lds_bytes = int32_t(n_lds_bytes);
+	r_rec.simt_bwd_br_groups.insert(r_rec.simt_bwd_br_groups.end(), records.begin(), records.end());
+	for(size_t n_item = 0; n_item < items.size(); ++ n_item)
+		bwd_split.push_back(items[n_item].b_split);
+}
+
 // The workgroup records of one stage for the two-wave factor form (sparse_kernels.h: TSimtBranchGroup).  Shapes stay grouped by
 // the whole task's program, so a chunk of split tasks has one program per segment, shared by its lanes; the segments' programs
 // and tables go to br_prog and br_tab (build_simt_tables() puts them behind the chunks' own and moves the offsets), the
@@ -1202,7 +1312,8 @@ namespace {
 // n_chunk0: the stage's first chunk; jobs: one per chunk of the stage, in the chunks' order
 void Build_Simt_Branches(const Plan &P, size_t W, bool b_split_all, int32_t n_stage_tasks, const std::vector<TSimtTask> &tasks_all,
 	const std::vector<std::vector<int32_t> > &groups, const std::vector<TSimtChunkJob> &jobs, size_t n_chunk0, raw_vector<int32_t> &index_pool,
-	SparseRecords &r_rec, TSimtBranchStage &r_stage, std::vector<int32_t> &br_prog, raw_vector<int64_t> &br_tab, std::vector<char> &br_split)
+	SparseRecords &r_rec, TSimtBranchStage &r_stage, std::vector<int32_t> &br_prog, raw_vector<int64_t> &br_tab, std::vector<char> &br_split,
+	std::vector<int32_t> &bwd_br_prog, std::vector<int64_t> &bwd_br_tab, std::vector<char> &bwd_br_split)
 {
 	r_stage = TSimtBranchStage();
 	r_stage.n_first = int32_t(r_rec.simt_br_groups.size());
@@ -1264,7 +1375,7 @@ void Build_Simt_Branches(const Plan &P, size_t W, bool b_split_all, int32_t n_st
 		}
 	}
 	// 3. layout: a program per segment of a split shape, a table per segment of its chunks; the records
-	struct TItem { int32_t n_chain; TSimtBranchGroup t_group; char b_split; };
+	typedef TSimtBranchItem TItem;
 	struct TSegJob { size_t n_group, n_first; int n_seg, n_fields; int64_t n_tab_off; };
 	std::vector<TItem> items;
 	std::vector<std::pair<int32_t, size_t> > whole; // columns, chunk
@@ -1301,6 +1412,9 @@ void Build_Simt_Branches(const Plan &P, size_t W, bool b_split_all, int32_t n_st
 			TItem t_item;
 			t_item.n_chain = chain[g];
 			t_item.b_split = 1;
+			t_item.n_group = g;
+			t_item.n_chunk[0] = n_chunk0 + n_job;
+			t_item.n_chunk[1] = size_t(-1);
 			for(size_t k = 0; k < 3; ++ k) {
 				TSimtChunk &ch = t_item.t_group.seg[k];
 				ch = t_none;
@@ -1346,6 +1460,9 @@ void Build_Simt_Branches(const Plan &P, size_t W, bool b_split_all, int32_t n_st
 		TItem t_item;
 		t_item.n_chain = whole[i].first;
 		t_item.b_split = 0;
+		t_item.n_group = size_t(-1);
+		t_item.n_chunk[0] = whole[i].second;
+		t_item.n_chunk[1] = (i + 1 < whole.size())? whole[i + 1].second : size_t(-1);
 		t_item.t_group.seg[0] = r_rec.simt_chunks[whole[i].second];
 		t_item.t_group.seg[1] = (i + 1 < whole.size())? r_rec.simt_chunks[whole[i + 1].second] : t_none;
 		t_item.t_group.seg[2] = t_none;
@@ -1364,6 +1481,7 @@ void Build_Simt_Branches(const Plan &P, size_t W, bool b_split_all, int32_t n_st
 	}
 	r_stage.n_groups = int32_t(items.size());
 	r_stage.n_lds_bytes = 2 * n_region_bytes;
+	Build_Simt_Bwd_Branches(P, W, segs, items, r_rec, r_stage, bwd_br_prog, bwd_br_tab, bwd_br_split);
 	for(std::map<std::pair<int32_t, int32_t>, int32_t>::const_iterator p = split_by.begin(); p != split_by.end(); ++ p) {
 		r_stage.split_by.push_back(p->first.first);
 		r_stage.split_by.push_back(p->first.second);
@@ -1386,6 +1504,7 @@ void build_simt_tables(const Plan &P, const SparseRecordOptions &t_opt, SparseRe
 	r_lists.simt_bwd_lds_bytes.clear();
 	r_lists.simt_br.clear();
 	r_rec.simt_br_groups.clear();
+	r_rec.simt_bwd_br_groups.clear();
 	r_rec.simt_bwd_chunks.clear(); r_rec.simt_bwd_prog.clear(); r_rec.simt_bwd_tab.clear();
 	if(!t_opt.n_simt || !b_Package_Dim(P))
 		return;
@@ -1407,12 +1526,15 @@ void build_simt_tables(const Plan &P, const SparseRecordOptions &t_opt, SparseRe
 	const size_t W = size_t(t_opt.n_simt_width);
 	// the workgroup records of the two-wave factor form, where the fetch-ahead form exists for the stage (block size 6, two lanes
 	// a task: widths 16 and 32).  Development aid SLAMPP_HIP_DEV_SIMT_FACTOR_BRANCHES (plan.h): 0 = none, 1 = every shape with two
-	// bins splits; the launches read the knob again (simt_kernel.hip)
-	const int n_branches_env = dev_knob("SLAMPP_HIP_DEV_SIMT_FACTOR_BRANCHES", -1);
-	const bool b_branches = n_branches_env != 0 && P.uniform_dim && P.max_dim == 6 && (W == 16 || W == 32);
-	std::vector<int32_t> br_prog;
+	// bins splits; the launches read the knob again (simt_kernel.hip).  The same items become the records of the two-wave backward
+	// form, with a knob of their own, SLAMPP_HIP_DEV_SIMT_BWD_BRANCHES: at 1 it too makes every shape with two bins split, and
+	// the records are built even where the factor knob is 0
+	const int n_branches_env = dev_knob("SLAMPP_HIP_DEV_SIMT_FACTOR_BRANCHES", -1), n_bwd_branches_env = dev_knob("SLAMPP_HIP_DEV_SIMT_BWD_BRANCHES", -1);
+	const bool b_branches = (n_branches_env != 0 || n_bwd_branches_env == 1) && P.uniform_dim && P.max_dim == 6 && (W == 16 || W == 32);
+	std::vector<int32_t> br_prog, bwd_br_prog;
 	raw_vector<int64_t> br_tab; // (written in full by Build_Simt_Branches())
-	std::vector<char> br_split; // per record: its segments are in br_prog and br_tab
+	std::vector<int64_t> bwd_br_tab;
+	std::vector<char> br_split, bwd_br_split; // per record: its segments are in br_prog and br_tab
 	for(int s = 0; s < r_lists.n_bottom_stages && s < n_stages && s < t_opt.n_simt_stages; ++ s) {
 		const int32_t t0 = P.stage_ptr[s], n_stage_tasks = P.stage_ptr[s + 1] - P.stage_ptr[s];
 		double t_simt_phase = wall_ms();
@@ -1453,8 +1575,8 @@ void build_simt_tables(const Plan &P, const SparseRecordOptions &t_opt, SparseRe
 		Simt_Phase("tables");
 		r_lists.simt_br.push_back(TSimtBranchStage());
 		if(b_branches) {
-			Build_Simt_Branches(P, W, n_branches_env == 1, n_stage_tasks, tasks_all, groups, jobs, r_rec.simt_chunks.size() - jobs.size(), index_pool,
-				r_rec, r_lists.simt_br.back(), br_prog, br_tab, br_split);
+			Build_Simt_Branches(P, W, n_branches_env == 1 || n_bwd_branches_env == 1, n_stage_tasks, tasks_all, groups, jobs, r_rec.simt_chunks.size() - jobs.size(), index_pool,
+				r_rec, r_lists.simt_br.back(), br_prog, br_tab, br_split, bwd_br_prog, bwd_br_tab, bwd_br_split);
 			Simt_Phase("branches");
 		}
 		std::sort(rest.begin() + r_lists.simt_rest_ptr.back(), rest.end());
@@ -1481,6 +1603,23 @@ void build_simt_tables(const Plan &P, const SparseRecordOptions &t_opt, SparseRe
 				if(ch.n_tasks > 0) {
 					ch.prog_off += n_prog_base;
 					ch.tab_off += n_tab_base;
+				}
+			}
+		}
+	}
+	if(!r_rec.simt_bwd_br_groups.empty()) { // the same for the backward records (a chunk of whole tasks keeps the table it has)
+		const int32_t n_prog_base = int32_t(r_rec.simt_bwd_prog.size());
+		const int64_t n_tab_base = int64_t(r_rec.simt_bwd_tab.size());
+		r_rec.simt_bwd_prog.insert(r_rec.simt_bwd_prog.end(), bwd_br_prog.begin(), bwd_br_prog.end());
+		r_rec.simt_bwd_tab.resize(size_t(n_tab_base) + bwd_br_tab.size());
+		std::copy(bwd_br_tab.begin(), bwd_br_tab.end(), r_rec.simt_bwd_tab.begin() + n_tab_base);
+		for(size_t i = 0; i < r_rec.simt_bwd_br_groups.size(); ++ i) {
+			for(int k = 0; k < 3; ++ k) {
+				TSimtChunk &ch = r_rec.simt_bwd_br_groups[i].seg[k];
+				if(ch.n_tasks > 0) {
+					ch.prog_off += n_prog_base;
+					if(bwd_br_split[i])
+						ch.tab_off += n_tab_base;
 				}
 			}
 		}

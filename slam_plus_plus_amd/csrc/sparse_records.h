@@ -33,6 +33,13 @@ struct TSimtBranchStage {
 	int32_t n_longest_task = 0, n_stage_tasks = 0;
 	int32_t n_lds_bytes = 0;            // two regions of the largest segment table
 	std::vector<int32_t> split_by;      // triples: longer bin, join columns, tasks
+	// the same items in the same order as backward records (sparse_kernels.h: TSimtBwdBranchLaunch), in SparseRecords::simt_bwd_br_groups
+	int32_t n_bwd_first = 0, n_bwd_groups = 0; // (none: the LDS request is beyond a plain launch's, the stage keeps the one-wave backward forms)
+	int32_t n_bwd_tab_region = 0, n_bwd_x_region = 0, n_bwd_lds_bytes = 0; // entries, doubles, (3 tab + 2 x) * 8
+	// what the column loop meets in these records, for the report (SLAMPP_HIP_PLAN_TIMING): split tasks with three or more tips;
+	// columns of split tasks' segments with more blocks than a register set holds; columns of the records with two or more rows
+	// outside the task among the blocks held; chunks with spare lanes
+	int32_t n_bwd_tip3_tasks = 0, n_bwd_long_columns = 0, n_bwd_two_outside_columns = 0, n_bwd_spare_chunks = 0;
 };
 
 // what the launches of a step read on the host (sparse_enqueue.hip)
@@ -82,6 +89,7 @@ struct SparseRecords {
 	std::vector<int32_t> simt_prog, simt_rest, simt_bwd_prog;
 	raw_vector<int64_t> simt_tab, simt_bwd_tab; // (raw_vector: written in full by the table pass, never zero-filled)
 	std::vector<TSimtBranchGroup> simt_br_groups; // (the segments' programs and tables lie behind the chunks' in simt_prog and simt_tab)
+	std::vector<TSimtBranchGroup> simt_bwd_br_groups; // the same records of backward chunks (programs and tables behind the chunks' in simt_bwd_prog and simt_bwd_tab)
 };
 
 // index ranges on a few threads (the record loops of the cold path: every entry written once, from the plan alone)

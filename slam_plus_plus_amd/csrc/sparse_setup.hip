@@ -500,10 +500,14 @@ void slampp_hip_solver::Upload_Simt(const SparseRecords &r_rec)
 	d_simt_bwd_prog.Upload(r_rec.simt_bwd_prog, stream);
 	d_simt_bwd_tab.Upload(r_rec.simt_bwd_tab, stream);
 	d_simt_br_groups.Upload(r_rec.simt_br_groups, stream);
+	d_simt_bwd_br_groups.Upload(r_rec.simt_bwd_br_groups, stream);
 	SLAMPP_HIP_CHECK(hipStreamSynchronize(stream)); // (the host copies are no longer needed)
 	simt_branches_round_groups.clear();
 	for(size_t s = 0; s < lists.simt_br.size(); ++ s)
 		simt_branches_round_groups.push_back((lists.simt_br[s].n_groups > 0)? factor_simt_branches_groups(P.max_dim, n_simt_width, lists.simt_br[s].n_lds_bytes) : 0);
+	simt_bwd_branches_round_groups.clear();
+	for(size_t s = 0; s < lists.simt_br.size(); ++ s)
+		simt_bwd_branches_round_groups.push_back((lists.simt_br[s].n_bwd_groups > 0)? backward_simt_branches_groups(P.max_dim, n_simt_width, lists.simt_br[s].n_bwd_lds_bytes) : 0);
 	simt_bwd_ahead_waves.clear();
 	for(size_t s = 0; s < lists.simt_bwd_lds_bytes.size(); ++ s)
 		simt_bwd_ahead_waves.push_back(backward_simt_ahead_waves(P.max_dim, n_simt_width, lists.simt_bwd_lds_bytes[s]));
@@ -524,6 +528,14 @@ void slampp_hip_solver::Upload_Simt(const SparseRecords &r_rec)
 				"longest task %d; split tasks by (longer bin, join columns):%s; LDS %d bytes, one round holds %d workgroups\n", s, r_br.n_split_tasks, r_br.n_split_chunks,
 				r_br.n_whole_chunks, r_br.n_groups, r_br.n_tstar, r_br.n_longest_chain, r_br.n_longest_task, s_by.c_str(), r_br.n_lds_bytes,
 				(s < simt_branches_round_groups.size())? simt_branches_round_groups[s] : 0);
+			if(!r_br.n_bwd_groups)
+				continue;
+			fprintf(stderr, "[setup] stage %zu backward branches: %d split tasks in %d split chunks, %d whole chunks, %d workgroups of two waves, width %d, T* %d, longest chain %d, "
+				"longest task %d; split tasks by (longer bin, join columns):%s; split tasks with three tips or more: %d; segment columns with more than %d blocks: %d; "
+				"columns with two rows outside the task or more: %d; chunks with spare lanes: %d; LDS %d bytes (three table regions of %d entries, two x regions of %d doubles), "
+				"one round holds %d workgroups\n", s, r_br.n_split_tasks, r_br.n_split_chunks, r_br.n_whole_chunks, r_br.n_bwd_groups, n_simt_width, r_br.n_tstar, r_br.n_longest_chain,
+				r_br.n_longest_task, s_by.c_str(), r_br.n_bwd_tip3_tasks, int(SIMT_BWD_AHEAD) + 1, r_br.n_bwd_long_columns, r_br.n_bwd_two_outside_columns, r_br.n_bwd_spare_chunks,
+				r_br.n_bwd_lds_bytes, r_br.n_bwd_tab_region, r_br.n_bwd_x_region, (s < simt_bwd_branches_round_groups.size())? simt_bwd_branches_round_groups[s] : 0);
 		}
 		for(size_t s = 0; s + 1 < lists.simt_chunk_ptr.size(); ++ s) {
 			fprintf(stderr, "[setup] stage %zu: %d tasks -> %d chunks of 64 lanes, %d tasks left to the wave-per-task kernel\n", s,
