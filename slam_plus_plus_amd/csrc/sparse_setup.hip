@@ -180,8 +180,11 @@ void Setup_Dense_Top(slampp_hip_solver &s, const SparseRecords &r_rec, TSetupPha
 	// which 64 x 64 tiles of the dense top are structurally nonzero, and how long the dependent chain is if only
 	// those are touched and independent tile columns are factored side by side
 	s.b_dense_tiles = false;
-	if(s.n_dense_top_tiles == 0)
+	if(s.n_dense_top_tiles == 0) {
+		if(Phase.b_timing)
+			fprintf(stderr, "[setup] dense top: %d tiles per side, option dense_top_tiles = 0 -> dense schedule\n", n_dense_pad / dense_NB);
 		return;
+	}
 	std::vector<char> nonzero;
 	const int T = dense_top_tile_pattern(P, nonzero);
 	if(T != n_dense_pad / dense_NB)
