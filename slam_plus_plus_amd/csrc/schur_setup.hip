@@ -228,7 +228,7 @@ CSchurState *schur_analyze(slampp_hip_solver &s)
 				Early_Uploads(); // (a small system: a thread's start-up is what it would save)
 		}
 		// contributions to S grouped by block (row = camera of b, col = camera of a, a <= b within a point)
-		const int64_t ubase = S.n_ablocks * DC * DC;
+		// (the builders of schur_tile_tables.cpp)
 		std::vector<int64_t> sb_ptr;
 		std::vector<int32_t> sb_row, sb_col;
 		raw_vector<int32_t> ent_a;    // (the contribution lists -- 5 M entries at the uniform-visibility C4 -- and the counters they are
@@ -241,142 +241,19 @@ CSchurState *schur_analyze(slampp_hip_solver &s)
 				n_entries += k * (k + 1) / 2;
 			}
 			S.n_entries = n_entries;
+			const SchurStructure t_structure = {int(DC), int(DP), nc, np, ptr, brow, S.n_ablocks};
 			if(nc * nc <= (int64_t(1) << 26)) { // the dense key space
-				// Which blocks of S exist: a bit per camera pair, a bitmap per thread over its range of landmarks, OR-ed at the end
-				// (round 5; counting the contributions of every block was 19 ms on one core at C5 -- with atomic adds from eight,
-				// every landmark of the band structure on the same few thousand counters, 88 ms --, and the counts are only needed
-				// where the landmarks cannot be taken one by one: below)
-				const int64_t n_words = (nc * nc + 63) / 64;
-				std::vector<std::vector<uint64_t> > pair_bits(n_setup_workers, std::vector<uint64_t>(size_t(n_words), 0));
-				for_ranges(0, np, n_setup_workers, [&](int t, int64_t n_first, int64_t n_last) {
-					std::vector<uint64_t> &r_bits = pair_bits[t];
-					for(int64_t pt = n_first; pt < n_last; ++ pt) {
-						const int64_t o0 = ptr[nc + pt] - ptr[nc] - pt, o1 = ptr[nc + pt + 1] - ptr[nc] - (pt + 1);
-						for(int64_t a = o0; a < o1; ++ a) {
-							const int64_t n_base = int64_t(obs_cam[a]) * nc;
-							for(int64_t b = a; b < o1; ++ b) {
-								const int64_t key = n_base + obs_cam[b];
-								r_bits[size_t(key >> 6)] |= uint64_t(1) << (key & 63);
-							}
-						}
-					}
-				});
-				for(int64_t w = 0; w < n_words; ++ w) {
-					uint64_t n_word = 0;
-					for(int t = 0; t < n_setup_workers; ++ t)
-						n_word |= pair_bits[t][size_t(w)];
-					for(; n_word; n_word &= n_word - 1) {
-						const int64_t key = w * 64 + __builtin_ctzll(n_word);
-						sb_col.push_back(int32_t(key / nc));
-						sb_row.push_back(int32_t(key % nc));
-					}
-				}
-				pair_bits.clear();
+				schur_blocks_from_bitmap(sb_row, sb_col, t_structure, obs_cam, n_setup_workers);
 				SCHUR_SETUP_PHASE("blocks of S");
 				// the blocks of S are known: can the landmarks be taken one by one (schur_tiles.hip)?  Then the per-block
 				// contribution lists -- 12 bytes and a scattered write per contribution -- are not needed at all
 				schur_tiles_build(S.tiles, s.n_schur_tiles, int(DC), int(DP), nc, np, ptr, brow, sb_row, sb_col, S.n_ablocks, s.stream);
 				b_tiles_built = true;
 				SCHUR_SETUP_PHASE("runs and tiles");
-				if(!S.tiles.b_enabled) {
-					// the lists of every block after all: a counting sort of the contributions by block.  Round 6: on the threads of
-					// the passes above, a counter array per thread over its range of landmarks (one thread counted and placed the
-					// five million contributions of the uniform-visibility C4 in 37 ms); every contribution lands where the serial
-					// pass put it: inside a block in landmark order
-					const int64_t n_keys = nc * nc;
-					const int n_list_workers = int(std::max<int64_t>(1, std::min<int64_t>(n_setup_workers, (int64_t(1) << 26) / std::max<int64_t>(n_keys, 1)))); // (at most 512 MB of counters)
-					std::vector<raw_vector<int64_t> > cnt(n_list_workers);
-					for_ranges(0, np, n_list_workers, [&](int t, int64_t n_first, int64_t n_last) {
-						raw_vector<int64_t> &r_cnt = cnt[t];
-						r_cnt.assign(size_t(n_keys), 0);
-						for(int64_t pt = n_first; pt < n_last; ++ pt) {
-							const int64_t o0 = ptr[nc + pt] - ptr[nc] - pt, o1 = ptr[nc + pt + 1] - ptr[nc] - (pt + 1);
-							for(int64_t a = o0; a < o1; ++ a)
-								for(int64_t b = a; b < o1; ++ b)
-									++ r_cnt[int64_t(obs_cam[a]) * nc + obs_cam[b]];
-						}
-					});
-					// where every thread's contributions to every block start: block by block, inside a block thread by thread --
-					// the ranges of blocks first by themselves, then shifted by what the ranges before them hold
-					std::vector<int64_t> range_total(n_list_workers, 0);
-					std::vector<std::vector<int64_t> > range_starts(n_list_workers); // start of every nonzero block of the range
-					for_ranges(0, n_keys, n_list_workers, [&](int r, int64_t n_first, int64_t n_last) {
-						int64_t n_sum = 0;
-						for(int64_t key = n_first; key < n_last; ++ key) {
-							const int64_t n_before = n_sum;
-							for(int t = 0; t < n_list_workers; ++ t) {
-								const int64_t n_here = cnt[t][size_t(key)];
-								cnt[t][size_t(key)] = n_sum;
-								n_sum += n_here;
-							}
-							if(n_sum != n_before)
-								range_starts[r].push_back(n_before);
-						}
-						range_total[r] = n_sum;
-					});
-					std::vector<int64_t> range_base(n_list_workers + 1, 0);
-					for(int r = 0; r < n_list_workers; ++ r)
-						range_base[r + 1] = range_base[r] + range_total[r];
-					for_ranges(0, n_keys, n_list_workers, [&](int r, int64_t n_first, int64_t n_last) {
-						if(!range_base[r])
-							return;
-						for(int t = 0; t < n_list_workers; ++ t) {
-							int64_t *p_cnt = cnt[t].data();
-							for(int64_t key = n_first; key < n_last; ++ key)
-								p_cnt[key] += range_base[r];
-						}
-					});
-					for(int r = 0; r < n_list_workers; ++ r) {
-						for(size_t i = 0; i < range_starts[r].size(); ++ i)
-							sb_ptr.push_back(range_starts[r][i] + range_base[r]);
-					}
-					sb_ptr.push_back(n_entries);
-					if(sb_ptr.size() != sb_row.size() + 1 || range_base[n_list_workers] != n_entries)
-						throw std::logic_error("reduced camera system: the block list and the contribution counts disagree");
-					ent_a.resize(n_entries);
-					ent_uoff.resize(n_entries);
-					for_ranges(0, np, n_list_workers, [&](int t, int64_t n_first, int64_t n_last) {
-						int64_t *p_fill = cnt[t].data();
-						for(int64_t pt = n_first; pt < n_last; ++ pt) {
-							const int64_t o0 = ptr[nc + pt] - ptr[nc] - pt, o1 = ptr[nc + pt + 1] - ptr[nc] - (pt + 1);
-							for(int64_t a = o0; a < o1; ++ a)
-								for(int64_t b = a; b < o1; ++ b) {
-									const int64_t d = p_fill[int64_t(obs_cam[a]) * nc + obs_cam[b]] ++;
-									ent_a[d] = int32_t(a);
-									ent_uoff[d] = ubase + b * DC * DP + pt * DP * DP;
-								}
-						}
-					});
-				}
-			} else { // comparison sort on (key, a, b)
-				ent_a.resize(n_entries);
-				ent_uoff.resize(n_entries);
-				struct TE { int64_t key; int32_t a, b; };
-				std::vector<TE> ents(n_entries);
-				int64_t e = 0;
-				for(int64_t pt = 0; pt < np; ++ pt) {
-					const int64_t o0 = ptr[nc + pt] - ptr[nc] - pt, o1 = ptr[nc + pt + 1] - ptr[nc] - (pt + 1);
-					for(int64_t a = o0; a < o1; ++ a)
-						for(int64_t b = a; b < o1; ++ b) {
-							ents[e].key = int64_t(obs_cam[a]) * nc + obs_cam[b];
-							ents[e].a = int32_t(a);
-							ents[e].b = int32_t(b);
-							++ e;
-						}
-				}
-				std::sort(ents.begin(), ents.end(), [](const TE &x, const TE &y) {
-					return x.key < y.key || (x.key == y.key && x.a < y.a); });
-				for(e = 0; e < n_entries; ++ e) {
-					if(!e || ents[e].key != ents[e - 1].key) {
-						sb_ptr.push_back(e);
-						sb_col.push_back(int32_t(ents[e].key / nc));
-						sb_row.push_back(int32_t(ents[e].key % nc));
-					}
-					ent_a[e] = ents[e].a;
-					ent_uoff[e] = ubase + int64_t(ents[e].b) * DC * DP + int64_t(obs_pt[ents[e].b]) * DP * DP;
-				}
-				sb_ptr.push_back(n_entries);
-			}
+				if(!S.tiles.b_enabled) // the lists of every block after all
+					schur_lists_by_counting(sb_ptr, ent_a, ent_uoff, t_structure, obs_cam, n_entries, sb_row.size(), n_setup_workers);
+			} else
+				schur_lists_by_sorting(sb_ptr, sb_row, sb_col, ent_a, ent_uoff, t_structure, obs_cam, obs_pt, n_entries);
 		}
 		S.n_sblocks = int64_t(sb_row.size());
 		S.h_blk_row = sb_row;

@@ -1,6 +1,7 @@
 // schur_tiles.h -- landmark-major assembly of the reduced camera system (schur_tiles.hip)
 #pragma once
 #include "solver.h"
+#include "schur_tile_tables.h"
 #include <cstdint>
 #include <vector>
 #include <thread>
@@ -9,27 +10,17 @@
 
 namespace slampp {
 
-enum { SCHUR_TILE_SLOTS = 64, SCHUR_TILE_MAX_POINTS = 64 };
-
-struct TRunJob { // one wave of the run kernel
-	int32_t n_first, n_points; // landmarks [n_first, n_first + n_points) of the run list
-	int32_t n_k, n_rb, n_cb;   // cameras of the run's landmarks; observation blocks of the rows and of the columns
-	int32_t n_pad;
-	int64_t n_pbase;           // first partial block
-};
-
 // the run tables on their way to the device beside the rest of the analysis (schur_tiles_build starts it, schur_tiles_join
-// waits for it): the thread owns what it reads
+// waits for it): the thread owns what it reads, with the analysis that made it
 struct TRunUpload {
 	std::thread t;
-	raw_vector<TRunJob> jobs;
-	raw_vector<int32_t> run_lm, run_k;
+	std::shared_ptr<const SchurRunTables> p_tables;
 	std::exception_ptr p_error;
 	~TRunUpload() { if(t.joinable()) t.join(); }
 };
 
 struct CSchurTiles {
-	CTrashList trash;        // work arrays of schur_tiles_build that nobody reads any more: the caller frees them when it suits (host_pool.h: TTrash)
+	CTrashList trash;        // work arrays of the tile analysis (schur_tile_tables.h) that nobody reads any more: the caller frees them when it suits (host_pool.h: TTrash)
 	bool b_enabled = false;  // some landmarks go through the tiles
 	bool b_hybrid = false;   // ... and some through the contribution lists (the x-lists below)
 	int64_t n_tiles = 0, n_slots = 0, n_tile_points = 0, n_list_points = 0, n_tile_pairs = 0, n_all_pairs = 0, n_rb = 0, n_max_slots = 0, n_max_k = 0;
@@ -66,7 +57,7 @@ struct CSchurTiles {
 	std::shared_ptr<TRunUpload> p_run_upload; // (the last member: destroyed -- joined -- before the arrays it fills)
 };
 
-// host analysis: n_mode -1 = runs and tiles when together they take at least half of the contributions, 0 = never,
+// host analysis (the builders of schur_tile_tables.h, the uploads beside them): n_mode -1 = runs and tiles when together they take at least half of the contributions, 0 = never,
 // 1 = wherever possible, 2 = tiles only, 3 = runs only (of any length).  sb_row / sb_col: the blocks of S sorted by (col, row), as the contribution lists have them.
 // waits for the run tables to be on the device (throws what the upload threw); before the first use of the tiles and before
 // the analysis that built them returns

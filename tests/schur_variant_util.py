@@ -1,6 +1,6 @@
 """Helpers of tests/test_schur_variants_gpu.py and tests/test_schur_variant_systems_host.py: BA systems with designed
 visibility -- every landmark's camera list is written down, so that the host analysis of the landmark-major assembly
-(schur_tiles_build, csrc/schur_tiles.hip) meets the job shape a case is about --, their dense high-precision references
+(schur_tile_routes, csrc/schur_tile_tables.cpp) meets the job shape a case is about --, their dense high-precision references
 (never the library under test), the analysis' rules restated (which jobs a run of landmarks becomes), the parser of the
 "[schur report]" lines the analysis prints under SLAMPP_HIP_PLAN_TIMING, and the one list of checks every case goes through.
 
@@ -34,7 +34,7 @@ def ob_of(dc):
 
 
 def nt_of(dc, k):
-    """Tile_Class() of schur_tiles_build: 16-line tiles a side of a landmark's first job."""
+    """class_tiles of read_class_lists() (csrc/schur_tile_tables.cpp): 16-line tiles a side of a landmark's first job."""
     return (min(k, ob_of(dc)) * dc + 15) // 16
 
 
@@ -158,7 +158,7 @@ def with_indefinite_landmark(lam, p):
 # ---- the analysis' rules, restated ------------------------------------------------------------------------------------------
 
 def run_jobs(dc, members_k, mult=1):
-    """Emit_Run() of schur_tiles_build for one run whose members have ``members_k`` cameras (longest first): a Counter over
+    """CRunEmitter::Emit_Run() (csrc/schur_tile_tables.cpp) for one run whose members have ``members_k`` cameras (longest first): a Counter over
     (NT, diagonal, prefix, landmarks of the job).  Pieces of 64 landmarks -- 32 where a job keeps more than three tiles a
     side --, ``mult`` times that with SLAMPP_HIP_DEV_RUN_PIECE_MULT; a job per pair (rb >= cb) of observation blocks, over
     the piece's landmarks that reach into row block rb."""
@@ -203,7 +203,7 @@ def _counts(text):
 
 
 def parse_report(err):
-    """The "[schur report]" lines schur_tiles_build prints under SLAMPP_HIP_PLAN_TIMING."""
+    """The "[schur report]" lines the tile analysis (csrc/schur_tile_tables.cpp) prints under SLAMPP_HIP_PLAN_TIMING."""
     rep = {"runs": {}, "tiles": None, "reduce": None, "routes": None, "lists_keep": None,
            "lines": [l for l in err.splitlines() if l.startswith("[schur report]") or l.startswith("[schur] of")]}
     for m in re.finditer(r"\[schur report\] runs: NT=(\d) diag=(\d) prefix=(\d) quad=(\d) jobs=(\d+) max_points=(\d+) points=(\S+)", err):
