@@ -712,7 +712,14 @@ int slampp_hip_get_profile_reference_names(slampp_hip_solver *p_solver, slampp_h
  * block column n_unary_vertex: U^T U is added to its diagonal block and the error to its eta.
  * Writes the packed block values of Lambda (the layout slampp_hip_factor_solve_device reads) and eta;
  * with b_accumulate != 0 adds to what the two arrays hold instead (a second edge set of the same Lambda).
- * Sums run in a fixed order: results are bit-reproducible.  Enqueue-only, on the solver's stream. */
+ * Sums run in a fixed order: results are bit-reproducible.  Enqueue-only, on the solver's stream.
+ *
+ * Alignment of p_J0_dev, p_J1_dev, p_sigma_inv_dev and p_error_dev: where the handle formed vertex groups
+ * (slampp_hip_assembly_get_info: n_groups > 0) and n_residual_dim is 2 or 6, the group kernel copies the four arrays
+ * with 16-byte loads, and each must start at a multiple of 16 bytes -- what hipMalloc and every allocator on top of it
+ * give; a pointer into the middle of a larger allocation need not.  slampp_hip_assemble_device_async and
+ * slampp_hip_assemble_sets_device_async return SLAMPP_HIP_ERR_INVALID otherwise, before anything is enqueued.  In every
+ * other case the natural alignment of a double is enough. */
 /* Levenberg-Marquardt damping of device-resident values (the ones slampp_hip_assemble_device_async wrote): adds
  * f_alpha to the diagonal of the diagonal blocks of block columns [n_first_vertex, n_last_vertex) -- the reference's
  * ApplyDamping(r_lambda, f_alpha, n_first_vertex, n_last_vertex), include/slam/NonlinearSolver_Lambda_LM.h:228-239,
@@ -725,6 +732,20 @@ typedef struct slampp_hip_assembly slampp_hip_assembly; /* opaque */
 int slampp_hip_assembly_create(slampp_hip_solver *p_solver, slampp_hip_assembly **pp_assembly, int64_t n_edges,
 	const int64_t *p_vertex0, const int64_t *p_vertex1, int n_residual_dim);
 void slampp_hip_assembly_destroy(slampp_hip_assembly *p_assembly); /* in either order with its solver's destroy */
+/* What create built, by the kernel that takes it (read-only): consecutive vertices with few edges go
+ * to the group kernel (n_groups groups of at most n_grp_cap_edges edges, one package of n_grp_pkg_stride words each; no
+ * groups where n_grp_cap_edges < 8 or option "assembly_groups" is 0); of the others, n_long vertices of dimension
+ * n_long_dim with 96 edges or more to the edge-parallel kernel, n_small to the packed kernel (n_small_elems lanes each),
+ * n_plain_diag to the one-wave kernel; the n_offdiag off-diagonal blocks outside the groups (n_off_elems: the largest, in
+ * elements) to the packed kernel (b_offdiag_packed) or the one-wave kernel. */
+typedef struct slampp_hip_assembly_info {
+	int rd, d0, d1; /* n_residual_dim and the two vertex dimensions of the set */
+	int n_grp_cap_edges, n_grp_pkg_stride;
+	int n_long_dim, n_small_elems, n_off_elems, b_offdiag_packed;
+	int n_pad;
+	int64_t n_groups, n_long, n_small, n_plain_diag, n_offdiag;
+} slampp_hip_assembly_info;
+int slampp_hip_assembly_get_info(const slampp_hip_assembly *p_assembly, slampp_hip_assembly_info *p_info);
 int slampp_hip_assemble_device_async(slampp_hip_assembly *p_assembly, const double *p_J0_dev, const double *p_J1_dev,
 	const double *p_sigma_inv_dev, const double *p_error_dev, const double *p_weight_dev, int64_t n_unary_vertex,
 	const double *p_unary_factor, const double *p_unary_error, double *p_values_dev, double *p_eta_dev, int b_accumulate);

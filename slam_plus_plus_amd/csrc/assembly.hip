@@ -13,19 +13,12 @@
 // (no atomics, bit-reproducible) and writes the block where the solver's packed value array expects it, so
 // that factor_solve_device can run on the result without Lambda ever visiting the host.  HBM-bound.
 #include "solver.h"
+#include "assembly_tables.h"
 
 #include <algorithm>
 #include <cstring>
 
 namespace slampp {
-
-struct TAsmBlk { // 32 B: one block of Lambda and the edges that contribute to it
-	int64_t dst;       // offset in the packed Lambda values
-	int64_t e0;        // first entry of its edge list
-	int64_t eta_off;   // diagonal blocks: scalar offset of the vertex in eta
-	int32_t ne;        // number of entries
-	int16_t rows, cols;
-};
 
 struct CAssemblyState {
 	int64_t n_edges;
@@ -47,7 +40,7 @@ struct CAssemblyState {
 	// groups of consecutive vertices whose edges fit in LDS together: every edge record is read once for the off-diagonal
 	// block and both diagonal contributions (assemble_group_kernel)
 	int64_t n_groups;
-	CDevArray<int32_t> d_grp_words; // per group, n_grp_pkg_stride words: n_edges, n_blocks, n_entries, 0 | edges (n_grp_cap_edges, padded) | blocks (6 words each) | entries (slot * 2 + flag)
+	CDevArray<int32_t> d_grp_words; // per group, n_grp_pkg_stride words: n_edges, n_blocks, n_entries, n_items | edges (n_grp_cap_edges, padded) | blocks (6 words each) | entries (slot * 2 + flag) | items (assembly_tables.cpp)
 	int n_grp_pkg_stride, n_grp_cap_edges;
 	int n_grp_resident[2];          // workgroups of the kernel a CU holds (without / with accumulation; 0: not asked yet)
 	CDevArray<double> d_unary;      // [64 + 8]: U^T U (column-major d x d), unary error
@@ -58,286 +51,40 @@ struct CAssemblyState {
 
 void assembly_destroy(CAssemblyState *p) { delete p; }
 
-// (residual dimension, vertex dimension) pairs the edge-parallel kernel is instantiated for
-static bool long_kernel_exists(int rd, int d)
-{
-	return (rd == 2 && (d == 6 || d == 7 || d == 3)) || (rd == 3 && d == 3) || (rd == 6 && d == 6) || (rd == 7 && d == 7);
-}
-
-enum { GRP_LDS_BYTES = 160 * 1024 / 6 - 576 - 1536, GRP_PACKAGE_WORDS = 1024, GRP_PKG_PER_THREAD = 4, GRP_MAX_INSTR = 4 }; // LDS of a workgroup (six to a CU); its package; copy instructions per wave // LDS of a group: its edges' records; its package
-
-// the group kernel's shape for an edge set: bytes of an edge in LDS (J0 | J1 | Sigma^-1 | error as they lie in memory,
-// M = Sigma^-1 [J0 J1 e], the weight), edges per wave, copy instructions per wave
-struct TAsmGroupShape {
-	int n_edge_bytes, n_ew, n_instr;
-};
-
-static inline TAsmGroupShape asm_group_shape(int rd, int d0, int d1)
-{
-	const int n_sz = (rd % 2 == 0 && (rd == 2 || rd == 6))? 16 : 4; // (the instantiations with 16-byte copies: assemble_group_kernel's SZ)
-	const int n_raw = rd * (d0 + d1 + rd + 1), n_mw = (rd * (d0 + d1 + 1) + 1) & ~1, n_units = n_raw * 8 / n_sz;
-	TAsmGroupShape t;
-	t.n_edge_bytes = (n_raw + n_mw + 1) * 8;
-	t.n_ew = std::min(std::min(int(GRP_LDS_BYTES) / t.n_edge_bytes / 4, 64 * int(GRP_MAX_INSTR) / n_units), 32);
-	t.n_instr = (t.n_ew * n_units + 63) / 64;
-	return t;
-}
-
 CAssemblyState *assembly_setup(slampp_hip_solver &s, int64_t n_edges, const int64_t *v0, const int64_t *v1, int rd)
 {
 	if(!s.b_has_structure)
 		throw std::invalid_argument("assembly_setup: set_structure was not called");
-	if(n_edges <= 0 || !v0 || !v1 || rd <= 0 || rd > 8)
-		throw std::invalid_argument("assembly_setup: bad edge set");
-	const int64_t n = int64_t(s.cumsum.size()) - 1;
-	const int64_t *cs = s.cumsum.data(), *ptr = s.bcol_ptr.data();
-	const int32_t *brow = s.brow.data();
-	for(int64_t e = 0; e < n_edges; ++ e) {
-		if(v0[e] < 0 || v0[e] >= n || v1[e] < 0 || v1[e] >= n || v0[e] == v1[e])
-			throw std::invalid_argument("assembly_setup: edge refers to a vertex outside Lambda, or to one vertex twice");
-	}
-	const int d0 = int(cs[v0[0] + 1] - cs[v0[0]]), d1 = int(cs[v1[0] + 1] - cs[v1[0]]);
-	if(d0 > 7 || d1 > 7)
-		throw std::domain_error("assembly: vertex dimensions above 7 are not supported");
-	for(int64_t e = 0; e < n_edges; ++ e) {
-		if(cs[v0[e] + 1] - cs[v0[e]] != d0 || cs[v1[e] + 1] - cs[v1[e]] != d1)
-			throw std::domain_error("assembly: all edges of a set must join vertices of the same two dimensions");
-	}
-	// value offset of every block of Lambda
-	std::vector<int64_t> voff(ptr[n] + 1, 0);
-	for(int64_t c = 0; c < n; ++ c)
-		for(int64_t k = ptr[c]; k < ptr[c + 1]; ++ k)
-			voff[k + 1] = voff[k] + (cs[brow[k] + 1] - cs[brow[k]]) * (cs[c + 1] - cs[c]);
-	// edge lists per block: count, then fill (stable: edges stay in their given order inside a list)
-	std::vector<int64_t> blk_of_edge(n_edges);
-	std::vector<int32_t> cnt_off(ptr[n], 0), cnt_diag(n, 0);
-	for(int64_t e = 0; e < n_edges; ++ e) {
-		const int64_t r = std::min(v0[e], v1[e]), c = std::max(v0[e], v1[e]);
-		const int32_t *b = std::lower_bound(brow + ptr[c], brow + ptr[c + 1], int32_t(r));
-		if(b == brow + ptr[c + 1] || *b != r)
-			throw std::invalid_argument("assembly_setup: Lambda has no block for an edge");
-		blk_of_edge[e] = b - brow;
-		++ cnt_off[b - brow];
-		++ cnt_diag[v0[e]];
-		++ cnt_diag[v1[e]];
-	}
-	std::vector<TAsmBlk> offdiag, diag(n);
-	std::vector<int64_t> off_slot(ptr[n], -1);
-	int64_t n_entries = 0;
-	for(int64_t c = 0; c < n; ++ c) {
-		for(int64_t k = ptr[c]; k < ptr[c + 1]; ++ k) {
-			if(brow[k] == c)
-				continue;
-			TAsmBlk b;
-			b.dst = voff[k]; b.e0 = n_entries; b.ne = cnt_off[k]; b.eta_off = 0;
-			b.rows = int16_t(cs[brow[k] + 1] - cs[brow[k]]); b.cols = int16_t(cs[c + 1] - cs[c]);
-			n_entries += cnt_off[k];
-			off_slot[k] = int64_t(offdiag.size());
-			offdiag.push_back(b); // blocks without an edge are written as zeros
-		}
-	}
-	for(int64_t v = 0; v < n; ++ v) {
-		if(ptr[v + 1] == ptr[v] || brow[ptr[v + 1] - 1] != v)
-			throw std::invalid_argument("assembly_setup: a diagonal block is missing");
-		TAsmBlk &b = diag[v];
-		b.dst = voff[ptr[v + 1] - 1]; b.e0 = n_entries; b.ne = cnt_diag[v]; b.eta_off = cs[v];
-		b.rows = b.cols = int16_t(cs[v + 1] - cs[v]);
-		if(b.rows > 7)
-			throw std::domain_error("assembly: vertex dimensions above 7 are not supported");
-		n_entries += cnt_diag[v];
-	}
-	if(n_edges >= (int64_t(1) << 30))
-		throw std::domain_error("assembly: too many edges");
-	std::vector<int32_t> entries(n_entries);
-	{
-		std::vector<int64_t> fill_off(offdiag.size()), fill_diag(n);
-		for(size_t i = 0; i < offdiag.size(); ++ i) fill_off[i] = offdiag[i].e0;
-		for(int64_t v = 0; v < n; ++ v) fill_diag[v] = diag[v].e0;
-		for(int64_t e = 0; e < n_edges; ++ e) {
-			entries[fill_off[off_slot[blk_of_edge[e]]] ++] = int32_t(e * 2 + (v0[e] > v1[e]));
-			entries[fill_diag[v0[e]] ++] = int32_t(e * 2);
-			entries[fill_diag[v1[e]] ++] = int32_t(e * 2 + 1);
-		}
-	}
-	// Groups of consecutive vertices (a pose graph's odometry chain makes neighbours of them): the workgroup of a group
-	// brings the records of all edges that touch its vertices into LDS once and writes every block of their columns --
-	// an edge inside a group is read once instead of three times (off-diagonal block, two diagonal blocks), one that
-	// leaves it twice.  A group closes at GRP_VERTICES vertices or when its edges would not fit; vertices with more edges
-	// than fit on their own stay with the kernels below.
-	std::vector<int64_t> grp_ptr;
-	std::vector<int32_t> grp_words;
-	std::vector<uint8_t> b_grouped(n, 0);
-	int n_grp_pkg_cap = 0, n_grp_cap_edges = 0;
-	{
-		const int n_grp_vertices = s.n_assembly_groups; // option "assembly_groups": as many as fit by default, 0 = the one-wave kernels for everything
-		const int n_mode = n_grp_vertices > 0;
-		const TAsmGroupShape t_shape = asm_group_shape(rd, d0, d1);
-		const int n_cap_edges = 4 * t_shape.n_ew; // as many edges as the workgroup copies in one go: n_ew per wave
-		n_grp_cap_edges = n_cap_edges;
-		if(n_mode > 0 && n_cap_edges >= 8) {
-			std::vector<int64_t> stamp(n_edges, -1);
-			std::vector<int32_t> slot_of(n_edges, 0);
-			std::vector<int32_t> g_edges, g_blocks, g_entries;
-			std::vector<uint16_t> g_items;
-			std::vector<int64_t> g_vertices;
-			auto Close = [&]() {
-				if(g_vertices.empty())
-					return;
-				g_blocks.clear(); g_entries.clear(); g_items.clear();
-				for(size_t i = 0; i < g_vertices.size(); ++ i) {
-					const int64_t v = g_vertices[i];
-					for(int64_t k = ptr[v]; k < ptr[v + 1]; ++ k) {
-						const bool b_diag = brow[k] == v;
-						const TAsmBlk &b = b_diag? diag[v] : offdiag[off_slot[k]];
-						const int32_t n_begin = int32_t(g_entries.size());
-						for(int64_t i2 = 0; i2 < b.ne; ++ i2) {
-							const int32_t ent = entries[b.e0 + i2];
-							g_entries.push_back(slot_of[ent >> 1] * 2 + (ent & 1));
-						}
-						g_blocks.push_back(int32_t(uint64_t(b.dst) & 0xffffffffu));
-						g_blocks.push_back(int32_t(uint64_t(b.dst) >> 32));
-						g_blocks.push_back(b_diag? int32_t(b.eta_off) : -1);
-						g_blocks.push_back(int32_t(v));
-						g_blocks.push_back(n_begin | (int32_t(b.ne) << 16));
-						g_blocks.push_back(int32_t(b.rows) | (int32_t(b.cols) << 8));
-						for(int q = 0; q < int(b.cols) + (b_diag? 1 : 0); ++ q)
-							g_items.push_back(uint16_t((g_blocks.size() / 6 - 1) * 8 + q)); // (block, column; column `cols` of a diagonal block: eta)
-					}
-					b_grouped[v] = 1;
-				}
-				// the lanes of a wave walk their blocks' edge lists in step: blocks with lists of the same length next to each other
-				std::stable_sort(g_items.begin(), g_items.end(), [&](uint16_t a, uint16_t b) {
-					return (uint32_t(g_blocks[6 * (a >> 3) + 4]) >> 16) < (uint32_t(g_blocks[6 * (b >> 3) + 4]) >> 16); });
-				grp_ptr.push_back(int64_t(grp_words.size()));
-				grp_words.push_back(int32_t(g_edges.size()));
-				grp_words.push_back(int32_t(g_blocks.size() / 6));
-				grp_words.push_back(int32_t(g_entries.size()));
-				grp_words.push_back(int32_t(g_items.size()));
-				grp_words.insert(grp_words.end(), g_edges.begin(), g_edges.end());
-				grp_words.insert(grp_words.end(), size_t(n_cap_edges) - g_edges.size(), g_edges.empty()? 0 : g_edges[0]); // (valid addresses for the requests)
-				grp_words.insert(grp_words.end(), g_blocks.begin(), g_blocks.end());
-				grp_words.insert(grp_words.end(), g_entries.begin(), g_entries.end());
-				for(size_t i = 0; i < g_items.size(); i += 2)
-					grp_words.push_back(int32_t(uint32_t(g_items[i]) | (uint32_t((i + 1 < g_items.size())? g_items[i + 1] : 0) << 16)));
-				n_grp_pkg_cap = std::max(n_grp_pkg_cap, int(4 + n_cap_edges + g_blocks.size() + g_entries.size() + (g_items.size() + 1) / 2));
-				g_edges.clear(); g_vertices.clear();
-			};
-			int64_t n_group = 0, n_group_words = 0; // number of the open group; words of its blocks and entries so far
-			for(int64_t v = 0; v < n; ++ v) {
-				const int64_t n_v_words = (6 + 4) * (ptr[v + 1] - ptr[v]) + 3 * int64_t(cnt_diag[v]) + 1; // blocks and their items, entries
-				if(cnt_diag[v] > n_cap_edges || n_v_words + 4 + n_cap_edges > GRP_PACKAGE_WORDS || int(diag[v].rows) * int(diag[v].rows) + int(diag[v].rows) > 64) {
-					Close(); // (consecutive vertices only)
-					++ n_group; n_group_words = 0;
-					continue;
-				}
-				int n_new = 0;
-				for(int64_t i = 0; i < diag[v].ne; ++ i)
-					n_new += stamp[entries[diag[v].e0 + i] >> 1] != n_group;
-				if(int(g_vertices.size()) == n_grp_vertices || int(g_edges.size()) + n_new > n_cap_edges ||
-				   n_group_words + n_v_words + 4 + n_cap_edges > GRP_PACKAGE_WORDS) {
-					Close();
-					++ n_group; n_group_words = 0;
-				}
-				for(int64_t i = 0; i < diag[v].ne; ++ i) {
-					const int64_t e = entries[diag[v].e0 + i] >> 1;
-					if(stamp[e] != n_group) {
-						stamp[e] = n_group;
-						slot_of[e] = int32_t(g_edges.size());
-						g_edges.push_back(int32_t(e));
-					}
-				}
-				g_vertices.push_back(v);
-				n_group_words += n_v_words;
-			}
-			Close();
-			grp_ptr.push_back(int64_t(grp_words.size()));
-			if(grp_ptr.size() == 1)
-				grp_ptr.clear();
-			else { // one stride for all packages: a workgroup finds its next one without a lookup
-				n_grp_pkg_cap = (n_grp_pkg_cap + 3) & ~3; // (the records behind it start at a multiple of 16 bytes)
-				std::vector<int32_t> t_fixed((grp_ptr.size() - 1) * size_t(n_grp_pkg_cap), 0);
-				for(size_t i = 0; i + 1 < grp_ptr.size(); ++ i)
-					std::copy(grp_words.begin() + grp_ptr[i], grp_words.begin() + grp_ptr[i + 1], t_fixed.begin() + i * size_t(n_grp_pkg_cap));
-				grp_words.swap(t_fixed);
-			}
-			// the kernels below keep what the groups did not take
-			std::vector<TAsmBlk> offdiag_rest;
-			for(int64_t c = 0; c < n; ++ c) {
-				if(b_grouped[c])
-					continue;
-				for(int64_t k = ptr[c]; k < ptr[c + 1]; ++ k)
-					if(brow[k] != c) offdiag_rest.push_back(offdiag[off_slot[k]]);
-			}
-			offdiag.swap(offdiag_rest);
-		}
-	}
-	// Three kernels share the vertices: long lists go to the edge-parallel kernel (one lane per edge, tree reduction)
-	// when it exists for their dimension; low-dimensional vertices with short lists (the landmarks of a BA system:
-	// 12 of 64 lanes busy otherwise) are packed several to a wave when the residual is small enough to unroll; the
-	// rest stay with one wave per vertex
-	std::vector<TAsmBlk> long_blks, small_blks, plain_blks;
-	std::vector<int32_t> long_vertex, small_vertex, plain_vertex;
-	int n_long_dim = 0, n_small_elems = 0;
-	{
-		enum { LONG_LIST = 96 };
-		const bool b_can_pack = rd == 2 || rd == 3;
-		for(int64_t v = 0; v < n; ++ v) {
-			const int d = diag[v].rows;
-			if(b_grouped[v])
-				continue;
-			if(diag[v].ne >= LONG_LIST && long_kernel_exists(rd, d) && (!n_long_dim || d == n_long_dim)) {
-				n_long_dim = d;
-				long_blks.push_back(diag[v]);
-				long_vertex.push_back(int32_t(v));
-			} else if(b_can_pack && 2 * (d * d + d) <= 64) {
-				n_small_elems = std::max(n_small_elems, d * d + d);
-				small_blks.push_back(diag[v]);
-				small_vertex.push_back(int32_t(v));
-			} else {
-				plain_blks.push_back(diag[v]);
-				plain_vertex.push_back(int32_t(v));
-			}
-		}
-	}
-	int n_off_elems = 1;
-	for(size_t i = 0; i < offdiag.size(); ++ i) {
-		n_off_elems = std::max(n_off_elems, int(offdiag[i].rows) * int(offdiag[i].cols));
-		if(offdiag[i].ne == 1)
-			offdiag[i].e0 = entries[offdiag[i].e0]; // a single entry rides in the record: one dependent load less
-	}
+	TAsmTables t; // validation, lists, groups, routes: assembly_tables.cpp
+	assembly_build_tables(t, int64_t(s.cumsum.size()) - 1, s.cumsum.data(), s.bcol_ptr.data(), s.brow.data(), n_edges, v0, v1,
+		rd, s.n_assembly_groups);
 	CAssemblyState *p = new CAssemblyState();
 	try {
-		p->n_long = int64_t(long_blks.size()); p->n_long_dim = n_long_dim; p->n_off_elems = n_off_elems;
-		if(!long_blks.empty()) {
-			p->d_long.Upload(long_blks, s.stream);
-			p->d_long_vertex.Upload(long_vertex, s.stream);
+		p->n_long = int64_t(t.long_blks.size()); p->n_long_dim = t.n_long_dim; p->n_off_elems = t.n_off_elems;
+		if(!t.long_blks.empty()) {
+			p->d_long.Upload(t.long_blks, s.stream);
+			p->d_long_vertex.Upload(t.long_vertex, s.stream);
 		}
-		p->n_small = int64_t(small_blks.size()); p->n_small_elems = n_small_elems;
-		if(!small_blks.empty()) {
-			p->d_small.Upload(small_blks, s.stream);
-			p->d_small_vertex.Upload(small_vertex, s.stream);
+		p->n_small = int64_t(t.small_blks.size()); p->n_small_elems = t.n_small_elems;
+		if(!t.small_blks.empty()) {
+			p->d_small.Upload(t.small_blks, s.stream);
+			p->d_small_vertex.Upload(t.small_vertex, s.stream);
 		}
-		p->n_edges = n_edges; p->d0 = d0; p->d1 = d1; p->rd = rd;
-		p->n_offdiag = int64_t(offdiag.size()); p->n_diag = int64_t(plain_blks.size());
-		if(!offdiag.empty())
-			p->d_offdiag.Upload(offdiag, s.stream);
-		p->n_groups = grp_ptr.empty()? 0 : int64_t(grp_ptr.size()) - 1;
-		p->n_grp_pkg_stride = n_grp_pkg_cap; p->n_grp_cap_edges = n_grp_cap_edges;
+		p->n_edges = n_edges; p->d0 = t.d0; p->d1 = t.d1; p->rd = rd;
+		p->n_offdiag = int64_t(t.offdiag.size()); p->n_diag = int64_t(t.plain_blks.size());
+		if(!t.offdiag.empty())
+			p->d_offdiag.Upload(t.offdiag, s.stream);
+		p->n_groups = t.n_groups;
+		p->n_grp_pkg_stride = t.n_grp_pkg_stride; p->n_grp_cap_edges = t.n_grp_cap_edges;
 		p->n_grp_resident[0] = p->n_grp_resident[1] = 0;
 		if(p->n_groups)
-			p->d_grp_words.Upload(grp_words, s.stream);
-		if(!plain_blks.empty()) {
-			p->d_diag.Upload(plain_blks, s.stream);
-			p->d_diag_vertex.Upload(plain_vertex, s.stream);
+			p->d_grp_words.Upload(t.grp_words, s.stream);
+		if(!t.plain_blks.empty()) {
+			p->d_diag.Upload(t.plain_blks, s.stream);
+			p->d_diag_vertex.Upload(t.plain_vertex, s.stream);
 		}
-		p->d_entries.Upload(entries, s.stream);
-		std::vector<int64_t> edge_state(size_t(3 * n_edges));
-		for(int64_t e = 0; e < n_edges; ++ e) {
-			edge_state[e] = cs[v0[e]];
-			edge_state[n_edges + e] = cs[v1[e]];
-			edge_state[2 * n_edges + e] = v0[e];
-		}
-		p->d_edge_state.Upload(edge_state, s.stream); // (the synchronization below ends the copy before the vector goes)
+		p->d_entries.Upload(t.entries, s.stream);
+		p->d_edge_state.Upload(t.edge_state, s.stream); // (the synchronization below ends the copy before the vector goes)
 		p->d_unary.Alloc(72);
 		p->b_unary_valid = false;
 		p->p_solver = &s;
@@ -347,6 +94,29 @@ CAssemblyState *assembly_setup(slampp_hip_solver &s, int64_t n_edges, const int6
 		throw;
 	}
 	return p;
+}
+
+void assembly_get_info(const CAssemblyState &a, slampp_hip_assembly_info &r_info)
+{
+	r_info.rd = a.rd; r_info.d0 = a.d0; r_info.d1 = a.d1;
+	r_info.n_groups = a.n_groups;
+	r_info.n_grp_cap_edges = a.n_grp_cap_edges; r_info.n_grp_pkg_stride = a.n_grp_pkg_stride;
+	r_info.n_long = a.n_long; r_info.n_long_dim = a.n_long_dim;
+	r_info.n_small = a.n_small; r_info.n_small_elems = a.n_small_elems;
+	r_info.n_plain_diag = a.n_diag;
+	r_info.n_offdiag = a.n_offdiag; r_info.n_off_elems = a.n_off_elems;
+	r_info.b_offdiag_packed = (a.rd == 2 || a.rd == 3) && 2 * a.n_off_elems <= 64;
+}
+
+// The group kernel of rd = 2 and rd = 6 copies J0 | J1 | Sigma^-1 | error with 16-byte loads that write LDS directly,
+// straight from the caller's pointers (every edge's record is a multiple of 16 bytes there): the arrays must start at
+// multiples of 16 bytes.  The other kernels take any array of doubles.
+void assembly_check_arrays(const CAssemblyState &a, const double *J0, const double *J1, const double *Si, const double *err)
+{
+	if(a.n_groups > 0 && (a.rd == 2 || a.rd == 6) &&
+	   ((reinterpret_cast<uintptr_t>(J0) | reinterpret_cast<uintptr_t>(J1) | reinterpret_cast<uintptr_t>(Si) |
+	   reinterpret_cast<uintptr_t>(err)) & 15) != 0)
+		throw std::invalid_argument("assemble: the edge arrays of a set with vertex groups and 2- or 6-dimensional residuals must start at multiples of 16 bytes");
 }
 
 __device__ __forceinline__ void wave_sync_lds()
@@ -578,7 +348,7 @@ assemble_diag_packed_kernel(const TAsmBlk *__restrict__ blks, const int32_t *__r
 		}
 		#pragma unroll
 		for(int u = 0; u < UNR; ++ u) {
-			double sum = 0; // the arithmetic and its order are those of the one-wave kernel
+			double sum = 0; // (J^T Sigma^-1) J, row by row; the one-wave kernel forms J^T (Sigma^-1 J): the same sum, not the same bits
 			#pragma unroll
 			for(int b = 0; b < RD; ++ b) {
 				double t = 0;
@@ -989,6 +759,7 @@ void assembly_enqueue(CAssemblyState &a, const double *J0, const double *J1, con
 	hipStream_t st = s.stream;
 	if(!J0 || !J1 || !Si || !err || !values_out || !eta_out)
 		throw std::invalid_argument("assemble: null device pointer");
+	assembly_check_arrays(a, J0, J1, Si, err);
 	int n_unary = -1;
 	if(p_unary_factor) {
 		if(n_unary_vertex < 0 || n_unary_vertex >= int64_t(s.cumsum.size()) - 1)

@@ -1163,6 +1163,15 @@ void slampp_hip_assembly_destroy(slampp_hip_assembly *p_assembly)
 	delete p_assembly;
 }
 
+int slampp_hip_assembly_get_info(const slampp_hip_assembly *p_assembly, slampp_hip_assembly_info *p_info)
+{
+	if(!p_assembly || !p_info || !p_assembly->p_solver || !p_assembly->p_state)
+		return SLAMPP_HIP_ERR_INVALID; // (a stale handle still says what it built)
+	memset(p_info, 0, sizeof(*p_info));
+	assembly_get_info(*p_assembly->p_state, *p_info);
+	return SLAMPP_HIP_OK;
+}
+
 int slampp_hip_assemble_device_async(slampp_hip_assembly *p_assembly, const double *p_J0_dev, const double *p_J1_dev,
 	const double *p_sigma_inv_dev, const double *p_error_dev, const double *p_weight_dev, int64_t n_unary_vertex,
 	const double *p_unary_factor, const double *p_unary_error, double *p_values_dev, double *p_eta_dev, int b_accumulate)
@@ -1190,6 +1199,8 @@ int slampp_hip_assemble_sets_device_async(const slampp_hip_edge_set *p_sets, int
 				throw std::invalid_argument("assemble_sets: the edge sets belong to different solvers (or one was destroyed)");
 			if(p_sets[i].p_assembly->b_stale)
 				throw std::invalid_argument("assemble_sets: set_structure was called after an assembly was created");
+			assembly_check_arrays(*p_sets[i].p_assembly->p_state, p_sets[i].p_J0_dev, p_sets[i].p_J1_dev, p_sets[i].p_sigma_inv_dev,
+				p_sets[i].p_error_dev); // (before the first set is enqueued)
 		}
 		if(!p_values_dev || !p_eta_dev)
 			throw std::invalid_argument("assemble_sets: null device pointer");

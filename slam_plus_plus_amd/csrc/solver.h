@@ -435,6 +435,8 @@ void assembly_enqueue(CAssemblyState &a, const double *J0, const double *J1, con
 	const double *wgt, int64_t n_unary_vertex, const double *p_unary_factor, const double *p_unary_error,
 	double *values_out, double *eta_out, int b_accumulate); // throws
 size_t assembly_device_bytes(const CAssemblyState *p);
+void assembly_get_info(const CAssemblyState &a, slampp_hip_assembly_info &r_info); // what assembly_setup built, by route
+void assembly_check_arrays(const CAssemblyState &a, const double *J0, const double *J1, const double *Si, const double *err); // throws where the group kernel's 16-byte copies cannot take the arrays (assembly_enqueue checks as well)
 // what the edge kernels of linearize.hip need of an edge set: its shape and, per edge, where its vertices' states lie
 struct TAsmEdgeView {
 	int64_t n_edges;

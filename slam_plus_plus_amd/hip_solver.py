@@ -114,6 +114,13 @@ class EdgeSetPtrs(C.Structure):
                 ("p_error_dev", C.c_void_p), ("p_weight_dev", C.c_void_p)]
 
 
+class AssemblyInfo(C.Structure):
+    """slampp_hip_assembly_info"""
+    _fields_ = [(n, C.c_int) for n in ("rd", "d0", "d1", "n_grp_cap_edges", "n_grp_pkg_stride", "n_long_dim", "n_small_elems",
+                                      "n_off_elems", "b_offdiag_packed", "n_pad")] + [
+        (n, C.c_int64) for n in ("n_groups", "n_long", "n_small", "n_plain_diag", "n_offdiag")]
+
+
 class LmEdgeSet(C.Structure):
     """slampp_hip_lm_edge_set"""
     _fields_ = [("p_assembly", C.c_void_p), ("n_edge_type", C.c_int), ("p_measurement_dev", C.c_void_p), ("p_params_dev", C.c_void_p),
@@ -219,6 +226,7 @@ ABI = {
     "slampp_hip_set_allreduce": (C.c_int, [_P, ALLREDUCE_FN, _P]),
     "slampp_hip_assembly_create": (C.c_int, [_P, C.POINTER(_P), C.c_int64, _P, _P, C.c_int]),
     "slampp_hip_assembly_destroy": (None, [_P]),
+    "slampp_hip_assembly_get_info": (C.c_int, [_P, C.POINTER(AssemblyInfo)]),
     "slampp_hip_assemble_device_async": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int]),
     "slampp_hip_assemble_sets_device_async": (C.c_int, [C.POINTER(EdgeSetPtrs), C.c_int, C.c_int64, _P, _P, _P, _P, C.c_int]),
     "slampp_hip_linearize_device_async": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P]),
@@ -1097,6 +1105,14 @@ class CLambdaAssembly_HIP:
                 self._a = None
         except Exception:
             pass
+
+    def info(self) -> dict:
+        """What the handle built, by the kernel that takes it (slampp_hip_assembly_get_info): ``rd``, ``d0``, ``d1``,
+        ``n_groups``, ``n_grp_cap_edges``, ``n_grp_pkg_stride``, ``n_long``, ``n_long_dim``, ``n_small``, ``n_small_elems``,
+        ``n_plain_diag``, ``n_offdiag``, ``n_off_elems``, ``b_offdiag_packed``."""
+        t = AssemblyInfo()
+        self._solver._check(self._lib.slampp_hip_assembly_get_info(self._a, C.byref(t)))
+        return {n: int(getattr(t, n)) for n, _ in AssemblyInfo._fields_ if n != "n_pad"}
 
     def Refresh_Lambda_device(self, J0_ptr: int, J1_ptr: int, sigma_inv_ptr: int, error_ptr: int, weight_ptr: int,
                               values_ptr: int, eta_ptr: int, unary_vertex: int = 0, unary_factor=None,
