@@ -779,24 +779,45 @@ int slampp_hip_assemble_sets_device_async(const slampp_hip_edge_set *p_sets, int
  *   SLAMPP_HIP_EDGE_P2C_XYZ  CEdgeP2C3D (BA_Types.h:403-505, BASolverBase.h:259-327, 558-619; DATA_UPSIDE_DOWN off): x = R X + t,
  *                            pinhole projection with the camera's intrinsics (fx, fy, cx, cy, k), then the one-coefficient
  *                            radial term with k / ((fx + fy) / 2); err = z - projection; the camera moves by the SE(3) (+)
- *                            above, the point additively.
- * Where the reference differences forwards with a step of 1e-9 (SE3, P2C_XYZ: 3DSolverBase.h:1331-1371, BASolverBase.h:577-619;
- * good to about 1e-7), these are the exact derivatives of the same functions in closed form.
+ *                            above, the point additively;
+ *   SLAMPP_HIP_EDGE_POSE_LANDMARK_2D  CEdgePoseLandmark2D (SE2_Types.h:340-596, 2DSolverBase.h:443-496), range and bearing:
+ *                            (de, dn) = l - p, r = sqrt(de^2 + dn^2), h = (r, f_ClampAngle_2Pi(atan2(dn, de) - theta)); an
+ *                            |r| < 1e-5 is replaced by 1e-5, in h and in the denominators of both Jacobians (:475-495);
+ *                            err = z - h, its angle through f_ClampAngularError_2Pi; the Jacobians are the closed forms of
+ *                            lines 488-494, for additive perturbations of pose and landmark;
+ *   SLAMPP_HIP_EDGE_POSE_LANDMARK_3D  CEdgePoseLandmark3D (SE3_Types.h:444-603, 3DSolverBase.h:1528-1638): h = R0^T (X - t0),
+ *                            err = z - h; J0 = [-I, [h]x] under the SE(3) (+) above, J1 = R0^T;
+ *   SLAMPP_HIP_EDGE_P2SC_XYZ CEdgeP2SC3D (BA_Types.h:705-850, BASolverBase.h:462-537, 781-841), the stereo camera: the left
+ *                            image is p = (fx x / z, fy y / z), projection = c + (1 + k' |p|) p with k' = k / ((fx + fy) / 2) --
+ *                            the radial term is linear in |p| here (:516-517), where P2C_XYZ has |p|^2 (:309-312); the right
+ *                            image is the same projection of the camera-frame point moved by -baseline along the camera's x
+ *                            axis (the reference takes b R.row(0) off the world point, :522, which is the same); h = (u, v) of
+ *                            the left image and u of the right one, err = z - h; the camera moves by the SE(3) (+), the point
+ *                            additively.
+ * Where the reference differences forwards with a step of 1e-9 (SE3, P2C_XYZ, POSE_LANDMARK_3D, P2SC_XYZ: 3DSolverBase.h:1331-1371,
+ * 1602-1637, BASolverBase.h:577-619, 801-840; good to about 1e-7), these are the exact derivatives of the same functions in
+ * closed form.
  *   p_state_dev        n_scalars doubles in Lambda's scalar order -- the layout of eta and dx: the state of block column v at
  *                      its scalar offset (for these vertex types the state dimension is the block dimension);
- *   p_measurement_dev  [n_edges][3 | 6 (xyz, axis-angle) | 2];
- *   p_params_dev       NULL but for P2C_XYZ: the five intrinsics of the camera at block column c at p_params_dev + 5 c (only
+ *   p_measurement_dev  [n_edges][3 | 6 (xyz, axis-angle) | 2 | 2 (range, bearing) | 3 (xyz) | 3 (u, v, u right)];
+ *   p_params_dev       NULL but for P2C_XYZ and P2SC_XYZ: the five intrinsics (fx, fy, cx, cy, k) of the camera at block column c
+ *                      at p_params_dev + 5 c, for P2SC_XYZ the six (fx, fy, cx, cy, k, baseline) at p_params_dev + 6 c (only
  *                      the entries of block columns that are some edge's vertex 0 are read);
  *   p_J0_dev [n_edges][rd x d0], p_J1_dev [n_edges][rd x d1], p_error_dev [n_edges][rd]: written, in the layout
  *                      slampp_hip_assemble_device_async reads (edge-major, matrices column-major).
  * A lane computes an edge; a workgroup stages the outputs of its 64 edges in LDS and writes whole lines.  No atomics: the same
  * call twice gives the same bits, and an edge's results do not depend on the other edges of the set.
  * SLAMPP_HIP_ERR_INVALID (text under "linearize"): a null handle or a null required pointer, an assembly that a set_structure
- * has outdated, an unknown type, a type whose (d0, d1, rd) are not the handle's, P2C_XYZ without p_params_dev.
- * Enqueue-only on the solver's stream. */
+ * has outdated, an unknown type, a type whose (d0, d1, rd) are not the handle's, P2C_XYZ or P2SC_XYZ without p_params_dev.
+ * Enqueue-only on the solver's stream.
+ * The value 4 is no edge type and stays unassigned: callers and tests use it as the unknown type ("linearize: unknown edge
+ * type", checked before the dimensions), so the types added later begin at 5. */
 #define SLAMPP_HIP_EDGE_SE2      1  /* CEdgePose2D: d0 = d1 = 3, rd = 3, measurement 3 doubles          */
 #define SLAMPP_HIP_EDGE_SE3      2  /* CEdgePose3D: d0 = d1 = 6, rd = 6, measurement 6 (xyz, axis-angle) */
 #define SLAMPP_HIP_EDGE_P2C_XYZ  3  /* CEdgeP2C3D:  d0 = 6 (camera), d1 = 3 (point), rd = 2, measurement 2 */
+#define SLAMPP_HIP_EDGE_POSE_LANDMARK_2D 5  /* CEdgePoseLandmark2D: d0 = 3 (pose), d1 = 2 (landmark), rd = 2, measurement 2 */
+#define SLAMPP_HIP_EDGE_POSE_LANDMARK_3D 6  /* CEdgePoseLandmark3D: d0 = 6 (pose), d1 = 3 (landmark), rd = 3, measurement 3 */
+#define SLAMPP_HIP_EDGE_P2SC_XYZ 7  /* CEdgeP2SC3D: d0 = 6 (camera), d1 = 3 (point), rd = 3, measurement 3, six parameters */
 int slampp_hip_linearize_device_async(slampp_hip_assembly *p_assembly, int n_edge_type, const double *p_state_dev,
 	const double *p_measurement_dev, const double *p_params_dev, double *p_J0_dev, double *p_J1_dev, double *p_error_dev);
 

@@ -28,19 +28,17 @@ int slampp_hip_linearize_device_async(slampp_hip_assembly *p_assembly, int n_edg
 			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "linearize: set_structure was called after this assembly was created");
 		if(!p_state_dev || !p_measurement_dev || !p_J0_dev || !p_J1_dev || !p_error_dev)
 			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "linearize: null pointer");
-		int d0, d1, rd;
-		switch(n_edge_type) {
-		case SLAMPP_HIP_EDGE_SE2: d0 = d1 = rd = 3; break;
-		case SLAMPP_HIP_EDGE_SE3: d0 = d1 = rd = 6; break;
-		case SLAMPP_HIP_EDGE_P2C_XYZ: d0 = 6; d1 = 3; rd = 2; break;
-		default: return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "linearize: unknown edge type");
-		}
+		const TEdgeTypeShape t_shape = edge_type_shape(n_edge_type);
+		if(!t_shape.b_known)
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "linearize: unknown edge type");
 		TAsmEdgeView t_edges;
 		assembly_edge_view(*p_assembly->p_state, t_edges);
-		if(t_edges.d0 != d0 || t_edges.d1 != d1 || t_edges.rd != rd)
+		if(t_edges.d0 != t_shape.d0 || t_edges.d1 != t_shape.d1 || t_edges.rd != t_shape.rd)
 			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "linearize: the edge type's dimensions are not this assembly's");
-		if(n_edge_type == SLAMPP_HIP_EDGE_P2C_XYZ && !p_params_dev)
-			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "linearize: SLAMPP_HIP_EDGE_P2C_XYZ needs p_params_dev");
+		if(t_shape.n_params && !p_params_dev) {
+			return fail(p_solver, SLAMPP_HIP_ERR_INVALID, (n_edge_type == SLAMPP_HIP_EDGE_P2C_XYZ)?
+				"linearize: SLAMPP_HIP_EDGE_P2C_XYZ needs p_params_dev" : "linearize: SLAMPP_HIP_EDGE_P2SC_XYZ needs p_params_dev");
+		}
 		linearize_enqueue(n_edge_type, t_edges, p_state_dev, p_measurement_dev, p_params_dev, p_J0_dev, p_J1_dev, p_error_dev,
 			p_solver->stream);
 		return SLAMPP_HIP_OK;

@@ -21,16 +21,6 @@ bool overlap(const double *p_a, const double *p_b, int64_t n)
 	return p_a < p_b + n && p_b < p_a + n;
 }
 
-bool edge_type_dims(int n_edge_type, int &d0, int &d1, int &rd)
-{
-	switch(n_edge_type) {
-	case SLAMPP_HIP_EDGE_SE2: d0 = d1 = rd = 3; return true;
-	case SLAMPP_HIP_EDGE_SE3: d0 = d1 = rd = 6; return true;
-	case SLAMPP_HIP_EDGE_P2C_XYZ: d0 = 6; d1 = 3; rd = 2; return true;
-	}
-	return false;
-}
-
 // an assembly handle of this solver that no set_structure has outdated, and an edge type of its dimensions (inside guarded())
 int check_edge_set(slampp_hip_solver *p_solver, const slampp_hip_assembly *p_assembly, int n_edge_type, bool b_params)
 {
@@ -38,12 +28,12 @@ int check_edge_set(slampp_hip_solver *p_solver, const slampp_hip_assembly *p_ass
 		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "lm: an edge set's assembly is null or belongs to another solver");
 	if(p_assembly->b_stale)
 		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "lm: set_structure was called after an assembly was created");
-	int d0, d1, rd;
+	const TEdgeTypeShape t_shape = edge_type_shape(n_edge_type);
 	TAsmEdgeView t_edges;
 	assembly_edge_view(*p_assembly->p_state, t_edges);
-	if(!edge_type_dims(n_edge_type, d0, d1, rd) || t_edges.d0 != d0 || t_edges.d1 != d1 || t_edges.rd != rd)
+	if(!t_shape.b_known || t_edges.d0 != t_shape.d0 || t_edges.d1 != t_shape.d1 || t_edges.rd != t_shape.rd)
 		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "lm: an edge type does not fit its assembly");
-	if(n_edge_type == SLAMPP_HIP_EDGE_P2C_XYZ && !b_params)
+	if(t_shape.n_params && !b_params)
 		return fail(p_solver, SLAMPP_HIP_ERR_INVALID, "lm: null pointer");
 	return SLAMPP_HIP_OK;
 }

@@ -1,6 +1,7 @@
 // linearize.hip -- the two ends of a Gauss-Newton / LM iteration that the assembly, the damping and the solve left on the host:
 //   linearize   every edge's error and Jacobians from the vertex states  (the reference's Calculate_Jacobians_Expectation_Error
-//               of CEdgePose2D, CEdgePose3D and CEdgeP2C3D: SE2_Types.h:308-318, SE3_Types.h:265-287, BA_Types.h:494-505),
+//               of CEdgePose2D, CEdgePose3D, CEdgeP2C3D, CEdgePoseLandmark2D, CEdgePoseLandmark3D and CEdgeP2SC3D: SE2_Types.h:308-318, 562-573,
+//               SE3_Types.h:265-287, 569-587, BA_Types.h:494-505, 796-811),
 //               written where assembly.hip reads them;
 //   state_plus  x <- x (+) s dx on the vertices' manifolds  (Operator_Plus / Operator_Minus of CVertexPose2D, CVertexPose3D,
 //               CVertexCam, CVertexXYZ, which PushValuesInGraphSystem runs over the vertex pool);
@@ -15,10 +16,12 @@
 
 namespace slampp {
 
-template <int n_edge_type> struct TEdgeShape;
-template <> struct TEdgeShape<SLAMPP_HIP_EDGE_SE2> { enum { D0 = 3, D1 = 3, RD = 3, MD = 3 }; };
-template <> struct TEdgeShape<SLAMPP_HIP_EDGE_SE3> { enum { D0 = 6, D1 = 6, RD = 6, MD = 6 }; };
-template <> struct TEdgeShape<SLAMPP_HIP_EDGE_P2C_XYZ> { enum { D0 = 6, D1 = 3, RD = 2, MD = 2 }; };
+// the row of edge_type_shape (linearize.h) as compile-time constants; NP: the parameters per block column of vertex 0
+template <int n_edge_type> struct TEdgeShape {
+	static_assert(edge_type_shape(n_edge_type).b_known, "no such edge type");
+	enum { D0 = edge_type_shape(n_edge_type).d0, D1 = edge_type_shape(n_edge_type).d1, RD = edge_type_shape(n_edge_type).rd,
+		MD = edge_type_shape(n_edge_type).n_measurement, NP = edge_type_shape(n_edge_type).n_params };
+};
 
 // The lanes of the workgroup hold N doubles each for n_here consecutive edges; in memory those are one run of n_here * N
 // doubles.  A lane storing its own N would walk memory with a stride of 8 N bytes (288 for an SE(3) Jacobian: every store
@@ -52,7 +55,7 @@ linearize_kernel(int64_t n_edges, const int64_t *__restrict__ p_off0, const int6
 	const double *__restrict__ p_params, double *__restrict__ p_J0, double *__restrict__ p_J1, double *__restrict__ p_error)
 {
 	typedef TEdgeShape<n_edge_type> S;
-	enum { D0 = S::D0, D1 = S::D1, RD = S::RD, MD = S::MD, N0 = RD * D0, N1 = RD * D1,
+	enum { D0 = S::D0, D1 = S::D1, RD = S::RD, MD = S::MD, NP = S::NP, N0 = RD * D0, N1 = RD * D1,
 		N_MAX = (!b_jacobians)? RD : (N0 > N1)? N0 : N1 };
 	__shared__ double p_tile[linearize_TILE_EDGES * (N_MAX | 1)];
 	const int64_t n_first = int64_t(blockIdx.x) * linearize_TILE_EDGES, e = n_first + threadIdx.x;
@@ -75,13 +78,20 @@ linearize_kernel(int64_t n_edges, const int64_t *__restrict__ p_off0, const int6
 			lin::edge_se2(x0, x1, z, J0, J1, err);
 		else if(n_edge_type == SLAMPP_HIP_EDGE_SE3)
 			lin::edge_se3(x0, x1, z, J0, J1, err);
+		else if(n_edge_type == SLAMPP_HIP_EDGE_POSE_LANDMARK_2D)
+			lin::edge_pose_landmark_2d(x0, x1, z, J0, J1, err);
+		else if(n_edge_type == SLAMPP_HIP_EDGE_POSE_LANDMARK_3D)
+			lin::edge_pose_landmark_3d(x0, x1, z, J0, J1, err);
 		else {
-			double k5[5];
-			const double *p_k = p_params + 5 * p_vertex0[e];
+			double k[(NP)? NP : 1];
+			const double *p_k = p_params + NP * p_vertex0[e];
 			#pragma unroll
-			for(int i = 0; i < 5; ++ i)
-				k5[i] = p_k[i];
-			lin::edge_p2c_xyz(x0, x1, z, k5, J0, J1, err);
+			for(int i = 0; i < NP; ++ i)
+				k[i] = p_k[i];
+			if(n_edge_type == SLAMPP_HIP_EDGE_P2C_XYZ)
+				lin::edge_p2c_xyz(x0, x1, z, k, J0, J1, err);
+			else
+				lin::edge_p2sc_xyz(x0, x1, z, k, J0, J1, err);
 		}
 	}
 	if(b_jacobians) {
@@ -108,6 +118,9 @@ void linearize_enqueue(int n_edge_type, const TAsmEdgeView &v, const double *p_s
 	case SLAMPP_HIP_EDGE_SE2: LAUNCH_LINEARIZE(SLAMPP_HIP_EDGE_SE2); break;
 	case SLAMPP_HIP_EDGE_SE3: LAUNCH_LINEARIZE(SLAMPP_HIP_EDGE_SE3); break;
 	case SLAMPP_HIP_EDGE_P2C_XYZ: LAUNCH_LINEARIZE(SLAMPP_HIP_EDGE_P2C_XYZ); break;
+	case SLAMPP_HIP_EDGE_POSE_LANDMARK_2D: LAUNCH_LINEARIZE(SLAMPP_HIP_EDGE_POSE_LANDMARK_2D); break;
+	case SLAMPP_HIP_EDGE_POSE_LANDMARK_3D: LAUNCH_LINEARIZE(SLAMPP_HIP_EDGE_POSE_LANDMARK_3D); break;
+	case SLAMPP_HIP_EDGE_P2SC_XYZ: LAUNCH_LINEARIZE(SLAMPP_HIP_EDGE_P2SC_XYZ); break;
 	default: throw std::invalid_argument("linearize: unknown edge type");
 	}
 #undef LAUNCH_LINEARIZE

@@ -14,6 +14,10 @@
 //   camera-point      x = R X + t, p = (fx x / z, fy y / z), projection = c + (1 + k' |p|^2) p with k' = k / ((fx + fy) / 2),
 //                     err = z - projection; the camera moves by the SE(3) (+) above (dx/de = R [I, -[X]x]), the point
 //                     additively (dx/dX = R).
+//   pose-landmark 2D  h = (max(|l - p|, 1e-5), fmod(atan2(l - p) - th, 2 pi)), err = z - h with the angle folded; additive Jacobians
+//   pose-landmark 3D  h = R0^T (X - t0), err = z - h; J0 = [-I, [h]x] under the SE(3) (+), J1 = R0^T
+//   stereo camera     the camera-point projection with a radial term linear in |p|, and u of the same projection of
+//                     x - (baseline, 0, 0): DESIGN.md section 4.12
 // Rotations travel as unit quaternions (w >= 0 picks the principal logarithm, and a small angle keeps its relative accuracy,
 // which a rotation matrix's off-diagonal differences would not).
 #pragma once
@@ -203,6 +207,91 @@ SLAMPP_LIN_FN void edge_p2c_xyz(const double *x0, const double *x1, const double
 		J0[6 + r] = J1[4 + r] * Y - J1[2 + r] * Z;
 		J0[8 + r] = J1[r] * Z - J1[4 + r] * X;
 		J0[10 + r] = J1[2 + r] * X - J1[r] * Y;
+	}
+}
+
+// x0 the pose (e, n, theta), x1 the landmark (e, n), z = (range, bearing).  A range below 1e-5 is replaced by 1e-5 in the
+// expectation and in the denominators of both Jacobians, as the reference does (2DSolverBase.h:475-495); the numerators keep
+// the true differences.  The operations are the reference's, in its order: a host build without contraction gives its bits.
+SLAMPP_LIN_FN void edge_pose_landmark_2d(const double *x0, const double *x1, const double *z, double *J0, double *J1, double *err)
+{
+	const double de = x1[0] - x0[0], dn = x1[1] - x0[1];
+	double r = sqrt(de * de + dn * dn);
+	const double b = clamp_angle_2pi(atan2(dn, de) - x0[2]);
+	if(fabs(r) < 1e-5)
+		r = 1e-5;
+	const double r2 = r * r;
+	err[0] = z[0] - r;
+	err[1] = clamp_angular_error_2pi(z[1] - b);
+	J0[0] = -de / r; J0[2] = -dn / r;  J0[4] = 0;
+	J0[1] = dn / r2; J0[3] = -de / r2; J0[5] = -1;
+	J1[0] = de / r;   J1[2] = dn / r;
+	J1[1] = -dn / r2; J1[3] = de / r2;
+}
+
+// x0 the pose (t, axis-angle), x1 the landmark, z the landmark in the pose's frame: h = R0^T (X - t0), J0 = [-I, [h]x]
+// (the SE(3) (+) of edge_se3), J1 = R0^T
+SLAMPP_LIN_FN void edge_pose_landmark_3d(const double *x0, const double *x1, const double *z, double *J0, double *J1, double *err)
+{
+	double R[9], h[3];
+	quat_to_rot(quat_exp(x0 + 3), R);
+	const double dt[3] = {x1[0] - x0[0], x1[1] - x0[1], x1[2] - x0[2]};
+	#pragma unroll
+	for(int i = 0; i < 3; ++ i) {
+		h[i] = R[3 * i] * dt[0] + R[3 * i + 1] * dt[1] + R[3 * i + 2] * dt[2]; // (row i of R0^T)
+		err[i] = z[i] - h[i];
+	}
+	#pragma unroll
+	for(int i = 0; i < 9; ++ i)
+		J0[i] = 0;
+	J0[0] = J0[4] = J0[8] = -1;
+	J0[9] = 0;      J0[12] = -h[2]; J0[15] = h[1]; // [h]x
+	J0[10] = h[2];  J0[13] = 0;     J0[16] = -h[0];
+	J0[11] = -h[1]; J0[14] = h[0];  J0[17] = 0;
+	#pragma unroll
+	for(int c = 0; c < 3; ++ c) {
+		#pragma unroll
+		for(int r = 0; r < 3; ++ r)
+			J1[3 * c + r] = R[3 * r + c];
+	}
+}
+
+// x0 the camera (t, axis-angle), x1 the point, k6 the stereo camera's (fx, fy, cx, cy, k, baseline); z = (u, v) in the left
+// image and u in the right one.  Each image is p = (fx x / z, fy y / z), projection = c + (1 + k' |p|) p with
+// k' = k / ((fx + fy) / 2): the radial term is linear in |p| here (BASolverBase.h:516-517, 530-531), where the monocular
+// edge has |p|^2.  The right image sees the camera-frame point moved by -baseline along x.  With A = d projection / dp
+// = (1 + k' |p|) I + k' p p^T / |p| (I at p = 0), D (3 x 3) = d (u, v, u_right) / d x stacks the two rows of the left image's
+// A [fx / z, 0, -px / z; 0, fy / z, -py / z] on the first row of the right one's; then as edge_p2c_xyz.
+SLAMPP_LIN_FN void edge_p2sc_xyz(const double *x0, const double *x1, const double *z, const double *k6, double *J0, double *J1,
+	double *err)
+{
+	double R[9];
+	quat_to_rot(quat_exp(x0 + 3), R);
+	const double X = x1[0], Y = x1[1], Z = x1[2];
+	const double cx = R[0] * X + R[3] * Y + R[6] * Z + x0[0], cy = R[1] * X + R[4] * Y + R[7] * Z + x0[1],
+		cz = R[2] * X + R[5] * Y + R[8] * Z + x0[2];
+	const double fx = k6[0], fy = k6[1], k = k6[4] / (.5 * (fx + fy)), iz = 1 / cz;
+	const double px = fx * cx * iz, py = fy * cy * iz, qx = fx * (cx - k6[5]) * iz;
+	const double rl = sqrt(px * px + py * py), rr = sqrt(qx * qx + py * py), gl = 1 + k * rl, gr = 1 + k * rr;
+	err[0] = z[0] - (k6[2] + gl * px);
+	err[1] = z[1] - (k6[3] + gl * py);
+	err[2] = z[2] - (k6[2] + gr * qx);
+	const double kl = (rl > 0)? k / rl : 0, kr = (rr > 0)? k / rr : 0;
+	const double a00 = gl + kl * px * px, a01 = kl * px * py, a11 = gl + kl * py * py, c00 = gr + kr * qx * qx, c01 = kr * qx * py;
+	const double b00 = fx * iz, b02 = -px * iz, b11 = fy * iz, b12 = -py * iz, e02 = -qx * iz;
+	const double D[9] = {a00 * b00, a01 * b00, c00 * b00, a01 * b11, a11 * b11, c01 * b11, a00 * b02 + a01 * b12, a01 * b02 + a11 * b12,
+		c00 * e02 + c01 * b12}; // column-major
+	#pragma unroll
+	for(int c = 0; c < 3; ++ c) {
+		#pragma unroll
+		for(int r = 0; r < 3; ++ r)
+			J1[3 * c + r] = J0[3 * c + r] = D[r] * R[3 * c] + D[3 + r] * R[3 * c + 1] + D[6 + r] * R[3 * c + 2]; // D R
+	}
+	#pragma unroll
+	for(int r = 0; r < 3; ++ r) { // -D R [X]x
+		J0[9 + r] = J1[6 + r] * Y - J1[3 + r] * Z;
+		J0[12 + r] = J1[r] * Z - J1[6 + r] * X;
+		J0[15 + r] = J1[3 + r] * X - J1[r] * Y;
 	}
 }
 

@@ -44,6 +44,7 @@ GRAM_CHUNK_ROWS = 2048     # SLAMPP_HIP_GRAM_CHUNK_ROWS
 # (SLAMPP_HIP_MULTIPLY_* in include/slampp_hip.h; the development option "multiply_long_row" lowers the threshold)
 MULTIPLY_LONG_ROW, MULTIPLY_CHUNK = 256, 256
 EDGE_SE2, EDGE_SE3, EDGE_P2C_XYZ = 1, 2, 3             # SLAMPP_HIP_EDGE_*: CEdgePose2D, CEdgePose3D, CEdgeP2C3D
+EDGE_POSE_LANDMARK_2D, EDGE_POSE_LANDMARK_3D, EDGE_P2SC_XYZ = 5, 6, 7   # CEdgePoseLandmark2D, CEdgePoseLandmark3D, CEdgeP2SC3D (4: none)
 VERTEX_EUCLIDEAN, VERTEX_SE2, VERTEX_SE3 = 0, 1, 2     # SLAMPP_HIP_VERTEX_*: x + dx, x + dx with the angle clamped, SE(3) (+)
 LINEARIZE_TILE_EDGES = 64   # edges of a workgroup of slampp_hip_linearize_device_async (their outputs leave through one LDS tile)
 # SLAMPP_HIP_LM_*: the scalars of the device-decided Levenberg-Marquardt loop, its status values and its trace record
@@ -1130,8 +1131,9 @@ class CLambdaAssembly_HIP:
                          params_ptr: int = 0) -> None:
         """Every edge's error and Jacobians from the vertex states, written where Refresh_Lambda_device reads them
         (slampp_hip_linearize_device_async; the reference's Calculate_Jacobians_Expectation_Error).  ``edge_type``: EDGE_SE2,
-        EDGE_SE3 or EDGE_P2C_XYZ, matching this edge set's dimensions; ``state_ptr``: the states in the layout of eta;
-        ``params_ptr``: five intrinsics per block column (EDGE_P2C_XYZ only).  Enqueue-only."""
+        EDGE_SE3, EDGE_P2C_XYZ, EDGE_POSE_LANDMARK_2D, EDGE_POSE_LANDMARK_3D or EDGE_P2SC_XYZ, matching this edge set's
+        dimensions; ``state_ptr``: the states in the layout of eta; ``params_ptr``: per block column five intrinsics
+        (EDGE_P2C_XYZ) or six, the baseline last (EDGE_P2SC_XYZ); 0 for the other types.  Enqueue-only."""
         self._solver._check(self._lib.slampp_hip_linearize_device_async(
             self._a, int(edge_type), state_ptr or None, measurement_ptr or None, params_ptr or None, J0_ptr or None, J1_ptr or None,
             error_ptr or None))
@@ -1200,7 +1202,8 @@ def Refresh_Lambda_sets_device(assemblies, pointer_sets, values_ptr: int, eta_pt
         values_ptr, eta_ptr, int(bool(accumulate))))
 
 
-_EDGE_DIMS = {EDGE_SE2: (3, 3, 3, 3), EDGE_SE3: (6, 6, 6, 6), EDGE_P2C_XYZ: (6, 3, 2, 2)}   # d0, d1, rd, measurement
+_EDGE_DIMS = {EDGE_SE2: (3, 3, 3, 3), EDGE_SE3: (6, 6, 6, 6), EDGE_P2C_XYZ: (6, 3, 2, 2),       # d0, d1, rd, measurement
+              EDGE_POSE_LANDMARK_2D: (3, 2, 2, 2), EDGE_POSE_LANDMARK_3D: (6, 3, 3, 3), EDGE_P2SC_XYZ: (6, 3, 3, 3)}
 
 
 class CLevenbergMarquardt_HIP:
@@ -1210,8 +1213,9 @@ class CLevenbergMarquardt_HIP:
     ``Sync`` (slampp_hip_lm_begin_device_async, slampp_hip_lm_iterate_device_async).
 
     ``edge_sets``: a list of dicts with ``assembly`` (a CLambdaAssembly_HIP of ``solver``), ``edge_type`` (EDGE_*),
-    ``measurement`` [E, 3 | 6 | 2], ``sigma_inv`` [E, rd, rd] (every matrix column-major, as the assembly reads them), and
-    optionally ``params`` (five intrinsics per block column, EDGE_P2C_XYZ) and ``weight`` [E]; arrays or CUDA tensors.  A set
+    ``measurement`` [E, 3 | 6 | 2 | 2 | 3 | 3], ``sigma_inv`` [E, rd, rd] (every matrix column-major, as the assembly reads
+    them), and optionally ``params`` (per block column five intrinsics for EDGE_P2C_XYZ, six with the baseline for
+    EDGE_P2SC_XYZ) and ``weight`` [E]; arrays or CUDA tensors.  A set
     may carry ``robust`` instead of ``weight``: a dict of the arguments of ``CLambdaAssembly_HIP.Set_Robust`` (``kernel``,
     ``basis``, ``mode``, ``scale``, ``param``), which is set on the set's assembly; the loop then computes the weights itself.
     ``lam``: Lambda's block structure, as CLambdaAssembly_HIP takes it.
